@@ -16,6 +16,11 @@ library's own CeedXHalo* (--halo torch: torch.distributed point-to-point).
     python bench.py --gpus 1 --steps 50 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 5
+
+A plain run sets up, warms up, times exactly --steps steps in one block and prints the line.  --full adds everything else
+the line can carry: five timed blocks and their spread, the cold figure after an idle second, the shader clock under load,
+the roofline, the exchange alone (N > 1) and the CPU baseline.  --dump-outputs DIR writes y of the last timed step (a fixed
+seeded sample of it) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -220,6 +225,33 @@ def valu_issue(kernel_name: str, ngroups: int, seconds: float):
     return None
 
 
+DUMP_ENTRIES = 1 << 21   # --dump-outputs: entries of y kept (all ranks together); f64 values + f64 indices = 32 MiB
+DUMP_SEED = 20261016
+
+
+def dump_sample_index(n: int, k: int) -> np.ndarray:
+    """Sorted indices of the entries --dump-outputs keeps of an n-vector: all of them up to k, else k distinct ones drawn with a
+    fixed seed (the same for every run of the same workload)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname: str, yt: "torch.Tensor", rank: int, world: int) -> None:
+    """--dump-outputs DIR: what the timed path computed in its last step, the L-vector y = J(u) x, as float64 .npy files --
+    y.npy (the sampled entries), y_index.npy (their positions in y) and y_summary.npy (length, 2-norm, sum, max |y| of the
+    WHOLE vector).  At N > 1 every rank writes its own share with a _rank<r> suffix."""
+    os.makedirs(dirname, exist_ok=True)
+    n = yt.numel()
+    idx = dump_sample_index(n, max(1, DUMP_ENTRIES // world))
+    vals = yt[torch.from_numpy(idx).to(yt.device)].cpu().numpy().astype(np.float64)
+    summary = np.array([float(n), float(torch.linalg.vector_norm(yt).item()), float(yt.sum().item()), float(yt.abs().max().item())], dtype=np.float64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"y{sfx}.npy"), vals)
+    np.save(os.path.join(dirname, f"y_index{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, f"y_summary{sfx}.npy"), summary)
+
+
 def self_launch(n: int) -> None:
     """`python bench.py --gpus N` run directly (no launcher in the environment): start the N ranks as a CHILD process --
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same
@@ -351,7 +383,12 @@ def main():
                          "exiting non-zero (the line then says \"halo_path\": \"torch-fallback\"); strict is the default")
     ap.add_argument("--nu", type=float, default=0.3)
     ap.add_argument("--E", type=float, default=1.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure, off by default: --blocks timed blocks (default 5 under --full) and their "
+                         "spread, the cold figure, the shader-clock probe, the roofline, the exchange alone (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: y of the last one as DIR/y.npy (a fixed seeded sample), DIR/y_index.npy, DIR/y_summary.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: do not hide the halo exchange under the interior elements")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-sample-layers", type=int, default=3)
@@ -363,8 +400,9 @@ def main():
                          "split-phase apply exactly as at N > 1, and the library's RCCL exchange on a one-rank communicator whose "
                          "neighbour lists have the TRUE sizes, sent to this rank itself (everything one GPU can tell about the N-GPU regime)")
     ap.add_argument("--of", type=int, default=8, metavar="N")
-    ap.add_argument("--cold-idle-s", type=float, default=1.0,
-                    help="idle time before the COLD timing of --steps applies (reported as ms_per_step_cold; 0: skipped)")
+    ap.add_argument("--cold-idle-s", type=float, default=None,
+                    help="idle time before the COLD timing of --steps applies (reported as ms_per_step_cold; 0: skipped; "
+                         "default 1 under --full, else 0)")
     ap.add_argument("--per-apply-events", action="store_true",
                     help="kernel_avg_us from a pair of hipEvents around EVERY apply (round 1-3's form) instead of one pair around the timed steps")
     ap.add_argument("--graph", action="store_true",
@@ -386,15 +424,20 @@ def main():
     ap.add_argument("--reorder", action="store_true",
                     help="sort the elements along a Morton curve through their centroids before numbering the nodes (mesh.reorder_elements_locality): "
                          "what the mesh layer can do for a badly ordered mesh (use with --scramble or --workload mesh)")
-    ap.add_argument("--blocks", type=int, default=5,
+    ap.add_argument("--blocks", type=int, default=None,
                     help="timed blocks of --steps applies each (every block between a barrier + synchronize on both sides, one hipEvent pair "
-                         "each): ms_per_step and value are the MEDIAN block's, the spread over the blocks is reported beside them")
+                         "each): ms_per_step and value are the MEDIAN block's, the spread over the blocks is reported beside them "
+                         "(default 5 under --full, else 1: a plain run times exactly --steps applies)")
     ap.add_argument("--no-clock-probe", action="store_true",
-                    help="skip the untimed block of applies with the shader-clock probe beside it (profiling runs: the trace then ends with the timed block)")
+                    help="--full without the untimed block of applies with the shader-clock probe beside it (profiling runs: the trace then ends with the timed block)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no device, no operator: the N ranks rendezvous on gloo, partition the mesh as the real run does and time the "
                          "interface sums of a test vector over torch.distributed; the line says \"dry_run\": true and \"value\": null")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
+    if args.cold_idle_s is None:
+        args.cold_idle_s = 1.0 if args.full else 0.0
     # `python bench.py --gpus N` without a launcher: start the ranks ourselves, as a child, before any GPU call here
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -540,7 +583,7 @@ def main():
             prob.apply_jacobian(prob.fine, X, Y)   # ApplyJacobian_Ceed: k_fused_pencil + k_assemble on `stream`
             chalo.add(Y) if chalo else halo.add(yt)   # interface sum (no-op at N = 1)
 
-    # cold figure (reported beside the warm one): the first --steps applies after a 1 s idle, before any pre-warm -- the
+    # cold figure (--full; reported beside the warm one): the first --steps applies after a 1 s idle, before any pre-warm -- the
     # clock / power transient after idle makes them ~8 % slower (profiles/r02_dispatch_series.txt)
     ms_cold = None
     if args.cold_idle_s > 0:
@@ -614,10 +657,12 @@ def main():
         op.set_timing(False)
     else:
         kernel_ms, launches = blk_dev[imed], args.steps
+    if args.dump_outputs:   # y of the last timed step, before anything below runs another step
+        dump_outputs(args.dump_outputs, yt, rank, world)
     # the shader clock WHILE the applies run: one more (untimed) block is queued and a one-wave probe on a stream of its own counts
     # shader cycles against the 100 MHz counter for part of it -- a slow box (clock) is then distinguishable from a slow build
     clock_ghz = None
-    if not args.no_clock_probe:
+    if args.full and not args.no_clock_probe:
         try:
             for _ in range(args.steps):
                 step()
@@ -653,7 +698,7 @@ def main():
                         % float((d / ((tb[:, 25] - tb[:, 24]) * 10.0)).mean()))
     # the exchange alone (outside the timed region): mean of 20 back-to-back interface sums
     halo_us = None
-    if world > 1 or emu:
+    if args.full and (world > 1 or emu):
         ykeep = yt.clone()
         torch.cuda.synchronize()
         if world > 1:
@@ -670,15 +715,9 @@ def main():
 
     if rank == 0:
         P, Q = args.degree + 1, args.degree + 1
-        abytes = algorithmic_bytes(mesh.nelem, P, Q, n, args.problem != "linElas")
-        avg_s = kernel_ms * 1e-3 / max(args.steps, 1)   # per APPLY (a split-phase apply is two timed launch pairs)
-        if avg_s <= 0.0:   # --graph with --per-apply-events: the replays carry no hipEvents; the step time stands in
-            avg_s = elapsed / args.steps
         li = op.launch_info()
         assembly_form = ("pipelined: %d segments on %d streams, last segment %d elements" % (li["segments"], li["streams"], li["last_segment_elements"])
                          if li["segments"] > 1 else os.environ.get("CEED_MI355X_ASSEMBLE", "serial (launch too small to pipeline, split-phase apply, or switched off)"))
-        achieved = abytes / avg_s / 1e9
-        traffic, traffic_src = traffic_from_profile(op.kernel_name, mesh.nelem, li)
         out = {
             "metric": "MDoF/s for matrix-free Jacobian apply, p=4 hyperFS hex, 1/2/4/8 GPU",
             "value": 1e-6 * n_global * args.steps / elapsed,
@@ -688,7 +727,7 @@ def main():
             "halo_path": halo_path,   # N > 1: "rccl" = the library's CeedXHalo* (pack kernel, RCCL group, unpack-add); "torch" on request / on gloo; "torch-fallback" only with --no-strict-halo
             "prewarm_ms": args.prewarm_ms, "prewarm_steps": prewarm_steps,
             "launch": "hipGraph replay of one recorded step" if args.graph else "direct",
-            "ms_per_step": 1e3 * elapsed / args.steps,     # the MEDIAN of the timed blocks (below)
+            "ms_per_step": 1e3 * elapsed / args.steps,     # the MEDIAN of the timed blocks (below; one block of --steps applies unless --full / --blocks)
             "timed_blocks": {"blocks": nblk, "steps_per_block": args.steps, "ms_per_step": [1e3 * w / args.steps for w in blk_wall],
                              "device_ms_per_step": [d / args.steps for d in blk_dev],
                              "min": 1e3 * min(blk_wall) / args.steps, "median": 1e3 * elapsed / args.steps, "max": 1e3 * max(blk_wall) / args.steps,
@@ -711,31 +750,37 @@ def main():
                        "halo_dofs_rank0": halo.n_shared_dofs, "kernel": op.kernel_name,
                        "assembly": assembly_form, "schedule": os.environ.get("CEED_MI355X_SCHED", "static"),
                        "partition": partition_text(args, world, overlap, use_rccl, emu),
-                       "halo_exchange_us_alone": halo_us, "halo_note": halo_note, "multi_gpu_measured": (None if world == 1 else "this run")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         # `achieved` prices the REFERENCE formulation's bytes (qdata and gradu streamed) over the
-                         # measured time: an effective rate.  The kernel as built recomputes qdata (own_floor_bytes) and makes
-                         # an E-vector round trip (the difference between traffic and own_floor_bytes).
-                         "own_floor_bytes": own_floor_bytes(mesh.nelem, P, Q, n, args.problem != "linElas"),
-                         "measured_traffic_GBs": (traffic / avg_s / 1e9) if traffic else None,
-                         "algorithmic_bytes_per_launch": abytes, "kernel_avg_us": avg_s * 1e6,
-                         "kernel_launches_timed": launches,
-                         "kernel_avg_us_from": "a pair of hipEvents around every apply" if args.per_apply_events else "one pair of hipEvents on the operator's stream around the timed steps / steps",
-
-                         "launches_per_apply": li["segments"] + li["assemble_launches"],
-                         "kernels": ("k_fused_pencil (gather..physics..shell E-vector, interior nodes straight to y) + k_assemble (deterministic per-node sum of the shared nodes): "
-                                     + ("the two launches of one CeedOperatorApply, timed together with hipEvents on their stream" if li["segments"] <= 1 else
-                                        "one CeedOperatorApply = %d segments of consecutive elements, each a fused launch followed by the k_assemble of the rows it completes, alternating between %d streams so that the rows of a segment are summed beside the next fused kernel; kernel_avg_us is the hipEvent time of the WHOLE apply on the operator's stream (fork to join), not a sum of per-kernel durations, which overlap (profiles/README.md)" % (li["segments"], li["streams"]))),
-                         "peak_measured_copy_GBs": 6290.0,
-                         "valu_issue": valu_issue(op.kernel_name, (mesh.nelem + (2 if Q == 5 else (1 if Q >= 6 else (4 if Q >= 3 else 8))) - 1) // (2 if Q == 5 else (1 if Q >= 6 else (4 if Q >= 3 else 8))), avg_s)},
+                       "halo_exchange_us_alone": halo_us, "halo_note": halo_note, "multi_gpu_measured": (None if world == 1 else "this run")}
         }
+        if args.full:   # the roofline: the algorithmic bytes over the device time of the timed steps, and what the committed profiles say
+            abytes = algorithmic_bytes(mesh.nelem, P, Q, n, args.problem != "linElas")
+            avg_s = kernel_ms * 1e-3 / max(args.steps, 1)   # per APPLY (a split-phase apply is two timed launch pairs)
+            if avg_s <= 0.0:   # --graph with --per-apply-events: the replays carry no hipEvents; the step time stands in
+                avg_s = elapsed / args.steps
+            achieved = abytes / avg_s / 1e9
+            traffic, traffic_src = traffic_from_profile(op.kernel_name, mesh.nelem, li)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                               # `achieved` prices the REFERENCE formulation's bytes (qdata and gradu streamed) over the
+                               # measured time: an effective rate.  The kernel as built recomputes qdata (own_floor_bytes) and makes
+                               # an E-vector round trip (the difference between traffic and own_floor_bytes).
+                               "own_floor_bytes": own_floor_bytes(mesh.nelem, P, Q, n, args.problem != "linElas"),
+                               "measured_traffic_GBs": (traffic / avg_s / 1e9) if traffic else None,
+                               "algorithmic_bytes_per_launch": abytes, "kernel_avg_us": avg_s * 1e6,
+                               "kernel_launches_timed": launches,
+                               "kernel_avg_us_from": "a pair of hipEvents around every apply" if args.per_apply_events else "one pair of hipEvents on the operator's stream around the timed steps / steps",
+                               "launches_per_apply": li["segments"] + li["assemble_launches"],
+                               "kernels": ("k_fused_pencil (gather..physics..shell E-vector, interior nodes straight to y) + k_assemble (deterministic per-node sum of the shared nodes): "
+                                           + ("the two launches of one CeedOperatorApply, timed together with hipEvents on their stream" if li["segments"] <= 1 else
+                                              "one CeedOperatorApply = %d segments of consecutive elements, each a fused launch followed by the k_assemble of the rows it completes, alternating between %d streams so that the rows of a segment are summed beside the next fused kernel; kernel_avg_us is the hipEvent time of the WHOLE apply on the operator's stream (fork to join), not a sum of per-kernel durations, which overlap (profiles/README.md)" % (li["segments"], li["streams"]))),
+                               "peak_measured_copy_GBs": 6290.0,
+                               "valu_issue": valu_issue(op.kernel_name, (mesh.nelem + (2 if Q == 5 else (1 if Q >= 6 else (4 if Q >= 3 else 8))) - 1) // (2 if Q == 5 else (1 if Q >= 6 else (4 if Q >= 3 else 8))), avg_s)}
         if emu:
             out["emulated_rank"] = {"rank": args.emulate_rank, "of": args.of, "lead_elements": int(lead.sum()),
                                     "neighbour_dofs": [int(nb.dof_idx.numel()) for nb in halo.neigh],
                                     "us_per_apply_incl_exchange": 1e6 * elapsed / args.steps,
                                     "note": "value = dofs this rank OWNS x steps / time: one rank's share of the N-rank job, NOT the job's rate"}
-        if not args.no_cpu_baseline and world == 1 and args.workload == "cylinder" and not emu:
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "cylinder" and not emu:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.nr, args.nth)
             except Exception as e:  # the baseline is informational; never hide the GPU number

@@ -3,7 +3,9 @@ through `gcc -std=c99 -fsyntax-only -Werror=incompatible-pointer-types` with thi
 stand-in for the PETSc headers (tests/petsc_stub: type names and error macros, no PETSc function declared -- nothing is compiled
 to code or linked).  Every diagnostic that names a Ceed* / CEED_* identifier is a hole in the boundary: an undeclared libCEED
 function or constant, a wrong argument type, a wrong arity.  Calls to PETSc functions are implicit declarations and are ignored.
-Skipped where /root/reference is absent (the GPU box)."""
+The type check is skipped where the reference tree is absent (the GPU box); the token-level check reads the list of the reference's
+Ceed* / CEED_* names stored in tests/golden (oracle/gen_reference_identifiers.py) and runs everywhere."""
+import json
 import os
 import re
 import shutil
@@ -11,7 +13,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 REF = "/root/reference"
 SOURCES = ["src/setuplibceed.c", "src/matops.c", "src/misc.c", "src/boundary.c", "src/cloptions.c", "src/setupdm.c", "elasticity.c"]
@@ -39,23 +41,14 @@ def test_reference_sources_type_check_against_the_boundary(src):
     assert not errors, "\n".join(errors[:20])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree")
 def test_every_ceed_identifier_the_reference_uses_is_declared():
-    """Token-level cross-check: each Ceed* / CEED_* identifier in the reference's sources is declared by include/ceed.h, or is one
-    of the reference's own names (its CeedData struct family, the CEED_DIR Makefile variable quoted in a comment)."""
+    """Token-level cross-check: each Ceed* / CEED_* identifier in the reference's sources (comments and string literals stripped;
+    the list is tests/golden/reference_ceed_identifiers.json, written by oracle/gen_reference_identifiers.py) is declared by
+    include/ceed.h, or is one of the reference's own names (its CeedData struct family, the CEED_DIR Makefile variable quoted in a
+    comment)."""
     hdr = open(os.path.join(ROOT, "include", "ceed.h")).read()
     declared = set(re.findall(r"\b(Ceed[A-Za-z0-9_]*|CEED_[A-Z0-9_]+)\b", hdr))
-    own = set()
-    used = set()
-    for src in SOURCES + ["elasticity.h"]:
-        txt = open(os.path.join(REF, src)).read()
-        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-        txt = re.sub(r"//[^\n]*", "", txt)
-        txt = re.sub(r'"(?:\\.|[^"\\])*"', '""', txt)                       # string literals (option prefixes such as "CEED_MEM_")
-        used |= set(re.findall(r"\b(Ceed[A-Za-z0-9_]*|CEED_[A-Z0-9_]+)\b", txt))
-        own |= set(re.findall(r"(?:struct|typedef struct)\s+(Ceed[A-Za-z0-9_]*)", txt))
-        own |= set(re.findall(r"}\s*\*?\s*(Ceed[A-Za-z0-9_]*)\s*;", txt))
-        own |= set(re.findall(r"typedef\s+struct\s+\w+\s*\*\s*(Ceed[A-Za-z0-9_]*)\s*;", txt))
-        own |= set(re.findall(r"PetscErrorCode\s+(Ceed[A-Za-z0-9_]*)\s*\(", txt))       # functions the reference defines itself
-    missing = sorted(used - declared - own)
+    ref = json.load(open(os.path.join(GOLDEN, "reference_ceed_identifiers.json")))
+    assert sorted(ref["sources"]) == sorted(SOURCES + ["elasticity.h"]) and ref["used"]
+    missing = sorted(set(ref["used"]) - declared - set(ref["own"]))
     assert not missing, missing

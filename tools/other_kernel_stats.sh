@@ -3,8 +3,8 @@
 cd /tmp && export TMPDIR=/tmp; R=${GRAFT_REPO_ROOT:-/root/repo}
 run() {
   tag=$1; shift; rm -rf /tmp/os_$tag
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/os_$tag -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline "$@" > /tmp/os_$tag.log 2>&1
-  echo "== $tag: bench.py --steps 30 --warmup 3 --no-cpu-baseline $*"
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/os_$tag -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline "$@" > /tmp/os_$tag.log 2>&1
+  echo "== $tag: bench.py --full --steps 30 --warmup 3 --no-cpu-baseline $*"
   python3 - "$(find /tmp/os_$tag -name '*kernel_stats.csv' | head -1)" /tmp/os_$tag.log <<'PY'
 import csv, json, sys
 for r in csv.DictReader(open(sys.argv[1])):

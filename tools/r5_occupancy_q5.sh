@@ -4,7 +4,7 @@
 #   aliasbz5w2 the smaller slab alone (still 8 waves per CU by registers): control
 #   minw3      the register limit alone (LDS still caps at 8 waves per CU): what the squeeze costs
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-run() { python3 bench.py "$@" --no-cpu-baseline 2>/dev/null | python3 -c "import sys, json; d=[json.loads(l) for l in sys.stdin if l.startswith('{')][-1]; print('%.4f ms  %.1f GDoF/s  spread %.2f %%' % (d['ms_per_step'], d['value'] / 1e3, d['timed_blocks']['spread_pct']))"; }
+run() { python3 bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python3 -c "import sys, json; d=[json.loads(l) for l in sys.stdin if l.startswith('{')][-1]; print('%.4f ms  %.1f GDoF/s  spread %.2f %%' % (d['ms_per_step'], d['value'] / 1e3, d['timed_blocks']['spread_pct']))"; }
 for w in "" "--problem hyperSS"; do
   echo "== config 4 ${w:-hyperFS}"
   for v in default aliasbz5 aliasbz5w2 minw3 default aliasbz5 default; do

@@ -6,14 +6,14 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/profiles_new; mkdir -p $O; T=${1:-r03}; COMMIT=${2:-unknown}; KPAT=${3:-"k_fused_pencil<5, 5, 6"}; shift 3
 export KPAT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err || { echo bench failed; tail -5 $O/${T}_bench.err; exit 1; }
+python3 $R/bench.py "$@" --full > $O/${T}_bench.json 2> $O/${T}_bench.err || { echo bench failed; tail -5 $O/${T}_bench.err; exit 1; }
 echo "bench done: $(python3 -c "import json; d=json.loads(open('$O/${T}_bench.json').read()); print(d['value'], d['ms_per_step'], d.get('ms_per_step_cold'), d['roofline']['frac'], (d.get('cpu_baseline') or {}).get('value'), (d['roofline'].get('valu_issue') or {}).get('valu_issue_frac'))")"
 for pw in 150 0; do
   rm -rf /tmp/prof_stats_$pw
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_$pw -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --blocks 1 --no-clock-probe --prewarm-ms $pw --cold-idle-s 0 --no-cpu-baseline > $O/${T}_stats_run_$pw.log 2>&1 || { echo stats failed; tail -5 $O/${T}_stats_run_$pw.log; exit 1; }
 done
 rm -rf /tmp/prof_stats_serial
-CEED_MI355X_ASSEMBLE=serial timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_serial -- python3 $R/bench.py "$@" --steps 50 --warmup 5 --blocks 1 --no-clock-probe --cold-idle-s 0 --no-cpu-baseline > $O/${T}_stats_run_serial.log 2>&1 || { echo serial stats failed; tail -5 $O/${T}_stats_run_serial.log; exit 1; }
+CEED_MI355X_ASSEMBLE=serial timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_serial -- python3 $R/bench.py "$@" --full --steps 50 --warmup 5 --blocks 1 --no-clock-probe --cold-idle-s 0 --no-cpu-baseline > $O/${T}_stats_run_serial.log 2>&1 || { echo serial stats failed; tail -5 $O/${T}_stats_run_serial.log; exit 1; }
 grep '^{"metric"' $O/${T}_stats_run_serial.log > $O/${T}_bench_serial_form.json
 cp $(find /tmp/prof_stats_serial -name "*kernel_stats.csv" | head -1) $O/${T}_kernel_stats_serial_form.csv
 cp $(find /tmp/prof_stats_150 -name "*kernel_stats.csv" | head -1) $O/${T}_kernel_stats.csv
