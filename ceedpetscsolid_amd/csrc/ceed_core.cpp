@@ -74,13 +74,9 @@ extern "C" int CeedInit(const char *resource, Ceed *ceed) {
   o.derived_state = !env_is("CEED_MI355X_DERIVED", "0");
   if (env_is("CEED_MI355X_ASSEMBLE", "serial")) o.pipe_segments = 0;
   else { const int ps = env_int("CEED_MI355X_PIPE_SEGMENTS", 0); o.pipe_segments = ps >= 2 ? std::min(ps, 16) : -1; }
-  o.pipe_blocks = env_int("CEED_MI355X_PIPE_BLOCKS", 0);
   o.pipe_mb = std::max(0, env_int("CEED_MI355X_PIPE_MB", o.pipe_mb));
-  o.pipe_last_rounds = std::max(0, env_int("CEED_MI355X_PIPE_LAST", o.pipe_last_rounds));
   o.pipe_min_total_rounds = std::max(0, env_int("CEED_MI355X_PIPE_MIN_TOTAL", o.pipe_min_total_rounds));
   o.pipe_min_rounds = std::max(0, env_int("CEED_MI355X_PIPE_MIN_ROUNDS", o.pipe_min_rounds));
-  o.pipe_debug = getenv("CEED_MI355X_PIPE_DEBUG") != nullptr;
-  o.graph_memset = env_int("CEED_MI355X_GRAPH_MEMSET", 0) != 0;
   o.pencil_waves = std::max(0, env_int("CEED_MI355X_PENCIL_WAVES", 0));
   o.ovl_mode = env_int("CEED_MI355X_OVL_MODE", o.ovl_mode);
   o.ovl_groups0 = std::max(0, env_int("CEED_MI355X_OVL_G0", o.ovl_groups0));
@@ -88,9 +84,6 @@ extern "C" int CeedInit(const char *resource, Ceed *ceed) {
   o.comm_priority = env_int("CEED_MI355X_COMM_PRIO", o.comm_priority);
   o.comm_inline = env_int("CEED_MI355X_COMM_INLINE", o.comm_inline);
   o.fold_pack = env_int("CEED_MI355X_FOLD_PACK", o.fold_pack);
-  o.spgemm_row = !env_is("CEED_MI355X_SPGEMM", "entry");
-  o.spmv_stream = !env_is("CEED_MI355X_SPMV", "vector");
-  o.epi_pipelined = env_int("CEED_MI355X_EPI_PIPELINED", 0) != 0;
   *ceed = c;
   return 0;
 }
@@ -268,12 +261,11 @@ int ceed_need_evec(Ceed c, size_t len) {
 static size_t vbytes(CeedVector v) { return sizeof(double) * (size_t)(v->length > 0 ? v->length : 1); }
 // Zero `n` doubles on the Ceed's stream.  While a hipGraph is being recorded this is a fill KERNEL rather than a memset node
 // (same cost).  Round 1 had blamed a wrong replay on recorded memset nodes losing their order; a library-free reproducer
-// (tools/microbench/graph_memset_repro.hip) and this library with CEED_MI355X_GRAPH_MEMSET=1 both replay correctly: the
-// cause was the scratch E-vector being re-allocated under recorded nodes (see ceed_need_evec).  CEED_MI355X_GRAPH_MEMSET=1
-// records memset nodes instead (A/B: tools/graph_replay_check.py).
+// (tools/microbench/graph_memset_repro.hip) and this library recording memset nodes both replayed correctly (round 2): the
+// cause was the scratch E-vector being re-allocated under recorded nodes (see ceed_need_evec).
 int dev_zero(Ceed c, double *p, size_t n) {
   if (!n) return 0;
-  if (c->capturing && !c->opt.graph_memset) HIPCHK(launch_set_value(p, n, 0.0, c->stream));
+  if (c->capturing) HIPCHK(launch_set_value(p, n, 0.0, c->stream));
   else HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * n, c->stream));
   return 0;
 }

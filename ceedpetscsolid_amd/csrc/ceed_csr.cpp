@@ -106,11 +106,8 @@ extern "C" int CeedXCsrApply(CeedXCsr A, CeedVector x, CeedVector y) {
   if (x->length < A->ncols || y->length < A->nrows) return ceed_error("CeedXCsrApply: vector shorter than the matrix");
   double *px, *py;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, true, &py));
-  if (A->ceed->opt.spmv_stream) {
-    CHK(csr_row_blocks(A));
-    HIPCHK(launch_csr_spmv_stream(A->d_row_block, A->n_row_blocks, A->d_rowptr, A->d_cols, A->d_vals, px, py, A->ceed->stream));
-  } else
-  HIPCHK(launch_csr_spmv(A->d_rowptr, A->d_cols, A->d_vals, px, py, A->nrows, A->ceed->stream));
+  CHK(csr_row_blocks(A));
+  HIPCHK(launch_csr_spmv_stream(A->d_row_block, A->n_row_blocks, A->d_rowptr, A->d_cols, A->d_vals, px, py, A->ceed->stream));
   return 0;
 }
 extern "C" int CeedXCsrGetDiagonal(CeedXCsr A, CeedVector d) {
@@ -235,7 +232,7 @@ extern "C" int CeedXCsrUpdate(CeedXCsr A) {
   if (!A->src || !A->src2) return ceed_error("CeedXCsrUpdate: not a product (CeedXCsrCreateProduct)");
   CeedXCsr Lm = A->src, Rm = A->src2;
   HIPCHK(launch_csr_spgemm(Lm->d_rowptr, Lm->d_cols, Lm->d_vals, Rm->d_rowptr, Rm->d_cols, Rm->d_vals, A->d_rowptr, A->d_cols, A->d_vals,
-                           A->nrows, A->ceed->stream, A->dense ? A->ncols : 0, A->ceed->opt.spgemm_row ? A->max_row : 0));
+                           A->nrows, A->ceed->stream, A->dense ? A->ncols : 0, A->max_row));
   return 0;
 }
 extern "C" int CeedXCsrGetValues(CeedXCsr A, CeedVector v) {

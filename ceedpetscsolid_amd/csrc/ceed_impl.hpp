@@ -26,10 +26,11 @@ int ceed_error(const char *fmt, ...);
   return ceed_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 // ---------------------------------------------------------------------------
-// Run-time options, read ONCE from the environment by CeedInit (never on an apply path).  A/B switches of shipped
-// features only; the experiments of rounds 1-2 (row kernel, atomics, dynamic / gated / folded / pair forms) are gone.
+// Run-time options, read ONCE from the environment by CeedInit (never on an apply path).  Only the switches a test, bench.py
+// or a tuning run on a real multi-GPU node still needs: the settled single-GPU A/B switches of rounds 1-5 are gone (HISTORY.md).
 // ---------------------------------------------------------------------------
 struct CeedOptions {
+  // bitwise / rounding references of the GPU tests
   bool recompute_geo = true;     // CEED_MI355X_GEO=0: the fused kernels read qdata instead of recomputing it from the element maps
   bool direct_interior = true;   // CEED_MI355X_DIRECT=0: element-interior nodes go through the E-vector like the shared ones
   bool derived_state = true;     // CEED_MI355X_DERIVED=0: HyperFSdF forms F^-1 and ln J from the stored grad u at every point
@@ -39,21 +40,14 @@ struct CeedOptions {
   int pipe_segments = -1;        // 0: never (CEED_MI355X_ASSEMBLE=serial); -1: chosen per launch; >= 2: CEED_MI355X_PIPE_SEGMENTS
   int pipe_mb = 0;               // CEED_MI355X_PIPE_MB: one segment per this many MB of E-vector when the count is chosen per launch
                                  // (0: 160 for the finite-strain kernels, 90 for the cheaper ones -- see get_pipe)
-  int pipe_blocks = 0;           // CEED_MI355X_PIPE_BLOCKS: cap on the workgroups of a k_assemble that runs beside a fused kernel
-  int pipe_last_rounds = 4;      // CEED_MI355X_PIPE_LAST: rounds of the persistent waves in the LAST segment
   int pipe_min_total_rounds = 20;   // CEED_MI355X_PIPE_MIN_TOTAL: rounds a whole apply must have to be pipelined
   int pipe_min_rounds = 4;       // CEED_MI355X_PIPE_MIN_ROUNDS: rounds a segment must have (0: tests on small meshes)
-  bool pipe_debug = false;       // CEED_MI355X_PIPE_DEBUG
-  bool graph_memset = false;     // CEED_MI355X_GRAPH_MEMSET=1: recorded zero-fills as memset nodes instead of fill kernels
   int pencil_waves = 0;          // CEED_MI355X_PENCIL_WAVES: persistent waves per CU of the fused kernel (tuning hook)
-  // split-phase apply with the halo exchange (CeedXOperatorApplyWithHalo)
+  // split-phase apply with the halo exchange (CeedXOperatorApplyWithHalo): kept for tuning on a real multi-GPU node
   int ovl_mode = 0;              // CEED_MI355X_OVL_MODE: 0 (default) the whole apply, then the exchange, in order on one stream;
                                  // 1 split-phase on one stream (interface elements, exchange started, interior elements: round 2's
                                  // sequence); 2 split-phase on two streams (both phases' fused kernels side by side)
   int ovl_groups0 = 1, ovl_groups1 = 0;   // CEED_MI355X_OVL_G0 / _G1: groups per wave of the two phases (0: persistent grid)
-  bool epi_pipelined = false;    // CEED_MI355X_EPI_PIPELINED=1: the apply fused with its consumer in the pipelined form too (default: serial, measured faster)
-  bool spmv_stream = true;       // CEED_MI355X_SPMV=vector: CeedXCsrApply a wave per row (rounds 2-4's kernel, A/B) instead of the CSR-stream form
-  bool spgemm_row = true;        // CEED_MI355X_SPGEMM=entry: Galerkin products an entry of C per lane with binary searches in global memory (round 3's kernel, A/B)
   int fold_pack = 1;             // CEED_MI355X_FOLD_PACK=0: the exchange's pack as a launch of its own (A/B)
   int comm_inline = 1;           // CEED_MI355X_COMM_INLINE=0: the exchange's sends / receives on a stream of their own (see halo_pack_and_send)
   int comm_priority = 0;         // CEED_MI355X_COMM_PRIO=1: the exchange on a highest-priority stream -- measured 4x SLOWER (see CeedXCommInit)

@@ -370,6 +370,10 @@ struct TimerScope {
   }
 };
 
+// how the last apply was launched (CeedXOperatorGetLaunchInfo)
+static void set_launch_info(CeedOperator op, int segments, int streams, int assemble_launches, int last_segment_elems) {
+  op->launch_info[0] = segments; op->launch_info[1] = streams; op->launch_info[2] = assemble_launches; op->launch_info[3] = last_segment_elems;
+}
 
 // ---------------------------------------------------------------------------
 // The residual / Jacobian operator: k_fused_pencil (+ k_assemble)
@@ -501,13 +505,13 @@ static int fused_launch(CeedOperator op, const FusedApply &F, int e0, int ne, in
   op->geo_mode = F.a.geo_aff && F.a.geo ? 2 : (F.a.geo_swept && F.a.geo ? 3 : (F.a.geo ? 1 : 0));
   return 0;
 }
-static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s, int max_blocks = 0, const HaloUnpackArgs *un = nullptr,
+static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s, const HaloUnpackArgs *un = nullptr,
                          const HaloPackFold *pk = nullptr) {
   const CsrMap *M = F.M;
   HaloPackFold p0{nullptr, nullptr, nullptr};
   if (pk) p0 = HaloPackFold{pk->ptr + row0, pk->slot, pk->send};
   HIPCHK(launch_assemble(M->d_rowptr + row0, M->d_cols, M->d_node_off + row0, F.flags ? F.flags + row0 : nullptr, F.a.evec, F.py,
-                         nrows, F.add ? 1 : 0, s, max_blocks, un, pk ? &p0 : nullptr));
+                         nrows, F.add ? 1 : 0, s, un, pk ? &p0 : nullptr));
   return 0;
 }
 // The pack of halo H folded into the launch that sums the rows of map M: per row the send slots of its node's entries.
@@ -554,7 +558,7 @@ static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const CsrMap *M
 // segment k + 1 sits in the other queue and fills the chip as the waves of segment k retire (no kernel boundary between
 // fused kernels), every k_assemble but the last runs beside a fused kernel.  Every row is summed in contributor order by
 // one thread, whatever the segment: bitwise the serial result.
-static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM, const char **kname, const EpilogueArgs *ep = nullptr) {
+static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM, const char **kname) {
   Ceed c = op->ceed;
   hipStream_t s = c->stream;
   CHK(ceed_need_side_stream(c));
@@ -571,8 +575,7 @@ static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM, co
     }
   }
   const int nseg = PM->nseg;
-  op->launch_info[0] = nseg; op->launch_info[1] = 2; op->launch_info[2] = nseg;
-  op->launch_info[3] = PM->elem_bound[nseg] - PM->elem_bound[nseg - 1];
+  set_launch_info(op, nseg, 2, nseg, PM->elem_bound[nseg] - PM->elem_bound[nseg - 1]);
   HIPCHK(hipEventRecord(c->ev_fork, s));
   HIPCHK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
   for (int k = 0; k < nseg; k++) {
@@ -584,20 +587,28 @@ static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM, co
     HIPCHK(hipEventRecord(c->ev_seg[k], sk));
     if (k >= 1) HIPCHK(hipStreamWaitEvent(sk, c->ev_seg[k - 1], 0));
     const int r0 = PM->row_bound[k], nr = PM->row_bound[k + 1] - r0;
-    if (ep) {   // the consumer of the output in place of its store; the segment's own element-interior nodes ride along
-      EpilogueArgs ek = *ep;
-      const int nint = F.direct ? F.r->int_per_elem : 0;
-      ek.int_off = nint ? F.r->d_int_off + (size_t)PM->elem_bound[k] * nint : nullptr;
-      ek.n_int = (PM->elem_bound[k + 1] - PM->elem_bound[k]) * nint;
-      HIPCHK(launch_assemble_epi(PM->d_rowptr + r0, PM->d_cols, PM->d_node_off + r0, fl ? fl + r0 : nullptr, F.a.evec, nr, ek, sk,
-                                 k + 1 < nseg ? c->opt.pipe_blocks : 0));
-    } else
-    HIPCHK(launch_assemble(PM->d_rowptr + r0, PM->d_cols, PM->d_node_off + r0, fl ? fl + r0 : nullptr, F.a.evec, F.py, nr, 0,
-                           sk, k + 1 < nseg ? c->opt.pipe_blocks : 0));
+    HIPCHK(launch_assemble(PM->d_rowptr + r0, PM->d_cols, PM->d_node_off + r0, fl ? fl + r0 : nullptr, F.a.evec, F.py, nr, 0, sk));
   }
   HIPCHK(hipEventRecord(c->ev_join, c->side_stream));
   HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
   return 0;
+}
+
+// The segments of the pipelined form for a whole apply (get_pipe): from the persistent waves of a full launch of THIS kernel
+// (LDS-limited from Q = 6 on), the E-vector records per element and the MB of E-vector per segment.  *PM null or of one
+// segment: the serial form.
+static int choose_pipe(CeedOperator op, const FusedApply &F, PipeMap **PM) {
+  Ceed c = op->ceed;
+  int waves = 0;
+  FusedGradArgs aq = F.a;
+  aq.query_waves = &waves;
+  const char *nm = "";
+  HIPCHK(launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, aq, c->stream, &nm));
+  if (waves <= 0) return ceed_error("pipelined assembly: no persistent-wave count for P=%d Q=%d", F.b->P1d, F.b->Q1d);
+  const int per_elem = F.direct ? evec_block_records(F.b->P1d) : F.r->elemsize;
+  const bool fs = F.qfkind == QF_HYPERFS_DF || F.qfkind == QF_HYPERFS_DF_DS || F.qfkind == QF_HYPERFS_F;
+  const int mb = c->opt.pipe_mb > 0 ? c->opt.pipe_mb : (fs ? 160 : 90);     // MB of E-vector per segment (get_pipe)
+  return get_pipe(F.r, *F.M, pencil_group_elems(F.b->Q1d), per_elem, std::max(c->opt.pipe_segments, 0), waves, mb, PM);
 }
 
 // phase -1: whole apply; phase 0 / 1: the two halves of a split-phase apply (CeedXOperatorApplyPhase), one after the other
@@ -622,42 +633,29 @@ static int apply_fused_grad(CeedOperator op, CeedVector in, CeedVector out, bool
     const int lead = op->ovl_lead;
     if (phase == 0) { CHK(fused_launch(op, F, 0, lead, 0, s, kname)); CHK(assemble_rows(F, 0, M->nprio, s)); }
     else { CHK(fused_launch(op, F, lead, F.r->nelem - lead, 0, s, kname)); CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s)); }
-    op->launch_info[0] = 1; op->launch_info[1] = 1; op->launch_info[2] = 1; op->launch_info[3] = phase == 0 ? lead : F.r->nelem - lead;
+    set_launch_info(op, 1, 1, 1, phase == 0 ? lead : F.r->nelem - lead);
     op->launches++;
     return 0;
   }
   // pipelined assembly: whole applies in overwrite mode, large enough for two segments
-  if (c->opt.pipe_segments != 0 && !add) {
-    int waves = 0;            // persistent waves of a full launch of THIS kernel (LDS-limited from Q = 6 on)
-    {
-      FusedGradArgs aq = F.a;
-      aq.query_waves = &waves;
-      const char *nm = "";
-      HIPCHK(launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, aq, s, &nm));
-      if (waves <= 0) return ceed_error("pipelined assembly: no persistent-wave count for P=%d Q=%d", F.b->P1d, F.b->Q1d);
+  PipeMap *PM = nullptr;
+  if (c->opt.pipe_segments != 0 && !add) CHK(choose_pipe(op, F, &PM));
+  if (PM && PM->nseg >= 2) {
+    CHK(apply_pipelined(op, F, PM, kname));
+    if (H) {
+      CHK(halo_pack_and_send(H, F.py, s));
+      CHK(halo_wait_arrivals(H, s));
+      HIPCHK(launch_halo_unpack_add(halo_unpack_args(H), F.py, s));
     }
-    const int per_elem = F.direct ? evec_block_records(F.b->P1d) : F.r->elemsize;
-    PipeMap *PM = nullptr;
-    const bool fs = F.qfkind == QF_HYPERFS_DF || F.qfkind == QF_HYPERFS_DF_DS || F.qfkind == QF_HYPERFS_F;
-    const int mb = c->opt.pipe_mb > 0 ? c->opt.pipe_mb : (fs ? 160 : 90);     // MB of E-vector per segment (get_pipe)
-    CHK(get_pipe(F.r, *M, pencil_group_elems(F.b->Q1d), per_elem, std::max(c->opt.pipe_segments, 0), waves, mb, &PM));
-    if (PM && PM->nseg >= 2) {
-      CHK(apply_pipelined(op, F, PM, kname));
-      if (H) {
-        CHK(halo_pack_and_send(H, F.py, s));
-        CHK(halo_wait_arrivals(H, s));
-        HIPCHK(launch_halo_unpack_add(halo_unpack_args(H), F.py, s));
-      }
-      op->launches++;
-      return 0;
-    }
+    op->launches++;
+    return 0;
   }
-  op->launch_info[0] = 1; op->launch_info[1] = 1; op->launch_info[2] = 1; op->launch_info[3] = F.r->nelem;
+  set_launch_info(op, 1, 1, 1, F.r->nelem);
   CHK(fused_launch(op, F, 0, F.r->nelem, 0, s, kname));
   HaloPackFold pk{nullptr, nullptr, nullptr};
   bool folded = false;
   if (H && c->opt.fold_pack) CHK(get_pack_fold(op, F.r, M, H, &pk, &folded));
-  CHK(assemble_rows(F, 0, M->nnodes, s, 0, nullptr, folded ? &pk : nullptr));   // timed together with the fused kernel: the launches ARE the operator apply
+  CHK(assemble_rows(F, 0, M->nnodes, s, nullptr, folded ? &pk : nullptr));   // timed together with the fused kernel: the launches ARE the operator apply
   if (H) {
     if (folded) CHK(halo_send(H, s)); else CHK(halo_pack_and_send(H, F.py, s));
     CHK(halo_wait_arrivals(H, s));
@@ -673,8 +671,7 @@ static int apply_fused_grad(CeedOperator op, CeedVector in, CeedVector out, bool
 // *fused = false (nothing launched): the apply is not of that shape (nodes without an element: full_cover) -- the caller runs the two
 // steps one after the other.
 static int apply_fused_epilogue(CeedOperator op, CeedVector in, CeedVector t, EpilogueArgs ep, const char **kname, bool *fused) {
-  Ceed c = op->ceed;
-  hipStream_t s = c->stream;
+  hipStream_t s = op->ceed->stream;
   FusedApply F;
   *fused = false;
   CHK(fused_prepare(op, in, t, false, false, F));
@@ -685,30 +682,10 @@ static int apply_fused_epilogue(CeedOperator op, CeedVector in, CeedVector t, Ep
   *fused = true;
   ep.t = F.py;
   TimerScope ts(op, s);
-  // Serial form by default: with the consumer in the epilogue the rows' launch is no longer light enough to hide beside the next
+  // Always the serial form: with the consumer in the epilogue the rows' launch is no longer light enough to hide beside the next
   // segment's fused kernel, and the fork / join costs inside a replayed graph -- V-cycle at config 4's size: serial 6.05 ms eager and
-  // replayed, pipelined 6.10 eager / 6.83 replayed (profiles/r05_ab_experiments.txt item 10).  CEED_MI355X_EPI_PIPELINED=1: pipelined (tests).
-  if (c->opt.epi_pipelined && c->opt.pipe_segments != 0) {
-    int waves = 0;
-    {
-      FusedGradArgs aq = F.a;
-      aq.query_waves = &waves;
-      const char *nm = "";
-      HIPCHK(launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, aq, s, &nm));
-      if (waves <= 0) return ceed_error("pipelined assembly: no persistent-wave count for P=%d Q=%d", F.b->P1d, F.b->Q1d);
-    }
-    const int per_elem = F.direct ? evec_block_records(F.b->P1d) : F.r->elemsize;
-    PipeMap *PM = nullptr;
-    const bool fs = F.qfkind == QF_HYPERFS_DF || F.qfkind == QF_HYPERFS_DF_DS || F.qfkind == QF_HYPERFS_F;
-    const int mb = c->opt.pipe_mb > 0 ? c->opt.pipe_mb : (fs ? 160 : 90);
-    CHK(get_pipe(F.r, *M, pencil_group_elems(F.b->Q1d), per_elem, std::max(c->opt.pipe_segments, 0), waves, mb, &PM));
-    if (PM && PM->nseg >= 2) {
-      CHK(apply_pipelined(op, F, PM, kname, &ep));
-      op->launches++;
-      return 0;
-    }
-  }
-  op->launch_info[0] = 1; op->launch_info[1] = 1; op->launch_info[2] = 1; op->launch_info[3] = F.r->nelem;
+  // replayed, pipelined 6.10 eager / 6.83 replayed (profiles/r05_ab_experiments.txt item 10).
+  set_launch_info(op, 1, 1, 1, F.r->nelem);
   CHK(fused_launch(op, F, 0, F.r->nelem, 0, s, kname));
   ep.int_off = nint ? F.r->d_int_off : nullptr;
   ep.n_int = F.r->nelem * nint;
@@ -748,14 +725,14 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
   TimerScope ts(op, s);
   const CeedOptions &o = c->opt;
   const HaloUnpackArgs un = halo_unpack_args(H);
-  op->launch_info[0] = 2; op->launch_info[1] = o.ovl_mode == 2 ? 2 : 1; op->launch_info[2] = 2; op->launch_info[3] = rest;
+  set_launch_info(op, 2, o.ovl_mode == 2 ? 2 : 1, 2, rest);
   if (o.ovl_mode != 2) {   // round 2's sequence on one stream
     CHK(fused_launch(op, F, 0, lead, 0, s, kname));
     CHK(assemble_rows(F, 0, M->nprio, s));
     CHK(halo_pack_and_send(H, F.py, s));
     CHK(fused_launch(op, F, lead, rest, 0, s, kname));
     CHK(halo_wait_arrivals(H, s));
-    CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s, 0, &un));
+    CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s, &un));
     op->launches++;
     return 0;
   }
@@ -771,7 +748,7 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
   CHK(halo_pack_and_send(H, F.py, s));
   HIPCHK(hipStreamWaitEvent(s1, c->ev_seg[0], 0));
   CHK(halo_wait_arrivals(H, s1));
-  CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s1, 0, &un));
+  CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s1, &un));
   HIPCHK(hipEventRecord(c->ev_join, s1));
   HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
   op->launches++;
@@ -805,6 +782,19 @@ static int transfer_owner_map(CeedOperator op, CeedElemRestriction rf) {
   HIPCHK(hipMemcpy(op->d_own_f, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
   return 0;
 }
+// Set-up time only (never while recording): `n` counters on the device, zeroed, counted into by `count` on the Ceed's stream,
+// and read back into h[0 .. n).
+template <class Count>
+static int count_on_device(Ceed c, int n, int *h, Count count) {
+  int *d_cnt = nullptr;
+  HIPCHK(hipMalloc((void **)&d_cnt, n * sizeof(int)));
+  HIPCHK(hipMemsetAsync(d_cnt, 0, n * sizeof(int), c->stream));
+  CHK(count(d_cnt));
+  HIPCHK(hipMemcpyAsync(h, d_cnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  (void)hipFree(d_cnt);
+  return 0;
+}
 // w = (fine-side scale, CeedXOperatorSetFineScale, or 1) x (local multiplicity of the fine restriction) per fine dof; *w = null
 // when every covered entry is 1 (the scale IS 1 / local multiplicity: one rank).  Recomputed when the scale vector was written
 // since (CeedVector_private::version) -- with one host read of a counter, so never while recording.
@@ -824,172 +814,180 @@ static int transfer_weights(CeedOperator op, CeedElemRestriction rf, const doubl
     HIPCHK(hipMalloc((void **)&op->d_w, sizeof(double) * (n ? n : 1)));
     op->w_len = n;
   }
-  int *d_cnt = nullptr, cnt = 1;
-  HIPCHK(hipMalloc((void **)&d_cnt, sizeof(int)));
-  HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
-  CHK(dev_zero(c, op->d_w, n));
-  HIPCHK(launch_multiplicity(rf->d_offsets, rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w, c->stream));
-  HIPCHK(launch_transfer_weights(op->d_w, psc, n, d_cnt, c->stream));
-  HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));      // set-up time only
-  (void)hipFree(d_cnt);
+  int cnt = 1;
+  CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) {
+    CHK(dev_zero(c, op->d_w, n));
+    HIPCHK(launch_multiplicity(rf->d_offsets, rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w, c->stream));
+    HIPCHK(launch_transfer_weights(op->d_w, psc, n, d_cnt, c->stream));
+    return 0;
+  }));
   op->w_unit = cnt == 0; op->w_scale = sc; op->w_version = ver; op->w_ready = true;
   if (op->w_unit) { ceed_retire(c, op->d_w); op->d_w = nullptr; op->w_len = 0; }     // (not needed again until the scale is rewritten: 8 B per fine dof given back)
   *w = op->w_unit ? nullptr : op->d_w;
   return 0;
 }
+static int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add, const char **kname) {
+  hipStream_t s = op->ceed->stream;
+  const bool pro = op->plan == PLAN_PROLONG;
+  CeedElemRestriction rc = pro ? op->in[0].rstr : op->out[0].rstr, rf = pro ? op->out[0].rstr : op->in[0].rstr;
+  CeedBasis b = pro ? op->in[0].basis : op->out[0].basis;
+  if (in == out) return ceed_error("in-place operator apply is not supported");
+  if (in->length < (pro ? rc : rf)->lsize || out->length < (pro ? rf : rc)->lsize) return ceed_error("transfer vector too short");
+  TransferArgs a{};
+  double *px, *py;
+  CHK(vec_dev(in, false, &px));
+  CHK(vec_dev(out, true, &py));
+  if (op->scale && op->scale->length < rf->lsize) return ceed_error("scale vector too short");
+  // OWNER form (kernels_misc.hip): the fine nodes each element owns, and the weights (null: all 1, the one-rank case)
+  CHK(transfer_owner_map(op, rf));
+  CHK(transfer_weights(op, rf, &a.w_f));
+  // the coarse side's flagged offsets: the input side of a prolongation, the output side of a restriction
+  const uint32_t *fc = pro ? op->d_off_flagged_in : op->d_off_flagged_out;
+  a.off_c = fc ? fc : rc->d_offsets;
+  a.own_f = op->d_own_f;
+  a.x = px; a.y = py; a.nelem = rc->nelem; a.add = add ? 1 : 0;
+  const int m_in = (op->mask_mode & 1) ? 1 : 0, m_out = (op->mask_mode & 2) ? 1 : 0;
+  a.mask_c = pro ? m_in : m_out; a.mask_f = pro ? m_out : m_in;
+  if (pro) {
+    // every fine node is stored by its owner: no E-vector, no sum
+    if (!add && !op->own_full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  } else {
+    // deterministic scatter on the COARSE side (Pc^3 nodes per element): element results -> E-vector -> per-node sums in
+    // element order over the coarse restriction's transpose map (masked entries travel as zeros)
+    CHK(build_csr(rc, rc->csr, nullptr));
+    CHK(ceed_need_evec(op->ceed, (size_t)rc->nelem * rc->ncomp * rc->elemsize));
+    a.evec = op->ceed->evec;
+    if (!add && !rc->csr.full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  }
+  TimerScope ts(op, s);
+  hipError_t e = launch_transfer(b->P1d, b->Q1d, pro, op->tables, a, s, kname);
+  if (e == hipErrorInvalidValue && !**kname) return ceed_error("no transfer kernel for Pc=%d Pf=%d", b->P1d, b->Q1d);
+  HIPCHK(e);
+  if (!pro) HIPCHK(launch_assemble(rc->csr.d_rowptr, rc->csr.d_cols, rc->csr.d_node_off, nullptr, a.evec, py, rc->csr.nnodes, add ? 1 : 0, s));
+  op->launches++;
+  return 0;
+}
 
+// ---------------------------------------------------------------------------
+// SetupGeo, and the coordinate-driven and energy operators
+// ---------------------------------------------------------------------------
+// Provenance for the fused kernels, kept with the qdata vector SetupGeo just wrote from trilinear elements: the map coefficients,
+// and the constant factors of the whole mesh's element class when it has one (affine; else swept along one reference direction).
+// Operators reading this vector may then recompute the factors instead of streaming them.  Set-up time only.
+static int geo_provenance(CeedOperator op, CeedVector out, const uint32_t *off_x, const double *px, int nelem) {
+  Ceed c = op->ceed;
+  hipStream_t s = c->stream;
+  CeedBasis xb = op->in[0].basis;
+  HIPCHK(hipMalloc((void **)&out->geo, sizeof(double) * GEO_NCOEF * (size_t)nelem));
+  HIPCHK(launch_geo_coeffs(off_x, px, out->geo, nelem, s));
+  out->geo_nelem = nelem; out->geo_Q = xb->Q1d;
+  if (c->opt.affine_geo) {   // all elements affine (box meshes)?  then dXdx and det J are per-ELEMENT constants
+    int cnt = 1;
+    HIPCHK(hipMalloc((void **)&out->geo_aff, sizeof(double) * GEO_NAFF * (size_t)nelem));
+    CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) { HIPCHK(launch_geo_affine(out->geo, out->geo_aff, nelem, d_cnt, s)); return 0; }));
+    if (cnt != 0) { (void)hipFree(out->geo_aff); out->geo_aff = nullptr; }   // a mixed mesh takes the general recompute everywhere
+  }
+  if (!out->geo_aff && c->opt.swept_geo) {   // every element swept along ONE reference direction (extruded meshes)?
+    int cnt[4] = {0, 0, 0, 1};
+    HIPCHK(hipMalloc((void **)&out->geo_swept, sizeof(double) * GEO_NSWEPT * (size_t)nelem));
+    CHK(count_on_device(c, 4, cnt, [&](int *d_cnt) {     // count: every direction an element qualifies for
+      HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, d_cnt, -1, s));
+      return 0;
+    }));
+    int axis = -1;
+    for (int d = 2; d >= 0; d--) if (cnt[d] == nelem) axis = d;      // a direction ALL elements share
+    if (axis < 0) { (void)hipFree(out->geo_swept); out->geo_swept = nullptr; }   // no common direction or general hexes: the general recompute
+    else { HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, nullptr, axis, s)); out->geo_axis = axis; }
+  }
+  for (int i = 0; i < xb->Q1d && i < MAXN1D; i++) { out->geo_qref[i] = xb->qref1d[i]; out->geo_qwt[i] = xb->qweight1d[i]; }
+  return 0;
+}
+static int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out, const char **kname) {
+  hipStream_t s = op->ceed->stream;
+  OpField &x = op->in[0];
+  if (!in || in->length < x.rstr->lsize) return ceed_error("coordinate vector too short");
+  SetupGeoArgs a{};
+  double *px, *pq;
+  CHK(vec_dev(in, false, &px));
+  CHK(vec_dev(out, true, &pq));
+  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.qdata = pq; a.nelem = x.rstr->nelem;
+  if ((size_t)out->length < (size_t)a.nelem * 10 * x.basis->Q1d * x.basis->Q1d * x.basis->Q1d) return ceed_error("qdata vector too short");
+  TimerScope ts(op, s);
+  hipError_t e = launch_setup_geo(x.basis->Q1d, op->tables, a, s, kname);
+  if (e == hipErrorInvalidValue && !**kname) return ceed_error("no setup_geo kernel for Q=%d", x.basis->Q1d);
+  HIPCHK(e);
+  op->launches++;
+  // trilinear elements (coordinate basis P = 2): keep the map coefficients with the qdata vector
+  if (op->ceed->opt.recompute_geo && !op->ceed->capturing && x.basis->P1d == 2 && x.rstr->elemsize == 8 && x.rstr->ncomp == 3 && x.rstr->compstride == 1)
+    CHK(geo_provenance(op, out, a.off_x, px, a.nelem));
+  return 0;
+}
+static int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add, const char **kname) {
+  CeedQFunction qf = op->qf;
+  OpField &u = op->in[0], &en = op->out[0];
+  if (!in || in->length < u.rstr->lsize || !out || out->length < en.rstr->lsize) return ceed_error("displacement / energy vector too short");
+  EnergyOpArgs a{};
+  double *pu, *py, *pq;
+  CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
+  a.off_u = u.rstr->d_offsets; a.u = pu; a.off_e = en.rstr->d_offsets; a.y = py; a.qdata = pq;
+  a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
+  const int kd = qf->kind;
+  a.diag = (kd == QF_DIAG_LINELAS || kd == QF_DIAG_HYPERSS || kd == QF_DIAG_HYPERFS) ? 1 : 0;
+  a.model = (kd == QF_ENERGY_LINELAS || kd == QF_DIAG_LINELAS) ? 0 : ((kd == QF_ENERGY_HYPERSS || kd == QF_DIAG_HYPERSS) ? 1 : 2);
+  CHK(read_phys(qf, &a.nu, &a.E));
+  memcpy(a.interp, u.basis->interp1d.data(), sizeof(double) * u.basis->interp1d.size());
+  memcpy(a.grad, u.basis->grad1d.data(), sizeof(double) * u.basis->grad1d.size());
+  if (!a.diag) memcpy(a.interp_e, en.basis->interp1d.data(), sizeof(double) * en.basis->interp1d.size());
+  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  hipError_t e = launch_energy_op(a, op->ceed->stream);
+  if (e == hipErrorInvalidValue) return ceed_error("energy operator: Q=%d / P=%d outside the supported range", a.Q, a.P);
+  HIPCHK(e);
+  *kname = a.diag ? (a.model == 0 ? "diagnostic_op<LinElasDiagnostic>" : (a.model == 1 ? "diagnostic_op<HyperSSDiagnostic>" : "diagnostic_op<HyperFSDiagnostic>"))
+                  : (a.model == 0 ? "energy_op<LinElasEnergy>" : (a.model == 1 ? "energy_op<HyperSSEnergy>" : "energy_op<HyperFSEnergy>"));
+  op->launches++;
+  return 0;
+}
+static int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add, const char **kname) {
+  CeedQFunction qf = op->qf;
+  OpField &x = op->in[0], &o = op->out[0];
+  if (!in || in->length < x.rstr->lsize || !out || out->length < o.rstr->lsize) return ceed_error("coordinate / output vector too short");
+  CoordOpArgs a{};
+  double *px, *py, *pq = nullptr;
+  CHK(vec_dev(in, false, &px)); CHK(vec_dev(out, true, &py));
+  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.off_u = o.rstr->d_offsets; a.y = py;
+  a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
+  a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
+  if (a.mode != 2) {
+    CHK(vec_dev(op->in[1].vec, false, &pq)); a.qdata = pq;
+    a.Pout = o.basis->P1d;
+    memcpy(a.bu, o.basis->interp1d.data(), sizeof(double) * o.basis->interp1d.size());
+    if (!qf->ctx) return ceed_error("QFunction '%s' needs its context", qf->name.c_str());
+    const double *cx = (const double *)qf->ctx;   // pointer pass-through: forcing vector (3) or Physics {nu, E} (setuplibceed.c:563-566)
+    for (int i = 0; i < (a.mode == 0 ? 3 : 2); i++) a.ctx[i] = cx[i];
+  } else {
+    a.Pout = a.Q;
+  }
+  memcpy(a.bx, x.basis->interp1d.data(), sizeof(double) * x.basis->interp1d.size());
+  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  hipError_t e = launch_coord_op(a, op->ceed->stream);
+  if (e == hipErrorInvalidValue) return ceed_error("coordinate operator: Q=%d / P=%d outside the supported range", a.Q, a.Pout);
+  HIPCHK(e);
+  *kname = a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>");
+  op->launches++;
+  return 0;
+}
+
+// One apply of a non-composite operator: the plan its fields were lowered to (op_plan).
 static int op_apply_single(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CHK(op_plan(op));
-  CeedQFunction qf = op->qf;
-  hipStream_t s = op->ceed->stream;
   const char *kname = "";
   switch (op->plan) {
-  case PLAN_FUSED_GRAD:
-    CHK(apply_fused_grad(op, in, out, add, -1, &kname));
-    break;
-  case PLAN_SETUP_GEO: {
-    OpField &x = op->in[0];
-    if (!in || in->length < x.rstr->lsize) return ceed_error("coordinate vector too short");
-    SetupGeoArgs a{};
-    double *px, *pq;
-    CHK(vec_dev(in, false, &px));
-    CHK(vec_dev(out, true, &pq));
-    a.off_x = x.rstr->d_offsets; a.xcoord = px; a.qdata = pq; a.nelem = x.rstr->nelem;
-    if ((size_t)out->length < (size_t)a.nelem * 10 * x.basis->Q1d * x.basis->Q1d * x.basis->Q1d) return ceed_error("qdata vector too short");
-    TimerScope ts(op, s);
-    hipError_t e = launch_setup_geo(x.basis->Q1d, op->tables, a, s, &kname);
-    if (e == hipErrorInvalidValue && !*kname) return ceed_error("no setup_geo kernel for Q=%d", x.basis->Q1d);
-    HIPCHK(e);
-    op->launches++;
-    // provenance for the fused kernels: trilinear elements (coordinate basis P = 2) -> keep the map coefficients with
-    // the qdata vector; operators reading this vector may then recompute the factors instead of streaming them
-    if (op->ceed->opt.recompute_geo && !op->ceed->capturing && x.basis->P1d == 2 && x.rstr->elemsize == 8 && x.rstr->ncomp == 3 && x.rstr->compstride == 1) {
-      HIPCHK(hipMalloc((void **)&out->geo, sizeof(double) * GEO_NCOEF * (size_t)a.nelem));
-      HIPCHK(launch_geo_coeffs(a.off_x, px, out->geo, a.nelem, s));
-      out->geo_nelem = a.nelem; out->geo_Q = x.basis->Q1d;
-      if (op->ceed->opt.affine_geo) {   // all elements affine (box meshes)?  then dXdx and det J are per-ELEMENT constants
-        int *d_cnt = nullptr, cnt = 1;
-        HIPCHK(hipMalloc((void **)&out->geo_aff, sizeof(double) * GEO_NAFF * (size_t)a.nelem));
-        HIPCHK(hipMalloc((void **)&d_cnt, sizeof(int)));
-        HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), s));
-        HIPCHK(launch_geo_affine(out->geo, out->geo_aff, a.nelem, d_cnt, s));
-        HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));      // set-up time only
-        (void)hipFree(d_cnt);
-        if (cnt != 0) { (void)hipFree(out->geo_aff); out->geo_aff = nullptr; }   // a mixed mesh takes the general recompute everywhere
-      }
-      if (!out->geo_aff && op->ceed->opt.swept_geo) {   // every element swept along ONE reference direction (extruded meshes)?
-        int *d_cnt = nullptr, cnt[4] = {0, 0, 0, 1};
-        HIPCHK(hipMalloc((void **)&out->geo_swept, sizeof(double) * GEO_NSWEPT * (size_t)a.nelem));
-        HIPCHK(hipMalloc((void **)&d_cnt, 4 * sizeof(int)));
-        HIPCHK(hipMemsetAsync(d_cnt, 0, 4 * sizeof(int), s));
-        HIPCHK(launch_geo_swept(out->geo, out->geo_swept, a.nelem, d_cnt, -1, s));     // count: every direction an element qualifies for
-        HIPCHK(hipMemcpyAsync(cnt, d_cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));      // set-up time only
-        (void)hipFree(d_cnt);
-        int axis = -1;
-        for (int d = 2; d >= 0; d--) if (cnt[d] == a.nelem) axis = d;      // a direction ALL elements share
-        if (axis < 0) { (void)hipFree(out->geo_swept); out->geo_swept = nullptr; }   // no common direction or general hexes: the general recompute
-        else { HIPCHK(launch_geo_swept(out->geo, out->geo_swept, a.nelem, nullptr, axis, s)); out->geo_axis = axis; }
-      }
-      for (int i = 0; i < x.basis->Q1d && i < MAXN1D; i++) { out->geo_qref[i] = x.basis->qref1d[i]; out->geo_qwt[i] = x.basis->qweight1d[i]; }
-    }
-    break;
-  }
+  case PLAN_FUSED_GRAD: CHK(apply_fused_grad(op, in, out, add, -1, &kname)); break;
+  case PLAN_SETUP_GEO: CHK(apply_setup_geo(op, in, out, &kname)); break;
   case PLAN_PROLONG:
-  case PLAN_RESTRICT: {
-    const bool pro = op->plan == PLAN_PROLONG;
-    CeedElemRestriction rc = pro ? op->in[0].rstr : op->out[0].rstr, rf = pro ? op->out[0].rstr : op->in[0].rstr;
-    CeedBasis b = pro ? op->in[0].basis : op->out[0].basis;
-    if (in == out) return ceed_error("in-place operator apply is not supported");
-    if (in->length < (pro ? rc : rf)->lsize || out->length < (pro ? rf : rc)->lsize) return ceed_error("transfer vector too short");
-    TransferArgs a{};
-    double *px, *py;
-    CHK(vec_dev(in, false, &px));
-    CHK(vec_dev(out, true, &py));
-    if (op->scale && op->scale->length < rf->lsize) return ceed_error("scale vector too short");
-    // OWNER form (kernels_misc.hip): the fine nodes each element owns, and the weights (null: all 1, the one-rank case)
-    CHK(transfer_owner_map(op, rf));
-    CHK(transfer_weights(op, rf, &a.w_f));
-    // the coarse side's flagged offsets: the input side of a prolongation, the output side of a restriction
-    const uint32_t *fc = pro ? op->d_off_flagged_in : op->d_off_flagged_out;
-    a.off_c = fc ? fc : rc->d_offsets;
-    a.own_f = op->d_own_f;
-    a.x = px; a.y = py; a.nelem = rc->nelem; a.add = add ? 1 : 0;
-    const int m_in = (op->mask_mode & 1) ? 1 : 0, m_out = (op->mask_mode & 2) ? 1 : 0;
-    a.mask_c = pro ? m_in : m_out; a.mask_f = pro ? m_out : m_in;
-    if (pro) {
-      // every fine node is stored by its owner: no E-vector, no sum
-      if (!add && !op->own_full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-    } else {
-      // deterministic scatter on the COARSE side (Pc^3 nodes per element): element results -> E-vector -> per-node sums in
-      // element order over the coarse restriction's transpose map (masked entries travel as zeros)
-      CHK(build_csr(rc, rc->csr, nullptr));
-      CHK(ceed_need_evec(op->ceed, (size_t)rc->nelem * rc->ncomp * rc->elemsize));
-      a.evec = op->ceed->evec;
-      if (!add && !rc->csr.full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-    }
-    TimerScope ts(op, s);
-    hipError_t e = launch_transfer(b->P1d, b->Q1d, pro, op->tables, a, s, &kname);
-    if (e == hipErrorInvalidValue && !*kname) return ceed_error("no transfer kernel for Pc=%d Pf=%d", b->P1d, b->Q1d);
-    HIPCHK(e);
-    if (!pro) HIPCHK(launch_assemble(rc->csr.d_rowptr, rc->csr.d_cols, rc->csr.d_node_off, nullptr, a.evec, py, rc->csr.nnodes, add ? 1 : 0, s));
-    op->launches++;
-    break;
-  }
-  case PLAN_ENERGY: {
-    OpField &u = op->in[0], &en = op->out[0];
-    if (!in || in->length < u.rstr->lsize || !out || out->length < en.rstr->lsize) return ceed_error("displacement / energy vector too short");
-    EnergyOpArgs a{};
-    double *pu, *py, *pq;
-    CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
-    a.off_u = u.rstr->d_offsets; a.u = pu; a.off_e = en.rstr->d_offsets; a.y = py; a.qdata = pq;
-    a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
-    const int kd = qf->kind;
-    a.diag = (kd == QF_DIAG_LINELAS || kd == QF_DIAG_HYPERSS || kd == QF_DIAG_HYPERFS) ? 1 : 0;
-    a.model = (kd == QF_ENERGY_LINELAS || kd == QF_DIAG_LINELAS) ? 0 : ((kd == QF_ENERGY_HYPERSS || kd == QF_DIAG_HYPERSS) ? 1 : 2);
-    CHK(read_phys(qf, &a.nu, &a.E));
-    memcpy(a.interp, u.basis->interp1d.data(), sizeof(double) * u.basis->interp1d.size());
-    memcpy(a.grad, u.basis->grad1d.data(), sizeof(double) * u.basis->grad1d.size());
-    if (!a.diag) memcpy(a.interp_e, en.basis->interp1d.data(), sizeof(double) * en.basis->interp1d.size());
-    if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-    hipError_t e = launch_energy_op(a, s);
-    if (e == hipErrorInvalidValue) return ceed_error("energy operator: Q=%d / P=%d outside the supported range", a.Q, a.P);
-    HIPCHK(e);
-    kname = a.diag ? (a.model == 0 ? "diagnostic_op<LinElasDiagnostic>" : (a.model == 1 ? "diagnostic_op<HyperSSDiagnostic>" : "diagnostic_op<HyperFSDiagnostic>"))
-                   : (a.model == 0 ? "energy_op<LinElasEnergy>" : (a.model == 1 ? "energy_op<HyperSSEnergy>" : "energy_op<HyperFSEnergy>"));
-    op->launches++;
-    break;
-  }
-  case PLAN_COORD: {
-    OpField &x = op->in[0], &o = op->out[0];
-    if (!in || in->length < x.rstr->lsize || !out || out->length < o.rstr->lsize) return ceed_error("coordinate / output vector too short");
-    CoordOpArgs a{};
-    double *px, *py, *pq = nullptr;
-    CHK(vec_dev(in, false, &px)); CHK(vec_dev(out, true, &py));
-    a.off_x = x.rstr->d_offsets; a.xcoord = px; a.off_u = o.rstr->d_offsets; a.y = py;
-    a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
-    a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
-    if (a.mode != 2) {
-      CHK(vec_dev(op->in[1].vec, false, &pq)); a.qdata = pq;
-      a.Pout = o.basis->P1d;
-      memcpy(a.bu, o.basis->interp1d.data(), sizeof(double) * o.basis->interp1d.size());
-      if (!qf->ctx) return ceed_error("QFunction '%s' needs its context", qf->name.c_str());
-      const double *cx = (const double *)qf->ctx;   // pointer pass-through: forcing vector (3) or Physics {nu, E} (setuplibceed.c:563-566)
-      for (int i = 0; i < (a.mode == 0 ? 3 : 2); i++) a.ctx[i] = cx[i];
-    } else {
-      a.Pout = a.Q;
-    }
-    memcpy(a.bx, x.basis->interp1d.data(), sizeof(double) * x.basis->interp1d.size());
-    if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-    hipError_t e = launch_coord_op(a, s);
-    if (e == hipErrorInvalidValue) return ceed_error("coordinate operator: Q=%d / P=%d outside the supported range", a.Q, a.Pout);
-    HIPCHK(e);
-    kname = a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>");
-    op->launches++;
-    break;
-  }
+  case PLAN_RESTRICT: CHK(apply_transfer(op, in, out, add, &kname)); break;
+  case PLAN_ENERGY: CHK(apply_energy(op, in, out, add, &kname)); break;
+  case PLAN_COORD: CHK(apply_coord(op, in, out, add, &kname)); break;
   default: return ceed_error("operator has no plan");
   }
   op->kernel_name = kname;

@@ -205,16 +205,16 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   PipeMap *Gp = new PipeMap;
   PipeMap &G = *Gp;
   G.E = E; G.req_seg = req_seg_in; G.waves = waves; G.mb = mb; G.base = (const void *)&M;
-  if (opt.pipe_debug) fprintf(stderr, "get_pipe: %d elements, E %d, %d segments asked, %d waves -> %d\n", r->nelem, E, req_seg_in, waves, nseg);
   if (nseg < 2) { G.nseg = 1; G.built = true; r->pipes.push_back(Gp); *out = Gp; return 0; }
   // Boundaries are laid out FROM THE END in whole rounds of the waves: the last segment (whose rows are summed with nothing
   // to hide behind) is `last_rounds` rounds, the others share the rest equally in whole rounds, and the odd remainder of the
-  // mesh lands in the FIRST segment, where the next fused kernel fills the chip behind its ragged last round.
+  // mesh lands in the FIRST segment, where the next fused kernel fills the chip behind its ragged last round.  (Four rounds:
+  // the pipe sweeps of rounds 3-4.)
   G.elem_bound.assign(1, 0);
-  const int last_rounds = opt.pipe_last_rounds;
+  constexpr int last_rounds = 4;
   const long total_rounds = ngroups / std::max(waves, 1);
   std::vector<long> gb;        // group boundaries, descending
-  if (min_rounds > 0 && last_rounds > 0 && total_rounds >= last_rounds + (long)(nseg - 1) * min_rounds) {
+  if (min_rounds > 0 && total_rounds >= last_rounds + (long)(nseg - 1) * min_rounds) {
     long g = (long)ngroups - (long)last_rounds * waves;
     gb.push_back(g);
     const long per = (total_rounds - last_rounds) / (nseg - 1);       // rounds of the middle segments
@@ -255,10 +255,6 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
     no2[j] = G.h_node_off[j] = M.h_node_off[i];
   }
   G.nrows = nn;
-  if (opt.pipe_debug)
-    for (int k = 0; k < nseg; k++)
-      fprintf(stderr, "  segment %d: elements %d..%d (%.2f rounds), rows %d..%d\n", k, G.elem_bound[k], G.elem_bound[k + 1],
-              (double)(G.elem_bound[k + 1] - G.elem_bound[k]) / E / waves, G.row_bound[k], G.row_bound[k + 1]);
   auto up = [](uint32_t **dst, const std::vector<uint32_t> &v) -> int {
     HIPCHK(hipMalloc((void **)dst, sizeof(uint32_t) * (v.size() ? v.size() : 1)));
     if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice));

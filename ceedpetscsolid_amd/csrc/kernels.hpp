@@ -234,8 +234,7 @@ struct HaloUnpackArgs { const uint32_t *dst, *ptr, *slot; const double *recv; in
 struct HaloPackFold { const uint32_t *ptr, *slot; double *send; };
 hipError_t launch_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off,
                            const unsigned char *flags, const double *evec, double *y, int nnodes,
-                           int add, hipStream_t s, int max_blocks = 0, const HaloUnpackArgs *unpack = nullptr,
-                           const HaloPackFold *pack = nullptr);   // max_blocks: cap on the grid (pipelined assembly)
+                           int add, hipStream_t s, const HaloUnpackArgs *unpack = nullptr, const HaloPackFold *pack = nullptr);
 
 // The same sum with an epilogue in place of the store of y (kernels_misc.hip, k_assemble_epi): the output of a fused apply consumed
 // where it is formed -- a Chebyshev step or the residual b - A v.
@@ -256,7 +255,7 @@ struct EpilogueArgs {
   const double *b;
 };
 hipError_t launch_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const unsigned char *flags,
-                               const double *evec, int nnodes, const EpilogueArgs &ep, hipStream_t s, int max_blocks = 0);
+                               const double *evec, int nnodes, const EpilogueArgs &ep, hipStream_t s);
 
 // Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.
 struct CoordOpArgs {
@@ -296,9 +295,7 @@ hipError_t launch_halo_unpack_add(const HaloUnpackArgs &u, double *y, hipStream_
 // Assembled coarse-level operator (kernels_csr.hip).
 hipError_t launch_csr_sum(const uint32_t *slotptr, const uint32_t *perm, const double *coo, double *vals, int nnz,
                           const uint32_t *unit_diag_slot, int n_unit, hipStream_t s);
-hipError_t launch_csr_spmv(const uint32_t *rowptr, const uint32_t *cols, const double *vals, const double *x, double *y,
-                           int nrows, hipStream_t s);
-// CSR-stream form: row_block[b] .. row_block[b + 1] are consecutive rows with at most 2048 entries in all (a longer row is a run of its
+// y = A x, CSR-stream form: row_block[b] .. row_block[b + 1] are consecutive rows with at most 2048 entries in all (a longer row is a run of its
 // own), at most 256 rows per run; cut by csr_row_blocks() on the host
 hipError_t launch_csr_spmv_stream(const uint32_t *row_block, int nblocks, const uint32_t *rowptr, const uint32_t *cols, const double *vals,
                                   const double *x, double *y, hipStream_t s);

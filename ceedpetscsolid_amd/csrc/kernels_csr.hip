@@ -17,18 +17,6 @@ __global__ void k_csr_sum(const uint32_t *slotptr, const uint32_t *perm, const d
 __global__ void k_csr_unit_diag(const uint32_t *diag_slot, double *vals, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) vals[diag_slot[i]] = 1.;
 }
-// one wave64 per row
-__global__ __launch_bounds__(256) void k_csr_spmv(const uint32_t *rowptr, const uint32_t *cols, const double *vals,
-                                                 const double *x, double *y, int nrows) {
-  const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-  for (int r = wave; r < nrows; r += nw) {
-    double a = 0.;
-    for (uint32_t k = rowptr[r] + lane; k < rowptr[r + 1]; k += 64) a += vals[k] * x[cols[k]];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-    if (lane == 0) y[r] = a;
-  }
-}
 // y = A x, "CSR-stream" form (round 5): a workgroup owns a run of CONSECUTIVE rows holding at most SPMV_CHUNK entries (row_block[b] ..
 // row_block[b + 1], cut on the host once per pattern).  Its entries are fetched in ONE coalesced sweep that does not wait for rowptr
 // (cols and vals of the run are contiguous), multiplied by the gathered x into LDS, and every row is then summed from LDS by T lanes (T a
@@ -218,12 +206,6 @@ hipError_t launch_csr_sum(const uint32_t *slotptr, const uint32_t *perm, const d
                           const uint32_t *unit_diag_slot, int n_unit, hipStream_t s) {
   if (nnz > 0) hipLaunchKernelGGL(k_csr_sum, grid_for((size_t)nnz, 256), dim3(256), 0, s, slotptr, perm, coo, vals, nnz);
   if (n_unit > 0) hipLaunchKernelGGL(k_csr_unit_diag, grid_for((size_t)n_unit, 256), dim3(256), 0, s, unit_diag_slot, vals, n_unit);
-  return hipGetLastError();
-}
-hipError_t launch_csr_spmv(const uint32_t *rowptr, const uint32_t *cols, const double *vals, const double *x, double *y,
-                           int nrows, hipStream_t s) {
-  if (nrows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_csr_spmv, grid_for((size_t)nrows, 4), dim3(256), 0, s, rowptr, cols, vals, x, y, nrows);
   return hipGetLastError();
 }
 hipError_t launch_csr_diag(const uint32_t *diag_slot_of_row, const double *vals, double *d, int nrows, hipStream_t s) {

@@ -805,13 +805,11 @@ __global__ void k_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, con
   }
 }
 hipError_t launch_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const unsigned char *flags,
-                               const double *evec, int nnodes, const EpilogueArgs &ep, hipStream_t s, int max_blocks) {
+                               const double *evec, int nnodes, const EpilogueArgs &ep, hipStream_t s) {
   if (nnodes <= 0 && ep.n_int <= 0) return hipSuccess;
   constexpr int AB = 256;
-  unsigned nb_rows = (unsigned)((std::max(nnodes, 0) + AB - 1) / AB);
-  if (max_blocks > 0 && nb_rows > (unsigned)max_blocks) nb_rows = (unsigned)max_blocks;
-  unsigned nb_int = (unsigned)std::min<size_t>(((size_t)std::max(ep.n_int, 0) * 3 + AB - 1) / AB, 4096);
-  if (max_blocks > 0 && nb_int > (unsigned)max_blocks) nb_int = (unsigned)max_blocks;
+  const unsigned nb_rows = (unsigned)((std::max(nnodes, 0) + AB - 1) / AB);
+  const unsigned nb_int = (unsigned)std::min<size_t>(((size_t)std::max(ep.n_int, 0) * 3 + AB - 1) / AB, 4096);
   hipLaunchKernelGGL(k_assemble_epi, dim3(nb_rows + nb_int), dim3(AB), 0, s, rowptr, cols, node_off, flags, evec, nnodes, (int)nb_rows, ep);
   return hipGetLastError();
 }
@@ -934,15 +932,14 @@ hipError_t launch_multiplicity(const uint32_t *off, int nelem, int elemsize, int
 }
 hipError_t launch_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off,
                            const unsigned char *flags, const double *evec, double *y, int nnodes,
-                           int add, hipStream_t s, int max_blocks, const HaloUnpackArgs *unpack, const HaloPackFold *pack) {
+                           int add, hipStream_t s, const HaloUnpackArgs *unpack, const HaloPackFold *pack) {
   const int nun = unpack ? unpack->n : 0;
   if (nnodes <= 0 && nun <= 0) return hipSuccess;
 #ifndef CPS_ASM_BLOCK
 #define CPS_ASM_BLOCK 256    // (tuning hook) threads per workgroup of k_assemble: 128 and 512 measured in round 4, nothing
 #endif
   constexpr int AB = CPS_ASM_BLOCK;
-  unsigned nb_rows = (unsigned)((std::max(nnodes, 0) + AB - 1) / AB);
-  if (max_blocks > 0 && nb_rows > (unsigned)max_blocks) nb_rows = (unsigned)max_blocks;     // (grid-stride loop over the rows)
+  const unsigned nb_rows = (unsigned)((std::max(nnodes, 0) + AB - 1) / AB);
   const unsigned nb_un = (unsigned)std::min((nun + AB - 1) / AB, 1024);
   hipLaunchKernelGGL(k_assemble, dim3(nb_rows + nb_un), dim3(AB), 0, s, rowptr, cols, node_off, flags, evec, y, nnodes, add,
                      (int)nb_rows, unpack ? *unpack : HaloUnpackArgs{nullptr, nullptr, nullptr, nullptr, 0},

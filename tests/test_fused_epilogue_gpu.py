@@ -1,34 +1,20 @@
 """The Jacobian apply fused with its consumer (CeedXOperatorApplyChebyshev / CeedXOperatorApplyResidual, round 5): the Chebyshev
 step of the smoother (elasticity.c:539-552) and the residual of the V-cycle (:588-590) formed in the epilogue of the apply's
 restriction transpose instead of a pass of their own.  The fused forms must give the SAME BITS as CeedOperatorApply followed by
-CeedXVectorChebyshevUpdate / ChebyshevStart / WAXPBY -- serial and pipelined assembly, every level of a ladder (P < Q kernels,
-P = 2 without element-interior nodes), in-place input (the recurrence applies the operator to its own direction d), recorded
-into a hipGraph -- and match the oracle's restatement at the parity bar."""
+CeedXVectorChebyshevUpdate / ChebyshevStart / WAXPBY -- every level of a ladder (P < Q kernels, P = 2 without element-interior
+nodes), in-place input (the recurrence applies the operator to its own direction d), recorded into a hipGraph -- and match the
+oracle's restatement at the parity bar.  The fused forms always sum the rows serially (ceed_operator.cpp, apply_fused_epilogue)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-from ceedpetscsolid_amd import ceed as cd
+from _ceed_env import ceed_with_env
 from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh
 from ceedpetscsolid_amd.solid import SolidProblem
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def _ceed_with_env(product_lib, env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return cd.Ceed(product_lib, "/gpu/hip/mi355x")      # the switches are read at CeedInit
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _vectors(c, n, arrs):
@@ -79,12 +65,11 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("form", ["serial", "pipelined"])
+@pytest.mark.parametrize("form", ["serial"])
 @pytest.mark.parametrize("name,mk,degree,problem,bc", CASES, ids=[c[0] for c in CASES])
 def test_fused_chebyshev_step_and_residual_equal_the_two_steps_bitwise(product_lib, oracle, form, name, mk, degree, problem, bc):
     mesh = mk()
-    env = {"CEED_MI355X_ASSEMBLE": "serial"} if form == "serial" else {"CEED_MI355X_PIPE_MIN_ROUNDS": "0", "CEED_MI355X_PIPE_SEGMENTS": "3", "CEED_MI355X_EPI_PIPELINED": "1"}
-    gpu = _ceed_with_env(product_lib, env)
+    gpu = ceed_with_env(product_lib, {"CEED_MI355X_ASSEMBLE": form})
     p = SolidProblem(gpu, mesh, degree, problem, nu=0.3, E=1.0, bc_sides=bc)
     po = SolidProblem(oracle, mesh, degree, problem, nu=0.3, E=1.0, bc_sides=bc)
     n = p.lsize()
@@ -103,7 +88,7 @@ def test_fused_chebyshev_step_and_residual_equal_the_two_steps_bitwise(product_l
             for k in ("x", "d", "r"):
                 assert np.array_equal(oa[k], ob[k]) and rel_err(b[k], ob[k]) < 1e-10, (lv, first, k)
         info = p.levels[lv].opJacob.launch_info()
-        assert info["segments"] == (1 if form == "serial" else 3), info
+        assert info["segments"] == 1, info
         # residual w = b - A x
         c, L, op = p.ceed, p.ceed.L, p.levels[lv].opJacob
         nl = p.lsize(lv)
@@ -117,9 +102,9 @@ def test_fused_chebyshev_step_and_residual_equal_the_two_steps_bitwise(product_l
 
 
 def test_fused_chebyshev_sweep_recorded_and_replayed(product_lib):
-    """Three fused steps recorded into a hipGraph (pipelined form: fork and join inside the capture) and replayed on new data
-    against the eager two-step form."""
-    gpu = _ceed_with_env(product_lib, {"CEED_MI355X_PIPE_MIN_ROUNDS": "0", "CEED_MI355X_PIPE_SEGMENTS": "2", "CEED_MI355X_EPI_PIPELINED": "1"})
+    """Three fused steps recorded into a hipGraph (the serial form that ships) and replayed on new data against the eager two-step
+    form, whose plain applies are pipelined in two segments (fork and join of the second stream)."""
+    gpu = ceed_with_env(product_lib, {"CEED_MI355X_PIPE_MIN_ROUNDS": "0", "CEED_MI355X_PIPE_SEGMENTS": "2"})
     mesh = hollow_cylinder_mesh(4, 16, 8)
     p = SolidProblem(gpu, mesh, 4, "hyperFS", nu=0.3, E=1.0, bc_sides=[998], multigrid="none")
     n = p.lsize()

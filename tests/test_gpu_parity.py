@@ -11,6 +11,7 @@ import pytest
 from ceedpetscsolid_amd import ceed as cd
 from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh, load_mesh_npz
 from ceedpetscsolid_amd.solid import SolidProblem, smooth_displacement
+from _ceed_env import ceed_with_env
 from conftest import GOLDEN, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -436,11 +437,7 @@ def test_one_call_apply_with_halo_equals_its_parts_bitwise(product_lib, workload
     # every form of the one call: whole apply then exchange (0, default), split-phase on one stream (1), on two (2); the
     # RCCL group in order on the producing stream (default) or on the communicator's own stream
     for mode, inline in ((0, 1), (2, 1), (1, 1), (2, 0), (1, 0), (0, 0)):
-        os.environ["CEED_MI355X_COMM_INLINE"] = str(inline)
-        try:
-            ceed = _ceed_with_env(product_lib, "CEED_MI355X_OVL_MODE", str(mode))
-        finally:
-            os.environ.pop("CEED_MI355X_COMM_INLINE", None)
+        ceed = ceed_with_env(product_lib, {"CEED_MI355X_OVL_MODE": str(mode), "CEED_MI355X_COMM_INLINE": str(inline)})
         got = _one_call_routes(ceed, mesh, vw, lead, degree, bc, record=(True if inline else "refused") if mode in (0, 2) else False)
         if want is None:
             want = got
@@ -507,7 +504,7 @@ def test_split_phase_exchange_refuses_a_halo_outside_the_priority_rows(product_l
     from ceedpetscsolid_amd.halo import HaloExchange, RcclHalo, interface_elements, part_cylinder, virtual_world
     from ceedpetscsolid_amd.harness import SolidApp
     from ceedpetscsolid_amd.mesh import reorder_elements_first
-    ceed = _ceed_with_env(product_lib, "CEED_MI355X_OVL_MODE", "1")
+    ceed = ceed_with_env(product_lib, {"CEED_MI355X_OVL_MODE": "1"})
     part = lambda r: part_cylinder(r, 4, 3, 12, 8)
     mesh = part(1)
     vw = virtual_world(1, 4, mesh, part, 2)
@@ -736,12 +733,8 @@ def test_pipelined_assembly_equals_serial_assembly_bitwise(product_lib, mk, degr
     -3 ... +5 % and left the tree in round 3.)"""
     mesh = mk()
     # three segments whatever the mesh size (the default asks for four rounds of the waves per segment)
-    os.environ["CEED_MI355X_PIPE_MIN_ROUNDS"], os.environ["CEED_MI355X_PIPE_SEGMENTS"] = "0", "3"
-    try:
-        gated = _ceed_with_env(product_lib, "CEED_MI355X_ASSEMBLE", mode)
-    finally:
-        os.environ.pop("CEED_MI355X_PIPE_MIN_ROUNDS", None); os.environ.pop("CEED_MI355X_PIPE_SEGMENTS", None)
-    serial = _ceed_with_env(product_lib, "CEED_MI355X_ASSEMBLE", "serial")
+    gated = ceed_with_env(product_lib, {"CEED_MI355X_PIPE_MIN_ROUNDS": "0", "CEED_MI355X_PIPE_SEGMENTS": "3", "CEED_MI355X_ASSEMBLE": mode})
+    serial = ceed_with_env(product_lib, {"CEED_MI355X_ASSEMBLE": "serial"})
     probs = [SolidProblem(c, mesh, degree, problem, nu=0.3, E=1.0, bc_sides=[sorted(mesh.side_sets)[0]], multigrid="none") for c in (gated, serial)]
     n = probs[0].lsize()
     rng = np.random.default_rng(11)
@@ -809,7 +802,7 @@ def test_full_size_properties_config5_whole_box(product_lib):
     size-independent properties of the tangent (symmetry, linearity, rigid-translation null space)."""
     mesh = box_mesh(64, 64, 64)
     pipe = cd.Ceed(product_lib, "/gpu/hip/mi355x")
-    serial = _ceed_with_env(product_lib, "CEED_MI355X_ASSEMBLE", "serial")
+    serial = ceed_with_env(product_lib, {"CEED_MI355X_ASSEMBLE": "serial"})
     probs = [SolidProblem(c, mesh, 6, "hyperFS", nu=0.3, E=1.0, multigrid="none") for c in (pipe, serial)]
     n = probs[0].lsize()
     assert n == 3 * 385 ** 3
@@ -833,12 +826,8 @@ def test_properties_unstructured_cylinder_all_levels_pipelined(product_lib):
     10.97 rounds of the waves: two segments with a non-trivial remainder in the first) against the serial form, BITWISE, plus the
     tangent's properties on every level."""
     mesh = load_mesh_npz(os.path.join(GOLDEN, "mesh_cylinder8_44928e_2ss_us.npz"))
-    os.environ["CEED_MI355X_PIPE_MIN_TOTAL"] = "0"
-    try:
-        pipe = cd.Ceed(product_lib, "/gpu/hip/mi355x")
-    finally:
-        os.environ.pop("CEED_MI355X_PIPE_MIN_TOTAL", None)
-    serial = _ceed_with_env(product_lib, "CEED_MI355X_ASSEMBLE", "serial")
+    pipe = ceed_with_env(product_lib, {"CEED_MI355X_PIPE_MIN_TOTAL": "0"})
+    serial = ceed_with_env(product_lib, {"CEED_MI355X_ASSEMBLE": "serial"})
     probs = [SolidProblem(c, mesh, 4, "hyperFS", nu=0.3, E=1.0) for c in (pipe, serial)]
     nl = len(probs[0].levels)
     assert [lv.degree for lv in probs[0].levels] == [1, 2, 4]
@@ -914,25 +903,13 @@ def test_apply_add_and_empty_vectors(gpu):
     assert e.to_numpy().size == 0
 
 
-def _ceed_with_env(product_lib, key, val):
-    old = os.environ.get(key)
-    os.environ[key] = val
-    try:
-        return cd.Ceed(product_lib, "/gpu/hip/mi355x")      # the switches are read at CeedInit
-    finally:
-        if old is None:
-            os.environ.pop(key, None)
-        else:
-            os.environ[key] = old
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("problem", ["linElas", "hyperSS", "hyperFS"])
 def test_recomputed_geometry_equals_stored_qdata(gpu, product_lib, problem):
     """The pencil kernel recomputes SetupGeo's factors (common.h:47-101) per point from the element's trilinear map
     when the qdata vector still is what the SetupGeo operator wrote (FusedGradArgs::geo); CEED_MI355X_GEO=0 reads the
     stored 10 values per point instead.  Same numbers to rounding on distorted (non-affine) elements, every level."""
-    plain = _ceed_with_env(product_lib, "CEED_MI355X_GEO", "0")
+    plain = ceed_with_env(product_lib, {"CEED_MI355X_GEO": "0"})
     for mesh, degree in ((distorted_box(3, 2, 3, seed=2, amp=0.2), 4), (distorted_box(2, 2, 1, seed=3, amp=0.2), 6),
                          (distorted_box(5, 3, 1, seed=5, amp=0.2), 1), (hollow_cylinder_mesh(2, 8, 3), 3)):
         outs = []
@@ -962,7 +939,7 @@ def test_affine_elements_take_the_per_element_factors(gpu, oracle, product_lib, 
     (qfunctions/common.h:47-101 is the arithmetic either way).  Same results as the general per-point recompute
     (CEED_MI355X_AFFINE=0) and as the oracle on sheared, stretched boxes, every level; a mesh with ONE non-affine element
     takes the general path everywhere."""
-    general = _ceed_with_env(product_lib, "CEED_MI355X_AFFINE", "0")
+    general = ceed_with_env(product_lib, {"CEED_MI355X_AFFINE": "0"})
     shear = np.array([[1.0, 0.3, -0.2], [0.1, 0.7, 0.25], [-0.15, 0.2, 1.4]])
     def sheared(nx, ny, nz):
         m = box_mesh(nx, ny, nz)
@@ -1019,7 +996,7 @@ def test_swept_elements_take_the_two_by_two_jacobian(gpu, oracle, product_lib, p
     arithmetic either way).  Same results as the general per-point recompute (CEED_MI355X_SWEPT=0) and as the oracle for the
     sweep along each of the three reference directions, every level; a mesh with ONE element that is no prism takes the general
     path everywhere; the reference's own unstructured cylinder is recognised."""
-    general = _ceed_with_env(product_lib, "CEED_MI355X_SWEPT", "0")
+    general = ceed_with_env(product_lib, {"CEED_MI355X_SWEPT": "0"})
     base = hollow_cylinder_mesh(2, 8, 3)
     mixed = hollow_cylinder_mesh(2, 6, 2)
     mixed.coords = mixed.coords.copy()
@@ -1059,7 +1036,7 @@ def test_derived_state_of_the_finite_strain_tangent(gpu, oracle, product_lib):
     series at every point of every apply (qfunctions_device.hpp; hyperFS.h:286-464 is the map).  Same numbers as the plain
     form (CEED_MI355X_DERIVED=0) and as the oracle, every level, nu up to 0.49; and the derived state is DROPPED when the
     application writes grad u itself: the Jacobian must then follow the new values."""
-    plain = _ceed_with_env(product_lib, "CEED_MI355X_DERIVED", "0")
+    plain = ceed_with_env(product_lib, {"CEED_MI355X_DERIVED": "0"})
     for mesh, degree, nu, amp in ((distorted_box(3, 2, 3, seed=2, amp=0.2), 5, 0.3, 0.1), (distorted_box(2, 2, 1, seed=3, amp=0.2), 6, 0.49, 0.05),
                                   (hollow_cylinder_mesh(2, 6, 2), 7, 0.3, 0.2), (hollow_cylinder_mesh(2, 8, 3), 4, 0.3, 0.3)):
         outs, probs = [], []
@@ -1116,15 +1093,7 @@ def test_direct_interior_stores_equal_the_assembled_path(gpu, product_lib):
     """Element-interior nodes have one contributor: the pencil kernel stores them straight into y and keeps a shell-only
     E-vector (FusedGradArgs::direct).  CEED_MI355X_DIRECT=0 sends every node through the E-vector; the two must give
     the SAME numbers (a single-term sum is exact), with Dirichlet rows, on every level, split-phase included."""
-    old = os.environ.get("CEED_MI355X_DIRECT")
-    os.environ["CEED_MI355X_DIRECT"] = "0"
-    try:
-        plain = cd.Ceed(product_lib, "/gpu/hip/mi355x")      # read at CeedInit
-    finally:
-        if old is None:
-            os.environ.pop("CEED_MI355X_DIRECT", None)
-        else:
-            os.environ["CEED_MI355X_DIRECT"] = old
+    plain = ceed_with_env(product_lib, {"CEED_MI355X_DIRECT": "0"})
     for mesh, degree in ((distorted_box(3, 2, 3, seed=2), 4), (distorted_box(2, 2, 1, seed=3), 6), (distorted_box(5, 1, 1), 2),
                          (hollow_cylinder_mesh(3, 8, 5), 4), (distorted_box(7, 3, 1, seed=5), 3)):
         outs = []
