@@ -403,12 +403,14 @@ extern "C" int CeedVectorDestroy(CeedVector *vec) {
 // ---------------------------------------------------------------------------
 // Vector helpers standing in for the PETSc Vec calls of src/matops.c on device data.
 extern "C" int CeedXVectorPointwiseMult(CeedVector w, CeedVector x, CeedVector y) {
+  if (x->length < w->length || y->length < w->length) return ceed_error("CeedXVectorPointwiseMult: operand shorter than the output");
   double *pw, *px, *py;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, false, &py)); CHK(vec_dev(w, true, &pw));
   HIPCHK(launch_pointwise_mult(pw, px, py, (size_t)w->length, w->ceed->stream));
   return 0;
 }
 extern "C" int CeedXVectorAXPBY(CeedVector y, double a, CeedVector x, double b) {
+  if (x->length < y->length) return ceed_error("CeedXVectorAXPBY: x shorter than y");
   double *px, *py;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, true, &py));
   HIPCHK(launch_axpby(py, a, px, b, (size_t)y->length, y->ceed->stream));
@@ -465,6 +467,8 @@ extern "C" int CeedXVectorWAXPBY(CeedVector w, double a, CeedVector x, double b,
   return 0;
 }
 extern "C" int CeedXVectorDot(CeedVector x, CeedVector y, CeedVector weight, double *result) {
+  if (y->length < x->length || (weight && weight != CEED_VECTOR_NONE && weight->length < x->length))
+    return ceed_error("CeedXVectorDot: operand shorter than x");
   double *px, *py, *pw = nullptr, *dres;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, false, &py));
   if (weight && weight != CEED_VECTOR_NONE) CHK(vec_dev(weight, false, &pw));
@@ -484,6 +488,7 @@ extern "C" int CeedXVectorDot(CeedVector x, CeedVector y, CeedVector weight, dou
 extern "C" int CeedXVectorDotTo(CeedVector x, CeedVector y, CeedVector weight, CeedVector scalars, CeedInt idx) {
   if (idx < 0 || idx >= scalars->length) return ceed_error("CeedXVectorDotTo: scalar %d of %d", idx, scalars->length);
   if (y->length != x->length) return ceed_error("CeedXVectorDotTo: vector lengths differ");
+  if (weight && weight != CEED_VECTOR_NONE && weight->length < x->length) return ceed_error("CeedXVectorDotTo: weight shorter than x");
   double *px, *py, *pw = nullptr, *ps;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, false, &py)); CHK(vec_dev(scalars, true, &ps));
   if (weight && weight != CEED_VECTOR_NONE) CHK(vec_dev(weight, false, &pw));

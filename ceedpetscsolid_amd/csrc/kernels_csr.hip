@@ -23,6 +23,7 @@ __global__ void k_csr_unit_diag(const uint32_t *diag_slot, double *vals, int n) 
 // power of two, the partial sums joined by a butterfly): two dependent memory trips (cols -> x) with up to 24 KB in flight per workgroup,
 // instead of three (rowptr -> cols, vals -> x) with 1.3 KB per wave in the wave-per-row form -- the p = 1 level of config 4 (330 k rows of
 // 81) ran at 2.7 TB/s that way.  A row longer than the chunk is a run of its own, summed by the whole workgroup.  Fixed summation order.
+// A run without entries (k0 == nnz when it is trailing: nothing at cols[k0]) stores zeros and loads nothing from cols, vals or x.
 constexpr int SPMV_CHUNK = 2048, SPMV_BLOCK = 256;
 __global__ __launch_bounds__(SPMV_BLOCK) void k_csr_spmv_stream(const uint32_t *row_block, const uint32_t *rowptr, const uint32_t *cols,
                                                                const double *vals, const double *x, double *y) {
@@ -31,6 +32,10 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_csr_spmv_stream(const uint32_t *
   const uint32_t r0 = row_block[blockIdx.x], r1 = row_block[blockIdx.x + 1];
   const uint32_t k0 = rowptr[r0], k1 = rowptr[r1], n = k1 - k0;
   const int nrows = (int)(r1 - r0);
+  if (n == 0) {                                 // (the same for the whole workgroup; a run holds at most SPMV_BLOCK rows)
+    if (tid < nrows) y[r0 + tid] = 0.;
+    return;
+  }
   if (n > (uint32_t)SPMV_CHUNK) {               // one long row: strided partial sums, then a fixed tree over the workgroup
     double a = 0.;
     for (uint32_t k = k0 + tid; k < k1; k += SPMV_BLOCK) a += vals[k] * x[cols[k]];

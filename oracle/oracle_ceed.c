@@ -1092,11 +1092,13 @@ int CeedXOperatorSetFineScale(CeedOperator op, CeedVector scale) {
   return 0;
 }
 int CeedXVectorPointwiseMult(CeedVector w, CeedVector x, CeedVector y) {
+  if (x->length < w->length || y->length < w->length) return oracle_error("CeedXVectorPointwiseMult: operand shorter than the output");
   vec_ensure(w); vec_ensure(x); vec_ensure(y);
   for (CeedInt i = 0; i < w->length; i++) w->array[i] = x->array[i] * y->array[i];
   return 0;
 }
 int CeedXVectorAXPBY(CeedVector y, double a, CeedVector x, double b) {
+  if (x->length < y->length) return oracle_error("CeedXVectorAXPBY: x shorter than y");
   vec_ensure(x); vec_ensure(y);
   for (CeedInt i = 0; i < y->length; i++) y->array[i] = a * x->array[i] + (b == 0. ? 0. : b * y->array[i]);
   return 0;
@@ -1169,6 +1171,8 @@ int CeedXOperatorApplyResidual(CeedOperator op, CeedVector in, CeedVector t, Cee
   return CeedXVectorWAXPBY(w, 1.0, b, -1.0, t);
 }
 int CeedXVectorDot(CeedVector x, CeedVector y, CeedVector weight, double *result) {
+  if (y->length < x->length || (weight && weight != CEED_VECTOR_NONE && weight->length < x->length))
+    return oracle_error("CeedXVectorDot: operand shorter than x");
   vec_ensure(x); vec_ensure(y);
   double s = 0.;
   if (weight && weight != CEED_VECTOR_NONE) {
@@ -1183,6 +1187,7 @@ int CeedXVectorDot(CeedVector x, CeedVector y, CeedVector weight, double *result
 int CeedXVectorDotTo(CeedVector x, CeedVector y, CeedVector weight, CeedVector scalars, CeedInt idx) {
   vec_ensure(scalars);
   if (idx < 0 || idx >= scalars->length) return oracle_error("CeedXVectorDotTo: index out of range");
+  if (y->length != x->length) return oracle_error("CeedXVectorDotTo: vector lengths differ");
   return CeedXVectorDot(x, y, weight, &scalars->array[idx]);
 }
 int CeedXScalarDivide(CeedVector scalars, CeedInt dst, CeedInt num, CeedInt den, double scale) {

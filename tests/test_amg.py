@@ -87,7 +87,7 @@ def test_products_follow_the_variable_operand_on_oracle(oracle):
     products_follow_the_variable_operand(oracle, 1e-13)
 
 
-@pytest.mark.parametrize("n", [1, 31, 32, 70])
+@pytest.mark.parametrize("n", [1, 31, 32, 64, 65, 70, 1500])
 def test_dense_inverse_on_oracle(oracle, n):
     dense_inverse(oracle, n, 1e-11)
 
@@ -212,7 +212,7 @@ def test_products_follow_the_variable_operand_on_device(gpu):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [1, 31, 32, 33, 70, 1080])
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 64, 65, 70, 1080, 1500])
 def test_dense_inverse_on_device(gpu, n):
     dense_inverse(gpu, n, 1e-10)
 
