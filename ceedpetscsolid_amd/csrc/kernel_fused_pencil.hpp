@@ -38,11 +38,9 @@ template <int P, int Q> struct PencilGeom {
   static constexpr int SJ = Q, SK = Q * Q, SC = Q3;                         // strides in doubles
   static constexpr int ARR = 3 * SC;                                        // one 3-component array
   static constexpr int PAD = Q == 5 ? 5 : 1;                                // tools/pencil_layout_search.py
-#ifdef CPS_TIMING_ALIAS_BZ   // TIMING-ONLY build (WRONG results): BZ aliased onto BX, a 6 Q^3 slab -- the upper bound of what holding the
-  static constexpr int SE = 2 * ARR + PAD;   // k-direction in registers could buy in occupancy at Q = 7 (profiles/r05_ab_experiments.txt item 1)
-#else
-  static constexpr int SE = 3 * ARR + PAD;                                  // element slab: A, BX, BZ
-#endif
+  static constexpr int SE = 3 * ARR + PAD;                                  // element slab: A, BX, BZ (a 6 Q^3 slab, the upper bound of
+                                                                            // holding the k-direction in registers, bought nothing at
+                                                                            // Q = 7: profiles/r05_ab_experiments.txt item 1)
   static constexpr int RQ = (E * Q3 + 63) / 64;                             // point rounds per group
   static constexpr int RN = (E * P3 + 63) / 64;                             // node rounds per group
   static constexpr int GEO = E * GEO_NCOEF + 2 * Q;                           // element map coefficients + 1-D points / weights
@@ -68,22 +66,9 @@ typedef volatile __attribute__((address_space(3))) char *ldsb_t;
 // (profiles/r03_ab_experiments.txt item 13): config 4 -2.6 %, 13 200 hexes -8 %, config 5's block -3.6 %, p = 2 -6.5 %; a
 // level for the requests / gather / final stores of their own, and for the loads and stores inside a q-point round: no
 // further gain; the staggered start of round 2 (-1.9 % then) adds nothing beside it and left the kernel.
-// (the levels are tuning hooks for variant builds, tools/mkvariant.sh; -1: never set)
-#ifndef CPS_PRIO_TOP
-#define CPS_PRIO_TOP -1    // requests for the next group, gather, final stores: stay at the passes' level
-#endif
-#ifndef CPS_PRIO_PASS
-#define CPS_PRIO_PASS 3    // the twelve pencil passes
-#endif
-#ifndef CPS_PRIO_PASS_B
-#define CPS_PRIO_PASS_B CPS_PRIO_PASS   // the transposed passes after the q-point rounds
-#endif
-#ifndef CPS_PRIO_PHYS
-#define CPS_PRIO_PHYS 0    // the q-point rounds
-#endif
-template <int LEVEL> CPS_DEV void set_prio() {
-  if constexpr (LEVEL >= 0) __builtin_amdgcn_s_setprio(LEVEL);
-}
+constexpr int PRIO_PASS = 3;   // the twelve pencil passes, forward and transposed alike (item 15d of that file); the requests for the next
+                               // group, the gather and the final stores stay at it
+constexpr int PRIO_PHYS = 0;   // the q-point rounds
 // (diagnostic build only, tools/phase_timing.py) -DCPS_PHASE_TIMING=<k>: every wave writes the shader-clock time stamps of the
 // phase boundaries of its k-th group to the buffer whose address the environment gives (CEED_MI355X_PHASE_BUF), 32 per wave.
 #ifdef CPS_PHASE_TIMING
@@ -196,22 +181,21 @@ CPS_DEV bool pencil_ok(int lane, int r, int ntask) { return ntask == 0 ? lane < 
 // per group of two elements 2 021 -> 1 896 at Q = 5).  Validity keeps the form of pencil_ok: the pass is handed a VIRTUAL lane
 // (negative for the lanes of a real block, huge for idle ones) and ntask = 0, so that `vlane + 64 r < 0` holds exactly for the
 // rounds in which the lane's block exists.
-// Only the STORES of a blocked pass are predicated: an idle lane holds the address of its block's last pencil (identical addresses
-// broadcast: no bank conflict) and loads and multiplies like its neighbours -- predicated loads would keep every round's registers
-// live across the others' (256 VGPRs and scratch when tried).  Hence ntask = 0 means: every block exists (3 E blk = 64 rounds exactly).
-#ifndef CPS_PENCIL_BLOCKED
-#define CPS_PENCIL_BLOCKED 1
-#endif
+// A blocked pass is ONE exec region with the idle lanes off (pencil_pass), every round unconditional inside it: ntask = 0 means
+// that every block exists (3 E blk = 64 rounds exactly).  Measured (profiles/r04_ab_experiments.txt item 3): -0.6 % (config 4) to
+// -1.3 % (13 200 hexes) against flat, 198 -> 184 VGPRs.  The idle lanes loading and multiplying too, only their stores masked:
+// +2.7 % (28 % more lane-FMAs under the power limit); per-round predicates on the loads: 256 VGPRs and scratch.
 constexpr int pencil_blk(int n, int E) {   // lanes per block, or 0: flat
-  if (!CPS_PENCIL_BLOCKED) return 0;
   const int flat = (3 * E * n + 63) / 64, b = n <= 32 ? 32 : (n <= 64 ? 64 : 0);
   return (b && b != n && (3 * E * b) % 64 == 0 && (3 * E * b) / 64 == flat) ? b : 0;
 }
-// loads and arithmetic of round r: real task, or any lane of a blocked pass
-#ifndef CPS_BLOCKED_IDLE_MATH
-#define CPS_BLOCKED_IDLE_MATH 0   // 1: the idle lanes of a blocked pass load and multiply too (only their stores are masked)
-#endif
-CPS_DEV bool pencil_ok_ld(int lane, int r, int ntask) { return (ntask == 0 && CPS_BLOCKED_IDLE_MATH) ? true : pencil_ok(lane, r, ntask); }
+// the guard of a round's loads and arithmetic: pencil_ok under a second name, the stores inside test pencil_ok itself.  The same
+// predicate, and it stays a function of its own: with the two written as one name the compiler inlines them in another order and
+// schedules every kernel at Q = 2 and Q = 6 differently (HISTORY.md, "compile-time hooks retired").  That rests on one compiler's
+// inlining order: before folding or moving it, and after a compiler update, compare the disassembly of every kernel of every object
+// with the previous build's (llvm-objdump -d --mcpu=gfx950 on the code objects tools/isa_guard.py extracts) -- isa_summary.txt alone
+// shows only five of the 124 kernels that change
+CPS_DEV bool pencil_ok_ld(int lane, int r, int ntask) { return pencil_ok(lane, r, ntask); }
 
 // One single-input pass: every task reads its pencil (NIN entries at stride SB bytes from array SRC),
 // applies the NOUT x NIN matrix and writes NOUT entries to array DST (DST == SRC: in place).  All
@@ -279,25 +263,18 @@ CPS_DEV void pencil_pass_impl(ktab_t table, const ldsp_t (&addr)[R], int lane, i
 template <int NIN, int NOUT, int LD, bool TR, int SB, int SRC, int DST, int SGN, bool EO, int R>
 CPS_DEV void pencil_pass(ktab_t table, const ldsp_t (&addr)[R], int lane, int ntask) {
   if (ntask == 0) {
-    if (CPS_BLOCKED_IDLE_MATH || lane < 0) pencil_pass_impl<NIN, NOUT, LD, TR, SB, SRC, DST, SGN, EO, R>(table, addr, CPS_BLOCKED_IDLE_MATH ? lane : 0, CPS_BLOCKED_IDLE_MATH ? 0 : 64 * R);
+    if (lane < 0) pencil_pass_impl<NIN, NOUT, LD, TR, SB, SRC, DST, SGN, EO, R>(table, addr, 0, 64 * R);
   } else pencil_pass_impl<NIN, NOUT, LD, TR, SB, SRC, DST, SGN, EO, R>(table, addr, lane, ntask);
 }
 
-#ifndef CPS_PENCIL_MINW
-#define CPS_PENCIL_MINW 2   // waves per SIMD the register allocation is held to (256 VGPRs)
-#endif
-#ifndef CPS_PENCIL_NSET
-#define CPS_PENCIL_NSET 2   // q-point register sets: 2 = every round's data is requested two rounds ahead
-#endif                      // (198 VGPRs with the hyperFS tangent; 1 set: 4-6 % slower; 3 sets: no gain)
-#ifndef CPS_PENCIL_MINW5
-#define CPS_PENCIL_MINW5 CPS_PENCIL_MINW   // (tuning hook for variant builds: Q = 5 only)
-#endif
-constexpr int pencil_minw(int Q) { return Q == 5 ? CPS_PENCIL_MINW5 : CPS_PENCIL_MINW; }
-#ifndef CPS_PENCIL_NSET_BIGQ
-#define CPS_PENCIL_NSET_BIGQ 2   // Q >= 6: two sets as well since round 4.  Rounds 1-3 had ONE (a second set pushed the hyperFS tangent past
-#endif                           // 256 VGPRs: 26 spilled); the blocked task -> lane mapping freed ~18 registers at Q = 7 and the second set
-                                 // fits (202-236 VGPRs at Q = 6, 7).  Same-box A/B (profiles/r04_ab_experiments.txt item 12): config 5's block
-                                 // -3.3 %, the whole 64^3 box -4.5 %, Q = 6 -2.3 %, hyperSS at Q = 7 -7.1 %
+constexpr int PENCIL_MINW = 2;   // waves per SIMD the register allocation is held to (256 VGPRs), at every Q (a Q = 5 value of its
+                                 // own: profiles/r05_ab_experiments.txt item 13)
+constexpr int PENCIL_NSET = 2;   // q-point register sets: 2 = every round's data is requested two rounds ahead
+                                 // (198 VGPRs with the hyperFS tangent; 1 set: 4-6 % slower; 3 sets: no gain; profiles/r04_ab_experiments.txt
+                                 // item 10).  Q >= 6: two sets as well since round 4.  Rounds 1-3 had ONE (a second set pushed the hyperFS
+                                 // tangent past 256 VGPRs: 26 spilled); the blocked task -> lane mapping freed ~18 registers at Q = 7 and the
+                                 // second set fits (202-236 VGPRs at Q = 6, 7).  Same-box A/B (profiles/r04_ab_experiments.txt item 12):
+                                 // config 5's block -3.3 %, the whole 64^3 box -4.5 %, Q = 6 -2.3 %, hyperSS at Q = 7 -7.1 %
 // GEO = 1: the geometric factors are recomputed per point from the element's trilinear map (FusedGradArgs::geo) instead of
 // read; GEO = 2: every element of the mesh is AFFINE (a parallelepiped: the box meshes of configs 1, 2 and 5), dXdx and
 // det J are constants of the element (FusedGradArgs::geo_aff, ten doubles) and only the weight varies from point to point;
@@ -309,7 +286,7 @@ constexpr int pencil_minw(int Q) { return Q == 5 ? CPS_PENCIL_MINW5 : CPS_PENCIL
 // which of the three arrays it reads first -- a relabelling of a sum's terms, no arithmetic;
 // GEO = 0: qdata is read.  The 1-D tables are applied in even-odd form wherever that form exists (pencil_even_odd(Q)).
 template <int P, int Q, int QF, int GEO>
-__global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const BasisTables tab_, const FusedGradArgs a) {
+__global__ __launch_bounds__(64, PENCIL_MINW) void k_fused_pencil(const BasisTables tab_, const FusedGradArgs a) {
   static_assert(offsetof(BasisTables, interp) == 0 && offsetof(BasisTables, colo) == 8 * MAXN1D * MAXN1D &&
                 offsetof(BasisTables, grad) == 16 * MAXN1D * MAXN1D, "kernarg layout of the tables");
   (void)tab_;  // first kernel argument: lives at offset 0 of the kernarg segment, read through kt below
@@ -324,11 +301,7 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
   constexpr int Q3 = G::Q3, P3 = G::P3, E = G::E, RQ = G::RQ, RN = G::RN;
   constexpr int SJ = G::SJ, SK = G::SK, SC = G::SC, SE = G::SE;
   constexpr int BI = 8, BJ = 8 * SJ, BK = 8 * SK, BC = 8 * SC;        // byte strides
-#ifdef CPS_TIMING_ALIAS_BZ
-  constexpr int oA = 0, oBX = 8 * G::ARR, oBZ = 8 * G::ARR;
-#else
   constexpr int oA = 0, oBX = 8 * G::ARR, oBZ = 16 * G::ARR;         // byte offsets of the arrays
-#endif
   constexpr bool ST_IN = QFTraits<QF>::state_in, ST_OUT = QFTraits<QF>::state_out;
   constexpr int NST = QFTraits<QF>::nstate;
   constexpr int QS = Q3;
@@ -373,10 +346,10 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
   // what the passes are handed as (lane, ntask): the real ones (flat) or (virtual lane, 0) (blocked)
   constexpr int N_IP = B_PP ? 0 : E * T_IP, N_JP = B_QP ? 0 : E * T_JP, N_QQ = B_QQ ? 0 : E * T_IQ;
   const int lPP = pencil_vlane(P * P, B_PP), lQP = pencil_vlane(Q * P, B_QP), lQQ = pencil_vlane(Q * Q, B_QQ);
-  // the k passes and the two-input j pass are written out below: a blocked one sits in ONE exec region (lQQ < 0), all its rounds unconditional
-  constexpr bool PIN_ALL = !B_QQ || CPS_BLOCKED_IDLE_MATH;
-  const int lQQi = PIN_ALL ? lQQ : 0;
-  constexpr int N_QQi = PIN_ALL ? N_QQ : 64 * R_K;
+  // the k passes and the two-input j pass are written out below: a blocked one sits in ONE exec region (lQQ < 0), all its rounds
+  // unconditional inside it (as in pencil_pass: lane 0 of 64 R_K tasks)
+  const int lQQi = B_QQ ? 0 : lQQ;
+  constexpr int N_QQi = B_QQ ? 64 * R_K : N_QQ;
   ldsp_t aIP[R_IP], aIQ[R_IQ], aJP[R_JP], aJQ[R_JQ], aK[R_K];
 #pragma unroll
   for (int r = 0; r < R_IP; r++) aIP[r] = pencil_addr(lane + 64 * r, P, P, BJ, BK, B_PP);
@@ -434,7 +407,7 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
   // live element instead.
   auto nlive_of = [&](int nelem, int g) { const int n = nelem - g * E; return n < E ? n : E; };  // uniform, >= 1
   // (Q >= 6 with qdata READ -- ten more doubles per point and set -- keeps one set: the residual kernel at Q = 6 spilled with two)
-  constexpr int NSET = RQ >= 2 ? (Q >= 6 ? (GEO == 0 ? 1 : CPS_PENCIL_NSET_BIGQ) : CPS_PENCIL_NSET) : 1;
+  constexpr int NSET = RQ >= 2 ? (GEO == 0 && Q >= 6 ? 1 : PENCIL_NSET) : 1;
   double qd[NSET][10], st[NSET][NST];
   auto load_point = [&](double *qdv, double *stv, int g, int r) {
     const kargs_t ka = kargs_fresh<KA>();  // one scalar load for the fields used here
@@ -524,13 +497,13 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
     }
 
     // ---- B: nodes -> points, in place -----------------------------------------------------------------
-    set_prio<CPS_PRIO_PASS>();
+    __builtin_amdgcn_s_setprio(PRIO_PASS);
     CPS_PH(1);
     pencil_pass<P, Q, P, false, BI, oA, oA, +1, EO>(tBf, aIP, lPP, N_IP);   // F1: along i at nodal (j, k)
     CPS_PH(2);
     pencil_pass<P, Q, P, false, BJ, oA, oA, +1, EO>(tBf, aJP, lQP, N_JP);   // F2: along j at (i', nodal k)
     CPS_PH(3);
-    if (PIN_ALL || lQQ < 0) {  // F3: along k at (i', j'): U -> A in place and dU/dz -> BZ (grad1d on the nodal values), one
+    if (!B_QQ || lQQ < 0) {  // F3: along k at (i', j'): U -> A in place and dU/dz -> BZ (grad1d on the nodal values), one
        // table at a time (both = 100 SGPRs = SGPR spills)
       double in[R_K][P];
 #pragma unroll
@@ -578,7 +551,7 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
     pencil_pass<Q, Q, Q, false, BJ, oA, oA, -1, EO>(tDf, aJQ, lQQ, N_QQ);   // F5: d/dy: A -> A in place
     CPS_PH(6);
 
-    set_prio<CPS_PRIO_PHYS>();
+    __builtin_amdgcn_s_setprio(PRIO_PHYS);
     if (geo) {
 #pragma unroll
       for (int i = 0; i < RG; i++)
@@ -701,11 +674,11 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
     }
 
     // ---- gradient^T --------------------------------------------------------------------------------------
-    set_prio<CPS_PRIO_PASS_B>();
+    __builtin_amdgcn_s_setprio(PRIO_PASS);
     CPS_PH(16);
     pencil_pass<Q, Q, Q, true, BI, oBX, oBX, -1, EO>(tDt, aIQ, lQQ, N_QQ);  // B1: W1 = Dx^T g0, BX in place
     CPS_PH(17);
-    if (PIN_ALL || lQQ < 0) {  // B2: W2 = W1 + Dy^T g1, A in place.  Two inputs per task: software-pipelined over the rounds
+    if (!B_QQ || lQQ < 0) {  // B2: W2 = W1 + Dy^T g1, A in place.  Two inputs per task: software-pipelined over the rounds
        // (two rounds of inputs live instead of all)
       if constexpr (table_splits<Q, Q, EO>() == 1) {
         const ktab_t tD = ktab_fresh(tDt);
@@ -737,7 +710,7 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
       }
     }
     CPS_PH(18);
-    if (PIN_ALL || lQQ < 0) {  // B3: along k: A[k<P] = B^T W2 + G^T g2, in two sweeps so that one coefficient table is live at a time
+    if (!B_QQ || lQQ < 0) {  // B3: along k: A[k<P] = B^T W2 + G^T g2, in two sweeps so that one coefficient table is live at a time
       double out[R_K][P];
       if constexpr (table_splits<P, Q, EO>() > 1) {  // large tables: all rounds live, the tables in row blocks
         double in[R_K][Q];
@@ -794,7 +767,6 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
     pencil_pass<Q, P, P, true, BI, oA, oA, +1, EO>(tBt, aIP, lPP, N_IP);    // B5: along i
     CPS_PH(21);
     // ---- final: node owners -> y (element-interior nodes) / shell E-vector (plain coalesced stores) ------------------
-    set_prio<CPS_PRIO_TOP>();
     {
       double v[RN][3];
 #pragma unroll
@@ -834,7 +806,7 @@ __global__ __launch_bounds__(64, pencil_minw(Q)) void k_fused_pencil(const Basis
 
 template <int P, int Q> constexpr int pencil_waves_per_cu() {
   constexpr int by_lds = (160 * 1024) / PencilGeom<P, Q>::LDS_BYTES;
-  return by_lds < 1 ? 1 : (by_lds > 4 * pencil_minw(Q) ? 4 * pencil_minw(Q) : by_lds);  // 8 waves per CU = 2 per SIMD at <= 256 VGPRs
+  return by_lds < 1 ? 1 : (by_lds > 4 * PENCIL_MINW ? 4 * PENCIL_MINW : by_lds);  // 8 waves per CU = 2 per SIMD at <= 256 VGPRs
 }
 
 // Launch shape.  Default: a PERSISTENT grid -- as many one-wave workgroups as the device holds at once (CUs x waves per
@@ -845,24 +817,17 @@ template <int P, int Q> constexpr int pencil_waves_per_cu() {
 template <int P, int Q, int QF>
 hipError_t launch_fused_pencil_t(const BasisTables &t, const FusedGradArgs &a_in, hipStream_t s) {
   using G = PencilGeom<P, Q>;
-#ifdef CPS_PHASE_TIMING   // (diagnostic build) the time-stamp buffer rides in the query pointer, which a real launch does not use
-  FusedGradArgs a = a_in;
-  const bool is_query = a_in.query_waves != nullptr;
-#else
-  const FusedGradArgs &a = a_in;
-  constexpr bool is_query_always = true;
-#endif
-  if (a.nelem <= 0 && !a.query_waves) return hipSuccess;
-  const int ngroups = (a.nelem + G::E - 1) / G::E;
+  if (a_in.nelem <= 0 && !a_in.query_waves) return hipSuccess;
+  const int ngroups = (a_in.nelem + G::E - 1) / G::E;
   const int ncu = device_cu_count();
   if (ncu <= 0) return hipErrorUnknown;
-  const int resident = ncu * (a.waves_per_cu > 0 ? a.waves_per_cu : pencil_waves_per_cu<P, Q>());
-#ifdef CPS_PHASE_TIMING
-  if (is_query) { *a.query_waves = resident; return hipSuccess; }
+  const int resident = ncu * (a_in.waves_per_cu > 0 ? a_in.waves_per_cu : pencil_waves_per_cu<P, Q>());
+  if (a_in.query_waves) { *a_in.query_waves = resident; return hipSuccess; }
+#ifdef CPS_PHASE_TIMING   // (diagnostic build) the time-stamp buffer rides in the query pointer, which a real launch does not use
+  FusedGradArgs a = a_in;
   if (const char *e = getenv("CEED_MI355X_PHASE_BUF")) a.query_waves = (int *)strtoull(e, nullptr, 0);
 #else
-  if (a.query_waves) { *a.query_waves = resident; return hipSuccess; }
-  (void)is_query_always;
+  const FusedGradArgs &a = a_in;
 #endif
   int grid = resident;
   if (a.wave_groups > 0) grid = ((ngroups + a.wave_groups - 1) / a.wave_groups + 7) / 8 * 8;

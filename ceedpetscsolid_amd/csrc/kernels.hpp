@@ -50,11 +50,9 @@ constexpr int OFF_FLAG_SHIFT = 29;
 // coefficients) no longer fits the 60 SGPRs a pass has for its table.
 constexpr bool pencil_even_odd(int Q) { return Q >= 4 && Q <= 7; }
 // The derived state of the finite-strain tangent (QF_HYPERFS_DF_DS) is used -- and written by the residual kernel -- from Q = 6 on:
-// measured -2.6 ... -3.1 % there, +-0 % at Q = 5 (profiles/r03_ab_experiments.txt item 3), for ten more doubles per point stored.
-#ifndef CPS_DERIVED_MIN_Q
-#define CPS_DERIVED_MIN_Q 6   // (tuning hook; the whole library must be built with the same value)
-#endif
-constexpr bool pencil_derived_state(int Q) { return Q >= CPS_DERIVED_MIN_Q; }
+// measured -2.6 ... -3.1 % there, +-0 % at Q = 5 (profiles/r03_ab_experiments.txt item 3; again r04 item 15), for ten more doubles
+// per point stored.
+constexpr bool pencil_derived_state(int Q) { return Q >= 6; }
 
 struct FusedGradArgs {
   const uint32_t *offsets;  // [nelem][P^3] (flagged)
@@ -115,43 +113,25 @@ static inline bool node_is_element_interior(int n, int P) {
 // included), then the two j-faces without the rows the k-faces hold, then the two i-faces' interiors -- so the nodes an
 // element shares with ONE neighbour are contiguous in both elements' blocks, and k_assemble, whose consecutive rows are
 // the nodes of one shared face, reads runs of whole faces instead of every fifth 24-byte record of an i-face (round 1's
-// lexicographic order: 0.15 GB of line over-fetch per apply).  CPS_SHELL_LEX restores the lexicographic order (A/B).
+// lexicographic order: 0.15 GB of line over-fetch per apply; profiles/r02_ab_experiments.txt item 5).
 #ifdef __HIPCC__
 __host__ __device__
 #endif
 static inline int node_shell_rank(int n, int P) {
   const int m = P - 2, i = n % P, j = (n / P) % P, k = n / (P * P);
-#ifdef CPS_SHELL_LEX
-#define CPS_CLAMPM(v) ((v) < 0 ? 0 : ((v) > m ? m : (v)))
-  int before = CPS_CLAMPM(k - 1) * m * m;                  // interior nodes in the planes below
-  if (k > 0 && k < P - 1) {
-    before += CPS_CLAMPM(j - 1) * m;                       // ... in the rows below of this plane
-    if (j > 0 && j < P - 1) before += CPS_CLAMPM(i - 1);   // ... to the left in this row
-  }
-#undef CPS_CLAMPM
-  return n - before;
-#else
   if (k == 0) return j * P + i;
   if (k == P - 1) return P * P + j * P + i;
   if (j == 0) return 2 * P * P + (k - 1) * P + i;
   if (j == P - 1) return 2 * P * P + P * m + (k - 1) * P + i;
   if (i == 0) return 2 * P * P + 2 * P * m + (k - 1) * m + (j - 1);
   return 2 * P * P + 2 * P * m + m * m + (k - 1) * m + (j - 1);   // i == P - 1 (interior nodes have no rank)
-#endif
 }
+// shell nodes of an element = 24-byte records between the shell E-vector blocks of consecutive elements: the blocks are packed
+// (every block padded to whole 128-byte lines was measured in round 4, nothing: profiles/r04_ab_experiments.txt item 19)
 #ifdef __HIPCC__
 __host__ __device__
 #endif
 static inline int element_shell_size(int P) { return P * P * P - (P > 2 ? (P - 2) * (P - 2) * (P - 2) : 0); }
-// 24-byte records between the shell E-vector blocks of consecutive elements (tuning hook, round 4: 16 makes every block a whole number
-// of 128-byte lines -- measured, nothing: profiles/r04_ab_experiments.txt item 19)
-#ifndef CPS_EVEC_ALIGN
-#define CPS_EVEC_ALIGN 1
-#endif
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-static inline int evec_block_records(int P) { return (element_shell_size(P) + CPS_EVEC_ALIGN - 1) / CPS_EVEC_ALIGN * CPS_EVEC_ALIGN; }
 
 // p-multigrid transfer in OWNER form (kernels_misc.hip, k_transfer): every fine node belongs to the first element that holds it.
 struct TransferArgs {
@@ -219,10 +199,8 @@ hipError_t launch_diag(int P, int Q, int qf, const BasisTables &t, const DiagArg
 constexpr int pencil_inst_parts(int Q) { return Q == 8 ? 4 : (Q == 7 ? 2 : 1); }
 // elements per wave (= per group) of the pencil kernel, PencilGeom<P, Q>::E: 3 Q^2 pencils per element and pass against 64
 // lanes and the 9 Q^3-double LDS slab per element
-#ifndef CPS_PENCIL_E5
-#define CPS_PENCIL_E5 2      // (tuning hook for variant builds: elements per wave at Q = 5)
-#endif
-constexpr int pencil_group_elems(int Q) { return Q <= 2 ? 8 : (Q <= 4 ? 4 : (Q == 5 ? CPS_PENCIL_E5 : 1)); }
+// (Q = 5: two; one element per wave was 8-25 % slower, profiles/r03_ab_experiments.txt item 12)
+constexpr int pencil_group_elems(int Q) { return Q <= 2 ? 8 : (Q <= 4 ? 4 : (Q == 5 ? 2 : 1)); }
 
 // Deterministic, atomic-free E^T: y[node_off[r] + c] (+)= sum over the node's contributors, in element
 // order, of E[3 * cols[k] + c] (cols[k] = e * P3 + n).  `flags` (one byte per node, bit c = component c constrained) may be null.

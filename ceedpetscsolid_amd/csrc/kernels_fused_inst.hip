@@ -23,7 +23,8 @@ namespace cps {
 #define CPS_STR_(x) #x
 #define CPS_STR(x) CPS_STR_(x)
 
-// (the part test depends on the template parameter, so the kernels of the other parts are not instantiated here)
+// (Every `if constexpr` below tests the template parameter PART, too: only then is a discarded branch not instantiated -- the kernels
+// of the other parts, of P > Q and the derived-state tangent below Q = 6 do not exist in this object.)
 #define CPS_CASE(Pv, QFv, QFname)                                                   \
   if constexpr ((CPS_Q - (Pv)) % pencil_inst_parts(CPS_Q) == PART) {                \
     if (P == Pv && qf == QFv) {                                                     \
@@ -33,11 +34,8 @@ namespace cps {
   }
 // The derived-state tangent is instantiated where it measured a gain: Q >= 6 (one element per wave; -2.6 ... -3.1 % on config 5's
 // block, same box); at Q = 5 it removes 9 % of the VALU instructions and 0 % of the time (pencil_derived_state, kernels.hpp).
-#if CPS_Q >= CPS_DERIVED_MIN_Q
-#define CPS_DERIVED(Pv) CPS_CASE(Pv, QF_HYPERFS_DF_DS, "HyperFSdF+derived")
-#else
-#define CPS_DERIVED(Pv)
-#endif
+#define CPS_DERIVED(Pv) \
+  if constexpr (PART >= 0 && pencil_derived_state(CPS_Q)) { CPS_CASE(Pv, QF_HYPERFS_DF_DS, "HyperFSdF+derived") }
 #define CPS_JACOBIANS(Pv)              \
   CPS_CASE(Pv, QF_LINELAS, "LinElas")  \
   CPS_CASE(Pv, QF_HYPERSS_DF, "HyperSSdF") \
@@ -48,47 +46,19 @@ namespace cps {
 // (src/cloptions.c:53-55: Q = degree + 1 + qextra, setuplibceed.c:252).  A larger qextra is a loud "no fused kernel instantiated".
 #define CPS_RESIDUALS(Pv) CPS_CASE(Pv, QF_HYPERSS_F, "HyperSSF") CPS_CASE(Pv, QF_HYPERFS_F, "HyperFSF")
 #define CPS_FINE_WITH_QEXTRA(Pv) ((CPS_Q) > (Pv) && (CPS_Q) - (Pv) <= 2)
+// a coarse degree (or the fine one under -qextra): its Jacobians, and the residuals where it can be the fine level
+#define CPS_LEVEL(Pv)                                                                  \
+  if constexpr (PART >= 0 && (CPS_Q) > (Pv)) {                                         \
+    CPS_JACOBIANS(Pv)                                                                  \
+    if constexpr (PART >= 0 && CPS_FINE_WITH_QEXTRA(Pv)) { CPS_RESIDUALS(Pv) }         \
+  }
 
 template <int PART>
 static hipError_t dispatch_part(int P, int qf, const BasisTables &t, const FusedGradArgs &a, hipStream_t s, const char **name) {
   CPS_JACOBIANS(CPS_Q)
   CPS_RESIDUALS(CPS_Q)
-#if CPS_Q > 2
-  CPS_JACOBIANS(2)
-#if CPS_FINE_WITH_QEXTRA(2)
-  CPS_RESIDUALS(2)
-#endif
-#endif
-#if CPS_Q > 3
-  CPS_JACOBIANS(3)
-#if CPS_FINE_WITH_QEXTRA(3)
-  CPS_RESIDUALS(3)
-#endif
-#endif
-#if CPS_Q > 4
-  CPS_JACOBIANS(4)
-#if CPS_FINE_WITH_QEXTRA(4)
-  CPS_RESIDUALS(4)
-#endif
-#endif
-#if CPS_Q > 5
-  CPS_JACOBIANS(5)
-#if CPS_FINE_WITH_QEXTRA(5)
-  CPS_RESIDUALS(5)
-#endif
-#endif
-#if CPS_Q > 6      // (uniform ladders of degrees 6 and 7, cloptions.c:195-225: every degree below the fine one is a level)
-  CPS_JACOBIANS(6)
-#if CPS_FINE_WITH_QEXTRA(6)
-  CPS_RESIDUALS(6)
-#endif
-#endif
-#if CPS_Q > 7
-  CPS_JACOBIANS(7)
-#if CPS_FINE_WITH_QEXTRA(7)
-  CPS_RESIDUALS(7)
-#endif
-#endif
+  // (degrees 6 and 7: the uniform ladders, cloptions.c:195-225 -- every degree below the fine one is a level)
+  CPS_LEVEL(2) CPS_LEVEL(3) CPS_LEVEL(4) CPS_LEVEL(5) CPS_LEVEL(6) CPS_LEVEL(7)
   return hipErrorInvalidValue;
 }
 

@@ -185,10 +185,7 @@ hipError_t launch_setup_geo(int Q, const BasisTables &t, const SetupGeoArgs &a, 
 // lane-fastest index of the pass that reads them is contiguous: U0 [kc][jc][ic][c], U1 [kc][jc][if][c], U2 [kc][jf][if][c].
 // ===========================================================================
 constexpr uint32_t XFER_SKIP = 0xFFFFFFFFu;    // own_f entry of a fine node another element owns
-#ifndef CPS_XFER_E5
-#define CPS_XFER_E5 2
-#endif
-constexpr int xfer_group_elems(int PF) { return PF <= 3 ? 4 : (PF == 4 ? 4 : (PF == 5 ? CPS_XFER_E5 : 1)); }
+constexpr int xfer_group_elems(int PF) { return PF <= 3 ? 4 : (PF == 4 ? 4 : (PF == 5 ? 2 : 1)); }
 template <int PC, int PF> struct XferGeom {
   static constexpr int C3 = PC * PC * PC, F2 = PF * PF, F3 = PF * PF * PF;
   static constexpr int E = xfer_group_elems(PF);
@@ -677,9 +674,7 @@ __global__ void k_rstr(const uint32_t *off, size_t total, int elemsize, int ncom
 __global__ void k_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off,
                            const unsigned char *flags, const double *evec, double *y, int nnodes, int add, int nb_rows,
                            const HaloUnpackArgs un, const HaloPackFold pk) {
-#ifdef CPS_ASM_PRIO   // (tuning hook) wave priority of the row sums beside a fused kernel
-  __builtin_amdgcn_s_setprio(CPS_ASM_PRIO);
-#endif
+  // (no wave priority of its own: the row sums at priority 3 beside a fused kernel measured +2 %, profiles/r03_ab_experiments.txt item 15c)
   if ((int)blockIdx.x >= nb_rows) {
     for (int u = ((int)blockIdx.x - nb_rows) * blockDim.x + threadIdx.x; u < un.n; u += ((int)gridDim.x - nb_rows) * blockDim.x) {
       double v = y[un.dst[u]];
@@ -935,10 +930,7 @@ hipError_t launch_assemble(const uint32_t *rowptr, const uint32_t *cols, const u
                            int add, hipStream_t s, const HaloUnpackArgs *unpack, const HaloPackFold *pack) {
   const int nun = unpack ? unpack->n : 0;
   if (nnodes <= 0 && nun <= 0) return hipSuccess;
-#ifndef CPS_ASM_BLOCK
-#define CPS_ASM_BLOCK 256    // (tuning hook) threads per workgroup of k_assemble: 128 and 512 measured in round 4, nothing
-#endif
-  constexpr int AB = CPS_ASM_BLOCK;
+  constexpr int AB = 256;      // threads per workgroup of k_assemble: 64, 128 and 512 measured in round 4, nothing (profiles/r04_ab_experiments.txt item 18)
   const unsigned nb_rows = (unsigned)((std::max(nnodes, 0) + AB - 1) / AB);
   const unsigned nb_un = (unsigned)std::min((nun + AB - 1) / AB, 1024);
   hipLaunchKernelGGL(k_assemble, dim3(nb_rows + nb_un), dim3(AB), 0, s, rowptr, cols, node_off, flags, evec, y, nnodes, add,

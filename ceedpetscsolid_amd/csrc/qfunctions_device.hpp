@@ -165,11 +165,7 @@ CPS_DEV double log1p_series4_shifted(double x) {  // hyperFS.h:45-67
 // 0:(0,0) 1:(1,1) 2:(2,2) 3:(1,2) 4:(0,2) 5:(0,1)
 #define CPS_SYM(w, a, b) ((a) == (b) ? w[a] : w[6 - (a) - (b)])
 struct FSState { double S[6], Ci[6], llnj; };
-// FAST_S: S = mu I + (llnj - mu) C^-1, algebraically equal to the reference's
-// llnj C^-1 + mu C^-1 E2 (since C^-1 E2 = I - C^-1).  Used ONLY by the Jacobian, where S enters
-// through grad(du) S next to the O(mu) term F dS, so its cancellation error (~1e-16 mu absolute) is
-// far inside the 1e-10 bar; the residual keeps the reference's cancellation-free form.
-template <bool FAST_S>
+// S in the reference's cancellation-free form llnj C^-1 + mu C^-1 E2 (the residual's; the tangent is qf_hyperfs_df)
 CPS_DEV void fs_state(double lambda, double mu, const double g[3][3], FSState &s) {  // hyperFS.h:85-142
   constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
   double E2[6];
@@ -191,18 +187,12 @@ CPS_DEV void fs_state(double lambda, double mu, const double g[3][3], FSState &s
 #pragma unroll
   for (int m = 0; m < 6; m++) s.Ci[m] = A[m] * rden;
   s.llnj = lambda * log1p_series4_shifted(detCm1) / 2.;
-  if constexpr (FAST_S) {
-    const double f = s.llnj - mu;
 #pragma unroll
-    for (int m = 0; m < 6; m++) s.S[m] = f * s.Ci[m] + (m < 3 ? mu : 0.);
-  } else {
+  for (int m = 0; m < 6; m++) {
+    double t = s.llnj * s.Ci[m];
 #pragma unroll
-    for (int m = 0; m < 6; m++) {
-      double t = s.llnj * s.Ci[m];
-#pragma unroll
-      for (int n = 0; n < 3; n++) t += mu * CPS_SYM(s.Ci, J[m], n) * CPS_SYM(E2, n, K[m]);
-      s.S[m] = t;
-    }
+    for (int n = 0; n < 3; n++) t += mu * CPS_SYM(s.Ci, J[m], n) * CPS_SYM(E2, n, K[m]);
+    s.S[m] = t;
   }
 }
 CPS_DEV void fs_lame(const Phys ph, double &lambda, double &mu) {  // hyperFS.h:164-167
@@ -223,7 +213,7 @@ CPS_DEV void qf_hyperfs_f(const Phys ph, const double *ug, const double *qd, dou
     for (int k = 0; k < 3; k++) st[3 * c + k] = g[c][k];
   if (ds) fs_derived_state(lambda, mu, g, ds);
   FSState s;
-  fs_state<false>(lambda, mu, g, s);
+  fs_state(lambda, mu, g, s);
 #pragma unroll
   for (int a = 0; a < 3; a++)  // P = F S, F = I + grad u   (hyperFS.h:262-268)
 #pragma unroll
@@ -363,68 +353,7 @@ CPS_DEV void qf_hyperfs_df_ds(const Phys ph, const double *dug, const double *qd
     }
   pull_back<SW>(dP, qd, dv);
 }
-// The reference's own evaluation order (kept for A/B and as documentation of the map above).
-template <bool SW = false>
-CPS_DEV void qf_hyperfs_df_reference_form(const Phys ph, const double *dug, const double *qd, const double *st, double *dv) {
-  constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
-  double lambda, mu, dg[3][3], g[3][3], F[3][3];
-  fs_lame(ph, lambda, mu);
-  physical_grad<SW>(dug, qd, dg);
-#pragma unroll
-  for (int c = 0; c < 3; c++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      g[c][k] = st[3 * c + k];
-      F[c][k] = g[c][k] + (c == k ? 1. : 0.);
-    }
-  FSState s;
-  fs_state<true>(lambda, mu, g, s);
-  double dE[6];  // sym(grad(du)^T F)   (hyperFS.h:381-389); on the diagonal the two products coincide
-#pragma unroll
-  for (int m = 0; m < 6; m++) {
-    double t = 0.;
-    if (J[m] == K[m]) {
-#pragma unroll
-      for (int n = 0; n < 3; n++) t += dg[n][J[m]] * F[n][J[m]];
-    } else {
-#pragma unroll
-      for (int n = 0; n < 3; n++) t += dg[n][J[m]] * F[n][K[m]] + F[n][J[m]] * dg[n][K[m]];
-      t *= 0.5;
-    }
-    dE[m] = t;
-  }
-  // C^-1 : dE  (symmetric: diagonal + twice the off-diagonal)
-  const double CidE = s.Ci[0] * dE[0] + s.Ci[1] * dE[1] + s.Ci[2] * dE[2] +
-                      2. * (s.Ci[3] * dE[3] + s.Ci[4] * dE[4] + s.Ci[5] * dE[5]);
-  double dECi[3][3], dS[6], dP[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int b = 0; b < 3; b++) {
-      double t = 0.;
-#pragma unroll
-      for (int m = 0; m < 3; m++) t += CPS_SYM(dE, a, m) * CPS_SYM(s.Ci, m, b);
-      dECi[a][b] = t;
-    }
-  const double llnj_m2 = 2. * (s.llnj - mu), lCidE = lambda * CidE;
-#pragma unroll
-  for (int m = 0; m < 6; m++) {  // dS = lambda (C^-1:dE) C^-1 - 2 (llnj - mu) C^-1 dE C^-1: symmetric, 6 entries
-    double t = 0.;
-#pragma unroll
-    for (int n = 0; n < 3; n++) t += CPS_SYM(s.Ci, J[m], n) * dECi[n][K[m]];
-    dS[m] = lCidE * s.Ci[m] - llnj_m2 * t;  // hyperFS.h:438-442
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++)  // dP = grad(du) S + F dS    (hyperFS.h:444-451)
-#pragma unroll
-    for (int b = 0; b < 3; b++) {
-      double t = 0.;
-#pragma unroll
-      for (int m = 0; m < 3; m++) t += dg[a][m] * CPS_SYM(s.S, m, b) + F[a][m] * CPS_SYM(dS, m, b);
-      dP[a][b] = t;
-    }
-  pull_back<SW>(dP, qd, dv);
-}
+// (The reference's own evaluation order, dP = grad(du) S + F dS, is restated in oracle/oracle_qfunctions.c: Oracle_HyperFSdF.)
 
 // ---- geometry (common.h:47-101).  Jg[d*3+c] = d x_c / d xi_d ---------------
 CPS_DEV void qf_setup_geo(const double *Jg, double w, double *qd) {
@@ -485,11 +414,7 @@ CPS_DEV void qf_point(const Phys ph, const double *ug, const double *qd, const d
   else if constexpr (QF == QF_HYPERSS_DF) qf_hyperss_df<SW>(ph, ug, qd, st_in, dv);
   else if constexpr (QF == QF_HYPERFS_F) qf_hyperfs_f<SW>(ph, ug, qd, dv, st_out, derived_out);
   else if constexpr (QF == QF_HYPERFS_DF_DS) qf_hyperfs_df_ds<SW>(ph, ug, qd, st_in, dv);
-#ifdef CPS_FS_REFERENCE_FORM  // A/B builds only
-  else if constexpr (QF == QF_HYPERFS_DF) qf_hyperfs_df_reference_form<SW>(ph, ug, qd, st_in, dv);
-#else
   else if constexpr (QF == QF_HYPERFS_DF) qf_hyperfs_df<SW>(ph, ug, qd, st_in, dv);
-#endif
 }
 
 }  // namespace cps

@@ -1,8 +1,9 @@
 #!/bin/bash
 # usage: tools/mkvariant.sh <name> "<extra hipcc flags>" [Q ... | all]   (CPU; default Q list: 5; all: every object, host side included)
 # Builds a variant of the product library out of tree (tools/variants/<name>/*.so, git-ignored): the in-tree objects are
-# reused, only the fused kernels of the listed quadrature sizes are recompiled with the extra flags (-D tuning hooks of
-# kernel_fused_pencil.hpp, -mllvm options).  tools/r3_variants.sh runs variants against the default on one box.
+# reused, only the fused kernels of the listed quadrature sizes are recompiled with the extra flags: -DCPS_PHASE_TIMING=<k>
+# (the phase-timing build of kernel_fused_pencil.hpp) and -mllvm options.  The -DCPS_* tuning hooks of rounds 2 to 5 are
+# gone from the sources, their A/Bs settled (HISTORY.md, "compile-time hooks retired"): a flag that names one builds the default.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); name=$1; flags=$2; shift 2; qs=${@:-5}
 T=/tmp/variants/$name; W=$T/pkg/csrc; rm -rf $T; mkdir -p $W $T/include; cp -r $R/ceedpetscsolid_amd/csrc/. $W/; cp $R/include/*.h $T/include/
