@@ -48,10 +48,10 @@ class AssembledLevel:
         self.qf.set_context(prob.phys, reported_size=8)
         self.op = c.operator(self.qf)
         self.op.set_field("deltadu", self.rstr, lv.basisu, "active")
-        self.op.set_field("qdata", prob.Erestrictqdi, None, prob.qdata)
-        self.op.set_field("deltadv", self.rstr, lv.basisu, "active")
+        self.op.set_field("qdata", lv.Erestrictqdi, None, lv.qdata)       # the level's own quadrature data and state: the problem's
+        self.op.set_field("deltadv", self.rstr, lv.basisu, "active")      # (fine Q) unless coarse_quadrature="own"
         if prob.info["state"]:
-            self.op.set_field("gradu", prob.ErestrictGradui, None, prob.gradu)
+            self.op.set_field("gradu", lv.ErestrictGradui, None, lv.gradu)
         # --- unit vectors and the COO value buffer: entry [j][e][n][c] = K_e[(n,c), j] -----------------
         self.units = []
         for j in range(self.nd):

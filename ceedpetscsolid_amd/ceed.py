@@ -73,6 +73,9 @@ class CeedLib:
         "CeedXCsrCreate", "CeedXCsrAssemble", "CeedXCsrApply", "CeedXCsrGetDiagonal", "CeedXCsrDestroy",
         "CeedXCsrCreateRect", "CeedXCsrCreateProduct", "CeedXCsrGetPattern", "CeedXCsrUpdate", "CeedXCsrGetValues", "CeedXCsrInvertDenseSPD",
     ]
+    # declared CEED_EXTERN_OPTIONAL in include/ceed.h: the product library exports them, another backend of the ABI (the CPU oracle) may
+    # not -- the callers look them up (``has``) and otherwise take the portable form built from the entry points above
+    OPTIONAL = ["CeedXOperatorApplyState"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -112,8 +115,14 @@ class CeedLib:
             msg = self.lib.CeedXLastError()
             raise CeedError(msg.decode() if msg else f"Ceed error {rc}")
 
-    def missing_symbols(self):
-        return [s for s in self.FUNCTIONS + self.DATA if not hasattr(self.lib, s)]
+    def has(self, symbol: str) -> bool:
+        return hasattr(self.lib, symbol)
+
+    def missing_symbols(self, optional: bool = True):
+        """Declared symbols this library lacks.  ``optional=False`` leaves the CEED_EXTERN_OPTIONAL ones out: what another backend of
+        the ABI must export; the product library exports all of them (build() checks with the default)."""
+        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL if optional else [])
+        return [s for s in want if not hasattr(self.lib, s)]
 
 
 def _np_f64(a) -> np.ndarray:
@@ -522,6 +531,10 @@ class Operator:
             m = np.ascontiguousarray(priority, dtype=np.uint8)
             self.L.chk(self.L.lib.CeedXOperatorSetOverlapSplit(
                 self.h, c_int(n_leading_elems), m.ctypes.data_as(C.POINTER(C.c_ubyte)), c_int(m.size)))
+
+    def apply_state(self, u: "Vector"):
+        """CeedXOperatorApplyState: write only the stored state (passive gradu output) of a residual-shaped operator."""
+        self.L.chk(self.L.lib.CeedXOperatorApplyState(self.h, u.h))
 
     def apply_phase(self, vin: "Vector", vout: "Vector", phase: int):
         self.L.chk(self.L.lib.CeedXOperatorApplyPhase(self.h, vin.h, vout.h, C.c_int(phase)))

@@ -5,6 +5,8 @@
 //
 //   fused_grad : GRAD active in, NONE qdata (+ NONE state in / out), GRAD active out
 //                -> opApply (setuplibceed.c:517-542) and opJacob per level (:817-839)
+//                (CeedXOperatorApplyState of a residual-shaped operator: its stored state alone, kernels_state.hip --
+//                 also on a basis with more nodes than points, for which no fused kernel exists)
 //   setup_geo  : GRAD coords + WEIGHT -> NONE qdata             (:370-389)
 //   prolong    : Identity, INTERP in -> NONE out                (:857-862)
 //   restrict   : Identity, NONE in  -> INTERP out               (:849-854)
@@ -229,7 +231,7 @@ static int op_plan(CeedOperator op) {
     if (st_in) { OpField &s = op->in[op->i_state]; if (!is_strided(s.rstr) || s.rstr->elemsize != Q3 || s.rstr->ncomp != 9) return unsupported("state input must be strided 9 x Q^3"); }
     if (st_out) { OpField &s = op->out[op->o_state]; if (!is_strided(s.rstr) || s.rstr->elemsize != Q3 || s.rstr->ncomp != 9) return unsupported("state output must be strided 9 x Q^3"); }
     fill_tables(op->tables, b);
-    if (pencil_even_odd(Q)) {   // even-odd forms of the six products, built once here (not per apply)
+    if (pencil_even_odd(Q) && P <= Q) {   // even-odd forms of the six products, built once here (not per apply); P > Q: the state kernel only
       const BasisTables &t = op->tables;
       const bool ok = build_eo_table(t.interp, Q, P, P, false, +1, op->eo[0]) && build_eo_table(t.interp, P, Q, P, true, +1, op->eo[1]) &&
                       build_eo_table(t.colo, Q, Q, Q, false, -1, op->eo[2]) && build_eo_table(t.colo, Q, Q, Q, true, -1, op->eo[3]) &&
@@ -409,6 +411,9 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
   if (!in || in == CEED_VECTOR_NONE || !out || out == CEED_VECTOR_NONE) return ceed_error("active vectors required");
   if (in->length < r->lsize || out->length < r->lsize) return ceed_error("active vector shorter than the restriction's L-size");
   if (in == out) return ceed_error("in-place operator apply is not supported");
+  if (ai.basis->P1d > ai.basis->Q1d)   // planned for CeedXOperatorApplyState only (op_plan builds no even-odd tables for it)
+    return ceed_error("operator with QFunction '%s' on a basis with more nodes than points (P=%d > Q=%d): no fused kernel applies it; "
+                      "only its stored state can be written (CeedXOperatorApplyState)", qf->name.c_str(), ai.basis->P1d, ai.basis->Q1d);
   FusedGradArgs &a = F.a;
   F.r = r; F.b = ai.basis; F.qfkind = qf->kind; F.add = add; F.split = split;
   double *px, *pq, *ps = nullptr;
@@ -1041,9 +1046,52 @@ extern "C" int CeedOperatorLinearAssembleDiagonal(CeedOperator op, CeedVector as
 // ---------------------------------------------------------------------------
 // extensions
 // ---------------------------------------------------------------------------
+// The stored state alone (include/ceed.h): of an operator of the residual's shape -- du GRAD active, qdata NONE, dv GRAD active, gradu NONE
+// passive -- only the passive output is written, grad u of `u` at the points of the operator's basis.  That basis may have MORE nodes than
+// points (P_f, Q_c < P_f): the state of a coarse multigrid level that carries its own quadrature, refreshed from the fine displacement
+// (solid.py, coarse_quadrature="own").  No physics, no transpose contraction, no E-vector, no k_assemble; the active output is not touched.
+// The state vector is written through vec_dev(write): its version moves on and a derived state it may have carried is invalid from here,
+// exactly as after any other writer -- recorded graphs that read the plain array replay correctly.
+extern "C" int CeedXOperatorApplyState(CeedOperator op, CeedVector u) {
+  if (op->composite) return ceed_error("CeedXOperatorApplyState: not provided for composite operators");
+  CHK(op_plan(op));
+  if (op->plan != PLAN_FUSED_GRAD || op->o_state < 0)
+    return ceed_error("CeedXOperatorApplyState is provided for the residual operators (the ones that store grad u)");
+  Ceed c = op->ceed;
+  hipStream_t s = c->stream;
+  OpField &ai = op->in[op->i_active];
+  CeedElemRestriction r = ai.rstr;
+  CeedBasis b = ai.basis;
+  CeedVector qv = op->in[op->i_qdata].vec, sv = op->out[op->o_state].vec;
+  if (!u || u == CEED_VECTOR_NONE || u == CEED_VECTOR_ACTIVE || u->length < r->lsize) return ceed_error("CeedXOperatorApplyState: displacement vector missing or shorter than the restriction's L-size");
+  if (!sv || sv == CEED_VECTOR_NONE || sv == CEED_VECTOR_ACTIVE) return ceed_error("state output needs a passive vector");
+  if (!qv || qv == CEED_VECTOR_NONE || qv == CEED_VECTOR_ACTIVE) return ceed_error("qdata needs a passive vector");
+  const size_t Q3 = (size_t)b->Q1d * b->Q1d * b->Q1d;
+  if ((size_t)sv->length < (size_t)r->nelem * 9 * Q3 || (size_t)qv->length < (size_t)r->nelem * 10 * Q3)
+    return ceed_error("CeedXOperatorApplyState: state / qdata vector shorter than nelem x 9 (10) x Q^3");
+  if (sv == u || qv == u || sv == qv) return ceed_error("CeedXOperatorApplyState: the vectors alias");
+  StateArgs a{};
+  double *px, *pq, *ps;
+  CHK(vec_dev(u, false, &px));
+  CHK(vec_dev(qv, false, &pq));
+  CHK(vec_dev(sv, true, &ps));
+  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : r->d_offsets;
+  a.x = px; a.qdata = pq; a.state_out = ps; a.nelem = r->nelem; a.mask_in = (op->mask_mode & 1) ? 1 : 0;
+  const char *kname = "";
+  {
+    TimerScope ts(op, s);
+    hipError_t e = launch_state_at_points(b->P1d, b->Q1d, op->tables, a, s, &kname);
+    if (e == hipErrorInvalidValue && !*kname) return ceed_error("no state kernel instantiated for Pf=%d Qc=%d", b->P1d, b->Q1d);
+    HIPCHK(e);
+  }
+  op->launches++;
+  op->kernel_name = kname;
+  return 0;
+}
 // the instantiation of the last apply; for the fused operators also how the geometric factors were obtained
 extern "C" int CeedXOperatorGetKernelName(CeedOperator op, const char **name) {
-  if (op->plan == PLAN_FUSED_GRAD && !op->kernel_name.empty() && op->kernel_name.find(" [") == std::string::npos)
+  if (op->plan == PLAN_FUSED_GRAD && !op->kernel_name.empty() && op->kernel_name.find(" [") == std::string::npos &&
+      op->kernel_name.compare(0, 6, "state<") != 0)
     op->kernel_name += op->geo_mode == 2 ? " [affine elements: dXdx per element]" : (op->geo_mode == 3 ? " [swept elements: 2 x 2 dXdx recomputed per point]" : (op->geo_mode == 1 ? " [dXdx recomputed per point]" : " [qdata read]"));
   *name = op->kernel_name.c_str();
   return 0;

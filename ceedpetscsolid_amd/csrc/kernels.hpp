@@ -182,6 +182,17 @@ struct DiagArgs {
   double *evec;  // element contributions ([elem][P^3][3]); launch_assemble() sums them
 };
 
+// The stored state of a level with its own quadrature (kernels_state.hip, k_state_at_points): grad u of the FINE displacement at the
+// level's Q_c^3 points, through the basis (P_f, Q_c) and the dXdx entries of the level's qdata.
+struct StateArgs {
+  const uint32_t *offsets;  // fine restriction [nelem][Pf^3] (flagged)
+  const double *x;          // the displacement L-vector, interlaced [node][3]
+  const double *qdata;      // the level's [nelem][10][Qc^3]
+  double *state_out;        // the level's [nelem][9][Qc^3]: every entry is overwritten
+  int nelem;
+  int mask_in;              // honour the Dirichlet flags on the gather (constrained entries read as zero)
+};
+
 // Each returns hipSuccess or the launch error; `name` receives a static string
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
@@ -193,6 +204,8 @@ hipError_t launch_setup_geo(int Q, const BasisTables &t, const SetupGeoArgs &a, 
                             const char **name);
 hipError_t launch_diag(int P, int Q, int qf, const BasisTables &t, const DiagArgs &a, hipStream_t s,
                        const char **name);
+hipError_t launch_state_at_points(int Pf, int Qc, const BasisTables &t, const StateArgs &a, hipStream_t s,
+                                  const char **name);
 
 // The instantiations of one quadrature size are compiled as pencil_inst_parts(Q) objects (kernels_fused_inst.hip, -DCPS_PART=<k>): the kernels
 // with (Q - P) % parts == k -- the Q = 8 object alone took 72 s of a 90 s build.  csrc/Makefile lists the same parts.

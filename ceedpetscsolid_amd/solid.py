@@ -7,6 +7,8 @@ Mirrors, call for call, what the reference does above libCEED:
   restrictions, bases, qdata via opSetupGeo, residual operator ``opApply``.
 * ``SolidProblem._setup_level``      ~ ``SetupLibceedLevel`` (:748-939): per-level Jacobian
   operator (coarse P, FINE quadrature and q-data), prolong / restrict operators.
+  ``coarse_quadrature="own"`` departs from :757,833-839 on purpose, inside the preconditioner only: a level below
+  the fine one then carries Q_c = P_level + qextra Gauss points, its own q-data and its own stored state.
 * ``apply_jacobian`` / ``form_residual`` / ``prolong`` / ``restrict`` / ``get_diag``
   ~ ``ApplyJacobian_Ceed`` / ``FormResidual_Ceed`` / ``Prolong_Ceed`` / ``Restrict_Ceed`` /
   ``GetDiag_Ceed`` (src/matops.c:98,63,115,160,206) incl. ``ApplyLocalCeedOp`` (:26-60).
@@ -81,24 +83,41 @@ class LevelData:  # CeedData, elasticity.h:218-240
     xceed: cd.Vector = None
     yceed: cd.Vector = None
     multinv: cd.Vector = None             # 1/multiplicity on this level (misc.c:115-143)
+    # quadrature of this level's Jacobian: the problem's own objects (fine Q) unless coarse_quadrature="own"
+    Q: int = 0
+    Erestrictqdi: cd.ElemRestriction = None
+    ErestrictGradui: cd.ElemRestriction = None
+    qdata: cd.Vector = None
+    gradu: cd.Vector = None
+    own_quadrature: bool = False
+    basisState: cd.Basis = None           # own quadrature: (P_fine, Q) -- the fine displacement's gradient at this level's points
+    opState: cd.Operator = None           # own quadrature: the residual operator once more on basisState; only its stored state is used
 
 
 class SolidProblem:
     def __init__(self, ceed: cd.Ceed, mesh: HexMesh, degree: int, problem: str = "hyperFS",
                  nu: float = 0.3, E: float = 1.0, multigrid: str = "logarithmic", qextra: int = 0,
                  bc_sides: Optional[Sequence[int]] = None, bc_all_boundary: bool = False,
-                 fused_bc: bool = True, shared_multiplicity=None, qf_callbacks=None):
+                 fused_bc: bool = True, shared_multiplicity=None, qf_callbacks=None, coarse_quadrature: str = "fine"):
         """``qf_callbacks``: name -> user callback pointer handed to CeedQFunctionCreateInterior, as the reference hands
         ``problemOptions[...].apply`` / ``.jacob`` (setuplibceed.c:470-474,822-824); a host backend calls it, this device
         backend resolves the name after ':' in the source string to its precompiled functor and ignores the pointer.
         ``fused_bc=False``: build the operator graphs exactly as the reference does and call NO extension of this
         backend (no Dirichlet flags folded into the offsets, no fused multiplicity scale): the drop-in form, in which the
         caller does what src/matops.c does around CeedOperatorApply.
+        ``coarse_quadrature``: "fine" (default, the reference: every level integrates on the fine level's Q points,
+        setuplibceed.c:757,833-839) or "own": a level below the fine one integrates its Jacobian on Q_c = P_level + qextra Gauss
+        points, with q-data and stored state of its own (``lv.qdata`` / ``lv.gradu``); ``form_residual`` refreshes that state from
+        the fine displacement.  A preconditioner option: residual, fine-level operator and Newton iteration are the same.
         ``bc_sides``: side-set ids clamped (all three components; -bc_clamp, setupdm.c:171-190);
         ``bc_all_boundary``: the "marker" label of -test mode (setupdm.c:160-170)."""
         if problem not in PROBLEMS:
             raise ValueError(f"unknown problem {problem!r} (hyperFSIncomp is not implemented: dead code upstream)")
         self.ceed, self.mesh, self.problem, self.info = ceed, mesh, problem, PROBLEMS[problem]
+        if coarse_quadrature not in ("fine", "own"):
+            raise ValueError(f"coarse_quadrature must be 'fine' or 'own', not {coarse_quadrature!r}")
+        self.coarse_quadrature, self.qextra = coarse_quadrature, qextra
+        self._state_scratch = None
         self.phys = np.array([nu, E], dtype=np.float64)  # Physics {nu, E}
         self.degrees = level_degrees(degree, multigrid)
         self.fine = len(self.degrees) - 1
@@ -145,15 +164,8 @@ class SolidProblem:
         if self.gradu is not None:
             self.gradu.set_value(0.0)
         # geometric factors (:370-393)
-        qf = c.qfunction("SetupGeo", f=self._qf_cb("SetupGeo"), source="qfunctions/common.h:SetupGeo")
-        qf.add_input("dx", 9, cd.EVAL_GRAD).add_input("weight", 1, cd.EVAL_WEIGHT).add_output("qdata", 10, cd.EVAL_NONE)
-        op = c.operator(qf)
-        op.set_field("dx", self.Erestrictx, self.basisx, "active")
-        op.set_field("weight", None, self.basisx, None)
-        op.set_field("qdata", self.Erestrictqdi, None, "active")
-        op.apply(self.xcoord, self.qdata)
-        self.setupgeo_kernel = op.kernel_name
-        op.destroy(); qf.destroy()
+        self.setupgeo_kernel = self._setup_geo(self.basisx, self.Erestrictqdi, self.qdata)
+        lv.Q, lv.Erestrictqdi, lv.ErestrictGradui, lv.qdata, lv.gradu = Q, self.Erestrictqdi, self.ErestrictGradui, self.qdata, self.gradu
         # residual operator (:518-542)
         name = self.info["apply"]
         self.qfApply = c.qfunction(name, f=self._qf_cb(name), source=f"qfunctions/{self.info['src']}:{name}")
@@ -171,6 +183,48 @@ class SolidProblem:
         if self.fused_bc:
             # residual: BC values stay in the input (matops.c:70-71), constrained rows dropped (:57)
             self._set_mask(self.opApply, lv.mask, mode=2)
+
+    def _setup_geo(self, basisx: cd.Basis, rstr_qd: cd.ElemRestriction, qdata: cd.Vector) -> str:
+        """The SetupGeo operator (setuplibceed.c:370-393) on the points of ``basisx``; returns the kernel it ran."""
+        c = self.ceed
+        qf = c.qfunction("SetupGeo", f=self._qf_cb("SetupGeo"), source="qfunctions/common.h:SetupGeo")
+        qf.add_input("dx", 9, cd.EVAL_GRAD).add_input("weight", 1, cd.EVAL_WEIGHT).add_output("qdata", 10, cd.EVAL_NONE)
+        op = c.operator(qf)
+        op.set_field("dx", self.Erestrictx, basisx, "active")
+        op.set_field("weight", None, basisx, None)
+        op.set_field("qdata", rstr_qd, None, "active")
+        op.apply(self.xcoord, qdata)
+        name = op.kernel_name
+        op.destroy(); qf.destroy()
+        return name
+
+    def _setup_own_quadrature(self, lv: LevelData):
+        """Quadrature, q-data and stored state of a level below the fine one on Q_c = P_level + qextra Gauss points, and the operator
+        that refreshes the state: the residual operator once more with the basis (P_fine, Q_c) and this level's q-data -- its passive
+        output is grad u of the FINE displacement at this level's points, which is what HyperSSF / HyperFSF store (hyperFS.h:215-220)."""
+        c, ne, fine = self.ceed, self.mesh.nelem, self.levels[self.fine]
+        Qc = lv.degree + 1 + self.qextra
+        nq = Qc ** 3
+        lv.own_quadrature, lv.Q = True, Qc
+        lv.basisu = c.basis_lagrange(3, 3, lv.degree + 1, Qc, cd.GAUSS)
+        lv.Erestrictqdi = c.strided_restriction(ne, nq, 10, 10 * ne * nq)
+        lv.qdata = c.vector(10 * ne * nq)
+        basisx = c.basis_lagrange(3, 3, 2, Qc, cd.GAUSS)
+        self._setup_geo(basisx, lv.Erestrictqdi, lv.qdata)
+        basisx.destroy()
+        if not self.info["state"]:
+            return
+        lv.ErestrictGradui = c.strided_restriction(ne, nq, 9, 9 * ne * nq)
+        lv.gradu = c.vector(9 * ne * nq)
+        lv.gradu.set_value(0.0)
+        lv.basisState = c.basis_lagrange(3, 3, fine.degree + 1, Qc, cd.GAUSS)
+        lv.opState = c.operator(self.qfApply)
+        lv.opState.set_field("du", fine.Erestrictu, lv.basisState, "active")
+        lv.opState.set_field("qdata", lv.Erestrictqdi, None, lv.qdata)
+        lv.opState.set_field("dv", fine.Erestrictu, lv.basisState, "active")
+        lv.opState.set_field("gradu", lv.ErestrictGradui, lv.basisState, lv.gradu)
+        if self.fused_bc:
+            self._set_mask(lv.opState, fine.mask, mode=2)   # as opApply: boundary values stay in the input
 
     def _set_mask(self, op: cd.Operator, mask_in, mask_out=None, mode=3):
         L = self.ceed.L
@@ -191,7 +245,11 @@ class SolidProblem:
         fine = self.levels[self.fine]
         if level != self.fine:  # (:771-784)
             lv.Erestrictu = c.elem_restriction(ne, P ** 3, 3, 1, lv.dofmap.lsize, lv.dofmap.offsets())
-            lv.basisu = c.basis_lagrange(3, 3, P, Q, cd.GAUSS)
+            if self.coarse_quadrature == "own":
+                self._setup_own_quadrature(lv)
+            else:
+                lv.basisu = c.basis_lagrange(3, 3, P, Q, cd.GAUSS)
+                lv.Q, lv.Erestrictqdi, lv.ErestrictGradui, lv.qdata, lv.gradu = Q, self.Erestrictqdi, self.ErestrictGradui, self.qdata, self.gradu
         if level != 0:          # (:799-803)
             lv.basisCtoF = c.basis_lagrange(3, 3, self.levels[level - 1].degree + 1, P, cd.GAUSS_LOBATTO)
         lv.xceed = c.vector(lv.dofmap.lsize)  # (:808-809)
@@ -206,10 +264,10 @@ class SolidProblem:
         lv.qfJacob.set_context(self.phys, reported_size=8)  # sizeof(phys) quirk, :826
         lv.opJacob = c.operator(lv.qfJacob)
         lv.opJacob.set_field("deltadu", lv.Erestrictu, lv.basisu, "active")
-        lv.opJacob.set_field("qdata", self.Erestrictqdi, None, self.qdata)
+        lv.opJacob.set_field("qdata", lv.Erestrictqdi, None, lv.qdata)
         lv.opJacob.set_field("deltadv", lv.Erestrictu, lv.basisu, "active")
         if self.info["state"]:
-            lv.opJacob.set_field("gradu", self.ErestrictGradui, None, self.gradu)
+            lv.opJacob.set_field("gradu", lv.ErestrictGradui, None, lv.gradu)
         if self.fused_bc:
             self._set_mask(lv.opJacob, lv.mask, mode=3)
         # multiplicity (SetupProlongRestrictCtx, misc.c:115-143)
@@ -252,8 +310,24 @@ class SolidProblem:
         self.levels[level].opJacob.apply(x, y)
 
     def form_residual(self, x: cd.Vector, y: cd.Vector):
-        """FormResidual_Ceed (matops.c:63-79) after boundary values have been inserted into x."""
+        """FormResidual_Ceed (matops.c:63-79) after boundary values have been inserted into x.  The Jacobian's state is whatever the last
+        residual evaluation stored: the levels that carry their own quadrature are refreshed from the same x in the same call."""
         self.opApply.apply(x, y)
+        self.refresh_level_state(x)
+
+    def refresh_level_state(self, x: cd.Vector, portable: bool = False):
+        """Stored state of every own-quadrature level from the fine displacement x.  The library's CeedXOperatorApplyState where it is
+        exported (the device kernel: the state alone); else -- or with ``portable`` -- the whole operator through include/ceed.h entry
+        points only, its active output discarded into a scratch vector."""
+        for lv in self.levels:
+            if lv.opState is None:
+                continue
+            if not portable and self.ceed.L.has("CeedXOperatorApplyState"):
+                lv.opState.apply_state(x)
+            else:
+                if self._state_scratch is None:
+                    self._state_scratch = self.ceed.vector(self.lsize())
+                lv.opState.apply(x, self._state_scratch)
 
     def prolong(self, level: int, xc: cd.Vector, yf: cd.Vector):
         """Prolong_Ceed (matops.c:115-157), coarse level-1 -> level."""
@@ -284,6 +358,12 @@ class SolidProblem:
                       lv.xceed, lv.yceed, lv.multinv):
                 if o is not None:
                     o.destroy()
+            if lv.own_quadrature:
+                for o in (lv.opState, lv.basisState, lv.Erestrictqdi, lv.ErestrictGradui, lv.qdata, lv.gradu):
+                    if o is not None:
+                        o.destroy()
+        if self._state_scratch is not None:
+            self._state_scratch.destroy()
         for o in (self.opApply, self.qfApply, self.Erestrictx, self.Erestrictqdi, self.ErestrictGradui, self.basisx,
                   self.xcoord, self.qdata, self.gradu):
             if o is not None:

@@ -64,6 +64,7 @@ class SolveStats:
     increments: int = 0
     converged: bool = True
     history: list = field(default_factory=list)
+    initial_residuals: list = field(default_factory=list)   # |R| at the start of every load increment (what snes_rtol is relative to)
 
 
 class Vec:
@@ -664,6 +665,7 @@ class NewtonPMG:
             self.residual(self.U, self.R)
             rnorm0 = np.sqrt(self.dot(self.R, self.R, True))
             rnorm = rnorm0
+            st.initial_residuals.append(rnorm0)
             if self.verbose:
                 print(f"increment {inc}/{num_increments}: |R| = {rnorm0:.6e}")
             for it in range(self.snes_maxit):

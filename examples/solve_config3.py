@@ -40,8 +40,14 @@ ap.add_argument("--amg-coarse-cycles", type=int, default=1, help="cycles of an i
 ap.add_argument("--amg-max-coarse", type=int, default=1500, help="rows up to which a level of the aggregation hierarchy is stored dense and inverted")
 ap.add_argument("--coarse-maxit", type=int, default=200)
 ap.add_argument("--coarse-rtol", type=float, default=1e-3)
+ap.add_argument("--coarse-quadrature", default="fine", choices=["fine", "own"],
+                help="fine: every multigrid level integrates on the fine level's points (the reference); own: a level below the fine one on "
+                     "P_level + qextra Gauss points of its own (preconditioner only)")
+ap.add_argument("--level-times", action="store_true", help="time every level's Jacobian applies and the own-quadrature state refresh (CeedXOperatorSetTiming)")
 ap.add_argument("--no-fuse", action="store_true", help="A/B: the smoother's Chebyshev step and the V-cycle's residual as passes of their own")
 args = ap.parse_args()
+if args.level_times and (args.graph or args.auto):
+    ap.error("--level-times reads device events of every apply: they cannot be read back from a recorded graph (drop --graph / --auto)")
 
 # several GPUs: `python -m torch.distributed.run --nproc-per-node N examples/solve_config3.py ...` -- one element
 # partition (z-slabs) per rank, halo sums inside the solver (SOLVE_DIST_BACKEND=gloo rehearses it on one GPU)
@@ -70,7 +76,13 @@ else:
         ceed.set_stream(torch.cuda.current_stream().cuda_stream)
 t0 = time.perf_counter()
 bc_sides = [s for s in (998, 999) if s in mesh.side_sets and len(mesh.side_sets[s])]
-prob = SolidProblem(ceed, mesh, args.degree, args.problem, nu=args.nu, E=args.E, bc_sides=bc_sides)
+prob = SolidProblem(ceed, mesh, args.degree, args.problem, nu=args.nu, E=args.E, bc_sides=bc_sides,
+                    coarse_quadrature=args.coarse_quadrature)
+if args.level_times:
+    for lv in prob.levels:
+        for op in (lv.opJacob, lv.opState):
+            if op is not None:
+                op.set_timing(True)
 if world > 1:
     halos = [HaloExchange(mesh, lv.dofmap, device="cpu" if args.oracle else torch.device("cuda", torch.cuda.current_device()))
              for lv in prob.levels]
@@ -85,6 +97,7 @@ st = solver.solve(args.increments)
 u = solver.U.to_numpy().reshape(-1, 3)
 out = {"resource": ceed.resource, "problem": args.problem, "mesh": os.path.basename(args.mesh), "elements": mesh.nelem,
        "level_degrees": prob.degrees, "global_dofs_per_level": [prob.n_free(l) for l in range(len(prob.levels))],
+       "coarse_quadrature": args.coarse_quadrature, "level_points_1d": [lv.Q for lv in prob.levels],
        "translate_998": list(tr), "coarse_solver": args.coarse, "vcycle_graph": solver.graph, "fused_epilogue": solver.fuse_epilogue, "vcycle_tuning": solver.tuning, "load_increments": st.increments, "converged": st.converged, "snes_its": st.newton_its, "ksp_its": st.ksp_its,
        "coarse_cg_its": st.coarse_its, "jacobian_applies": st.jacobian_applies, "residual_evals": st.residual_evals, "coarse_spmv": st.coarse_spmv,
        "setup_s": t_setup, "snes_solve_s": st.seconds,
@@ -92,6 +105,12 @@ out = {"resource": ceed.resource, "problem": args.problem, "mesh": os.path.basen
        "ranks": world,
        "MDoFs_per_s_in_SNES": 1e-6 * (halos[-1].global_count((prob.levels[prob.fine].mask == 0).astype(np.float64)) if halos else prob.n_free()) * st.ksp_its / st.seconds,   # elasticity.c:755-764
        "max_abs_displacement": np.abs(u).max(axis=0).tolist(), "final_residual_norm": st.history[-1][4] if st.history else None}
+if args.level_times:
+    def _t(op):
+        ms, n = op.get_timing()
+        return {"kernel": op.kernel_name, "ms": ms, "launches": n, "us_per_launch": 1e3 * ms / max(n, 1)}
+    out["level_apply_times"] = [{"degree": lv.degree, "jacobian": _t(lv.opJacob), "state": _t(lv.opState) if lv.opState is not None else None}
+                                for lv in prob.levels]
 if rank == 0:
     print(json.dumps(out))
 if world > 1:

@@ -36,6 +36,9 @@
 #else
 #  define CEED_EXTERN extern
 #endif
+/* Entry points a backend of this ABI MAY leave out (same linkage): a caller looks */
+/* the symbol up in the loaded library and takes the portable path without it.     */
+#define CEED_EXTERN_OPTIONAL CEED_EXTERN
 
 /* ------------------------------------------------------------------------- */
 /* Scalar / index types (f64 data, int32 indices)                   */
@@ -332,6 +335,17 @@ CEED_EXTERN int CeedXOperatorApplyChebyshev(CeedOperator op, CeedVector in, Ceed
 /* of its own, `spin_us` long).  bench.py reports it beside the timed blocks. */
 CEED_EXTERN int CeedXClockProbe(Ceed ceed, int spin_us, double *ghz);
 CEED_EXTERN int CeedXOperatorApplyResidual(CeedOperator op, CeedVector in, CeedVector t, CeedVector b, CeedVector w);
+/* OPTIONAL entry point: a caller looks it up in the loaded library and, where */
+/* it is absent, applies the operator itself with a scratch output (the same   */
+/* stored state, by include/ceed.h calls alone).                               */
+/* The stored state alone: for an operator of the residual's shape (du GRAD    */
+/* active, qdata NONE, dv GRAD active, gradu NONE passive) write ONLY the      */
+/* passive gradu output, the physical gradient of `u` at the points of the     */
+/* operator's basis (hyperFS.h:215-220).  The basis may have more nodes than   */
+/* points: the state of a coarse p-multigrid level on its own quadrature,      */
+/* refreshed from the fine displacement.  The active output does not exist for */
+/* this call; kernel name "state<Pf=..,Qc=..>".                                */
+CEED_EXTERN_OPTIONAL int CeedXOperatorApplyState(CeedOperator op, CeedVector u);
 /* Assembled sparse operator on L-vectors: the coarse level of the multigrid. */
 /* The reference builds it by finite-difference colouring of the p=1 operator */
 /* (misc.c:151-183, elasticity.c:457-483) and hands it to GAMG; here the      */
