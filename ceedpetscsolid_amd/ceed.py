@@ -75,7 +75,8 @@ class CeedLib:
     ]
     # declared CEED_EXTERN_OPTIONAL in include/ceed.h: the product library exports them, another backend of the ABI (the CPU oracle) may
     # not -- the callers look them up (``has``) and otherwise take the portable form built from the entry points above
-    OPTIONAL = ["CeedXOperatorApplyState"]
+    OPTIONAL = ["CeedXOperatorApplyState", "CeedOperatorLinearAssemblePointBlockDiagonal", "CeedXVectorPointBlockInvert",
+                "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -127,6 +128,110 @@ class CeedLib:
 
 def _np_f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+# ---- point-block Jacobi: the portable forms of the CEED_EXTERN_OPTIONAL vector operations (NumPy on host arrays) -----------------
+def pointblock_invert_host(blocks: np.ndarray):
+    """(inverses, n_bad) of 3 x 3 blocks [n][c out][c in], as CeedXVectorPointBlockInvert defines them: a component whose diagonal
+    entry is exactly zero is dropped, the inverse of the remaining principal sub-block is embedded in zeros; n_bad counts the blocks
+    with a non-finite or non-positive pivot of the elimination without interchanges."""
+    B = _np_f64(blocks).reshape(-1, 3, 3)
+    keep = B[:, [0, 1, 2], [0, 1, 2]] != 0.0
+    kk = keep[:, :, None] & keep[:, None, :]
+    M = np.where(kk, B, np.eye(3)[None])
+    with np.errstate(all="ignore"):
+        p0 = M[:, 0, 0]
+        l1, l2 = M[:, 1, 0] / p0, M[:, 2, 0] / p0
+        b11, b12 = M[:, 1, 1] - l1 * M[:, 0, 1], M[:, 1, 2] - l1 * M[:, 0, 2]
+        b21, b22 = M[:, 2, 1] - l2 * M[:, 0, 1], M[:, 2, 2] - l2 * M[:, 0, 2]
+        p1 = b11
+        p2 = b22 - (b21 / p1) * b12
+        ok = np.ones(len(M), dtype=bool)
+        for p in (p0, p1, p2):
+            ok &= (p > 0.0) & np.isfinite(p)
+        c00 = M[:, 1, 1] * M[:, 2, 2] - M[:, 1, 2] * M[:, 2, 1]
+        c01 = M[:, 1, 2] * M[:, 2, 0] - M[:, 1, 0] * M[:, 2, 2]
+        c02 = M[:, 1, 0] * M[:, 2, 1] - M[:, 1, 1] * M[:, 2, 0]
+        det = (M[:, 0, 0] * c00 + M[:, 0, 1] * c01) + M[:, 0, 2] * c02
+        inv = np.empty_like(M)
+        inv[:, 0, 0], inv[:, 1, 0], inv[:, 2, 0] = c00 / det, c01 / det, c02 / det
+        inv[:, 0, 1] = (M[:, 0, 2] * M[:, 2, 1] - M[:, 0, 1] * M[:, 2, 2]) / det
+        inv[:, 1, 1] = (M[:, 0, 0] * M[:, 2, 2] - M[:, 0, 2] * M[:, 2, 0]) / det
+        inv[:, 2, 1] = (M[:, 0, 1] * M[:, 2, 0] - M[:, 0, 0] * M[:, 2, 1]) / det
+        inv[:, 0, 2] = (M[:, 0, 1] * M[:, 1, 2] - M[:, 0, 2] * M[:, 1, 1]) / det
+        inv[:, 1, 2] = (M[:, 0, 2] * M[:, 1, 0] - M[:, 0, 0] * M[:, 1, 2]) / det
+        inv[:, 2, 2] = (M[:, 0, 0] * M[:, 1, 1] - M[:, 0, 1] * M[:, 1, 0]) / det
+    return np.where(kk, inv, 0.0), int((~ok).sum())
+
+
+def pointblock_mult_host(blocks: np.ndarray, x: np.ndarray) -> np.ndarray:
+    """w_n = B_n x_n on host arrays (x of 3 n entries, blocks of at least 9 n)."""
+    xv = _np_f64(x).reshape(-1, 3)
+    B = _np_f64(blocks)[:9 * len(xv)].reshape(-1, 3, 3)
+    return ((B[:, :, 0] * xv[:, None, 0] + B[:, :, 1] * xv[:, None, 1]) + B[:, :, 2] * xv[:, None, 2]).reshape(-1)
+
+
+def chebyshev_step_pointblock_host(x, d, b, t, blocks, c1, c2, assign_x):
+    """(x, d, ri) after one step of CeedXVectorChebyshevStepPointBlock on host arrays: ri = b - t (t may be None),
+    d = c1 B ri + c2 d, x = d or x + d."""
+    ri = _np_f64(b) - _np_f64(t) if t is not None else _np_f64(b).copy()
+    dn = c1 * pointblock_mult_host(blocks, ri)
+    if c2 != 0.0:
+        dn = c2 * _np_f64(d) + dn
+    return (dn.copy() if assign_x else _np_f64(x) + dn), dn, ri
+
+
+def _pb_check(who: str, blocks: "Vector", n: int):
+    if n % 3:
+        raise CeedError(f"{who}: vector length {n} is not a multiple of 3")
+    if blocks.n < 3 * n:
+        raise CeedError(f"{who}: block vector of {blocks.n} entries is shorter than 3 x {n}")
+
+
+def pointblock_invert(blocks: "Vector", want_n_bad: bool = True) -> Optional[int]:
+    """CeedXVectorPointBlockInvert, in place; returns the number of blocks with a bad pivot (one sync) or, with
+    ``want_n_bad=False``, None without involving the host.  The portable NumPy form where the library lacks the entry point."""
+    L = blocks.L
+    if L.has("CeedXVectorPointBlockInvert"):
+        nb = C.c_int(0)
+        L.chk(L.lib.CeedXVectorPointBlockInvert(blocks.h, C.byref(nb) if want_n_bad else None))
+        return nb.value if want_n_bad else None
+    if blocks.n % 9:
+        raise CeedError(f"pointblock_invert: vector length {blocks.n} is not a multiple of 9")
+    inv, nb = pointblock_invert_host(blocks.to_numpy())
+    blocks.set_array(inv.reshape(-1))
+    return nb if want_n_bad else None
+
+
+def pointblock_mult(w: "Vector", blocks: "Vector", x: "Vector"):
+    """CeedXVectorPointBlockMult: w_n = B_n x_n."""
+    L = w.L
+    if L.has("CeedXVectorPointBlockMult"):
+        L.chk(L.lib.CeedXVectorPointBlockMult(w.h, blocks.h, x.h))
+        return
+    if w.n != x.n:
+        raise CeedError("pointblock_mult: vector lengths differ")
+    _pb_check("pointblock_mult", blocks, x.n)
+    w.set_array(pointblock_mult_host(blocks.to_numpy(), x.to_numpy()))
+
+
+def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b: "Vector", t: Optional["Vector"], blocks: "Vector",
+                              c1: float, c2: float, assign_x: bool):
+    """CeedXVectorChebyshevStepPointBlock: ri = b - t; d = c1 B ri + c2 d; x = d or x + d (ri stored if r is given)."""
+    L = x.L
+    if L.has("CeedXVectorChebyshevStepPointBlock"):
+        L.chk(L.lib.CeedXVectorChebyshevStepPointBlock(x.h, d.h, r.h if r is not None else None, b.h, t.h if t is not None else None,
+                                                       blocks.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        return
+    if any(v is not None and v.n != x.n for v in (d, r, b, t)):
+        raise CeedError("chebyshev_step_pointblock: vector lengths differ")
+    _pb_check("chebyshev_step_pointblock", blocks, x.n)
+    xn, dn, ri = chebyshev_step_pointblock_host(None if assign_x else x.to_numpy(), d.to_numpy() if c2 != 0.0 else None, b.to_numpy(),
+                                                t.to_numpy() if t is not None else None, blocks.to_numpy(), c1, c2, assign_x)
+    if r is not None:
+        r.set_array(ri)
+    d.set_array(dn)
+    x.set_array(xn)
 
 
 class Csr:
@@ -508,6 +613,11 @@ class Operator:
 
     def assemble_diagonal(self, vec: Vector):
         self.L.chk(self.L.lib.CeedOperatorLinearAssembleDiagonal(self.h, vec.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+
+    def assemble_pointblock_diagonal(self, vec: Vector):
+        """CeedOperatorLinearAssemblePointBlockDiagonal (CEED_EXTERN_OPTIONAL: check ``CeedLib.has`` first): the 3 x 3 nodal blocks,
+        [node][comp out][comp in], the block of the node at component-0 L-offset o at 3 * o."""
+        self.L.chk(self.L.lib.CeedOperatorLinearAssemblePointBlockDiagonal(self.h, vec.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
 
     @property
     def kernel_name(self) -> str:

@@ -6,6 +6,7 @@
 // setuplibceed.c:392-393).  There is NO host fallback: a missing GPU is a loud error (CeedInit).
 // ONE DEVICE PER PROCESS: the library caches device properties process-wide (one rank per GPU, as under torchrun / mpirun).
 #include "ceed_impl.hpp"
+#include "kernels_pointblock.hpp"
 
 using namespace cps;
 
@@ -115,6 +116,7 @@ void ceed_unref(Ceed c) {
   for (hipEvent_t ev : c->ev_seg) if (ev) (void)hipEventDestroy(ev);
   if (c->d_scalar) (void)hipFree(c->d_scalar);
   if (c->h_scalar) (void)hipHostFree(c->h_scalar);
+  if (c->d_pb_bad) (void)hipFree(c->d_pb_bad);
   delete c;
 }
 int ceed_need_side_stream(Ceed c) {
@@ -457,6 +459,59 @@ extern "C" int CeedXVectorChebyshevStep(CeedVector x, CeedVector d, CeedVector r
   if (has_r) CHK(vec_dev(r, true, &pr));
   CHK(vec_dev(d, true, &pd)); CHK(vec_dev(x, true, &px));
   HIPCHK(launch_cheb_update(px, pd, pr, pb, pt, pi, c1, c2, assign_x, (size_t)n, x->ceed->stream));
+  return 0;
+}
+// ---------------------------------------------------------------------------
+// point-block Jacobi on vectors of 3 x 3 nodal blocks (include/ceed.h; kernels_pointblock.hip)
+// ---------------------------------------------------------------------------
+static int pb_lengths(const char *who, CeedVector blocks, CeedInt n) {
+  if (n % 3) return ceed_error("%s: vector length %d is not a multiple of 3", who, (int)n);
+  if ((size_t)blocks->length < 3 * (size_t)n) return ceed_error("%s: block vector of %d entries is shorter than 3 x %d", who, (int)blocks->length, (int)n);
+  return 0;
+}
+extern "C" int CeedXVectorPointBlockInvert(CeedVector blocks, int *n_bad) {
+  Ceed c = blocks->ceed;
+  if (blocks->length % 9) return ceed_error("CeedXVectorPointBlockInvert: vector length %d is not a multiple of 9", (int)blocks->length);
+  if (n_bad && c->capturing) return ceed_error("CeedXVectorPointBlockInvert: the count of bad pivots cannot be read during graph capture (pass NULL)");
+  double *pb;
+  CHK(vec_dev(blocks, true, &pb));
+  if (n_bad) {
+    if (!c->d_pb_bad) HIPCHK(hipMalloc((void **)&c->d_pb_bad, sizeof(int)));
+    HIPCHK(hipMemsetAsync(c->d_pb_bad, 0, sizeof(int), c->stream));
+  }
+  HIPCHK(launch_pb_invert(pb, (size_t)blocks->length / 9, n_bad ? c->d_pb_bad : nullptr, c->stream));
+  if (n_bad) {
+    HIPCHK(hipMemcpyAsync(n_bad, c->d_pb_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+extern "C" int CeedXVectorPointBlockMult(CeedVector w, CeedVector blocks, CeedVector x) {
+  const CeedInt n = x->length;
+  if (w->length != n) return ceed_error("CeedXVectorPointBlockMult: vector lengths differ");
+  CHK(pb_lengths("CeedXVectorPointBlockMult", blocks, n));
+  if (w == blocks || x == blocks) return ceed_error("CeedXVectorPointBlockMult: the block vector aliases an operand");
+  double *pw, *pb, *px;
+  CHK(vec_dev(blocks, false, &pb)); CHK(vec_dev(x, false, &px)); CHK(vec_dev(w, true, &pw));
+  HIPCHK(launch_pb_mult(pw, pb, px, (size_t)n / 3, w->ceed->stream));
+  return 0;
+}
+extern "C" int CeedXVectorChebyshevStepPointBlock(CeedVector x, CeedVector d, CeedVector r, CeedVector b, CeedVector t, CeedVector blocks,
+                                                  double c1, double c2, int assign_x) {
+  double *px, *pd, *pr = nullptr, *pb, *pt = nullptr, *pk;
+  const CeedInt n = x->length;
+  const bool has_r = r && r != CEED_VECTOR_NONE, has_t = t && t != CEED_VECTOR_NONE;
+  if (d->length != n || b->length != n || (has_r && r->length != n) || (has_t && t->length != n))
+    return ceed_error("CeedXVectorChebyshevStepPointBlock: vector lengths differ");
+  CHK(pb_lengths("CeedXVectorChebyshevStepPointBlock", blocks, n));
+  if (b == x || b == d || (has_r && b == r)) return ceed_error("CeedXVectorChebyshevStepPointBlock: the right-hand side must be a vector of its own");
+  if (x == d || (has_r && (x == r || d == r)) || (has_t && (t == x || t == d || (has_r && t == r))) || blocks == x || blocks == d || (has_r && blocks == r))
+    return ceed_error("CeedXVectorChebyshevStepPointBlock: x, d, r alias each other or an input");
+  CHK(vec_dev(blocks, false, &pk)); CHK(vec_dev(b, false, &pb));
+  if (has_t) CHK(vec_dev(t, false, &pt));
+  if (has_r) CHK(vec_dev(r, true, &pr));
+  CHK(vec_dev(d, true, &pd)); CHK(vec_dev(x, true, &px));
+  HIPCHK(launch_pb_cheb_step(px, pd, pr, pb, pt, pk, c1, c2, assign_x, (size_t)n / 3, x->ceed->stream));
   return 0;
 }
 extern "C" int CeedXVectorWAXPBY(CeedVector w, double a, CeedVector x, double b, CeedVector y) {

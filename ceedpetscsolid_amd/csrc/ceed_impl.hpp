@@ -86,6 +86,7 @@ struct Ceed_private {
   hipStream_t comm_stream = nullptr;
   double *d_scalar = nullptr;   // device scalar for reductions (1 + 2048 doubles)
   double *h_scalar = nullptr;   // pinned host landing slot for it (pageable targets make the runtime stage + pin per copy)
+  int *d_pb_bad = nullptr;      // device counter of CeedXVectorPointBlockInvert (bad pivots), allocated when first asked for
   // hipGraph capture (CeedXGraphBeginCapture): device work is recorded on `capture_stream`
   hipStream_t capture_stream = nullptr, saved_stream = nullptr;
   bool capturing = false;

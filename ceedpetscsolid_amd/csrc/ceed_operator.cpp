@@ -14,6 +14,7 @@
 //
 // There is NO host fallback: a graph outside these families or a QFunction without a device functor is a loud error.
 #include "ceed_impl.hpp"
+#include "kernels_pointblock.hpp"
 
 using namespace cps;
 
@@ -1043,6 +1044,43 @@ extern "C" int CeedOperatorLinearAssembleDiagonal(CeedOperator op, CeedVector as
   return 0;
 }
 
+// libCEED's point-block diagonal for the Jacobian operators (include/ceed.h): the scalar diagonal's call with the 3 x 3 nodal blocks
+// kept whole (kernels_pointblock.hip).  Element contributions go to the scratch E-vector with nine values per element node and are
+// summed per node in element order (launch_pb_assemble: the transpose map of launch_assemble, nine values wide -- the destination of
+// node offset o is 3 o, which the three-value kernel cannot address).  No atomics.
+extern "C" int CeedOperatorLinearAssemblePointBlockDiagonal(CeedOperator op, CeedVector assembled, CeedRequest *) {
+  if (op->composite) return ceed_error("point-block diagonal of a composite operator not supported");
+  CHK(op_plan(op));
+  if (op->plan != PLAN_FUSED_GRAD || op->o_state >= 0) return ceed_error("point-block diagonal assembly is provided for the Jacobian operators");
+  CeedQFunction qf = op->qf;
+  hipStream_t s = op->ceed->stream;
+  OpField &ai = op->in[op->i_active];
+  if (ai.rstr->ncomp != 3 || ai.rstr->compstride != 1) return ceed_error("point-block diagonal: the active field must have 3 interlaced components");
+  if (!assembled || assembled == CEED_VECTOR_NONE || assembled == CEED_VECTOR_ACTIVE || (size_t)assembled->length < 3 * (size_t)ai.rstr->lsize)
+    return ceed_error("point-block diagonal vector too short: %d entries for 3 x the L-size %d", assembled ? (int)assembled->length : 0, (int)ai.rstr->lsize);
+  PbDiagArgs a{};
+  double *pd, *pq, *ps = nullptr;
+  CHK(vec_dev(assembled, true, &pd));
+  CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
+  if (op->i_state >= 0) CHK(vec_dev(op->in[op->i_state].vec, false, &ps));
+  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : ai.rstr->d_offsets;
+  a.qdata = pq; a.state_in = ps; a.nelem = ai.rstr->nelem;
+  a.mask_in = (op->d_off_flagged_in && (op->mask_mode & 1)) ? 1 : 0; a.mask_out = (op->d_off_flagged_in && (op->mask_mode & 2)) ? 1 : 0;
+  CHK(read_phys(qf, &a.nu, &a.E));
+  lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
+  CHK(dev_zero(op->ceed, pd, (size_t)assembled->length));  // overwrite semantics; nodes no element holds keep a zero block
+  CHK(build_csr(ai.rstr, ai.rstr->csr, nullptr));
+  CHK(ceed_need_evec(op->ceed, (size_t)ai.rstr->nelem * ai.rstr->elemsize * 9));
+  a.evec = op->ceed->evec;
+  const char *kname = "";
+  hipError_t e = launch_pbdiag(ai.basis->P1d, ai.basis->Q1d, qf->kind, op->tables, a, s, &kname);
+  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no point-block diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, qf->name.c_str());
+  HIPCHK(e);
+  HIPCHK(launch_pb_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, a.evec, pd, ai.rstr->csr.nnodes, s));
+  op->kernel_name = kname;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // extensions
 // ---------------------------------------------------------------------------
@@ -1091,7 +1129,7 @@ extern "C" int CeedXOperatorApplyState(CeedOperator op, CeedVector u) {
 // the instantiation of the last apply; for the fused operators also how the geometric factors were obtained
 extern "C" int CeedXOperatorGetKernelName(CeedOperator op, const char **name) {
   if (op->plan == PLAN_FUSED_GRAD && !op->kernel_name.empty() && op->kernel_name.find(" [") == std::string::npos &&
-      op->kernel_name.compare(0, 6, "state<") != 0)
+      op->kernel_name.compare(0, 6, "state<") != 0 && op->kernel_name.compare(0, 7, "pbdiag<") != 0)
     op->kernel_name += op->geo_mode == 2 ? " [affine elements: dXdx per element]" : (op->geo_mode == 3 ? " [swept elements: 2 x 2 dXdx recomputed per point]" : (op->geo_mode == 1 ? " [dXdx recomputed per point]" : " [qdata read]"));
   *name = op->kernel_name.c_str();
   return 0;

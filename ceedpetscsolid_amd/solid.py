@@ -118,6 +118,7 @@ class SolidProblem:
             raise ValueError(f"coarse_quadrature must be 'fine' or 'own', not {coarse_quadrature!r}")
         self.coarse_quadrature, self.qextra = coarse_quadrature, qextra
         self._state_scratch = None
+        self._pb_asm = {}                                # level -> AssembledLevel of the portable point-block diagonal
         self.phys = np.array([nu, E], dtype=np.float64)  # Physics {nu, E}
         self.degrees = level_degrees(degree, multigrid)
         self.fine = len(self.degrees) - 1
@@ -348,6 +349,39 @@ class SolidProblem:
         """GetDiag_Ceed (matops.c:206-244)."""
         self.levels[level].opJacob.assemble_diagonal(d)
 
+    def get_pointblock_diag(self, level: int, blocks: cd.Vector):
+        """The 3 x 3 nodal blocks of the level's Jacobian (CeedOperatorLinearAssemblePointBlockDiagonal): [node][comp out][comp in],
+        the block of the node at component-0 L-offset o at 3 * o; ``blocks`` holds 3 x the level's L-size.  Like ``get_diag`` it reads
+        the QFunction context of the level's Jacobian as it is at the call (a smoother Poisson ratio swapped in stays in force).
+        Where the library lacks the entry point (the CPU oracle) the blocks are the diagonal blocks of the element
+        matrices of ``AssembledLevel(self, level)``, summed over the elements of a node: 3 P^3 applies through include/ceed.h calls
+        only, exact.  Constrained rows and columns are zero there (not the unit diagonal of the assembled matrix)."""
+        lv = self.levels[level]
+        if blocks.n < 3 * lv.dofmap.lsize:
+            raise cd.CeedError(f"point-block diagonal vector too short: {blocks.n} entries for 3 x the L-size {lv.dofmap.lsize}")
+        if self.ceed.L.has("CeedOperatorLinearAssemblePointBlockDiagonal"):
+            lv.opJacob.assemble_pointblock_diagonal(blocks)
+            return
+        from .assembly import AssembledLevel
+        if level not in self._pb_asm:
+            self._pb_asm[level] = AssembledLevel(self, level)
+        asm = self._pb_asm[level]
+        asm.qf.set_context(lv.qfJacob._ctx, reported_size=8)
+        asm.assemble()
+        ne, nd = asm.ne, asm.nd
+        P3 = nd // 3
+        K = asm.coo.to_numpy().reshape(P3, 3, ne, P3, 3)              # [n' c_in][e][n c_out]: column (n', c_in) of every element matrix
+        n = np.arange(P3)
+        eb = K[n, :, :, n, :].transpose(2, 0, 3, 1)                   # [e][n][c_out][c_in]
+        off = np.asarray(lv.dofmap.offsets(), dtype=np.int64).reshape(ne, P3)
+        out = np.zeros((blocks.n // 9 + 1, 3, 3))
+        np.add.at(out, off // 3, eb)                                  # elements in order
+        if self.fused_bc:
+            m = (lv.mask.reshape(-1, 3) != 0)
+            nn = m.shape[0]
+            out[:nn][m[:, :, None] | m[:, None, :]] = 0.0
+        blocks.set_array(out.reshape(-1)[:blocks.n])
+
     # --------------------------------------------------------------- helpers
     def smooth_state(self, amplitude: float = 0.1, origin=None, span=None) -> np.ndarray:
         return smooth_displacement(self.levels[self.fine].dofmap.node_coords, amplitude, origin, span)
@@ -364,6 +398,8 @@ class SolidProblem:
                         o.destroy()
         if self._state_scratch is not None:
             self._state_scratch.destroy()
+        for asm in self._pb_asm.values():
+            asm.destroy()
         for o in (self.opApply, self.qfApply, self.Erestrictx, self.Erestrictqdi, self.ErestrictGradui, self.basisx,
                   self.xcoord, self.qdata, self.gradu):
             if o is not None:

@@ -81,11 +81,23 @@ class NewtonPMG:
                  coarse: str = "cg", coarse_cheb_its: int = 40, coarse_cheb_ratio: float = 100.0, graph: bool = False,
                  amg_smooth_its: int = 3, amg_smooth_ratio: float = 10.0, amg_max_coarse_dofs: int = 1500, amg_coarse_cycles: int = 1,
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
-                 line_search: str = "cp", fuse_epilogue: bool = True):
+                 line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi"):
         """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
         set but absent here are held at zero."""
         self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
+        # smoother: what the Chebyshev iteration of every p-multigrid level, its eigenvalue estimate and the Jacobi-preconditioned
+        # coarse CG are preconditioned with -- "jacobi" (default, the reference: PCJACOBI on GetDiag_Ceed) or "pbjacobi": the inverted
+        # 3 x 3 nodal blocks (PCPBJACOBI on CeedOperatorLinearAssemblePointBlockDiagonal), which keep the coupling between the
+        # displacement components of a node that the scalar diagonal drops.  One rank only: the blocks of the interface nodes of
+        # an element partition would have to be summed over the ranks before they are inverted, and no exchange here carries nine
+        # values per node.
+        if smoother not in ("jacobi", "pbjacobi"):
+            raise ValueError(f"smoother must be 'jacobi' or 'pbjacobi', not {smoother!r}")
+        if smoother == "pbjacobi" and halo is not None and (halo[-1] if isinstance(halo, (list, tuple)) else halo).world > 1:
+            raise ValueError("smoother='pbjacobi' is not provided with a halo (several ranks): the nodal blocks of the interface nodes "
+                             "are not summed over the ranks")
+        self.smoother, self._pb = smoother, smoother == "pbjacobi"
         self.clamp, self.mms, self.halo = clamp or {}, mms, halo
         # "cp": critical-point secant search, up to three secant steps, a step outside (0, 10] ends the search (this build's default);
         # "cp-petsc": SNESLINESEARCHCP with PETSc's defaults (elasticity.c:596-601 sets the type and nothing else) as recalled from its
@@ -177,6 +189,9 @@ class NewtonPMG:
                     level.opJacob.set_overlap_split(int(lead_elements), self.halos[lv].interface_dof_mask())
         self._split = bool(self.rhalos) and lead_elements > 0
         self.w = [{k: self._vec(prob.lsize(lv), lv) for k in ("x", "b", "r", "d", "t", "dinv", "z")} for lv in range(self.nlev)]
+        if self._pb:
+            for lv in range(self.nlev):
+                self.w[lv]["pb"] = self._vec(3 * prob.lsize(lv), lv)      # the inverted 3 x 3 blocks, [node][c out][c in]
         self.emax = [1.0] * self.nlev
         self._x0 = {}
         self._scal = None
@@ -222,6 +237,13 @@ class NewtonPMG:
 
     def pmult(self, w, x, y):
         self.L.chk(self.L.lib.CeedXVectorPointwiseMult(w.h, x.h, y.h))
+
+    def minv(self, lv, z, r):
+        """z = M^-1 r with the smoother's preconditioner of level lv: the inverted diagonal, or the inverted nodal blocks."""
+        if self._pb:
+            cd.pointblock_mult(z, self.w[lv]["pb"], r)
+        else:
+            self.pmult(z, r, self.w[lv]["dinv"])
 
     def dot(self, x, y, fine_weight=False, lv=None) -> float:
         """x . y; on several ranks each dof counts once (owner weights of level `lv`, default the fine level)."""
@@ -361,13 +383,21 @@ class NewtonPMG:
                 self.amg.setup()                # Galerkin matrix of THIS Jacobian and its inverse
         for lv in range(self.nlev):
             w = self.w[lv]
-            self.p.get_diag(lv, w["dinv"])
-            self._halo_sum(lv, w["dinv"])
-            # 1 / diagonal; constrained rows come out of the masked operator as zeros and stay zero (CeedVectorReciprocal
-            # leaves zeros alone): residuals and corrections are zero there anyway.  No trip through the host.
-            w["dinv"].reciprocal()
-            if hasattr(w["dinv"], "t"):
-                self._touched(w["dinv"])
+            if self._pb:
+                # the 3 x 3 nodal blocks and their inverses; constrained components come out of the masked operator as zero rows and
+                # columns and are dropped by the inversion, as the reciprocal leaves the zeros of the scalar diagonal alone
+                self.p.get_pointblock_diag(lv, w["pb"])
+                n_bad = cd.pointblock_invert(w["pb"])
+                if n_bad:
+                    raise RuntimeError(f"smoother='pbjacobi': {n_bad} nodal blocks of level {lv} have a non-positive or non-finite pivot")
+            else:
+                self.p.get_diag(lv, w["dinv"])
+                self._halo_sum(lv, w["dinv"])
+                # 1 / diagonal; constrained rows come out of the masked operator as zeros and stay zero (CeedVectorReciprocal
+                # leaves zeros alone): residuals and corrections are zero there anyway.  No trip through the host.
+                w["dinv"].reciprocal()
+                if hasattr(w["dinv"], "t"):
+                    self._touched(w["dinv"])
             mask = self.p.levels[lv].mask != 0
             # The start vector of the eigenvalue estimate is drawn once per level; no BLAS on the host (a threaded BLAS
             # call leaves its worker pool spinning, which starves a CPU-quota'd process for ~0.1 s a call).
@@ -399,7 +429,7 @@ class NewtonPMG:
         w = self.w[lv]
         r, z, pv, Ap = w["r"], w["z"], w["d"], w["t"]
         self.copy(r, self._x0[lv])
-        self.pmult(z, r, w["dinv"]); self.copy(pv, z)
+        self.minv(lv, z, r); self.copy(pv, z)
         rz = self.dot(r, z, lv=lv)
         alphas, betas = [], []
         for _ in range(steps):
@@ -409,7 +439,7 @@ class NewtonPMG:
                 break
             alpha = rz / pAp
             self.axpby(r, -alpha, Ap, 1.0)
-            self.pmult(z, r, w["dinv"])
+            self.minv(lv, z, r)
             rz_new = self.dot(r, z, lv=lv)
             alphas.append(alpha); betas.append(rz_new / rz)
             self.axpby(pv, 1.0, z, rz_new / rz)
@@ -427,7 +457,7 @@ class NewtonPMG:
         sc = self._scal
         sc.set_value(0.0)
         self.copy(r, self._x0[lv])
-        self.pmult(z, r, w["dinv"]); self.copy(pv, z)
+        self.minv(lv, z, r); self.copy(pv, z)
         one, neg = C.c_double(1.0), C.c_double(-1.0)
         wv = self.weights[lv].h if self.weights[lv] is not None else None      # several ranks: every dof counts once
         many = bool(self.rhalos)
@@ -443,7 +473,7 @@ class NewtonPMG:
             dot_to(pv, Ap, 1)
             chk(lib.CeedXScalarDivide(sc.h, ja, rz, 1, one))                           # alpha_j = rz / pAp (0 on breakdown)
             chk(lib.CeedXVectorAXPBYScalars(r.h, sc.h, ja, neg, Ap.h, -1, one))         # r -= alpha Ap
-            self.pmult(z, r, w["dinv"])
+            self.minv(lv, z, r)
             dot_to(r, z, rz_new)
             chk(lib.CeedXScalarDivide(sc.h, jb, rz_new, rz, one))                       # beta_j = rz_new / rz
             chk(lib.CeedXVectorAXPBYScalars(pv.h, sc.h, -1, one, z.h, jb, one))         # p = z + beta p
@@ -470,9 +500,18 @@ class NewtonPMG:
         fused = self.L.lib.CeedXOperatorApplyChebyshev
         op = self._fused_op(lv)
 
+        def one_pb(c1, c2, have_x):
+            """d = c1 B (b - A x) + c2 d;  x (+)= d with the inverted nodal blocks B: the apply, then the block step (the fused
+            epilogue is a lane-per-dof kernel and has no block form)"""
+            if have_x:
+                self.A(lv, x, t)
+            cd.chebyshev_step_pointblock(x, d, None, b, t if have_x else None, w["pb"], c1, c2, not have_x)
+
         def one(c1, c2, have_x):
             """d = c1 dinv (b - A x) + c2 d;  x (+)= d   (have_x False: x = 0, no apply)"""
-            if not have_x:
+            if self._pb:
+                one_pb(c1, c2, have_x)
+            elif not have_x:
                 self.L.chk(step(x.h, d.h, None, b.h, None, w["dinv"].h, C.c_double(c1), C.c_double(c2), 1))
             elif op is not None:      # the apply and the step in one: A x is consumed where it is formed
                 self.L.chk(fused(op.h, x.h, t.h, x.h, d.h, None, b.h, w["dinv"].h, C.c_double(c1), C.c_double(c2), 0))
@@ -492,7 +531,7 @@ class NewtonPMG:
         r, d, t, z = w["r"], w["d"], w["t"], w["z"]
         x.set_value(0.0)
         self.copy(r, b)
-        self.pmult(z, r, w["dinv"]); self.copy(d, z)
+        self.minv(0, z, r); self.copy(d, z)
         rz = self.dot(r, z, lv=0)
         rz0 = rz
         if rz0 <= 0.0:
@@ -501,7 +540,7 @@ class NewtonPMG:
             self.A(0, d, t)
             alpha = rz / self.dot(d, t, lv=0)
             self.axpby(x, alpha, d, 1.0); self.axpby(r, -alpha, t, 1.0)
-            self.pmult(z, r, w["dinv"])
+            self.minv(0, z, r)
             rz_new = self.dot(r, z, lv=0)
             self.stats.coarse_its += 1
             if rz_new <= self.coarse_rtol ** 2 * rz0:
@@ -618,7 +657,7 @@ class NewtonPMG:
             self.stats.coarse_its += self._pc_graph_counts[1]
             return
         if self.nlev == 1:          # -multigrid none: Jacobi (elasticity.c:516-519)
-            self.pmult(z, r, self.w[0]["dinv"])
+            self.minv(0, z, r)
         else:
             self.vcycle(self.nlev - 1, r, z)
 

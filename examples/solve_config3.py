@@ -44,6 +44,8 @@ ap.add_argument("--coarse-quadrature", default="fine", choices=["fine", "own"],
                 help="fine: every multigrid level integrates on the fine level's points (the reference); own: a level below the fine one on "
                      "P_level + qextra Gauss points of its own (preconditioner only)")
 ap.add_argument("--level-times", action="store_true", help="time every level's Jacobian applies and the own-quadrature state refresh (CeedXOperatorSetTiming)")
+ap.add_argument("--smoother", default="jacobi", choices=["jacobi", "pbjacobi"],
+                help="preconditioner inside the Chebyshev smoothers: the inverted diagonal (the reference) or the inverted 3 x 3 nodal blocks (one rank)")
 ap.add_argument("--no-fuse", action="store_true", help="A/B: the smoother's Chebyshev step and the V-cycle's residual as passes of their own")
 args = ap.parse_args()
 if args.level_times and (args.graph or args.auto):
@@ -91,13 +93,13 @@ solver = NewtonPMG(prob, clamp={s: (dict(translate=tr) if s == 998 else dict()) 
                    coarse_maxit=args.coarse_maxit, coarse_rtol=args.coarse_rtol, coarse=args.coarse, graph="auto" if args.auto else args.graph,
                    coarse_cheb_its=args.coarse_cheb_its, coarse_cheb_ratio=args.coarse_cheb_ratio,
                    amg_smooth_its=args.amg_smooth_its, amg_smooth_ratio=args.amg_smooth_ratio, amg_max_coarse_dofs=args.amg_max_coarse, amg_coarse_cycles=args.amg_coarse_cycles,
-                   fuse_epilogue="auto" if args.auto else not args.no_fuse)
+                   fuse_epilogue="auto" if args.auto else not args.no_fuse, smoother=args.smoother)
 t_setup = time.perf_counter() - t0
 st = solver.solve(args.increments)
 u = solver.U.to_numpy().reshape(-1, 3)
 out = {"resource": ceed.resource, "problem": args.problem, "mesh": os.path.basename(args.mesh), "elements": mesh.nelem,
        "level_degrees": prob.degrees, "global_dofs_per_level": [prob.n_free(l) for l in range(len(prob.levels))],
-       "coarse_quadrature": args.coarse_quadrature, "level_points_1d": [lv.Q for lv in prob.levels],
+       "coarse_quadrature": args.coarse_quadrature, "smoother": args.smoother, "nu": args.nu, "level_points_1d": [lv.Q for lv in prob.levels],
        "translate_998": list(tr), "coarse_solver": args.coarse, "vcycle_graph": solver.graph, "fused_epilogue": solver.fuse_epilogue, "vcycle_tuning": solver.tuning, "load_increments": st.increments, "converged": st.converged, "snes_its": st.newton_its, "ksp_its": st.ksp_its,
        "coarse_cg_its": st.coarse_its, "jacobian_applies": st.jacobian_applies, "residual_evals": st.residual_evals, "coarse_spmv": st.coarse_spmv,
        "setup_s": t_setup, "snes_solve_s": st.seconds,

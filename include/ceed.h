@@ -346,6 +346,38 @@ CEED_EXTERN int CeedXOperatorApplyResidual(CeedOperator op, CeedVector in, CeedV
 /* refreshed from the fine displacement.  The active output does not exist for */
 /* this call; kernel name "state<Pf=..,Qc=..>".                                */
 CEED_EXTERN_OPTIONAL int CeedXOperatorApplyState(CeedOperator op, CeedVector u);
+/* OPTIONAL entry points: point-block Jacobi (PCPBJACOBI) for the 3-component  */
+/* displacement field.  A caller looks them up and, where they are absent,     */
+/* forms the blocks from element matrices assembled through the entry points   */
+/* above and does the small dense algebra itself.                              */
+/* libCEED's CeedOperatorLinearAssemblePointBlockDiagonal for the Jacobian     */
+/* operators: the 3 x 3 block of every node, [node][comp out][comp in] row-    */
+/* major; the block of the node whose component-0 L-offset is o sits at 3 * o, */
+/* so `assembled` has at least 3 x the L-size entries.  Overwrites `assembled`. */
+/* Nothing is symmetrised.  With a Dirichlet mask entry (c', c) is zero where  */
+/* the masked operator gives zero (row c' dropped, input c read as zero).  The */
+/* QFunction context is read at call time (the -nu_smoother swap of            */
+/* matops.c:215-232 works as for the diagonal).  Kernel name                   */
+/* "pbdiag<P=..,Q=..,LinElas|HyperSSdF|HyperFSdF>".                            */
+CEED_EXTERN_OPTIONAL int CeedOperatorLinearAssemblePointBlockDiagonal(CeedOperator op,
+    CeedVector assembled, CeedRequest *request);
+/* In place, per node: the components whose diagonal entry is exactly zero     */
+/* (constrained, or an L-vector entry no element holds) are dropped and the    */
+/* inverse of the remaining principal sub-block is embedded in zeros -- what   */
+/* CeedVectorReciprocal leaving zeros alone is for the scalar diagonal.        */
+/* *n_bad (or NULL) receives the number of blocks with a non-finite or non-    */
+/* positive pivot; reading it synchronises, NULL leaves the host out (and is   */
+/* the form that can be recorded in a CeedXGraph).                             */
+CEED_EXTERN_OPTIONAL int CeedXVectorPointBlockInvert(CeedVector blocks, int *n_bad /* or NULL */);
+/* w_n = B_n x_n for every node n (the lengths are multiples of 3, `blocks`    */
+/* holds at least 3 x the length of x).                                        */
+CEED_EXTERN_OPTIONAL int CeedXVectorPointBlockMult(CeedVector w, CeedVector blocks, CeedVector x);
+/* CeedXVectorChebyshevStep with dinv .* ri replaced by B_n ri_n:              */
+/*   ri = b - t (t may be NULL);  d = c1 * B ri + c2 * d;  x = d or x + d;     */
+/*   ri is stored only if r is not NULL.  x may alias no other operand.        */
+/* Recordable into a CeedXGraph like the scalar step.                          */
+CEED_EXTERN_OPTIONAL int CeedXVectorChebyshevStepPointBlock(CeedVector x, CeedVector d, CeedVector r /* or NULL */,
+    CeedVector b, CeedVector t /* or NULL */, CeedVector blocks, double c1, double c2, int assign_x);
 /* Assembled sparse operator on L-vectors: the coarse level of the multigrid. */
 /* The reference builds it by finite-difference colouring of the p=1 operator */
 /* (misc.c:151-183, elasticity.c:457-483) and hands it to GAMG; here the      */
