@@ -1013,70 +1013,62 @@ extern "C" int CeedOperatorApplyAdd(CeedOperator op, CeedVector in, CeedVector o
   return op_apply_single(op, in, out, true);
 }
 
-extern "C" int CeedOperatorLinearAssembleDiagonal(CeedOperator op, CeedVector assembled, CeedRequest *) {
-  if (op->composite) return ceed_error("diagonal of a composite operator not supported");
+// What the scalar diagonal and the point-block diagonal (width 1 / 3 values per L-dof of `assembled`) share: the checks, the kernel's
+// arguments up to a.evec, `assembled` zeroed (overwrite semantics, matops.c:227; nodes no element holds keep zeros), the transpose map
+// and the scratch E-vector.  Deterministic: element contributions -> E-vector -> per-node sums in element order, no atomics.
+static int diag_prepare(CeedOperator op, CeedVector assembled, int width, const char *who, DiagArgs &a, double **pd) {
+  if (op->composite) return ceed_error("%s of a composite operator not supported", who);
   CHK(op_plan(op));
-  if (op->plan != PLAN_FUSED_GRAD || op->o_state >= 0) return ceed_error("diagonal assembly is provided for the Jacobian operators");
-  CeedQFunction qf = op->qf;
-  hipStream_t s = op->ceed->stream;
-  OpField &ai = op->in[op->i_active];
-  DiagArgs a{};
-  double *pd, *pq, *ps = nullptr;
-  CHK(vec_dev(assembled, true, &pd));
+  if (op->plan != PLAN_FUSED_GRAD || op->o_state >= 0) return ceed_error("%s assembly is provided for the Jacobian operators", who);
+  CeedElemRestriction r = op->in[op->i_active].rstr;
+  if (width == 3 && (r->ncomp != 3 || r->compstride != 1)) return ceed_error("%s: the active field must have 3 interlaced components", who);
+  if (!assembled || assembled == CEED_VECTOR_NONE || assembled == CEED_VECTOR_ACTIVE || (size_t)assembled->length < (size_t)width * (size_t)r->lsize)
+    return ceed_error("%s vector too short: %d entries for %d x the L-size %d", who, assembled ? (int)assembled->length : 0, width, (int)r->lsize);
+  double *pq, *ps = nullptr;
+  CHK(vec_dev(assembled, true, pd));
   CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
   if (op->i_state >= 0) CHK(vec_dev(op->in[op->i_state].vec, false, &ps));
-  if (assembled->length < ai.rstr->lsize) return ceed_error("diagonal vector too short");
-  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : ai.rstr->d_offsets;
-  a.diag = pd; a.qdata = pq; a.state_in = ps; a.nelem = ai.rstr->nelem; a.mask_out = (op->mask_mode & 2) ? 1 : 0;
-  CHK(read_phys(qf, &a.nu, &a.E));
+  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : r->d_offsets;
+  a.qdata = pq; a.state_in = ps; a.nelem = r->nelem;
+  // one form for both widths: without flagged offsets the plain ones carry no flag bits, so the kernels read "nothing masked" either way
+  a.mask_in = (op->d_off_flagged_in && (op->mask_mode & 1)) ? 1 : 0; a.mask_out = (op->d_off_flagged_in && (op->mask_mode & 2)) ? 1 : 0;
+  CHK(read_phys(op->qf, &a.nu, &a.E));
   lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
-  CHK(dev_zero(op->ceed, pd, (size_t)assembled->length));  // overwrite semantics (matops.c:227)
-  // deterministic: element contributions -> E-vector -> per-node sums in element order
-  CHK(build_csr(ai.rstr, ai.rstr->csr, nullptr));
-  CHK(ceed_need_evec(op->ceed, (size_t)ai.rstr->nelem * ai.rstr->ncomp * ai.rstr->elemsize));
+  CHK(dev_zero(op->ceed, *pd, (size_t)assembled->length));
+  CHK(build_csr(r, r->csr, nullptr));
+  CHK(ceed_need_evec(op->ceed, (size_t)r->nelem * r->elemsize * 3 * width));
   a.evec = op->ceed->evec;
+  return 0;
+}
+
+extern "C" int CeedOperatorLinearAssembleDiagonal(CeedOperator op, CeedVector assembled, CeedRequest *) {
+  DiagArgs a{};
+  double *pd;
+  CHK(diag_prepare(op, assembled, 1, "diagonal", a, &pd));
+  OpField &ai = op->in[op->i_active];
   const char *kname = "";
-  hipError_t e = launch_diag(ai.basis->P1d, ai.basis->Q1d, qf->kind, op->tables, a, s, &kname);
-  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, qf->name.c_str());
+  hipError_t e = launch_diag(ai.basis->P1d, ai.basis->Q1d, op->qf->kind, op->tables, a, op->ceed->stream, &kname);
+  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
   HIPCHK(e);
   HIPCHK(launch_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, nullptr, a.evec, pd,
-                         ai.rstr->csr.nnodes, 0, s));
+                         ai.rstr->csr.nnodes, 0, op->ceed->stream));
   return 0;
 }
 
 // libCEED's point-block diagonal for the Jacobian operators (include/ceed.h): the scalar diagonal's call with the 3 x 3 nodal blocks
-// kept whole (kernels_pointblock.hip).  Element contributions go to the scratch E-vector with nine values per element node and are
-// summed per node in element order (launch_pb_assemble: the transpose map of launch_assemble, nine values wide -- the destination of
-// node offset o is 3 o, which the three-value kernel cannot address).  No atomics.
+// kept whole (k_pbdiag_sf, kernel_diag_sf.hpp).  Element contributions go to the scratch E-vector with nine values per element node and
+// are summed per node in element order (launch_pb_assemble: the transpose map of launch_assemble, nine values wide -- the destination
+// of node offset o is 3 o, which the three-value kernel cannot address).
 extern "C" int CeedOperatorLinearAssemblePointBlockDiagonal(CeedOperator op, CeedVector assembled, CeedRequest *) {
-  if (op->composite) return ceed_error("point-block diagonal of a composite operator not supported");
-  CHK(op_plan(op));
-  if (op->plan != PLAN_FUSED_GRAD || op->o_state >= 0) return ceed_error("point-block diagonal assembly is provided for the Jacobian operators");
-  CeedQFunction qf = op->qf;
-  hipStream_t s = op->ceed->stream;
+  DiagArgs a{};
+  double *pd;
+  CHK(diag_prepare(op, assembled, 3, "point-block diagonal", a, &pd));
   OpField &ai = op->in[op->i_active];
-  if (ai.rstr->ncomp != 3 || ai.rstr->compstride != 1) return ceed_error("point-block diagonal: the active field must have 3 interlaced components");
-  if (!assembled || assembled == CEED_VECTOR_NONE || assembled == CEED_VECTOR_ACTIVE || (size_t)assembled->length < 3 * (size_t)ai.rstr->lsize)
-    return ceed_error("point-block diagonal vector too short: %d entries for 3 x the L-size %d", assembled ? (int)assembled->length : 0, (int)ai.rstr->lsize);
-  PbDiagArgs a{};
-  double *pd, *pq, *ps = nullptr;
-  CHK(vec_dev(assembled, true, &pd));
-  CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
-  if (op->i_state >= 0) CHK(vec_dev(op->in[op->i_state].vec, false, &ps));
-  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : ai.rstr->d_offsets;
-  a.qdata = pq; a.state_in = ps; a.nelem = ai.rstr->nelem;
-  a.mask_in = (op->d_off_flagged_in && (op->mask_mode & 1)) ? 1 : 0; a.mask_out = (op->d_off_flagged_in && (op->mask_mode & 2)) ? 1 : 0;
-  CHK(read_phys(qf, &a.nu, &a.E));
-  lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
-  CHK(dev_zero(op->ceed, pd, (size_t)assembled->length));  // overwrite semantics; nodes no element holds keep a zero block
-  CHK(build_csr(ai.rstr, ai.rstr->csr, nullptr));
-  CHK(ceed_need_evec(op->ceed, (size_t)ai.rstr->nelem * ai.rstr->elemsize * 9));
-  a.evec = op->ceed->evec;
   const char *kname = "";
-  hipError_t e = launch_pbdiag(ai.basis->P1d, ai.basis->Q1d, qf->kind, op->tables, a, s, &kname);
-  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no point-block diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, qf->name.c_str());
+  hipError_t e = launch_pbdiag(ai.basis->P1d, ai.basis->Q1d, op->qf->kind, op->tables, a, op->ceed->stream, &kname);
+  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no point-block diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
   HIPCHK(e);
-  HIPCHK(launch_pb_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, a.evec, pd, ai.rstr->csr.nnodes, s));
+  HIPCHK(launch_pb_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, a.evec, pd, ai.rstr->csr.nnodes, op->ceed->stream));
   op->kernel_name = kname;
   return 0;
 }

@@ -173,13 +173,16 @@ struct SetupGeoArgs {
   int nelem;
 };
 
+// The scalar diagonal and the point-block diagonal (kernel_diag_sf.hpp; launch_diag here, launch_pbdiag in kernels_pointblock.hpp)
 struct DiagArgs {
-  const uint32_t *offsets;
-  double *diag;  // pre-zeroed L-vector
+  const uint32_t *offsets;  // [nelem][P^3] (flagged)
   const double *qdata, *state_in;
-  int nelem, mask_out;
+  int nelem;
+  // a dropped row zeroes its entry (scalar) / row c' of the node's block (mask_out); blocks only: entry (c', c) is also zero where
+  // input c reads as zero (mask_in).  The scalar diagonal has c' == c and never reads mask_in.
+  int mask_in, mask_out;
   double nu, E, lambda, TwoMu;
-  double *evec;  // element contributions ([elem][P^3][3]); launch_assemble() sums them
+  double *evec;  // element contributions, [elem][P^3][3] (launch_assemble() sums them) or [elem][P^3][c'][c] (launch_pb_assemble())
 };
 
 // The stored state of a level with its own quadrature (kernels_state.hip, k_state_at_points): grad u of the FINE displacement at the

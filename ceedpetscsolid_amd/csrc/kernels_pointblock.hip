@@ -1,155 +1,17 @@
 // kernels_pointblock.hip -- point-block Jacobi: the 3 x 3 nodal blocks of B^T D B (CeedOperatorLinearAssemblePointBlockDiagonal,
 // the matrix PCPBJACOBI inverts), their inverses, and the Chebyshev step that multiplies by them.
 //
-//   block_n[c'][c] = sum_q sum_{d,d2} g_d(n,q) D^{c'c}_{d d2}(q) g_d2(n,q)
-//
-// The scalar diagonal (kernels_misc.hip, k_diag_sf) probes the tangent D with nine unit gradients per point and keeps the entries
-// with c' == c.  Here nothing is dropped: THREE ROUNDS, one per input component c.  Round c probes with the three unit gradients of
-// component c, forms the 18 tensors S^{c'}_pair (3 output components x 6 direction pairs; g_d g_d2 is symmetric in (d, d2), so an
-// off-diagonal pair holds D_{d d2} + D_{d2 d} whatever the symmetry of D itself), contracts them with the product tables BB / BG / GG
-// exactly as k_diag_sf does, and ends with column c of every node's block.  The LDS slab is therefore k_diag_sf's own (147 KB at
-// Q = 8: the dynamic-shared-memory attribute); all 54 tensors at once would not fit from Q = 7.  27 tangent entries are live per round.
-// Nothing assumes a symmetric block: the tangent is written as the QFunction gives it.
-#include "kernels_common.hpp"
+// The element blocks are k_pbdiag_sf's: the scalar diagonal's sum-factorised scheme in three rounds, one per input component, defined
+// beside k_diag_sf in kernel_diag_sf.hpp.  This file instantiates it (the scalar kernel's instantiations are kernels_misc.hip's) and
+// holds the four lane-per-node kernels: the sum over a node's elements, the inverses, the product, the smoother step.
+#include "kernel_diag_sf.hpp"
 #include "kernels_pointblock.hpp"
-#include "qfunctions_device.hpp"
 
 namespace cps {
 
-template <int P, int Q, int QF>
-__global__ __launch_bounds__(Geom<Q>::TPE) void k_pbdiag_sf(const BasisTables tab, const PbDiagArgs a) {
-  using G = Geom<Q>;
-  constexpr int Q3 = G::Q3, P3 = P * P * P, TPE = G::TPE, NT = 18;
-  constexpr int PQQ = P * Q * Q, PPQ = P * P * Q, S0 = Q3 > PPQ ? Q3 : PPQ;
-  constexpr bool ST_IN = QFTraits<QF>::state_in;
-  extern __shared__ double dyn[];
-  double *sT = dyn;                  // [3][Q * P]: BB, BG, GG
-  double *s0 = sT + 3 * Q * P;       // [NT][Q3] the tensors, later [NT][P * P * Q]
-  double *s1 = s0 + NT * S0;         // [NT][P * Q * Q]
-  const int q = threadIdx.x, e = blockIdx.x;
-  for (int i = q; i < Q * P; i += TPE) {
-    const double bb = tab.interp[i], gg = tab.grad[i];
-    sT[i] = bb * bb; sT[Q * P + i] = bb * gg; sT[2 * Q * P + i] = gg * gg;
-  }
-  double qd[10], st[9];
-  if (q < Q3) {
-    const double *qp = a.qdata + (size_t)e * 10 * Q3 + q;
-#pragma unroll
-    for (int c = 0; c < 10; c++) qd[c] = qp[c * Q3];
-    if constexpr (ST_IN) {
-      const double *sp = a.state_in + (size_t)e * 9 * Q3 + q;
-#pragma unroll
-      for (int c = 0; c < 9; c++) st[c] = sp[c * Q3];
-    }
-  }
-  uint32_t fl_in = 0u, fl_out = 0u;
-  if (q < P3) {
-    const uint32_t fl = a.offsets[(size_t)e * P3 + q] >> OFF_FLAG_SHIFT;
-    fl_in = a.mask_in ? fl : 0u; fl_out = a.mask_out ? fl : 0u;
-  }
-  // table kind of pair p in direction dir: (d == dir) + (d2 == dir)  (0 BB, 1 BG, 2 GG)
-  auto kind = [](int p, int dir) {
-    const int d = p < 3 ? p : (p == 5 ? 1 : 0), d2 = p < 3 ? p : (p == 3 ? 1 : 2);
-    return (d == dir) + (d2 == dir);
-  };
-#pragma unroll 1
-  for (int c = 0; c < 3; c++) {      // round c: column c of every block
-    if (q < Q3) {
-      double dv[9], sto[9], ug[9], D[3][3][3];   // D[c'][dout][din]
-#pragma unroll
-      for (int din = 0; din < 3; din++) {
-#pragma unroll
-        for (int s = 0; s < 9; s++) ug[s] = (s == din * 3 + c) ? 1. : 0.;
-        qf_point<QF>(Phys{a.nu, a.E, a.lambda, a.TwoMu}, ug, qd, st, dv, sto);
-#pragma unroll
-        for (int co = 0; co < 3; co++)
-#pragma unroll
-          for (int dout = 0; dout < 3; dout++) D[co][dout][din] = dv[dout * 3 + co];
-      }
-#pragma unroll
-      for (int co = 0; co < 3; co++) {
-        s0[(co * 6 + 0) * Q3 + q] = D[co][0][0];
-        s0[(co * 6 + 1) * Q3 + q] = D[co][1][1];
-        s0[(co * 6 + 2) * Q3 + q] = D[co][2][2];
-        s0[(co * 6 + 3) * Q3 + q] = D[co][0][1] + D[co][1][0];
-        s0[(co * 6 + 4) * Q3 + q] = D[co][0][2] + D[co][2][0];
-        s0[(co * 6 + 5) * Q3 + q] = D[co][1][2] + D[co][2][1];
-      }
-    }
-    __syncthreads();
-    // x: U1[t][k][j][a] = sum_i T(i,a) S[t][k][j][i]
-    for (int o = q; o < NT * PQQ; o += TPE) {
-      const int t = o / PQQ, r = o % PQQ, aa = r % P, kj = r / P;
-      const double *T = sT + kind(t % 6, 0) * Q * P, *src = s0 + t * Q3 + kj * Q;
-      double v = 0.;
-#pragma unroll
-      for (int i = 0; i < Q; i++) v += T[i * P + aa] * src[i];
-      s1[o] = v;
-    }
-    __syncthreads();
-    // y: U2[t][k][b][a] = sum_j T(j,b) U1[t][k][j][a]
-    for (int o = q; o < NT * PPQ; o += TPE) {
-      const int t = o / PPQ, r = o % PPQ, aa = r % P, bb = (r / P) % P, k = r / (P * P);
-      const double *T = sT + kind(t % 6, 1) * Q * P, *src = s1 + t * PQQ + k * Q * P + aa;
-      double v = 0.;
-#pragma unroll
-      for (int j = 0; j < Q; j++) v += T[j * P + bb] * src[j * P];
-      s0[o] = v;
-    }
-    __syncthreads();
-    // z, and the sum over the pairs: one node per thread; entry (c', c) of its block
-    if (q < P3) {
-      const int ab = q % (P * P), nc = q / (P * P);
-      double *out = a.evec + ((size_t)e * P3 + q) * 9 + c;
-      const bool dead_in = (fl_in >> c) & 1u;
-#pragma unroll
-      for (int co = 0; co < 3; co++) {
-        double acc = 0.;
-#pragma unroll
-        for (int p = 0; p < 6; p++) {
-          const double *T = sT + kind(p, 2) * Q * P, *src = s0 + (co * 6 + p) * PPQ + ab;
-          double v = 0.;
-#pragma unroll
-          for (int k = 0; k < Q; k++) v += T[k * P + nc] * src[k * P * P];
-          acc += v;
-        }
-        out[co * 3] = (dead_in || ((fl_out >> co) & 1u)) ? 0. : acc;
-      }
-    }
-    __syncthreads();   // the next round overwrites s0
-  }
-}
-template <int P, int Q, int QF>
-static hipError_t pbdiag_t(const BasisTables &t, const PbDiagArgs &a, hipStream_t s) {
-  using G = Geom<Q>;
-  if (a.nelem <= 0) return hipSuccess;
-  static_assert(P * P * P <= G::TPE, "a lane per node in the last pass");
-  constexpr int PQQ = P * Q * Q, PPQ = P * P * Q, S0 = G::Q3 > PPQ ? G::Q3 : PPQ;
-  constexpr size_t lds = sizeof(double) * (3 * Q * P + 18 * (S0 + PQQ));
-  static_assert(lds <= 160 * 1024, "the slab fits the CU's LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t er = hipFuncSetAttribute((const void *)k_pbdiag_sf<P, Q, QF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (er != hipSuccess) return er;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_pbdiag_sf<P, Q, QF>), dim3(a.nelem), dim3(G::TPE), lds, s, t, a);
-  return hipGetLastError();
-}
-hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const PbDiagArgs &a, hipStream_t s, const char **name) {
-#define CPS_PB(Pv, Qv, QFv, nm)                                   \
-  if (P == Pv && Q == Qv && qf == QFv) {                          \
-    *name = "pbdiag<P=" #Pv ",Q=" #Qv "," nm ">";                 \
-    return pbdiag_t<Pv, Qv, QFv>(t, a, s);                        \
-  }
-#define CPS_PB3(Pv, Qv) CPS_PB(Pv, Qv, QF_LINELAS, "LinElas") CPS_PB(Pv, Qv, QF_HYPERSS_DF, "HyperSSdF") \
-  CPS_PB(Pv, Qv, QF_HYPERFS_DF, "HyperFSdF")
-  // the (P, Q) set of the scalar diagonal (launch_diag)
-  CPS_PB3(2, 2) CPS_PB3(2, 3) CPS_PB3(3, 3) CPS_PB3(2, 4) CPS_PB3(3, 4) CPS_PB3(4, 4)
-  CPS_PB3(2, 5) CPS_PB3(3, 5) CPS_PB3(4, 5) CPS_PB3(5, 5) CPS_PB3(2, 7) CPS_PB3(3, 7) CPS_PB3(5, 7) CPS_PB3(7, 7)
-  CPS_PB3(2, 6) CPS_PB3(3, 6) CPS_PB3(4, 6) CPS_PB3(5, 6) CPS_PB3(6, 6) CPS_PB3(4, 7) CPS_PB3(6, 7)
-  CPS_PB3(2, 8) CPS_PB3(3, 8) CPS_PB3(4, 8) CPS_PB3(5, 8) CPS_PB3(6, 8) CPS_PB3(7, 8) CPS_PB3(8, 8)
-#undef CPS_PB3
+hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const DiagArgs &a, hipStream_t s, const char **name) {
+#define CPS_PB(Pv, Qv) CPS_DIAG_CASES(k_pbdiag_sf, "pbdiag", Pv, Qv)
+  CPS_DIAG_PQ(CPS_PB)
 #undef CPS_PB
   return hipErrorInvalidValue;
 }

@@ -6,17 +6,9 @@
 
 namespace cps {
 
-struct PbDiagArgs {
-  const uint32_t *offsets;  // [nelem][P^3] (flagged)
-  const double *qdata, *state_in;
-  int nelem;
-  int mask_in, mask_out;    // entry (c', c) of a node's block is zero where input c reads as zero / row c' is dropped
-  double nu, E, lambda, TwoMu;
-  double *evec;             // element contributions [elem][P^3][c'][c]; launch_pb_assemble() sums them
-};
 // `name` as for launch_diag: "pbdiag<P=..,Q=..,LinElas|HyperSSdF|HyperFSdF>", hipErrorInvalidValue with *name untouched when the
-// combination is not instantiated (the set of launch_diag)
-hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const PbDiagArgs &a, hipStream_t s, const char **name);
+// combination is not instantiated (the set of launch_diag: CPS_DIAG_PQ, kernel_diag_sf.hpp)
+hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const DiagArgs &a, hipStream_t s, const char **name);
 // blocks[3 * node_off[r] + j] = sum over the node's contributors, in element order, of evec[9 * cols[k] + j], j < 9: the transpose
 // map of launch_assemble() with nine values per contributor.  No atomics.
 hipError_t launch_pb_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const double *evec,

@@ -1,14 +1,14 @@
 """The device kernels a default build instantiates, restated as data, and the plan of problem builds that launches every one of them.
 
-The dispatch tables of csrc (kernels_fused_inst.hip CPS_CASE / CPS_LEVEL, kernels_misc.hip CPS_DG3 / CPS_TR / CPS_SG, kernels_state.hip
-CPS_ST) are the product; this module is their second statement.  test_kernel_inventory.py holds the two against each other on the code
-objects of the build (both directions), and holds the plan below against the matrix; test_kernel_matrix_gpu.py runs the plan.  Whoever
-adds or drops an instantiation has to change the matrix here, and the sweep follows.
+The dispatch tables of csrc (kernels_fused_inst.hip CPS_CASE / CPS_LEVEL, kernel_diag_sf.hpp CPS_DIAG_PQ, kernels_misc.hip CPS_TR / CPS_SG,
+kernels_state.hip CPS_ST) are the product; this module is their second statement.  test_kernel_inventory.py holds the two against each
+other on the code objects of the build (both directions), and holds the plan below against the matrix; test_kernel_matrix_gpu.py runs
+the plan.  Whoever adds or drops an instantiation has to change the matrix here, and the sweep follows.
 
 A kernel is a tuple:
   ("fused", P, Q, qf, geo)                k_fused_pencil<P, Q, QF, GEO>; qf one of FUSED_QF, geo 0 qdata read, 1 recomputed per point,
                                           2 affine elements, 3 swept elements
-  ("diag", P, Q, qf)                      k_diag_sf<P, Q, QF>
+  ("diag", P, Q, qf)                      k_diag_sf<P, Q, QF>; k_pbdiag_sf<P, Q, QF> is instantiated for the same set (pbdiag_of_symbol)
   ("transfer", Pc, Pf, prolong, weighted) k_transfer<Pc, Pf, PROLONG, WEIGHTED>
   ("state", Pf, Qc)                       k_state_at_points<Pf, Qc>
   ("setup_geo", Q)                        k_setup_geo<Q>
@@ -93,6 +93,16 @@ def kernel_of_symbol(mangled):
         if m:
             return make(m)
     return None
+
+
+_MANGLED_PBDIAG = re.compile(r"\d+k_pbdiag_sfILi(\d+)ELi(\d+)ELi(\d+)EE")
+
+
+def pbdiag_of_symbol(mangled):
+    """The ("diag", P, Q, qf) shape of a mangled k_pbdiag_sf<P, Q, QF>, else None: the point-block diagonal is no family of its own, it is
+    built for the shapes of the scalar one (one list in csrc, CPS_DIAG_PQ)."""
+    m = _MANGLED_PBDIAG.search(mangled)
+    return ("diag", int(m[1]), int(m[2]), DIAG_QF.get(int(m[3]), int(m[3]))) if m else None
 
 
 def show(k):

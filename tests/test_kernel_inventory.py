@@ -33,6 +33,7 @@ def built():
         pytest.skip("no objects under csrc/build: this checkout was never built")
     guard = _isa_guard()
     found = {fam: set() for fam in km.FAMILIES}
+    found["pbdiag"] = set()                                   # the shapes of k_pbdiag_sf: no family of its own (km.pbdiag_of_symbol)
     with tempfile.TemporaryDirectory() as tmp:
         for obj in objs:
             with open(obj, "rb") as f:
@@ -45,6 +46,10 @@ def built():
                 if k is not None:
                     assert k not in found[k[0]], f"{km.show(k)} is defined in two objects"
                     found[k[0]].add(k)
+                k = km.pbdiag_of_symbol(mangled)
+                if k is not None:
+                    assert k not in found["pbdiag"], f"k_pbdiag_sf of {km.show(k)} is defined in two objects"
+                    found["pbdiag"].add(k)
     return found
 
 
@@ -56,6 +61,13 @@ def _diff(have, want):
 def test_build_holds_exactly_the_matrix(built, family):
     missing, extra = _diff(built[family], km.matrix()[family])
     assert not missing and not extra, f"{family}: in the matrix but not built: {missing}; built but not in the matrix: {extra}"
+
+
+def test_point_block_diagonal_is_built_for_the_shapes_of_the_scalar_one(built):
+    """k_pbdiag_sf<P,Q,QF> against matrix()["diag"]: a level with a scalar diagonal and no blocks (or the reverse) fails at solve time."""
+    missing, extra = _diff(built["pbdiag"], km.matrix()["diag"])
+    assert len(built["pbdiag"]) == COUNTS["diag"] and not missing and not extra, \
+        f"k_pbdiag_sf: shapes of k_diag_sf without blocks: {missing}; blocks without a scalar diagonal: {extra}"
 
 
 @pytest.mark.parametrize("family", list(km.FAMILIES))
@@ -77,3 +89,6 @@ def test_symbol_parser_reads_the_template_arguments():
     assert km.kernel_of_symbol("_ZN3cps9k_diag_sfILi2ELi8ELi4EEEvNS_11BasisTablesENS_8DiagArgsE") == ("diag", 2, 8, "HyperSSdF")
     assert km.kernel_of_symbol("_ZN3cps11k_setup_geoILi8EEEvNS_11BasisTablesENS_12SetupGeoArgsE") == ("setup_geo", 8)
     assert km.kernel_of_symbol("_ZN3cps10k_assembleEPKjS1_S1_PKhPKdPdii") is None
+    assert km.kernel_of_symbol("_ZN3cps11k_pbdiag_sfILi2ELi8ELi4EEEvNS_11BasisTablesENS_8DiagArgsE") is None
+    assert km.pbdiag_of_symbol("_ZN3cps11k_pbdiag_sfILi2ELi8ELi4EEEvNS_11BasisTablesENS_8DiagArgsE") == ("diag", 2, 8, "HyperSSdF")
+    assert km.pbdiag_of_symbol("_ZN3cps9k_diag_sfILi2ELi8ELi4EEEvNS_11BasisTablesENS_8DiagArgsE") is None
