@@ -135,6 +135,7 @@ struct CsrMap {
   int nnodes = 0, nprio = 0, nskipped = 0;
   std::vector<uint32_t> h_node_off, h_rowptr, h_cols;   // host copies (the re-ordered maps are derived from them)
   uint32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_node_off = nullptr;
+  cps::NodeMap view() const { return cps::NodeMap{d_rowptr, d_cols, d_node_off, nnodes, 0}; }
   void release() {
     if (d_rowptr) (void)hipFree(d_rowptr);
     if (d_cols) (void)hipFree(d_cols);
@@ -153,6 +154,7 @@ struct PipeMap {
   std::vector<int> elem_bound, row_bound;  // nseg + 1 each
   std::vector<uint32_t> h_node_off;        // re-ordered (for the per-operator Dirichlet flags)
   uint32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_node_off = nullptr;
+  cps::NodeMap view() const { return cps::NodeMap{d_rowptr, d_cols, d_node_off, nrows, 0}; }
 };
 
 struct CeedElemRestriction_private {

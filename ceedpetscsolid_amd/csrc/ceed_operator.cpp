@@ -500,12 +500,14 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
   a.evec = c->evec;
   return 0;
 }
+// a dispatch that holds no instantiation for the shape returns hipErrorInvalidValue and leaves the name empty
+static bool no_kernel(hipError_t e, const char *const *kname) { return e == hipErrorInvalidValue && !**kname; }
 // one launch of the fused kernel over elements [e0, e0 + ne)
 static int fused_launch(CeedOperator op, const FusedApply &F, int e0, int ne, int wave_groups, hipStream_t s, const char **kname) {
   FusedGradArgs ak = F.a;
   ak.elem_begin = e0; ak.nelem = ne; ak.wave_groups = wave_groups;
   hipError_t e = launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, ak, s, kname);
-  if (e == hipErrorInvalidValue && !**kname)
+  if (no_kernel(e, kname))
     return ceed_error("no fused kernel instantiated for P=%d Q=%d QFunction %s", F.b->P1d, F.b->Q1d, op->qf->name.c_str());
   HIPCHK(e);
   op->geo_mode = F.a.geo_aff && F.a.geo ? 2 : (F.a.geo_swept && F.a.geo ? 3 : (F.a.geo ? 1 : 0));
@@ -513,11 +515,7 @@ static int fused_launch(CeedOperator op, const FusedApply &F, int e0, int ne, in
 }
 static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s, const HaloUnpackArgs *un = nullptr,
                          const HaloPackFold *pk = nullptr) {
-  const CsrMap *M = F.M;
-  HaloPackFold p0{nullptr, nullptr, nullptr};
-  if (pk) p0 = HaloPackFold{pk->ptr + row0, pk->slot, pk->send};
-  HIPCHK(launch_assemble(M->d_rowptr + row0, M->d_cols, M->d_node_off + row0, F.flags ? F.flags + row0 : nullptr, F.a.evec, F.py,
-                         nrows, F.add ? 1 : 0, s, un, pk ? &p0 : nullptr));
+  HIPCHK(launch_assemble(F.M->view().rows(row0, nrows), F.flags, F.a.evec, F.py, F.add ? 1 : 0, s, un, pk));
   return 0;
 }
 // The pack of halo H folded into the launch that sums the rows of map M: per row the send slots of its node's entries.
@@ -593,7 +591,7 @@ static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM, co
     HIPCHK(hipEventRecord(c->ev_seg[k], sk));
     if (k >= 1) HIPCHK(hipStreamWaitEvent(sk, c->ev_seg[k - 1], 0));
     const int r0 = PM->row_bound[k], nr = PM->row_bound[k + 1] - r0;
-    HIPCHK(launch_assemble(PM->d_rowptr + r0, PM->d_cols, PM->d_node_off + r0, fl ? fl + r0 : nullptr, F.a.evec, F.py, nr, 0, sk));
+    HIPCHK(launch_assemble(PM->view().rows(r0, nr), fl, F.a.evec, F.py, 0, sk));
   }
   HIPCHK(hipEventRecord(c->ev_join, c->side_stream));
   HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
@@ -615,6 +613,15 @@ static int choose_pipe(CeedOperator op, const FusedApply &F, PipeMap **PM) {
   const bool fs = F.qfkind == QF_HYPERFS_DF || F.qfkind == QF_HYPERFS_DF_DS || F.qfkind == QF_HYPERFS_F;
   const int mb = c->opt.pipe_mb > 0 ? c->opt.pipe_mb : (fs ? 160 : 90);     // MB of E-vector per segment (get_pipe)
   return get_pipe(F.r, *F.M, pencil_group_elems(F.b->Q1d), per_elem, std::max(c->opt.pipe_segments, 0), waves, mb, PM);
+}
+
+// The interface sum of y behind a whole apply, in order on s: the pack (unless the rows' launch has done it), the RCCL group, the
+// unpack-add launch.
+static int halo_sum_behind(CeedXHalo H, double *y, bool packed, hipStream_t s) {
+  if (packed) CHK(halo_send(H, s)); else CHK(halo_pack_and_send(H, y, s));
+  CHK(halo_wait_arrivals(H, s));
+  HIPCHK(launch_halo_unpack_add(halo_unpack_args(H), y, s));
+  return 0;
 }
 
 // phase -1: whole apply; phase 0 / 1: the two halves of a split-phase apply (CeedXOperatorApplyPhase), one after the other
@@ -648,11 +655,7 @@ static int apply_fused_grad(CeedOperator op, CeedVector in, CeedVector out, bool
   if (c->opt.pipe_segments != 0 && !add) CHK(choose_pipe(op, F, &PM));
   if (PM && PM->nseg >= 2) {
     CHK(apply_pipelined(op, F, PM, kname));
-    if (H) {
-      CHK(halo_pack_and_send(H, F.py, s));
-      CHK(halo_wait_arrivals(H, s));
-      HIPCHK(launch_halo_unpack_add(halo_unpack_args(H), F.py, s));
-    }
+    if (H) CHK(halo_sum_behind(H, F.py, false, s));
     op->launches++;
     return 0;
   }
@@ -662,11 +665,7 @@ static int apply_fused_grad(CeedOperator op, CeedVector in, CeedVector out, bool
   bool folded = false;
   if (H && c->opt.fold_pack) CHK(get_pack_fold(op, F.r, M, H, &pk, &folded));
   CHK(assemble_rows(F, 0, M->nnodes, s, nullptr, folded ? &pk : nullptr));   // timed together with the fused kernel: the launches ARE the operator apply
-  if (H) {
-    if (folded) CHK(halo_send(H, s)); else CHK(halo_pack_and_send(H, F.py, s));
-    CHK(halo_wait_arrivals(H, s));
-    HIPCHK(launch_halo_unpack_add(halo_unpack_args(H), F.py, s));
-  }
+  if (H) CHK(halo_sum_behind(H, F.py, folded, s));
   op->launches++;
   return 0;
 }
@@ -695,7 +694,7 @@ static int apply_fused_epilogue(CeedOperator op, CeedVector in, CeedVector t, Ep
   CHK(fused_launch(op, F, 0, F.r->nelem, 0, s, kname));
   ep.int_off = nint ? F.r->d_int_off : nullptr;
   ep.n_int = F.r->nelem * nint;
-  HIPCHK(launch_assemble_epi(M->d_rowptr, M->d_cols, M->d_node_off, F.flags, F.a.evec, M->nnodes, ep, s));
+  HIPCHK(launch_assemble_epi(M->view(), F.flags, F.a.evec, ep, s));
   op->launches++;
   return 0;
 }
@@ -762,7 +761,7 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
 }
 
 // ---------------------------------------------------------------------------
-// The transfer operators in OWNER form (kernels_misc.hip, k_transfer)
+// The transfer operators in OWNER form (kernels_transfer.hip, k_transfer)
 // ---------------------------------------------------------------------------
 // own_f[e][n] = offset | fine-side Dirichlet flags if element e is the FIRST (in element order) to hold fine node n, else
 // 0xFFFFFFFF.  Set-up time, host; rebuilt when the operator's mask changes.
@@ -844,7 +843,7 @@ static int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool a
   CHK(vec_dev(in, false, &px));
   CHK(vec_dev(out, true, &py));
   if (op->scale && op->scale->length < rf->lsize) return ceed_error("scale vector too short");
-  // OWNER form (kernels_misc.hip): the fine nodes each element owns, and the weights (null: all 1, the one-rank case)
+  // OWNER form (kernels_transfer.hip): the fine nodes each element owns, and the weights (null: all 1, the one-rank case)
   CHK(transfer_owner_map(op, rf));
   CHK(transfer_weights(op, rf, &a.w_f));
   // the coarse side's flagged offsets: the input side of a prolongation, the output side of a restriction
@@ -867,9 +866,9 @@ static int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool a
   }
   TimerScope ts(op, s);
   hipError_t e = launch_transfer(b->P1d, b->Q1d, pro, op->tables, a, s, kname);
-  if (e == hipErrorInvalidValue && !**kname) return ceed_error("no transfer kernel for Pc=%d Pf=%d", b->P1d, b->Q1d);
+  if (no_kernel(e, kname)) return ceed_error("no transfer kernel for Pc=%d Pf=%d", b->P1d, b->Q1d);
   HIPCHK(e);
-  if (!pro) HIPCHK(launch_assemble(rc->csr.d_rowptr, rc->csr.d_cols, rc->csr.d_node_off, nullptr, a.evec, py, rc->csr.nnodes, add ? 1 : 0, s));
+  if (!pro) HIPCHK(launch_assemble(rc->csr.view(), nullptr, a.evec, py, add ? 1 : 0, s));
   op->launches++;
   return 0;
 }
@@ -920,7 +919,7 @@ static int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out, const
   if ((size_t)out->length < (size_t)a.nelem * 10 * x.basis->Q1d * x.basis->Q1d * x.basis->Q1d) return ceed_error("qdata vector too short");
   TimerScope ts(op, s);
   hipError_t e = launch_setup_geo(x.basis->Q1d, op->tables, a, s, kname);
-  if (e == hipErrorInvalidValue && !**kname) return ceed_error("no setup_geo kernel for Q=%d", x.basis->Q1d);
+  if (no_kernel(e, kname)) return ceed_error("no setup_geo kernel for Q=%d", x.basis->Q1d);
   HIPCHK(e);
   op->launches++;
   // trilinear elements (coordinate basis P = 2): keep the map coefficients with the qdata vector
@@ -1048,10 +1047,9 @@ extern "C" int CeedOperatorLinearAssembleDiagonal(CeedOperator op, CeedVector as
   OpField &ai = op->in[op->i_active];
   const char *kname = "";
   hipError_t e = launch_diag(ai.basis->P1d, ai.basis->Q1d, op->qf->kind, op->tables, a, op->ceed->stream, &kname);
-  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
+  if (no_kernel(e, &kname)) return ceed_error("no diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
   HIPCHK(e);
-  HIPCHK(launch_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, nullptr, a.evec, pd,
-                         ai.rstr->csr.nnodes, 0, op->ceed->stream));
+  HIPCHK(launch_assemble(ai.rstr->csr.view(), nullptr, a.evec, pd, 0, op->ceed->stream));
   return 0;
 }
 
@@ -1066,9 +1064,9 @@ extern "C" int CeedOperatorLinearAssemblePointBlockDiagonal(CeedOperator op, Cee
   OpField &ai = op->in[op->i_active];
   const char *kname = "";
   hipError_t e = launch_pbdiag(ai.basis->P1d, ai.basis->Q1d, op->qf->kind, op->tables, a, op->ceed->stream, &kname);
-  if (e == hipErrorInvalidValue && !*kname) return ceed_error("no point-block diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
+  if (no_kernel(e, &kname)) return ceed_error("no point-block diagonal kernel for P=%d Q=%d %s", ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
   HIPCHK(e);
-  HIPCHK(launch_pb_assemble(ai.rstr->csr.d_rowptr, ai.rstr->csr.d_cols, ai.rstr->csr.d_node_off, a.evec, pd, ai.rstr->csr.nnodes, op->ceed->stream));
+  HIPCHK(launch_pb_assemble(ai.rstr->csr.view(), a.evec, pd, op->ceed->stream));
   op->kernel_name = kname;
   return 0;
 }
@@ -1111,7 +1109,7 @@ extern "C" int CeedXOperatorApplyState(CeedOperator op, CeedVector u) {
   {
     TimerScope ts(op, s);
     hipError_t e = launch_state_at_points(b->P1d, b->Q1d, op->tables, a, s, &kname);
-    if (e == hipErrorInvalidValue && !*kname) return ceed_error("no state kernel instantiated for Pf=%d Qc=%d", b->P1d, b->Q1d);
+    if (no_kernel(e, &kname)) return ceed_error("no state kernel instantiated for Pf=%d Qc=%d", b->P1d, b->Q1d);
     HIPCHK(e);
   }
   op->launches++;

@@ -15,7 +15,7 @@
 //                All 54 tensors at once would not fit the LDS from Q = 7; 27 tangent entries are live per round.  Nothing assumes a
 //                symmetric block: the tangent is written as the QFunction gives it.
 // Everything else -- the slab, the tables, the store of the tensors, the three passes -- is stated here once (sf_*), and so are the
-// launcher and the (P, Q) list.  The instantiations stay in two objects: kernels_misc.hip (scalar), kernels_pointblock.hip (blocks).
+// launcher and the (P, Q) list.  The instantiations stay in two objects: kernels_dispatch.hip (scalar), kernels_pointblock.hip (blocks).
 #pragma once
 #include "kernels_common.hpp"
 #include "qfunctions_device.hpp"

@@ -133,7 +133,7 @@ __host__ __device__
 #endif
 static inline int element_shell_size(int P) { return P * P * P - (P > 2 ? (P - 2) * (P - 2) * (P - 2) : 0); }
 
-// p-multigrid transfer in OWNER form (kernels_misc.hip, k_transfer): every fine node belongs to the first element that holds it.
+// p-multigrid transfer in OWNER form (kernels_transfer.hip, k_transfer): every fine node belongs to the first element that holds it.
 struct TransferArgs {
   const uint32_t *off_c;  // coarse [nelem][Pc^3], the coarse side's Dirichlet flags in the top bits
   const uint32_t *own_f;  // fine   [nelem][Pf^3]: offset | Dirichlet flags of the nodes this element OWNS, 0xFFFFFFFF for the others
@@ -218,19 +218,25 @@ constexpr int pencil_inst_parts(int Q) { return Q == 8 ? 4 : (Q == 7 ? 2 : 1); }
 // (Q = 5: two; one element per wave was 8-25 % slower, profiles/r03_ab_experiments.txt item 12)
 constexpr int pencil_group_elems(int Q) { return Q <= 2 ? 8 : (Q <= 4 ? 4 : (Q == 5 ? 2 : 1)); }
 
-// Deterministic, atomic-free E^T: y[node_off[r] + c] (+)= sum over the node's contributors, in element
-// order, of E[3 * cols[k] + c] (cols[k] = e * P3 + n).  `flags` (one byte per node, bit c = component c constrained) may be null.
+// The transpose map of a restriction as the kernels read it: rows [row0, row0 + nnodes) of rowptr / node_off, the contributors
+// of row r being cols[rowptr[r] .. rowptr[r + 1]).  Made from a CsrMap or a PipeMap by their view() (ceed_impl.hpp).
+struct NodeMap {
+  const uint32_t *rowptr, *cols, *node_off;
+  int nnodes, row0;
+  NodeMap rows(int first, int n) const { return NodeMap{rowptr, cols, node_off, n, first}; }
+};
+// Deterministic, atomic-free E^T (kernels_assemble.hip): y[node_off[r] + c] (+)= sum over the node's contributors, in element
+// order, of E[3 * cols[k] + c] (cols[k] = e * P3 + n).  `flags` (one byte per node of the whole map, bit c = component c constrained) may be null.
 // `unpack` (may be null): the arrivals of a halo exchange, added to y by extra workgroups of the SAME launch (one launch
 // less on the critical path of a split-phase apply): y[dst[u]] += recv[slot[k]], k in [ptr[u], ptr[u+1]), in list order.
 struct HaloUnpackArgs { const uint32_t *dst, *ptr, *slot; const double *recv; int n; };
 // `pack` (may be null): the pack of a halo exchange folded into the rows' launch -- row r's finished sums also go to
-// send[slot[k] & 0x3FFFFFFF], component slot[k] >> 30, k in [ptr[r], ptr[r+1]) (ptr over the rows of THIS launch).
+// send[slot[k] & 0x3FFFFFFF], component slot[k] >> 30, k in [ptr[r], ptr[r+1]) (ptr, like `flags`, over the rows of the whole map).
 struct HaloPackFold { const uint32_t *ptr, *slot; double *send; };
-hipError_t launch_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off,
-                           const unsigned char *flags, const double *evec, double *y, int nnodes,
-                           int add, hipStream_t s, const HaloUnpackArgs *unpack = nullptr, const HaloPackFold *pack = nullptr);
+hipError_t launch_assemble(const NodeMap &m, const unsigned char *flags, const double *evec, double *y, int add, hipStream_t s,
+                           const HaloUnpackArgs *unpack = nullptr, const HaloPackFold *pack = nullptr);
 
-// The same sum with an epilogue in place of the store of y (kernels_misc.hip, k_assemble_epi): the output of a fused apply consumed
+// The same sum with an epilogue in place of the store of y (k_assemble_epi): the output of a fused apply consumed
 // where it is formed -- a Chebyshev step or the residual b - A v.
 enum EpilogueKind : int { EPI_NONE = 0, EPI_CHEB = 1, EPI_RESID = 2 };
 struct EpilogueArgs {
@@ -248,8 +254,7 @@ struct EpilogueArgs {
   double *w;
   const double *b;
 };
-hipError_t launch_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const unsigned char *flags,
-                               const double *evec, int nnodes, const EpilogueArgs &ep, hipStream_t s);
+hipError_t launch_assemble_epi(const NodeMap &m, const unsigned char *flags, const double *evec, const EpilogueArgs &ep, hipStream_t s);
 
 // Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.
 struct CoordOpArgs {
@@ -301,7 +306,7 @@ hipError_t launch_csr_spgemm(const uint32_t *l_rowptr, const uint32_t *l_cols, c
                              // max_row_c > 0: the longest row of C -- up to 4096 entries a wave per row with an LDS accumulator (k_csr_spgemm_row)
 hipError_t launch_dense_spd_inverse(double *A, int n, double *scratch /* 1024 doubles */, int *info, hipStream_t s);
 
-// Vector / restriction utilities.
+// Vector utilities (kernels_vector.hip) and the plain restriction (kernels_assemble.hip).
 hipError_t launch_set_value(double *v, size_t n, double val, hipStream_t s);
 hipError_t launch_waxpby(double *w, double a, const double *x, double b, const double *y, size_t n, hipStream_t s);
 hipError_t launch_cheb_update(double *x, double *d, double *r, const double *r0, const double *t, const double *dinv, double c1, double c2,

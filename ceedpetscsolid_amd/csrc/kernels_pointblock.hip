@@ -2,7 +2,7 @@
 // the matrix PCPBJACOBI inverts), their inverses, and the Chebyshev step that multiplies by them.
 //
 // The element blocks are k_pbdiag_sf's: the scalar diagonal's sum-factorised scheme in three rounds, one per input component, defined
-// beside k_diag_sf in kernel_diag_sf.hpp.  This file instantiates it (the scalar kernel's instantiations are kernels_misc.hip's) and
+// beside k_diag_sf in kernel_diag_sf.hpp.  This file instantiates it (the scalar kernel's instantiations are kernels_dispatch.hip's) and
 // holds the four lane-per-node kernels: the sum over a node's elements, the inverses, the product, the smoother step.
 #include "kernel_diag_sf.hpp"
 #include "kernels_pointblock.hpp"
@@ -17,6 +17,7 @@ hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const DiagA
 }
 
 // One lane per L-node, the contributors summed in element order as k_assemble sums them; nine values per contributor.
+// (A loop of its own: node_sum3 written generically over the width compiles k_assemble to other code than the one its traffic profile was taken with.)
 __global__ void k_pb_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const double *evec,
                               double *blocks, int nnodes) {
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nnodes; r += gridDim.x * blockDim.x) {
@@ -32,11 +33,6 @@ __global__ void k_pb_assemble(const uint32_t *rowptr, const uint32_t *cols, cons
 #pragma unroll
     for (int j = 0; j < 9; j++) dst[j] = acc[j];
   }
-}
-
-static inline dim3 node_grid(size_t n) {
-  size_t b = (n + 255) / 256;
-  return dim3((unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)));
 }
 
 // Inverse of the principal sub-block of the kept components, embedded in zeros.  A dropped component is replaced by a unit row and
@@ -102,7 +98,7 @@ __global__ void k_pb_mult(double *w, const double *blocks, const double *x, size
     w[3 * n] = z[0]; w[3 * n + 1] = z[1]; w[3 * n + 2] = z[2];
   }
 }
-// One node of a Chebyshev step with blocks: cheb_dof's definition (kernels_misc.hip) with dinv .* r replaced by B_n r_n; explicit
+// One node of a Chebyshev step with blocks: cheb_dof's definition (kernel_node_sum.hpp) with dinv .* r replaced by B_n r_n; explicit
 // operation order, no contraction left to the compiler.
 __global__ void k_pb_cheb_step(double *x, double *d, double *r, const double *b, const double *t, const double *blocks, double c1,
                                double c2, int assign_x, size_t nnodes) {
@@ -126,27 +122,18 @@ __global__ void k_pb_cheb_step(double *x, double *d, double *r, const double *b,
   }
 }
 
-hipError_t launch_pb_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const double *evec,
-                              double *blocks, int nnodes, hipStream_t s) {
-  if (nnodes <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pb_assemble, node_grid((size_t)nnodes), dim3(256), 0, s, rowptr, cols, node_off, evec, blocks, nnodes);
-  return hipGetLastError();
+hipError_t launch_pb_assemble(const NodeMap &m, const double *evec, double *blocks, hipStream_t s) {
+  return launch_stream(k_pb_assemble, (size_t)(m.nnodes > 0 ? m.nnodes : 0), s, m.rowptr + m.row0, m.cols, m.node_off + m.row0, evec, blocks, m.nnodes);
 }
 hipError_t launch_pb_invert(double *blocks, size_t nnodes, int *n_bad, hipStream_t s) {
-  if (!nnodes) return hipSuccess;
-  hipLaunchKernelGGL(k_pb_invert, node_grid(nnodes), dim3(256), 0, s, blocks, nnodes, n_bad);
-  return hipGetLastError();
+  return launch_stream(k_pb_invert, nnodes, s, blocks, nnodes, n_bad);
 }
 hipError_t launch_pb_mult(double *w, const double *blocks, const double *x, size_t nnodes, hipStream_t s) {
-  if (!nnodes) return hipSuccess;
-  hipLaunchKernelGGL(k_pb_mult, node_grid(nnodes), dim3(256), 0, s, w, blocks, x, nnodes);
-  return hipGetLastError();
+  return launch_stream(k_pb_mult, nnodes, s, w, blocks, x, nnodes);
 }
 hipError_t launch_pb_cheb_step(double *x, double *d, double *r, const double *b, const double *t, const double *blocks, double c1,
                                double c2, int assign_x, size_t nnodes, hipStream_t s) {
-  if (!nnodes) return hipSuccess;
-  hipLaunchKernelGGL(k_pb_cheb_step, node_grid(nnodes), dim3(256), 0, s, x, d, r, b, t, blocks, c1, c2, assign_x, nnodes);
-  return hipGetLastError();
+  return launch_stream(k_pb_cheb_step, nnodes, s, x, d, r, b, t, blocks, c1, c2, assign_x, nnodes);
 }
 
 }  // namespace cps

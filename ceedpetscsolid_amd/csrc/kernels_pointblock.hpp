@@ -11,8 +11,7 @@ namespace cps {
 hipError_t launch_pbdiag(int P, int Q, int qf, const BasisTables &t, const DiagArgs &a, hipStream_t s, const char **name);
 // blocks[3 * node_off[r] + j] = sum over the node's contributors, in element order, of evec[9 * cols[k] + j], j < 9: the transpose
 // map of launch_assemble() with nine values per contributor.  No atomics.
-hipError_t launch_pb_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const double *evec,
-                              double *blocks, int nnodes, hipStream_t s);
+hipError_t launch_pb_assemble(const NodeMap &m, const double *evec, double *blocks, hipStream_t s);
 // In place, per node: components whose diagonal entry is exactly zero are dropped, the remaining principal sub-block is inverted and
 // embedded in zeros.  *n_bad (device, may be null; zeroed by the caller) counts the blocks with a non-finite or non-positive pivot.
 hipError_t launch_pb_invert(double *blocks, size_t nnodes, int *n_bad, hipStream_t s);

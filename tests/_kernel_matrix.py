@@ -1,6 +1,6 @@
 """The device kernels a default build instantiates, restated as data, and the plan of problem builds that launches every one of them.
 
-The dispatch tables of csrc (kernels_fused_inst.hip CPS_CASE / CPS_LEVEL, kernel_diag_sf.hpp CPS_DIAG_PQ, kernels_misc.hip CPS_TR / CPS_SG,
+The dispatch tables of csrc (kernels_fused_inst.hip CPS_CASE / CPS_LEVEL, kernel_diag_sf.hpp CPS_DIAG_PQ, kernels_transfer.hip CPS_TR, kernels_geometry.hip CPS_SG,
 kernels_state.hip CPS_ST) are the product; this module is their second statement.  test_kernel_inventory.py holds the two against each
 other on the code objects of the build (both directions), and holds the plan below against the matrix; test_kernel_matrix_gpu.py runs
 the plan.  Whoever adds or drops an instantiation has to change the matrix here, and the sweep follows.

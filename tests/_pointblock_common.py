@@ -16,22 +16,22 @@ def jittered_box(nx=2, seed=3):
     return mesh
 
 
-def problem_with_state(ceed, mesh, degree, model, qextra=0, nu=0.3):
-    p = SolidProblem(ceed, mesh, degree, model, nu=nu, E=1.0, bc_sides=[6], qextra=qextra, multigrid="none")
+def problem_with_state(ceed, mesh, degree, model, qextra=0, nu=0.3, bc_sides=(6,)):
+    p = SolidProblem(ceed, mesh, degree, model, nu=nu, E=1.0, bc_sides=list(bc_sides), qextra=qextra, multigrid="none")
     n = p.lsize()
     X, R = ceed.vector(n).set_array(p.smooth_state(0.1)), ceed.vector(n)
     p.form_residual(X, R)              # stores grad u for the hyperelastic tangents
     return p
 
 
-def level_problem(ceed, mesh, P, Q, model, nu=0.3):
+def level_problem(ceed, mesh, P, Q, model, nu=0.3, bc_sides=(6,)):
     """(problem, level) whose Jacobian has P nodes and Q points per direction, grad u of the smooth state stored.  Q - P <= 2 is a fine
     level with qextra = Q - P; a larger gap exists only as a coarse level under a fine one with Q points (the residual operator, which
     stores the state, runs on the fine level alone): the uniform ladder of degree Q - 1, whose level of degree P - 1 is taken."""
     if Q - P <= 2:
-        p = problem_with_state(ceed, mesh, P - 1, model, qextra=Q - P, nu=nu)
+        p = problem_with_state(ceed, mesh, P - 1, model, qextra=Q - P, nu=nu, bc_sides=bc_sides)
         return p, p.fine
-    p = SolidProblem(ceed, mesh, Q - 1, model, nu=nu, E=1.0, bc_sides=[6], multigrid="uniform")
+    p = SolidProblem(ceed, mesh, Q - 1, model, nu=nu, E=1.0, bc_sides=list(bc_sides), multigrid="uniform")
     n = p.lsize()
     X, R = ceed.vector(n).set_array(p.smooth_state(0.1)), ceed.vector(n)
     p.form_residual(X, R)

@@ -5,14 +5,15 @@ CeedXVectorChebyshevUpdate / ChebyshevStart / WAXPBY -- every level of a ladder 
 nodes), in-place input (the recurrence applies the operator to its own direction d), recorded into a hipGraph -- and match the
 oracle's restatement at the parity bar.  The fused forms always sum the rows serially (ceed_operator.cpp, apply_fused_epilogue)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
 from _ceed_env import ceed_with_env
-from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh
+from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh, load_mesh_npz
 from ceedpetscsolid_amd.solid import SolidProblem
-from conftest import rel_err
+from conftest import GOLDEN, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +63,9 @@ CASES = [
     ("box p2 ss", lambda: box_mesh(5, 4, 3), 2, "hyperSS", [1]),
     ("box p3 le", lambda: box_mesh(3, 3, 2), 3, "linElas", [1, 2]),
     ("box p6 fs", lambda: box_mesh(2, 2, 3), 6, "hyperFS", [1]),
+    # unstructured: rows of 3 and 6 contributors, which end inside a batch of four or run one batch and a part (the structured
+    # meshes above have 1, 2, 4 and 8 only); Q = 3, four elements per group
+    ("cyl672 p2 fs", lambda: load_mesh_npz(os.path.join(GOLDEN, "mesh_cylinder8_672e_4ss_us.npz")), 2, "hyperFS", [998, 999]),
 ]
 
 

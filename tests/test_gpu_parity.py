@@ -722,7 +722,8 @@ def test_apply_is_bitwise_reproducible(gpu):
     (lambda: distorted_box(12, 12, 12), 2, "hyperSS"),          # Q = 3: four elements per group
     (lambda: distorted_box(9, 7, 5), 1, "linElas"),             # Q = 2: eight elements per group, ragged last group
     (lambda: distorted_box(7, 6, 6), 6, "hyperFS"),             # Q = 7: one element per group
-], ids=["cyl1536 p4", "cyl8000 p4", "box p2", "box p1", "box p6"])
+    (lambda: load_mesh_npz(os.path.join(GOLDEN, "mesh_cylinder8_672e_4ss_us.npz")), 2, "hyperFS"),   # unstructured: rows of 3 and 6 contributors (the others: 1, 2, 4, 8)
+], ids=["cyl1536 p4", "cyl8000 p4", "box p2", "box p1", "box p6", "cyl672 p2"])
 @pytest.mark.parametrize("mode", ["pipelined"])
 def test_pipelined_assembly_equals_serial_assembly_bitwise(product_lib, mk, degree, problem, mode):
     """The pipelined form of the restriction transpose (default on large launches): the apply cut into segments, the rows of

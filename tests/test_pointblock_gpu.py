@@ -26,8 +26,8 @@ KERNEL_QF = {"linElas": "LinElas", "hyperSS": "HyperSSdF", "hyperFS": "HyperFSdF
 PQ = [(2, 2), (3, 3), (2, 5), (3, 5), (5, 5), (4, 6), (7, 7), (2, 8), (8, 8)]
 
 
-def oracle_blocks(oracle, mesh, P, Q, model, nu=0.3):
-    p, lv = level_problem(oracle, mesh, P, Q, model, nu=nu)
+def oracle_blocks(oracle, mesh, P, Q, model, nu=0.3, bc_sides=(6,)):
+    p, lv = level_problem(oracle, mesh, P, Q, model, nu=nu, bc_sides=bc_sides)
     B = oracle.vector(3 * p.lsize(lv))
     assert not oracle.L.has("CeedOperatorLinearAssemblePointBlockDiagonal")     # the portable form: AssembledLevel on the oracle
     p.get_pointblock_diag(lv, B)
@@ -36,9 +36,9 @@ def oracle_blocks(oracle, mesh, P, Q, model, nu=0.3):
     return out
 
 
-def device_blocks_match(oracle, gpu, mesh, P, Q, model):
-    want = oracle_blocks(oracle, mesh, P, Q, model)
-    p, lv = level_problem(gpu, mesh, P, Q, model)
+def device_blocks_match(oracle, gpu, mesh, P, Q, model, bc_sides=(6,)):
+    want = oracle_blocks(oracle, mesh, P, Q, model, bc_sides=bc_sides)
+    p, lv = level_problem(gpu, mesh, P, Q, model, bc_sides=bc_sides)
     n = p.lsize(lv)
     B, D = gpu.vector(3 * n).set_value(3.0), gpu.vector(n)          # prefilled: overwrite semantics
     p.get_pointblock_diag(lv, B)
@@ -57,10 +57,17 @@ def device_blocks_match(oracle, gpu, mesh, P, Q, model):
     p.destroy()
 
 
+# the unstructured 672-hex cylinder at degree 2: rows of 3 and 6 contributors beside 1, 2, 4 and 8 (the boxes have only those)
+CYL672 = os.path.join(GOLDEN, "mesh_cylinder8_672e_4ss_us.npz")
+
+
 @pytest.mark.parametrize("model", ["linElas", "hyperSS", "hyperFS"])
-@pytest.mark.parametrize("P,Q", PQ)
-def test_pbdiag_matches_the_oracle_blocks(oracle, gpu, P, Q, model):
-    device_blocks_match(oracle, gpu, jittered_box(2), P, Q, model)
+@pytest.mark.parametrize("P,Q,fixture", [(P, Q, None) for P, Q in PQ] + [(3, 3, CYL672)], ids=[f"{P}-{Q}" for P, Q in PQ] + ["cyl672-3-3"])
+def test_pbdiag_matches_the_oracle_blocks(oracle, gpu, P, Q, fixture, model):
+    if fixture:
+        device_blocks_match(oracle, gpu, load_mesh_npz(fixture), P, Q, model, bc_sides=(998,))
+    else:
+        device_blocks_match(oracle, gpu, jittered_box(2), P, Q, model)
 
 
 @pytest.mark.parametrize("model", ["linElas", "hyperFS"])

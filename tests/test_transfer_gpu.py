@@ -1,5 +1,5 @@
 """Prolong_Ceed / Restrict_Ceed (src/matops.c:115-203; opProlong / opRestrict, src/setuplibceed.c:847-862) in the OWNER form
-of round 5 (csrc/kernels_misc.hip k_transfer): every fine node is stored (prolong) or read (restrict) by ONE element.  The
+of round 5 (csrc/kernels_transfer.hip k_transfer): every fine node is stored (prolong) or read (restrict) by ONE element.  The
 result differs from the reference's sum over the sharing elements times 1 / multiplicity by rounding only; these tests pin
 that on every ladder pair, on unstructured meshes, with the weighted path of an element partition (scale != 1 / local
 multiplicity), in the extension-free form (no scale at all), under ApplyAdd, and after the scale vector is rewritten."""

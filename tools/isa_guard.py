@@ -64,7 +64,7 @@ QF_NAMES = {2: "LinElas", 3: "HyperSSF", 4: "HyperSSdF", 5: "HyperFSF", 6: "Hype
 
 
 def other_name(mangled):
-    """Kernels of kernels_misc.hip that ride along in the summary WITHOUT being guarded: the restriction transpose (half of the apply's
+    """Kernels of kernels_assemble.hip and kernels_transfer.hip that ride along in the summary WITHOUT being guarded: the restriction transpose (half of the apply's
     measured traffic: bench.py reports a PMC profile only while this row is unchanged too), its epilogue form, the transfer kernels."""
     if re.search(r"\d+k_assembleE", mangled):
         return "k_assemble"
