@@ -12,17 +12,11 @@ from ceedpetscsolid_amd import ceed as cd
 from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh, load_mesh_npz
 from ceedpetscsolid_amd.solid import SolidProblem, smooth_displacement
 from _ceed_env import ceed_with_env
+from _numbering import distorted_box
 from conftest import GOLDEN, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10  # north_star tolerance for the floating-point path
-
-
-def distorted_box(nx, ny, nz, seed=0, amp=0.04):
-    m = box_mesh(nx, ny, nz)
-    rng = np.random.default_rng(seed)
-    m.coords += amp / max(nx, ny, nz) * rng.uniform(-1, 1, m.coords.shape)
-    return m
 
 
 def build_pair(oracle, gpu, mesh, degree, problem, **kw):
@@ -664,6 +658,11 @@ def test_unsupported_graphs_fail_loudly(gpu):
 
 def test_split_phase_apply_equals_full_apply(gpu):
     """CeedXOperatorApplyPhase 0 then 1 == CeedOperatorApply (communication-overlap form, used at N > 1)."""
+    split_phase_equals_full_apply(gpu)
+
+
+def split_phase_equals_full_apply(gpu):
+    """The body of test_split_phase_apply_equals_full_apply; tests/test_numbering_gpu.py runs it under another node numbering."""
     from ceedpetscsolid_amd.mesh import build_dofmap, reorder_elements_first
     mesh = distorted_box(4, 4, 4)
     zc = mesh.coords[mesh.cells][:, :, 2]
@@ -732,7 +731,11 @@ def test_pipelined_assembly_equals_serial_assembly_bitwise(product_lib, mk, degr
     BITWISE equal.  The inputs alternate between applies, so an E-vector entry read before its producer had finished would
     show as the previous apply's value.  (Round 2's dependent in-kernel forms -- gated, folded, dynamic -- were measured
     -3 ... +5 % and left the tree in round 3.)"""
-    mesh = mk()
+    pipelined_assembly_equals_serial_assembly(product_lib, mk(), degree, problem, mode)
+
+
+def pipelined_assembly_equals_serial_assembly(product_lib, mesh, degree, problem, mode="pipelined"):
+    """The body of test_pipelined_assembly_equals_serial_assembly_bitwise; tests/test_numbering_gpu.py runs it under another node numbering."""
     # three segments whatever the mesh size (the default asks for four rounds of the waves per segment)
     gated = ceed_with_env(product_lib, {"CEED_MI355X_PIPE_MIN_ROUNDS": "0", "CEED_MI355X_PIPE_SEGMENTS": "3", "CEED_MI355X_ASSEMBLE": mode})
     serial = ceed_with_env(product_lib, {"CEED_MI355X_ASSEMBLE": "serial"})
