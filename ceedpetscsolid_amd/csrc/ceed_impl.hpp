@@ -1,6 +1,7 @@
 // ceed_impl.hpp -- private object layouts and helpers shared by the host-side sources of the MI355X backend
-// (ceed_core.cpp: Ceed, vectors, graphs; ceed_basis.cpp; ceed_restriction.cpp; ceed_operator.cpp; ceed_halo.cpp;
-// ceed_csr.cpp).  Nothing here is part of the ABI: include/ceed.h is.
+// (ceed_core.cpp: Ceed, vectors, graphs; ceed_basis.cpp; ceed_restriction.cpp; ceed_qfunction.cpp; the operators: ceed_operator.cpp
+// with ceed_op_fused.cpp and ceed_op_other.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
+// Nothing here is part of the ABI: include/ceed.h is.
 #pragma once
 #include <ceed.h>
 #include <hip/hip_runtime_api.h>
@@ -130,6 +131,7 @@ struct CeedVector_private {
 // Transpose map of an offsets restriction: distinct node offsets and, per node, the E-vector
 // positions (e*elemsize + n) of its contributors in element order.  Rows [0, nprio) are the
 // "priority" nodes when the map was built with a priority mask (split-phase apply).
+void ceed_retire(Ceed c, void *p);   // (see the helpers below)
 struct CsrMap {
   bool built = false, full_cover = false;
   int nnodes = 0, nprio = 0, nskipped = 0;
@@ -140,6 +142,11 @@ struct CsrMap {
     if (d_rowptr) (void)hipFree(d_rowptr);
     if (d_cols) (void)hipFree(d_cols);
     if (d_node_off) (void)hipFree(d_node_off);
+    d_rowptr = d_cols = d_node_off = nullptr; built = false;
+  }
+  // the same for a map recorded launches may have read (an operator's own split map): the arrays leave through ceed_retire
+  void release(Ceed c) {
+    ceed_retire(c, d_rowptr); ceed_retire(c, d_cols); ceed_retire(c, d_node_off);
     d_rowptr = d_cols = d_node_off = nullptr; built = false;
   }
 };
@@ -215,9 +222,11 @@ struct CeedOperator_private {
   int i_active = -1, i_qdata = -1, i_state = -1, i_weight = -1, o_active = -1, o_state = -1, o_qdata = -1;
   cps::BasisTables tables;
   double eo[6][cps::EO_TAB];          // even-odd forms of the six 1-D products (fused operators with pencil_even_odd(Q))
-  std::string kernel_name;
-  int geo_mode = 0;                   // last fused launch: 0 qdata read, 1 recomputed per point, 2 affine elements
-  // Dirichlet flags
+  std::string kernel_name;            // instantiation of the last launch (set_kernel_name), and whether that was a fused kernel:
+  bool kernel_fused = false;          // CeedXOperatorGetKernelName then adds how the geometric factors were obtained (kernel_name_full)
+  std::string kernel_name_full;
+  int geo_mode = 0;                   // last fused launch: 0 qdata read, 1 recomputed per point, 2 affine elements, 3 swept elements
+  // Dirichlet flags.  Every device array of an operator that a launch may have read leaves through ceed_retire (op_free_flags)
   uint32_t *d_off_flagged_in = nullptr, *d_off_flagged_out = nullptr;  // same array unless transfer
   unsigned char *d_node_flags = nullptr;        // per node of the restriction's transpose map
   unsigned char *d_node_flags_ovl = nullptr;    // per node of the operator's own (priority-first) map
@@ -230,7 +239,7 @@ struct CeedOperator_private {
   int mask_mode = 0;
   // optional fine-side scale for transfers
   CeedVector scale = nullptr;
-  // transfer operators in OWNER form (ceed_operator.cpp: transfer_owner_map, transfer_weights)
+  // transfer operators in OWNER form (ceed_op_other.cpp: transfer_owner_map, transfer_weights)
   std::vector<unsigned char> h_mask_fine;  // the fine side's Dirichlet mask (empty: none)
   uint32_t *d_own_f = nullptr;             // [nelem][Pf^3] offset | flags of the fine nodes each element owns
   bool own_full_cover = false;             // every entry of the fine L-vector has an owner

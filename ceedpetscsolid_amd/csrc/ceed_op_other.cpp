@@ -1,0 +1,231 @@
+// ceed_op_other.cpp -- the operator families beside the residual / Jacobian one (op_plan, ceed_operator.cpp): the transfer operators in
+// owner form, SetupGeo with the provenance it leaves on the qdata vector, and the coordinate-driven and energy operators.
+#include "ceed_operator.hpp"
+
+using namespace cps;
+
+// The transfer operators in OWNER form (kernels_transfer.hip, k_transfer).
+// own_f[e][n] = offset | fine-side Dirichlet flags if element e is the FIRST (in element order) to hold fine node n, else
+// 0xFFFFFFFF.  Set-up time, host; rebuilt when the operator's mask changes.
+static int transfer_owner_map(CeedOperator op, CeedElemRestriction rf) {
+  if (op->d_own_f) return 0;
+  Ceed c = op->ceed;
+  if (c->capturing) return ceed_error("first apply of a transfer operator during graph capture: apply it once before recording");
+  const size_t n = rf->h_offsets.size();
+  std::vector<uint32_t> own(n ? n : 1);
+  std::vector<unsigned char> seen((size_t)rf->lsize, 0);
+  const std::vector<unsigned char> &mk = op->h_mask_fine;
+  size_t distinct = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t o = (uint32_t)rf->h_offsets[i];
+    if (seen[o]) { own[i] = 0xFFFFFFFFu; continue; }
+    seen[o] = 1; distinct++;
+    own[i] = o | ((mk.empty() ? 0u : node_flag_bits(mk.data(), o, rf)) << OFF_FLAG_SHIFT);
+  }
+  op->own_full_cover = distinct * 3 == (size_t)rf->lsize;
+  HIPCHK(hipMalloc((void **)&op->d_own_f, sizeof(uint32_t) * own.size()));
+  HIPCHK(hipMemcpy(op->d_own_f, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+// Set-up time only (never while recording): `n` counters on the device, zeroed, counted into by `count` on the Ceed's stream,
+// and read back into h[0 .. n).
+template <class Count>
+static int count_on_device(Ceed c, int n, int *h, Count count) {
+  int *d_cnt = nullptr;
+  HIPCHK(hipMalloc((void **)&d_cnt, n * sizeof(int)));
+  HIPCHK(hipMemsetAsync(d_cnt, 0, n * sizeof(int), c->stream));
+  CHK(count(d_cnt));
+  HIPCHK(hipMemcpyAsync(h, d_cnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  (void)hipFree(d_cnt);
+  return 0;
+}
+// w = (fine-side scale, CeedXOperatorSetFineScale, or 1) x (local multiplicity of the fine restriction) per fine dof; *w = null
+// when every covered entry is 1 (the scale IS 1 / local multiplicity: one rank).  Recomputed when the scale vector was written
+// since (CeedVector_private::version) -- with one host read of a counter, so never while recording.
+static int transfer_weights(CeedOperator op, CeedElemRestriction rf, const double **w) {
+  Ceed c = op->ceed;
+  CeedVector sc = op->scale;
+  const uint64_t ver = sc ? sc->version : 0;
+  if (op->w_ready && op->w_scale == sc && op->w_version == ver) { *w = op->w_unit ? nullptr : op->d_w; return 0; }
+  if (c->capturing)
+    return ceed_error("transfer operator during graph capture: its fine-side scale was written since the last apply (or this is the first); "
+                      "apply the operator once before recording");
+  double *psc = nullptr;
+  if (sc) CHK(vec_dev(sc, false, &psc));
+  const size_t n = (size_t)rf->lsize;
+  if (op->w_len < n) {
+    ceed_retire(c, op->d_w); op->d_w = nullptr; op->w_len = 0;
+    HIPCHK(hipMalloc((void **)&op->d_w, sizeof(double) * (n ? n : 1)));
+    op->w_len = n;
+  }
+  int cnt = 1;
+  CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) {
+    CHK(dev_zero(c, op->d_w, n));
+    HIPCHK(launch_multiplicity(rf->d_offsets, rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w, c->stream));
+    HIPCHK(launch_transfer_weights(op->d_w, psc, n, d_cnt, c->stream));
+    return 0;
+  }));
+  op->w_unit = cnt == 0; op->w_scale = sc; op->w_version = ver; op->w_ready = true;
+  if (op->w_unit) { ceed_retire(c, op->d_w); op->d_w = nullptr; op->w_len = 0; }     // (not needed again until the scale is rewritten: 8 B per fine dof given back)
+  *w = op->w_unit ? nullptr : op->d_w;
+  return 0;
+}
+int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add) {
+  hipStream_t s = op->ceed->stream;
+  const bool pro = op->plan == PLAN_PROLONG;
+  CeedElemRestriction rc = pro ? op->in[0].rstr : op->out[0].rstr, rf = pro ? op->out[0].rstr : op->in[0].rstr;
+  CeedBasis b = pro ? op->in[0].basis : op->out[0].basis;
+  if (in == out) return ceed_error("in-place operator apply is not supported");
+  if (in->length < (pro ? rc : rf)->lsize || out->length < (pro ? rf : rc)->lsize) return ceed_error("transfer vector too short");
+  TransferArgs a{};
+  double *px, *py;
+  CHK(vec_dev(in, false, &px));
+  CHK(vec_dev(out, true, &py));
+  if (op->scale && op->scale->length < rf->lsize) return ceed_error("scale vector too short");
+  // OWNER form (kernels_transfer.hip): the fine nodes each element owns, and the weights (null: all 1, the one-rank case)
+  CHK(transfer_owner_map(op, rf));
+  CHK(transfer_weights(op, rf, &a.w_f));
+  // the coarse side's flagged offsets: the input side of a prolongation, the output side of a restriction
+  const uint32_t *fc = pro ? op->d_off_flagged_in : op->d_off_flagged_out;
+  a.off_c = fc ? fc : rc->d_offsets;
+  a.own_f = op->d_own_f;
+  a.x = px; a.y = py; a.nelem = rc->nelem; a.add = add ? 1 : 0;
+  const int m_in = (op->mask_mode & 1) ? 1 : 0, m_out = (op->mask_mode & 2) ? 1 : 0;
+  a.mask_c = pro ? m_in : m_out; a.mask_f = pro ? m_out : m_in;
+  if (pro) {
+    // every fine node is stored by its owner: no E-vector, no sum
+    if (!add && !op->own_full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  } else {
+    // deterministic scatter on the COARSE side (Pc^3 nodes per element): element results -> E-vector -> per-node sums in
+    // element order over the coarse restriction's transpose map (masked entries travel as zeros)
+    CHK(build_csr(rc, rc->csr, nullptr));
+    CHK(ceed_need_evec(op->ceed, (size_t)rc->nelem * rc->ncomp * rc->elemsize));
+    a.evec = op->ceed->evec;
+    if (!add && !rc->csr.full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  }
+  TimerScope ts(op, s);
+  const char *kname = "";
+  hipError_t e = launch_transfer(b->P1d, b->Q1d, pro, op->tables, a, s, &kname);
+  if (no_kernel(e, kname)) return ceed_error("no transfer kernel for Pc=%d Pf=%d", b->P1d, b->Q1d);
+  HIPCHK(e);
+  if (!pro) HIPCHK(launch_assemble(rc->csr.view(), nullptr, a.evec, py, add ? 1 : 0, s));
+  set_kernel_name(op, kname, false);
+  op->launches++;
+  return 0;
+}
+
+// SetupGeo, and the coordinate-driven and energy operators.
+// Provenance for the fused kernels, kept with the qdata vector SetupGeo just wrote from trilinear elements: the map coefficients,
+// and the constant factors of the whole mesh's element class when it has one (affine; else swept along one reference direction).
+// Operators reading this vector may then recompute the factors instead of streaming them.  Set-up time only.
+static int geo_provenance(CeedOperator op, CeedVector out, const uint32_t *off_x, const double *px, int nelem) {
+  Ceed c = op->ceed;
+  hipStream_t s = c->stream;
+  CeedBasis xb = op->in[0].basis;
+  HIPCHK(hipMalloc((void **)&out->geo, sizeof(double) * GEO_NCOEF * (size_t)nelem));
+  HIPCHK(launch_geo_coeffs(off_x, px, out->geo, nelem, s));
+  out->geo_nelem = nelem; out->geo_Q = xb->Q1d;
+  if (c->opt.affine_geo) {   // all elements affine (box meshes)?  then dXdx and det J are per-ELEMENT constants
+    int cnt = 1;
+    HIPCHK(hipMalloc((void **)&out->geo_aff, sizeof(double) * GEO_NAFF * (size_t)nelem));
+    CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) { HIPCHK(launch_geo_affine(out->geo, out->geo_aff, nelem, d_cnt, s)); return 0; }));
+    if (cnt != 0) { (void)hipFree(out->geo_aff); out->geo_aff = nullptr; }   // a mixed mesh takes the general recompute everywhere
+  }
+  if (!out->geo_aff && c->opt.swept_geo) {   // every element swept along ONE reference direction (extruded meshes)?
+    int cnt[4] = {0, 0, 0, 1};
+    HIPCHK(hipMalloc((void **)&out->geo_swept, sizeof(double) * GEO_NSWEPT * (size_t)nelem));
+    CHK(count_on_device(c, 4, cnt, [&](int *d_cnt) {     // count: every direction an element qualifies for
+      HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, d_cnt, -1, s));
+      return 0;
+    }));
+    int axis = -1;
+    for (int d = 2; d >= 0; d--) if (cnt[d] == nelem) axis = d;      // a direction ALL elements share
+    if (axis < 0) { (void)hipFree(out->geo_swept); out->geo_swept = nullptr; }   // no common direction or general hexes: the general recompute
+    else { HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, nullptr, axis, s)); out->geo_axis = axis; }
+  }
+  for (int i = 0; i < xb->Q1d && i < MAXN1D; i++) { out->geo_qref[i] = xb->qref1d[i]; out->geo_qwt[i] = xb->qweight1d[i]; }
+  return 0;
+}
+int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out) {
+  hipStream_t s = op->ceed->stream;
+  OpField &x = op->in[0];
+  if (!in || in->length < x.rstr->lsize) return ceed_error("coordinate vector too short");
+  SetupGeoArgs a{};
+  double *px, *pq;
+  CHK(vec_dev(in, false, &px));
+  CHK(vec_dev(out, true, &pq));
+  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.qdata = pq; a.nelem = x.rstr->nelem;
+  if ((size_t)out->length < (size_t)a.nelem * 10 * x.basis->Q1d * x.basis->Q1d * x.basis->Q1d) return ceed_error("qdata vector too short");
+  TimerScope ts(op, s);
+  const char *kname = "";
+  hipError_t e = launch_setup_geo(x.basis->Q1d, op->tables, a, s, &kname);
+  if (no_kernel(e, kname)) return ceed_error("no setup_geo kernel for Q=%d", x.basis->Q1d);
+  HIPCHK(e);
+  op->launches++;
+  set_kernel_name(op, kname, false);
+  // the elements are trilinear (op_plan takes no other coordinates): keep the map coefficients with the qdata vector
+  if (op->ceed->opt.recompute_geo && !op->ceed->capturing) CHK(geo_provenance(op, out, a.off_x, px, a.nelem));
+  return 0;
+}
+int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
+  CeedQFunction qf = op->qf;
+  OpField &u = op->in[0], &en = op->out[0];
+  if (!in || in->length < u.rstr->lsize || !out || out->length < en.rstr->lsize) return ceed_error("displacement / energy vector too short");
+  EnergyOpArgs a{};
+  double *pu, *py, *pq;
+  CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
+  a.off_u = u.rstr->d_offsets; a.u = pu; a.off_e = en.rstr->d_offsets; a.y = py; a.qdata = pq;
+  a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
+  const int kd = qf->kind;
+  a.diag = (kd == QF_DIAG_LINELAS || kd == QF_DIAG_HYPERSS || kd == QF_DIAG_HYPERFS) ? 1 : 0;
+  a.model = (kd == QF_ENERGY_LINELAS || kd == QF_DIAG_LINELAS) ? 0 : ((kd == QF_ENERGY_HYPERSS || kd == QF_DIAG_HYPERSS) ? 1 : 2);
+  CHK(read_phys(qf, &a.nu, &a.E));
+  memcpy(a.interp, u.basis->interp1d.data(), sizeof(double) * u.basis->interp1d.size());
+  memcpy(a.grad, u.basis->grad1d.data(), sizeof(double) * u.basis->grad1d.size());
+  if (!a.diag) memcpy(a.interp_e, en.basis->interp1d.data(), sizeof(double) * en.basis->interp1d.size());
+  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  hipError_t e = launch_energy_op(a, op->ceed->stream);
+  if (e == hipErrorInvalidValue) return ceed_error("energy operator: Q=%d / P=%d outside the supported range", a.Q, a.P);
+  HIPCHK(e);
+  set_kernel_name(op, a.diag ? (a.model == 0 ? "diagnostic_op<LinElasDiagnostic>" : (a.model == 1 ? "diagnostic_op<HyperSSDiagnostic>" : "diagnostic_op<HyperFSDiagnostic>"))
+                  : (a.model == 0 ? "energy_op<LinElasEnergy>" : (a.model == 1 ? "energy_op<HyperSSEnergy>" : "energy_op<HyperFSEnergy>")), false);
+  op->launches++;
+  return 0;
+}
+int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
+  CeedQFunction qf = op->qf;
+  OpField &x = op->in[0], &o = op->out[0];
+  if (!in || in->length < x.rstr->lsize || !out || out->length < o.rstr->lsize) return ceed_error("coordinate / output vector too short");
+  CoordOpArgs a{};
+  double *px, *py, *pq = nullptr;
+  CHK(vec_dev(in, false, &px)); CHK(vec_dev(out, true, &py));
+  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.off_u = o.rstr->d_offsets; a.y = py;
+  a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
+  a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
+  if (a.mode != 2) {
+    CHK(vec_dev(op->in[1].vec, false, &pq)); a.qdata = pq;
+    a.Pout = o.basis->P1d;
+    memcpy(a.bu, o.basis->interp1d.data(), sizeof(double) * o.basis->interp1d.size());
+    if (!qf->ctx) return ceed_error("QFunction '%s' needs its context", qf->name.c_str());
+    const double *cx = (const double *)qf->ctx;   // pointer pass-through: forcing vector (3) or Physics {nu, E} (setuplibceed.c:563-566)
+    for (int i = 0; i < (a.mode == 0 ? 3 : 2); i++) a.ctx[i] = cx[i];
+  } else {
+    a.Pout = a.Q;
+  }
+  memcpy(a.bx, x.basis->interp1d.data(), sizeof(double) * x.basis->interp1d.size());
+  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  hipError_t e = launch_coord_op(a, op->ceed->stream);
+  if (e == hipErrorInvalidValue) return ceed_error("coordinate operator: Q=%d / P=%d outside the supported range", a.Q, a.Pout);
+  HIPCHK(e);
+  set_kernel_name(op, a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>"), false);
+  op->launches++;
+  return 0;
+}
+// Fine-side multiplicity scale of the transfer operators (matops.c:149,176); NULL clears.
+extern "C" int CeedXOperatorSetFineScale(CeedOperator op, CeedVector scale) {
+  CeedVectorDestroy(&op->scale);
+  op->w_ready = false;
+  if (scale && scale != CEED_VECTOR_NONE) { op->scale = scale; scale->refcount++; }
+  return 0;
+}

@@ -1,0 +1,51 @@
+// ceed_operator.hpp -- what the operator sources share: ceed_operator.cpp (the object, op_plan, the dispatch), ceed_op_fused.cpp (the
+// residual / Jacobian family), ceed_op_other.cpp (transfers, SetupGeo, coordinate and energy operators).  Private, like ceed_impl.hpp.
+#pragma once
+#include "ceed_impl.hpp"
+
+// the launches of one apply between two events on its stream, while the operator is timed (CeedXOperatorSetTiming)
+struct TimerScope {
+  CeedOperator op; hipStream_t s; hipEvent_t a = nullptr, b = nullptr;
+  TimerScope(CeedOperator o, hipStream_t st) : op(o), s(st) {
+    if (op->timing && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, s);
+  }
+  ~TimerScope() { if (a && b) { (void)hipEventRecord(b, s); op->events.emplace_back(a, b); } }
+};
+
+#pragma GCC visibility push(hidden)   // from here on: shared by the objects of the library, exported by none (TimerScope's two symbols were, before these sources were split)
+// Match the operator's field signature against the supported kernel families (once: CeedOperatorSetField resets the plan).
+int op_plan(CeedOperator op);
+// The preamble of an entry point `who`: no composite operator, the plan, and -- but for Kind::any -- an operator of the residual /
+// Jacobian family of the kind the entry point is provided for (residual: it stores grad u; Jacobian: it does not).
+enum class Kind { any, either, jacobian, residual };
+int need_fused(CeedOperator op, const char *who, Kind kind);
+
+// One apply of a planned operator, per family.  Each leaves the name of the kernel it launched on the operator (set_kernel_name).
+// apply_fused with `H` (overwrite mode only): the interface sum of the output follows IN ORDER on the same stream.
+int apply_fused(CeedOperator op, CeedVector in, CeedVector out, bool add, CeedXHalo H = nullptr);
+int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add);
+int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out);
+int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add);
+int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add);
+
+// fused: a launch of the fused kernel, whose name CeedXOperatorGetKernelName completes with how the geometric factors were obtained
+static inline void set_kernel_name(CeedOperator op, const char *name, bool fused) { op->kernel_name = name; op->kernel_fused = fused; }
+// a dispatch that holds no instantiation for the shape returns hipErrorInvalidValue and leaves the name empty
+static inline bool no_kernel(hipError_t e, const char *kname) { return e == hipErrorInvalidValue && !*kname; }
+// a vector of its own: neither missing nor one of the two sentinels
+static inline bool is_passive(CeedVector v) { return v && v != CEED_VECTOR_NONE && v != CEED_VECTOR_ACTIVE; }
+// the Dirichlet flag bits of the node at `offset` of restriction r: bit c set where component c is masked
+static inline uint32_t node_flag_bits(const unsigned char *mask, uint32_t offset, CeedElemRestriction r) {
+  uint32_t f = 0;
+  for (int c = 0; c < r->ncomp && c < 3; c++) if (mask[(size_t)offset + (size_t)c * r->compstride]) f |= 1u << c;
+  return f;
+}
+static inline int read_phys(CeedQFunction qf, double *nu, double *E) {
+  // The reference passes sizeof(pointer) as the context size at setuplibceed.c:826; the
+  // context is the 16-byte {nu, E} struct behind the pointer (elasticity.h:33-36).
+  if (!qf->ctx) return ceed_error("QFunction '%s' needs its Physics context", qf->name.c_str());
+  const double *p = (const double *)qf->ctx;
+  *nu = p[0]; *E = p[1];
+  return 0;
+}
+#pragma GCC visibility pop

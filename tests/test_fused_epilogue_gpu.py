@@ -3,7 +3,7 @@ step of the smoother (elasticity.c:539-552) and the residual of the V-cycle (:58
 restriction transpose instead of a pass of their own.  The fused forms must give the SAME BITS as CeedOperatorApply followed by
 CeedXVectorChebyshevUpdate / ChebyshevStart / WAXPBY -- every level of a ladder (P < Q kernels, P = 2 without element-interior
 nodes), in-place input (the recurrence applies the operator to its own direction d), recorded into a hipGraph -- and match the
-oracle's restatement at the parity bar.  The fused forms always sum the rows serially (ceed_operator.cpp, apply_fused_epilogue)."""
+oracle's restatement at the parity bar.  The fused forms always sum the rows serially (ceed_op_fused.cpp, apply_fused_epilogue)."""
 import ctypes as C
 import os
 
