@@ -27,12 +27,12 @@ Everything the cycle launches is on the Ceed's stream and recordable into the V-
 """
 from __future__ import annotations
 
-import ctypes as C
 import time
 
 import numpy as np
 
 from . import ceed as cd
+from .krylov import chebyshev_coefficients_on, lanczos_device, lanczos_emax
 
 
 def aggregate_nodes(indptr: np.ndarray, indices: np.ndarray) -> tuple[np.ndarray, int]:
@@ -139,7 +139,6 @@ class AggregationAMG:
         self.levels: list[_Level] = []
         self.rc = self.xc = None
         self.nc = 0
-        self._scal = None
         self.info = {}
 
     # two-level accessors (tests, older callers)
@@ -213,20 +212,19 @@ class AggregationAMG:
         """The Galerkin matrix of transfer lv for the current Jacobian: T = A P, A_next = P^T T on the device; on several ranks the
         first transfer's product is this rank's CONTRIBUTION P_r^T A_r P_r, summed over the ranks into the replicated matrix."""
         lv.T.update()
-        if getattr(lv, "dd", None) is None:
+        if lv.dd is None:
             lv.Anext.update()
             return
         d = lv.dd
         d["local"].update()
         # the rank's values into their places of the union pattern, summed over the ranks, assembled: all on the vectors' own memory
         # (device tensors on a GPU; RCCL through the library where it has a communicator, torch.distributed otherwise)
-        self.L.chk(self.L.lib.CeedXCsrGetValues(d["local"].h, d["vals"].h))
+        d["local"].get_values(d["vals"])
         if d["vals"].t.device.type == "cuda":
             self.ceed.synchronize()
         d["coo"].t.zero_()
         d["coo"].t.index_copy_(0, d["slot_t"], d["vals"].t[:d["slot_t"].numel()])
-        if d["coo"].t.device.type == "cuda":
-            d["coo"].set_device_pointer(d["coo"].t.data_ptr())
+        d["coo"].touched()
         self._allreduce(d["coo"])
         lv.Anext.assemble(d["coo"])
 
@@ -234,9 +232,8 @@ class AggregationAMG:
         import torch
         import torch.distributed as dist
         h = self.dist
-        on_dev = dist.get_backend(h.group) == "nccl"
         t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
-        if on_dev:
+        if dist.get_backend(h.group) == "nccl":
             t = t.to(h.device)
         dist.all_reduce(t, group=h.group)
         return t.cpu().numpy()
@@ -245,9 +242,7 @@ class AggregationAMG:
         """Sum of a (small, coarse) vector over the ranks, in place: RCCL on the Ceed's stream where the library has a communicator
         (recordable), else torch.distributed on the tensor behind the vector."""
         if self.ceed.comm_size()[0] > 1:
-            n = C.c_int()
-            self.L.chk(self.L.lib.CeedVectorGetLength(v.h, C.byref(n)))
-            self.L.chk(self.L.lib.CeedXCommAllReduce(self.ceed.h, v.h, 0, n.value))
+            self.ceed.all_reduce(v)
             return
         import torch.distributed as dist
         h = self.dist
@@ -259,19 +254,7 @@ class AggregationAMG:
             v.t.copy_(t)
         else:
             dist.all_reduce(v.t, group=h.group)
-        if v.t.device.type == "cuda":
-            v.set_device_pointer(v.t.data_ptr())
-
-    def _dist_vector(self, n: int) -> cd.Vector:
-        """A Ceed vector over a torch tensor (several ranks: torch.distributed sums it where the library has no communicator)."""
-        import torch
-        v = self.ceed.vector(n)
-        v.t = torch.zeros(max(n, 1), dtype=torch.float64, device=self.dist.device)[:n]
-        if v.t.device.type == "cuda":
-            v.set_device_pointer(v.t.data_ptr())
-        else:
-            v.set_array(v.t.numpy(), copy=False)
-        return v
+        v.touched()
 
     def _first_transfer_distributed(self, A_host, B, free_node, dense_limit):
         """The first transfer of the hierarchy on an ELEMENT-PARTITIONED level (the reference's PCGAMG is parallel, elasticity.c:568-585).
@@ -355,7 +338,6 @@ class AggregationAMG:
             return sp.csr_matrix((S.data[keep], (loc[pn[keep]] * 3 + comp[keep], S.col[keep])), shape=(n, ncols))
         # --- P0 on every local node: the rows of interface nodes owned elsewhere come from their owners ------------------------------
         pubs = gather(rows_of(P0, np.nonzero(shared & own_node)[0]))
-        P0 = P0.tolil() if False else P0
         for r, pub in enumerate(pubs):
             if r != h.rank:
                 M = place(pub, nc)
@@ -372,10 +354,10 @@ class AggregationAMG:
         keep_rows = np.ones(n); keep_rows[sh_dofs] = 0.0
         Tsum = sp.diags(keep_rows) @ T0                          # interior rows as they are; interface rows rebuilt below
         Dsum = sp.csr_matrix((n, 1))
-        mine_T, mine_D = T0[sh_dofs], diag[sh_dofs]
+        mine_T, mine_D = T0[sh_dofs].tocoo(), diag[sh_dofs]
         for r, pub in enumerate(pubs):                           # rank order: the same sums, in the same order, on every sharing rank
             if r == h.rank:
-                Tsum = Tsum + sp.csr_matrix((mine_T.tocoo().data, (sh_dofs[mine_T.tocoo().row], mine_T.tocoo().col)), shape=(n, nc))
+                Tsum = Tsum + sp.csr_matrix((mine_T.data, (sh_dofs[mine_T.row], mine_T.col)), shape=(n, nc))
                 Dsum = Dsum + sp.csr_matrix((mine_D, (sh_dofs, np.zeros(sh_dofs.size, dtype=np.int64))), shape=(n, 1))
             else:
                 Tsum = Tsum + place(pub["T"], nc)
@@ -432,12 +414,10 @@ class AggregationAMG:
             assert np.array_equal(key_u[slot], key_l)
         nnz_u = int(rp_u[-1])
         lv.Anext = cd.Csr(c, rp_u, cl_u, np.arange(nnz_u, dtype=np.int64), ())
-        wv = self._dist_vector(n)
-        wv.t.copy_(torch.from_numpy(w_own * (np.asarray(asm.mask) == 0)).to(wv.t.device))
-        if wv.t.device.type == "cuda":
-            wv.set_device_pointer(wv.t.data_ptr())
+        wv = c.tensor_vector(n, h.device)
+        wv.fill(w_own * (np.asarray(asm.mask) == 0))
         lv.dd = {"local": local, "slot_t": torch.from_numpy(np.ascontiguousarray(slot, dtype=np.int64)).to(h.device), "nnz_union": nnz_u,
-                 "coo": self._dist_vector(max(nnz_u, 1)), "vals": self._dist_vector(max(local.nnz, 1)), "w": wv, "rw": c.vector(n).set_value(0.0)}
+                 "coo": c.tensor_vector(max(nnz_u, 1), h.device), "vals": c.tensor_vector(max(local.nnz, 1), h.device), "w": wv, "rw": c.vector(n).set_value(0.0)}
         lv.info = dict(rows=int(n), aggregates=int(na), coarse_dofs=int(nc), coarse_dofs_of_this_rank=int(ncr), distributed_over=int(h.world),
                        nodes_per_aggregate=float(fn.size) / max(na, 1), prolongation_entries_per_row=float(P.nnz) / max(n, 1),
                        galerkin_entries=int(lv.T.nnz), lambda_max=lam, next_is_dense=bool(lv.dense_next), seconds=dict(aggregate=t_ag),
@@ -479,13 +459,13 @@ class AggregationAMG:
             free_node = np.ones(dof_ptr.size - 1, dtype=bool)
             # work vectors and the start vector of the eigenvalue estimate of the new level
             for k in ("x", "b", "r", "d", "t", "z", "dinv"):
-                lv.v[k] = self._dist_vector(lv.nc) if (self.dist is not None and k == "b" and len(self.levels) == 1) else c.vector(lv.nc).set_value(0.0)
+                lv.v[k] = c.tensor_vector(lv.nc, self.dist.device) if (self.dist is not None and k == "b" and len(self.levels) == 1) else c.vector(lv.nc).set_value(0.0)
             x0 = np.random.default_rng(4321 + len(self.levels)).uniform(-1.0, 1.0, lv.nc)
             lv.x0 = c.vector(lv.nc).set_array(x0 / np.sqrt(np.square(x0).sum()))
         last = self.levels[-1]
         self.rc, self.xc = c.vector(last.nc).set_value(0.0), c.vector(last.nc).set_value(0.0)
         if self.dist is not None and len(self.levels) == 1:      # the restricted residual is summed over the ranks: behind a tensor
-            self.rc = self._dist_vector(last.nc)
+            self.rc = c.tensor_vector(last.nc, self.dist.device)
         self.nc = self.levels[0].nc
         self.info = dict(levels=len(self.levels) + 1, rows=[self.levels[0].n] + [l.nc for l in self.levels],
                          aggregates=self.levels[0].info["aggregates"], coarse_dofs=self.levels[0].nc,
@@ -508,75 +488,35 @@ class AggregationAMG:
                 lv.emax = self._estimate_emax(lv)
 
     def _estimate_emax(self, lv, steps: int = 10) -> float:
-        """Largest eigenvalue of D^-1 A_next: the Lanczos tridiagonal of `steps` Jacobi-PCG steps, scalars on the device
-        (the same recurrence as solver.NewtonPMG._lanczos_device)."""
-        lib, chk, v = self.L.lib, self.L.chk, lv.v
-        r, z, pv, Ap = v["r"], v["z"], v["d"], v["t"]
-        if self._scal is None:
-            self._scal = self.ceed.vector(8 + 2 * 16)
-        sc = self._scal
-        sc.set_value(0.0)
-        one, neg = C.c_double(1.0), C.c_double(-1.0)
-        chk(lib.CeedXVectorAXPBY(r.h, one, lv.x0.h, C.c_double(0.0)))
-        chk(lib.CeedXVectorPointwiseMult(z.h, r.h, v["dinv"].h))
-        chk(lib.CeedXVectorAXPBY(pv.h, one, z.h, C.c_double(0.0)))
-        chk(lib.CeedXVectorDotTo(r.h, z.h, None, sc.h, 0))
-        for j in range(steps):
-            rz, rz_new, ja, jb = (0, 3, 8 + 2 * j, 9 + 2 * j) if j % 2 == 0 else (3, 0, 8 + 2 * j, 9 + 2 * j)
-            lv.Anext.apply(pv, Ap)
-            chk(lib.CeedXVectorDotTo(pv.h, Ap.h, None, sc.h, 1))
-            chk(lib.CeedXScalarDivide(sc.h, ja, rz, 1, one))
-            chk(lib.CeedXVectorAXPBYScalars(r.h, sc.h, ja, neg, Ap.h, -1, one))
-            chk(lib.CeedXVectorPointwiseMult(z.h, r.h, v["dinv"].h))
-            chk(lib.CeedXVectorDotTo(r.h, z.h, None, sc.h, rz_new))
-            chk(lib.CeedXScalarDivide(sc.h, jb, rz_new, rz, one))
-            chk(lib.CeedXVectorAXPBYScalars(pv.h, sc.h, -1, one, z.h, jb, one))
-        s = sc.to_numpy()
-        alphas, betas = [], []
-        for j in range(steps):
-            if not (s[8 + 2 * j] > 0.0) or not np.isfinite(s[9 + 2 * j]):
-                break
-            alphas.append(float(s[8 + 2 * j])); betas.append(float(s[9 + 2 * j]))
-        k = len(alphas)
-        if not k:
-            return 1.0
-        T = np.zeros((k, k))
-        for j in range(k):
-            T[j, j] = 1.0 / alphas[j] + (betas[j - 1] / alphas[j - 1] if j else 0.0)
-            if j + 1 < k:
-                T[j, j + 1] = T[j + 1, j] = np.sqrt(max(betas[j], 0.0)) / alphas[j]
-        return float(np.linalg.eigvalsh(T).max())
+        """Largest eigenvalue of D^-1 A_next: the Lanczos tridiagonal of `steps` Jacobi-PCG steps, scalars on the device."""
+        v = lv.v
+        return lanczos_emax(*lanczos_device(self.ceed, lv.Anext.apply, lambda z, r: z.pointwise_mult(r, v["dinv"]), lv.x0,
+                                            v["r"], v["z"], v["d"], v["t"], steps))
 
     # ---- the cycle ------------------------------------------------------------------------------------------------------
     def _chebyshev(self, lv, b, x, zero_guess):
         """Chebyshev-Jacobi sweep on lv.Anext (the matrix of the level BELOW transfer lv), bounds [emax / ratio, 1.1 emax]."""
-        lib, chk, v = self.L.lib, self.L.chk, lv.v
-        lmin, lmax = lv.emax / self.smooth_ratio, 1.1 * lv.emax
-        theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
-        sigma = theta / delta
-        rho = 1.0 / sigma
+        v = lv.v
         r, d, t = v["r"], v["d"], v["t"]
-        if zero_guess:
-            chk(lib.CeedXVectorChebyshevStart(x.h, d.h, r.h, b.h, None, v["dinv"].h, C.c_double(1.0 / theta), 1))
-        else:
-            lv.Anext.apply(x, t)
-            chk(lib.CeedXVectorChebyshevStart(x.h, d.h, r.h, b.h, t.h, v["dinv"].h, C.c_double(1.0 / theta), 0))
-        for _ in range(1, self.smooth_its):
-            lv.Anext.apply(d, t)
-            rho_new = 1.0 / (2.0 * sigma - rho)
-            chk(lib.CeedXVectorChebyshevUpdate(x.h, d.h, r.h, t.h, v["dinv"].h, C.c_double(2.0 * rho_new / delta), C.c_double(rho_new * rho), 0))
-            rho = rho_new
+        for k, (c1, c2) in enumerate(chebyshev_coefficients_on(lv.emax / self.smooth_ratio, 1.1 * lv.emax, self.smooth_its)):
+            if k:
+                lv.Anext.apply(d, t)
+                x.chebyshev_update(d, r, t, v["dinv"], c1, c2)
+            elif zero_guess:
+                x.chebyshev_start(d, r, b, None, v["dinv"], c1, True)
+            else:
+                lv.Anext.apply(x, t)
+                x.chebyshev_start(d, r, b, t, v["dinv"], c1, False)
 
     def _cycle(self, i):
         """Solve approximately A_{i} x = b on the level below transfer i - 1 (its vectors live in levels[i - 1].v)."""
         up = self.levels[i - 1]             # the transfer that produced this level: its matrix is up.Anext
         b, x = up.v["b"], up.v["x"]
         lv = self.levels[i]                 # the transfer from this level to the next
-        lib, chk = self.L.lib, self.L.chk
         for rep in range(self.coarse_cycles):      # coarse_cycles = 2: two cycles of this level per visit (a W-cycle of the hierarchy)
             self._chebyshev(up, b, x, rep == 0)
             up.Anext.apply(x, up.v["t"])
-            chk(lib.CeedXVectorWAXPBY(up.v["z"].h, C.c_double(1.0), b.h, C.c_double(-1.0), up.v["t"].h))
+            up.v["z"].waxpby(1.0, b, -1.0, up.v["t"])
             if lv.dense_next:
                 lv.Pt.apply(up.v["z"], self.rc)
                 lv.Anext.apply(self.rc, self.xc)
@@ -585,7 +525,7 @@ class AggregationAMG:
                 lv.Pt.apply(up.v["z"], lv.v["b"])
                 self._cycle(i + 1)
                 lv.P.apply(lv.v["x"], up.v["z"])
-            chk(lib.CeedXVectorAXPBY(x.h, C.c_double(1.0), up.v["z"].h, C.c_double(1.0)))
+            x.axpby(1.0, up.v["z"], 1.0)
             self._chebyshev(up, b, x, False)
 
     # ---- the coarse correction of level 0 (called by the solver between its own smoothing sweeps): x += P (...) P^T r
@@ -598,7 +538,7 @@ class AggregationAMG:
         # several ranks: r is a consistent L-vector -- every dof counts ONCE (owner weights), each rank restricts its share onto the
         # (global) coarse dofs and the shares are summed over the ranks: the coarse level below is replicated
         d = l0.dd
-        self.L.chk(self.L.lib.CeedXVectorPointwiseMult(d["rw"].h, r.h, d["w"].h))
+        d["rw"].pointwise_mult(r, d["w"])
         l0.Pt.apply(d["rw"], dst)
         self._allreduce(dst)
 
@@ -615,11 +555,11 @@ class AggregationAMG:
 
     def destroy(self):
         for lv in reversed(self.levels):
-            dd = getattr(lv, "dd", None) or {}
+            dd = lv.dd or {}
             for o in [lv.Anext, dd.get("local"), lv.T, lv.Pt, lv.P, lv.x0, dd.get("coo"), dd.get("vals"), dd.get("w"), dd.get("rw")] + list(lv.v.values()):
                 if o is not None:
                     o.destroy()
-        for o in (self.rc, self.xc, self._scal):
+        for o in (self.rc, self.xc):
             if o is not None:
                 o.destroy()
-        self.levels, self.rc, self.xc, self._scal = [], None, None, None
+        self.levels, self.rc, self.xc = [], None, None

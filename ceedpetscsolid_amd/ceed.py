@@ -220,8 +220,7 @@ def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b
     """CeedXVectorChebyshevStepPointBlock: ri = b - t; d = c1 B ri + c2 d; x = d or x + d (ri stored if r is given)."""
     L = x.L
     if L.has("CeedXVectorChebyshevStepPointBlock"):
-        L.chk(L.lib.CeedXVectorChebyshevStepPointBlock(x.h, d.h, r.h if r is not None else None, b.h, t.h if t is not None else None,
-                                                       blocks.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        L.chk(L.lib.CeedXVectorChebyshevStepPointBlock(x.h, d.h, _h(r), b.h, _h(t), blocks.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
         return
     if any(v is not None and v.n != x.n for v in (d, r, b, t)):
         raise CeedError("chebyshev_step_pointblock: vector lengths differ")
@@ -299,9 +298,12 @@ class Csr:
     def update(self):
         self.L.chk(self.L.lib.CeedXCsrUpdate(self.h))
 
+    def get_values(self, v: "Vector"):
+        self.L.chk(self.L.lib.CeedXCsrGetValues(self.h, v.h))
+
     def values(self, ceed: "Ceed" = None) -> np.ndarray:
         v = (ceed or self._ceed).vector(max(self.nnz, 1))
-        self.L.chk(self.L.lib.CeedXCsrGetValues(self.h, v.h))
+        self.get_values(v)
         out = v.to_numpy()[:self.nnz].copy()
         v.destroy()
         return out
@@ -338,6 +340,7 @@ class Ceed:
     def __init__(self, lib: CeedLib, resource: str):
         self.L = lib
         self.h = C.c_void_p()
+        self._scalars = None
         lib.chk(lib.lib.CeedInit(resource.encode(), C.byref(self.h)))
 
     @property
@@ -370,6 +373,21 @@ class Ceed:
         self.L.chk(self.L.lib.CeedXCommGetSize(self.h, C.byref(n), C.byref(r)))
         return n.value, r.value
 
+    @property
+    def scalars(self) -> "Vector":
+        """The Ceed's one register file of device scalars, made at first use: 8 working slots, two coefficients for each of 16 steps."""
+        if self._scalars is None:
+            self._scalars = self.vector(8 + 2 * 16)
+        return self._scalars
+
+    def scalar_divide(self, scalars: "Vector", dst: int, num: int, den: int, scale: float = 1.0):
+        """scalars[dst] = scale * scalars[num] / scalars[den] (den < 0: no division; a non-positive denominator gives 0)"""
+        self.L.chk(self.L.lib.CeedXScalarDivide(scalars.h, dst, num, den, C.c_double(scale)))
+
+    def all_reduce(self, v: "Vector", first: int = 0, n: Optional[int] = None):
+        """Entries [first, first + n) of v (default: all) summed over the ranks of the Ceed's communicator, in place, on its stream."""
+        self.L.chk(self.L.lib.CeedXCommAllReduce(self.h, v.h, first, v.n if n is None else n))
+
     def capture(self, fn) -> "Graph":
         """Record the device work `fn()` queues on this Ceed into a hipGraph (CeedXGraph*)."""
         self.L.chk(self.L.lib.CeedXGraphBeginCapture(self.h))
@@ -385,12 +403,25 @@ class Ceed:
         return Graph(self.L, g)
 
     def destroy(self):
+        if self._scalars is not None:
+            self._scalars.destroy()
         if self.h:
             self.L.lib.CeedDestroy(C.byref(self.h))
 
     # -- factories ---------------------------------------------------------
     def vector(self, n: int) -> "Vector":
         return Vector(self, n)
+
+    def tensor_vector(self, n: int, device) -> "Vector":
+        """A vector over a zeroed torch tensor ``.t`` on ``device`` (several ranks: interface sums and torch.distributed reductions act
+        on the tensor in place), borrowed as a host array or a device pointer; whoever changes ``.t`` behind the Ceed calls ``touched()``."""
+        import torch
+        v = self.vector(n)
+        v.t = torch.zeros(max(n, 1), dtype=torch.float64, device=device)[:n]
+        if v.t.device.type != "cuda":
+            v.set_array(v.t.numpy(), copy=False)
+        v.touched()                  # (a device tensor: handed over as a device pointer)
+        return v
 
     def elem_restriction(self, nelem, elemsize, ncomp, compstride, lsize, offsets) -> "ElemRestriction":
         return ElemRestriction(self, nelem, elemsize, ncomp, compstride, lsize, offsets=offsets)
@@ -411,7 +442,14 @@ class Ceed:
         return Operator(self, qf)
 
 
+def _h(vec: Optional["Vector"]):
+    """The handle of a vector, None (NULL) for an absent one."""
+    return vec.h if vec is not None else None
+
+
 class Vector:
+    t = None            # the torch tensor behind the vector (Ceed.tensor_vector only)
+
     def __init__(self, ceed: Ceed, n: int):
         self.ceed, self.L, self.n = ceed, ceed.L, int(n)
         self.h = C.c_void_p()
@@ -458,6 +496,50 @@ class Vector:
     def reciprocal(self):
         self.L.chk(self.L.lib.CeedVectorReciprocal(self.h))
 
+    # ---- vectors over a torch tensor (Ceed.tensor_vector) -----------------------------------------------------------------
+    def fill(self, arr):
+        """self := arr (host array), keeping the alias of a tensor-backed vector intact."""
+        if self.t is None:
+            return self.set_array(arr)
+        import torch
+        self.t.copy_(torch.from_numpy(_np_f64(arr)))
+        self.touched()
+
+    def touched(self):
+        """The tensor behind the vector was modified outside the Ceed: a device tensor is handed over again, which drops the host mirror."""
+        if self.t is not None and self.t.device.type == "cuda":
+            self.set_device_pointer(self.t.data_ptr())
+
+    # ---- CeedXVector* (formulas: include/ceed.h): self is the vector written (the left operand of a dot), None an absent operand ----
+    def axpby(self, a: float, x: "Vector", b: float):                      # self = a x + b self
+        self.L.chk(self.L.lib.CeedXVectorAXPBY(self.h, C.c_double(a), x.h, C.c_double(b)))
+
+    def waxpby(self, a: float, x: "Vector", b: float, y: "Vector"):        # self = a x + b y
+        self.L.chk(self.L.lib.CeedXVectorWAXPBY(self.h, C.c_double(a), x.h, C.c_double(b), y.h))
+
+    def pointwise_mult(self, x: "Vector", y: "Vector"):                    # self = x .* y
+        self.L.chk(self.L.lib.CeedXVectorPointwiseMult(self.h, x.h, y.h))
+
+    def dot(self, y: "Vector", weight: Optional["Vector"] = None) -> float:   # sum weight .* self .* y, read on the host
+        r = C.c_double()
+        self.L.chk(self.L.lib.CeedXVectorDot(self.h, y.h, _h(weight), C.byref(r)))
+        return r.value
+
+    def dot_to(self, y: "Vector", scalars: "Vector", slot: int, weight: Optional["Vector"] = None):   # the same into scalars[slot]
+        self.L.chk(self.L.lib.CeedXVectorDotTo(self.h, y.h, _h(weight), scalars.h, slot))
+
+    def axpby_scalars(self, scalars, ia: int, sa: float, x, ib: int, sb: float):   # axpby, a = sa scalars[ia], b = sb scalars[ib]; index < 0: 1
+        self.L.chk(self.L.lib.CeedXVectorAXPBYScalars(self.h, scalars.h, ia, C.c_double(sa), x.h, ib, C.c_double(sb)))
+
+    def chebyshev_start(self, d, r, b, t, dinv, c1: float, assign_x: bool):   # r = b - t;  d = c1 dinv .* r;  self = d or self + d
+        self.L.chk(self.L.lib.CeedXVectorChebyshevStart(self.h, d.h, r.h, b.h, _h(t), dinv.h, C.c_double(c1), int(bool(assign_x))))
+
+    def chebyshev_update(self, d, r, t, dinv, c1: float, c2: float, assign_x: bool = False):   # r -= t;  d = c1 dinv .* r + c2 d;  self (+)= d
+        self.L.chk(self.L.lib.CeedXVectorChebyshevUpdate(self.h, d.h, r.h, _h(t), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+
+    def chebyshev_step(self, d, r, b, t, dinv, c1: float, c2: float, assign_x: bool):   # ri = b - t (stored if r);  d = c1 dinv .* ri + c2 d;  self (+)= d
+        self.L.chk(self.L.lib.CeedXVectorChebyshevStep(self.h, d.h, _h(r), b.h, _h(t), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+
     def destroy(self):
         if self.h:
             self.L.lib.CeedVectorDestroy(C.byref(self.h))
@@ -479,19 +561,17 @@ class ElemRestriction:
                 ceed.h, c_int(nelem), c_int(elemsize), c_int(ncomp), c_int(compstride), c_int(lsize),
                 MEM_HOST, COPY_VALUES, off.ctypes.data_as(c_int_p), C.byref(self.h)))
 
-    def create_lvector(self) -> Vector:
+    def _create_vector(self, n: int, evector: bool) -> Vector:
         v = Vector.__new__(Vector)
-        v.ceed, v.L, v.n, v._keep = self.ceed, self.L, self.lsize, None
-        v.h = C.c_void_p()
-        self.L.chk(self.L.lib.CeedElemRestrictionCreateVector(self.h, C.byref(v.h), None))
+        v.ceed, v.L, v.n, v._keep, v.h = self.ceed, self.L, n, None, C.c_void_p()
+        self.L.chk(self.L.lib.CeedElemRestrictionCreateVector(self.h, *((None, C.byref(v.h)) if evector else (C.byref(v.h), None))))
         return v
 
+    def create_lvector(self) -> Vector:
+        return self._create_vector(self.lsize, False)
+
     def create_evector(self) -> Vector:
-        v = Vector.__new__(Vector)
-        v.ceed, v.L, v.n, v._keep = self.ceed, self.L, self.nelem * self.elemsize * self.ncomp, None
-        v.h = C.c_void_p()
-        self.L.chk(self.L.lib.CeedElemRestrictionCreateVector(self.h, None, C.byref(v.h)))
-        return v
+        return self._create_vector(self.nelem * self.elemsize * self.ncomp, True)
 
     def apply(self, tmode, u: Vector, v: Vector):
         self.L.chk(self.L.lib.CeedElemRestrictionApply(self.h, tmode, u.h, v.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
@@ -611,6 +691,16 @@ class Operator:
         o = vout.h if vout is not None else C.c_void_p(L.VECTOR_NONE)
         L.chk(L.lib.CeedOperatorApply(self.h, i, o, C.c_void_p(L.REQUEST_IMMEDIATE)))
 
+    def apply_add(self, vin: Vector, vout: Vector):                         # vout += A vin
+        self.L.chk(self.L.lib.CeedOperatorApplyAdd(self.h, vin.h, vout.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+
+    def apply_residual(self, vin: Vector, t: Vector, b: Vector, w: Vector):   # w = b - A vin in the apply's epilogue (t: scratch)
+        self.L.chk(self.L.lib.CeedXOperatorApplyResidual(self.h, vin.h, t.h, b.h, w.h))
+
+    def apply_chebyshev(self, vin, t, x, d, r, b, dinv, c1: float, c2: float, assign_x: bool = False):
+        """t = A vin consumed where it is formed by the smoother's step on x (with b: Vector.chebyshev_step, without: chebyshev_update)"""
+        self.L.chk(self.L.lib.CeedXOperatorApplyChebyshev(self.h, vin.h, t.h, x.h, d.h, _h(r), _h(b), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+
     def assemble_diagonal(self, vec: Vector):
         self.L.chk(self.L.lib.CeedOperatorLinearAssembleDiagonal(self.h, vec.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
 
@@ -625,22 +715,31 @@ class Operator:
         self.L.chk(self.L.lib.CeedXOperatorGetKernelName(self.h, C.byref(s)))
         return s.value.decode() if s.value else ""
 
-    def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
+    @staticmethod
+    def _bytes(mask):
+        """(the byte array to keep alive over the call, its pointer, its length) of a mask; (None, None, 0) of an absent one"""
         if mask is None:
-            self.L.chk(self.L.lib.CeedXOperatorSetDirichletMask(self.h, MEM_HOST, None, c_int(0)))
-        else:
-            m = np.ascontiguousarray(mask, dtype=np.uint8)
-            self.L.chk(self.L.lib.CeedXOperatorSetDirichletMask(
-                self.h, MEM_HOST, m.ctypes.data_as(C.POINTER(C.c_ubyte)), c_int(m.size)))
+            return None, None, c_int(0)
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte)), c_int(m.size)
+
+    def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
+        _, p, n = self._bytes(mask)
+        self.L.chk(self.L.lib.CeedXOperatorSetDirichletMask(self.h, MEM_HOST, p, n))
+
+    def set_dirichlet_mask_mode(self, mask_in, mask_out=None, mode: int = 3):
+        """1 = masked entries read as zero on input, 2 = masked rows dropped on output, 3 = both; transfer operators have different
+        L-vectors on their two sides and take both masks."""
+        mi, mo = self._bytes(mask_in), self._bytes(mask_out)
+        self.L.chk(self.L.lib.CeedXOperatorSetDirichletMaskMode(self.h, MEM_HOST, mi[1], mi[2], mo[1], mo[2], mode))
+
+    def set_fine_scale(self, scale: Optional[Vector]):      # the fine-side 1 / multiplicity of a transfer operator (None clears)
+        self.L.chk(self.L.lib.CeedXOperatorSetFineScale(self.h, _h(scale)))
 
     def set_overlap_split(self, n_leading_elems: int, priority: Optional[np.ndarray]):
         """CeedXOperatorSetOverlapSplit: leading elements / priority L-vector entries of the split-phase apply."""
-        if priority is None:
-            self.L.chk(self.L.lib.CeedXOperatorSetOverlapSplit(self.h, c_int(0), None, c_int(0)))
-        else:
-            m = np.ascontiguousarray(priority, dtype=np.uint8)
-            self.L.chk(self.L.lib.CeedXOperatorSetOverlapSplit(
-                self.h, c_int(n_leading_elems), m.ctypes.data_as(C.POINTER(C.c_ubyte)), c_int(m.size)))
+        _, p, n = self._bytes(priority)
+        self.L.chk(self.L.lib.CeedXOperatorSetOverlapSplit(self.h, c_int(n_leading_elems if priority is not None else 0), p, n))
 
     def apply_state(self, u: "Vector"):
         """CeedXOperatorApplyState: write only the stored state (passive gradu output) of a residual-shaped operator."""

@@ -28,7 +28,6 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-import ctypes as C
 import numpy as np
 
 from . import ceed as cd
@@ -228,15 +227,7 @@ class SolidProblem:
             self._set_mask(lv.opState, fine.mask, mode=2)   # as opApply: boundary values stay in the input
 
     def _set_mask(self, op: cd.Operator, mask_in, mask_out=None, mode=3):
-        L = self.ceed.L
-        mi = np.ascontiguousarray(mask_in, dtype=np.uint8)
-        pmi = mi.ctypes.data_as(C.POINTER(C.c_ubyte))
-        if mask_out is None:
-            L.chk(L.lib.CeedXOperatorSetDirichletMaskMode(op.h, cd.MEM_HOST, pmi, cd.c_int(mi.size), None, cd.c_int(0), mode))
-        else:
-            mo = np.ascontiguousarray(mask_out, dtype=np.uint8)
-            L.chk(L.lib.CeedXOperatorSetDirichletMaskMode(
-                op.h, cd.MEM_HOST, pmi, cd.c_int(mi.size), mo.ctypes.data_as(C.POINTER(C.c_ubyte)), cd.c_int(mo.size), mode))
+        op.set_dirichlet_mask_mode(mask_in, mask_out, mode)
 
     def _setup_level(self, level: int):
         c, Q = self.ceed, self.Q
@@ -288,10 +279,9 @@ class SolidProblem:
             lv.opProlong = c.operator(qfP)
             lv.opProlong.set_field("input", co.Erestrictu, lv.basisCtoF, "active")
             lv.opProlong.set_field("output", lv.Erestrictu, None, "active")
-            L = self.ceed.L
             if self.fused_bc:   # fused_bc=False is the EXTENSION-FREE form: no CeedX* call at all; the caller applies multVec
                 for op in (lv.opRestrict, lv.opProlong):   # (matops.c:149,176) and the Dirichlet handling (:33,57,106) itself
-                    L.chk(L.lib.CeedXOperatorSetFineScale(op.h, lv.multinv.h))
+                    op.set_fine_scale(lv.multinv)
             if self.fused_bc:
                 self._set_mask(lv.opProlong, co.mask, lv.mask, mode=3)
                 self._set_mask(lv.opRestrict, lv.mask, co.mask, mode=3)
@@ -338,8 +328,7 @@ class SolidProblem:
         """yf += Prolong_Ceed(xc): CeedOperatorApplyAdd of opProlong -- the correction of a V-cycle added in place (one rank: no interface
         sum between the prolongation and the addition).  Every fine node is written by its one owning element: the same bits as
         prolong into a scratch vector followed by an axpy."""
-        L = self.ceed.L
-        L.chk(L.lib.CeedOperatorApplyAdd(self.levels[level].opProlong.h, xc.h, yf.h, cd.C.c_void_p(L.REQUEST_IMMEDIATE)))
+        self.levels[level].opProlong.apply_add(xc, yf)
 
     def restrict(self, level: int, xf: cd.Vector, yc: cd.Vector):
         """Restrict_Ceed (matops.c:160-203), level -> level-1."""

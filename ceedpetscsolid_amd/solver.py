@@ -7,10 +7,13 @@ level, eigenvalue bounds (0, 0.1, 0, 1.1) x the estimate (:539-552, :588-590); p
 restriction MatShells (Prolong_Ceed / Restrict_Ceed); a coarse solve by GAMG on the FD-coloured
 p=1 matrix (:457-483,:568-585).  PETSc is absent here, so this is this build's own control flow with
 the same structure; every vector and operator operation runs on the device through the C ABI
-(CeedOperatorApply, CeedOperatorLinearAssembleDiagonal, CeedX vector helpers).  The coarse level is
-solved by Jacobi-preconditioned CG on the p=1 operator itself (no assembled matrix, no AMG); because
-that makes the preconditioner mildly non-linear the outer Krylov method is the flexible
-(Polak-Ribiere) CG, which coincides with CG for a fixed preconditioner.
+(CeedOperatorApply, CeedOperatorLinearAssembleDiagonal, CeedX vector helpers), through the methods of ceed.py; the eigenvalue
+estimate and the Chebyshev coefficients of the smoother are those of krylov.py.  The coarse level is solved, by choice
+(``coarse``): by Jacobi-preconditioned CG on the p=1 operator itself ("cg", the default), by a fixed Chebyshev polynomial on that
+operator ("chebyshev") or on the assembled p=1 matrix ("assembled", assembly.py), or by one cycle of a smoothed-aggregation
+hierarchy on the assembled matrix ("amg", amg.py: what the reference asks of PCGAMG).  Because the CG coarse solve makes the
+preconditioner mildly non-linear the outer Krylov method is the flexible (Polak-Ribiere) CG, which coincides with CG for a
+fixed preconditioner.
 
 Iteration counts are therefore this build's own, not PETSc's; the throughput figure reported is the
 reference's "DoFs/Sec in SNES" = 1e-6 * Ugsz * (total KSP iterations) / (solve time)
@@ -18,14 +21,14 @@ reference's "DoFs/Sec in SNES" = 1e-6 * Ugsz * (total KSP iterations) / (solve t
 """
 from __future__ import annotations
 
-import ctypes as C
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional
 
 import numpy as np
 
 from . import ceed as cd
+from .krylov import chebyshev_coefficients, lanczos_device, lanczos_emax
 from .solid import SolidProblem
 
 
@@ -67,14 +70,6 @@ class SolveStats:
     initial_residuals: list = field(default_factory=list)   # |R| at the start of every load increment (what snes_rtol is relative to)
 
 
-class Vec:
-    """Thin helpers over CeedVector + the CeedX vector extensions (stand-ins for PETSc Vec calls)."""
-
-    def __init__(self, ceed: cd.Ceed, n: int):
-        self.v = ceed.vector(n).set_value(0.0)
-        self.n = n
-
-
 class NewtonPMG:
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None,
                  halo=None, rccl="auto", lead_elements: int = 0, smooth_its: int = 3, coarse_rtol: float = 1e-3, coarse_maxit: int = 200,
@@ -94,11 +89,24 @@ class NewtonPMG:
         # values per node.
         if smoother not in ("jacobi", "pbjacobi"):
             raise ValueError(f"smoother must be 'jacobi' or 'pbjacobi', not {smoother!r}")
-        if smoother == "pbjacobi" and halo is not None and (halo[-1] if isinstance(halo, (list, tuple)) else halo).world > 1:
+        # Several ranks (one element partition per rank, halo.py): `halo` is one HaloExchange per multigrid level (a single one stands
+        # for a one-level list).  Every vector then aliases a torch tensor (host memory for the CPU oracle, device memory otherwise;
+        # the Ceed's stream must be torch's current stream, as in bench.py), so the interface sums of halo.add() act on the operators'
+        # outputs in place: the L -> G sum of matops.c:57 after each Jacobian / residual / transfer / diagonal.  Dots are owner-weighted.
+        single = halo is not None and not isinstance(halo, (list, tuple))
+        halo = [halo] if single else halo
+        many = halo is not None and halo[-1].world > 1
+        if smoother == "pbjacobi" and many:
             raise ValueError("smoother='pbjacobi' is not provided with a halo (several ranks): the nodal blocks of the interface nodes "
                              "are not summed over the ranks")
+        if many and single and len(prob.levels) > 1:
+            raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
+        if many and len(halo) != len(prob.levels):
+            raise ValueError("one HaloExchange per multigrid level expected")
+        self.halos = list(halo) if many else None
+        self.halo = self.halos[-1] if self.halos else None
         self.smoother, self._pb = smoother, smoother == "pbjacobi"
-        self.clamp, self.mms, self.halo = clamp or {}, mms, halo
+        self.clamp, self.mms = clamp or {}, mms
         # "cp": critical-point secant search, up to three secant steps, a step outside (0, 10] ends the search (this build's default);
         # "cp-petsc": SNESLINESEARCHCP with PETSc's defaults (elasticity.c:596-601 sets the type and nothing else) as recalled from its
         # source, which is NOT in this image (unverified): ONE secant step from (0, 1), downhill slope enforced, direction switched below
@@ -142,32 +150,15 @@ class NewtonPMG:
             # "local product, then the interface sum" like the matrix-free levels); with "amg" the first transfer of the aggregation
             # hierarchy is distributed over the ranks and everything under it is small and replicated (amg.py, round 5; rounds 3-4
             # all-gathered all element matrices and replicated the whole level)
-            many = halo is not None and isinstance(halo, (list, tuple)) and halo[-1].world > 1
             self.asm = AssembledLevel(prob, 0)
             if coarse == "amg":
                 from .amg import AggregationAMG
                 self.amg = AggregationAMG(self.asm, verbose=verbose, max_coarse_dofs=amg_max_coarse_dofs,
                                           smooth_its=amg_smooth_its, smooth_ratio=amg_smooth_ratio, coarse_cycles=amg_coarse_cycles,
-                                          dist_halo=halo[0] if many else None)
+                                          dist_halo=self.halos[0] if self.halos else None)
         self._pc_graph, self._pc_graph_io, self._pc_graph_counts, self._pc_warm = None, None, (0, 0), False
         self.ksp_rtol, self.snes_rtol, self.snes_maxit, self.verbose = ksp_rtol, snes_rtol, snes_maxit, verbose
         self.nlev = len(prob.levels)
-        c = self.ceed
-        # Several ranks (one element partition per rank, halo.py): `halo` is one HaloExchange per multigrid level.
-        # Every vector then aliases a torch tensor (host memory for the CPU oracle, device memory otherwise; the
-        # Ceed's stream must be torch's current stream, as in bench.py), so the interface sums of halo.add() act on
-        # the operators' outputs in place: after each Jacobian / residual / transfer / diagonal, the L -> G sum of
-        # matops.c:57.  Dots are weighted by ownership and all-reduced.
-        self.halos = None
-        if halo is not None and not isinstance(halo, (list, tuple)):
-            if halo.world > 1 and len(prob.levels) > 1:
-                raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
-            halo = [halo]
-        if halo is not None and halo[-1].world > 1:
-            if len(halo) != len(prob.levels):
-                raise ValueError("one HaloExchange per multigrid level expected")
-            self.halos = list(halo)
-        self.halo = self.halos[-1] if self.halos else None
         # the library's exchange per level (halo.RcclHalo), or None: torch.distributed point-to-point + index ops
         self.rhalos = None
         if self.halos:
@@ -194,13 +185,11 @@ class NewtonPMG:
                 self.w[lv]["pb"] = self._vec(3 * prob.lsize(lv), lv)      # the inverted 3 x 3 blocks, [node][c out][c in]
         self.emax = [1.0] * self.nlev
         self._x0 = {}
-        self._scal = None
         n = prob.lsize()
         top = self.nlev - 1
         self.U, self.R, self.dU, self.Xloc, self.bcv, self.Rtry, self.Utry = (self._vec(n, top) for _ in range(7))
         self.kp, self.kz, self.kAp = (self._vec(n, top) for _ in range(3))
-        lvf = prob.levels[prob.fine]
-        self.free = (lvf.mask == 0)
+        self.free = prob.levels[prob.fine].mask == 0
         self.weights = [None] * self.nlev
         if self.halos:
             for lv in range(self.nlev):
@@ -227,38 +216,27 @@ class NewtonPMG:
 
     # ---- vector helpers ---------------------------------------------------------------------
     def axpby(self, y, a, x, b):
-        self.L.chk(self.L.lib.CeedXVectorAXPBY(y.h, C.c_double(a), x.h, C.c_double(b)))
-
-    def waxpby(self, w, a, x, b, y):
-        self.L.chk(self.L.lib.CeedXVectorWAXPBY(w.h, C.c_double(a), x.h, C.c_double(b), y.h))
+        y.axpby(a, x, b)
 
     def copy(self, dst, src):
-        self.axpby(dst, 1.0, src, 0.0)
-
-    def pmult(self, w, x, y):
-        self.L.chk(self.L.lib.CeedXVectorPointwiseMult(w.h, x.h, y.h))
+        dst.axpby(1.0, src, 0.0)
 
     def minv(self, lv, z, r):
         """z = M^-1 r with the smoother's preconditioner of level lv: the inverted diagonal, or the inverted nodal blocks."""
         if self._pb:
             cd.pointblock_mult(z, self.w[lv]["pb"], r)
         else:
-            self.pmult(z, r, self.w[lv]["dinv"])
+            z.pointwise_mult(r, self.w[lv]["dinv"])
 
     def dot(self, x, y, fine_weight=False, lv=None) -> float:
         """x . y; on several ranks each dof counts once (owner weights of level `lv`, default the fine level)."""
-        r = C.c_double()
         lv = self.nlev - 1 if lv is None else lv
-        wv = self.weights[lv].h if self.weights[lv] is not None else None
         if self.rhalos:      # the sum over the ranks on the device (ncclAllReduce on the Ceed's stream), ONE read at the end
-            if self._scal is None:
-                self._scal = self.ceed.vector(8 + 2 * 16)
-            lib, chk = self.L.lib, self.L.chk
-            chk(lib.CeedXVectorDotTo(x.h, y.h, wv, self._scal.h, 7))
-            chk(lib.CeedXCommAllReduce(self.ceed.h, self._scal.h, 7, 1))
-            return float(self._scal.to_numpy()[7])
-        self.L.chk(self.L.lib.CeedXVectorDot(x.h, y.h, wv, C.byref(r)))
-        v = r.value
+            sc = self.ceed.scalars
+            x.dot_to(y, sc, 7, self.weights[lv])
+            self.ceed.all_reduce(sc, 7, 1)
+            return float(sc.to_numpy()[7])
+        v = x.dot(y, self.weights[lv])
         if self.halos:
             import torch, torch.distributed as dist
             t = torch.tensor([v], dtype=torch.float64, device="cpu" if self.halos[lv].device.type == "cpu" or self.halos[lv].stage_host else self.halos[lv].device)
@@ -268,32 +246,11 @@ class NewtonPMG:
 
     # ---- vectors that alias torch tensors (several ranks only) ----------------------------------------
     def _vec(self, n, lv):
-        c = self.ceed
-        if not self.halos:
-            return c.vector(n).set_value(0.0)
-        import torch
-        dev = self.halos[lv].device
-        v = c.vector(n)
-        v.t = torch.zeros(n, dtype=torch.float64, device=dev)
-        if dev.type == "cuda":
-            v.set_device_pointer(v.t.data_ptr())
-        else:
-            v.set_array(v.t.numpy(), copy=False)
-        return v
+        return self.ceed.tensor_vector(n, self.halos[lv].device) if self.halos else self.ceed.vector(n).set_value(0.0)
 
     def _set(self, vec, arr):
         """vec := arr (host array), keeping the torch alias intact."""
-        if hasattr(vec, "t"):
-            import torch
-            vec.t.copy_(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64)))
-            self._touched(vec)
-        else:
-            vec.set_array(arr)
-
-    def _touched(self, vec):
-        """The tensor behind a device vector was modified outside the Ceed: drop its host mirror."""
-        if vec.t.device.type == "cuda":
-            vec.set_device_pointer(vec.t.data_ptr())
+        vec.fill(arr)
 
     def _halo_sum(self, lv, vec):
         """Interface sum of an operator output at level lv (the DMLocalToGlobal(ADD_VALUES) of matops.c:57)."""
@@ -303,7 +260,7 @@ class NewtonPMG:
             if vec.t.device.type == "cuda":
                 self.ceed.synchronize()
             self.halos[lv].add(vec.t)
-            self._touched(vec)
+            vec.touched()
 
     def _refresh_multiplicity(self, lv):
         """multVec of misc.c:115-143 counted over ALL ranks: 1 / (halo-summed element multiplicity)."""
@@ -337,19 +294,16 @@ class NewtonPMG:
         """z = b - A x on level lv (t: the level's scratch)."""
         w, op = self.w[lv], self._fused_op(lv)
         if op is not None:
-            self.L.chk(self.L.lib.CeedXOperatorApplyResidual(op.h, x.h, w["t"].h, b.h, z.h))
+            op.apply_residual(x, w["t"], b, z)
             self.stats.jacobian_applies += 1
         else:
             self.A(lv, x, w["t"])
-            self.waxpby(z, 1.0, b, -1.0, w["t"])
+            z.waxpby(1.0, b, -1.0, w["t"])
 
     def _collect_bc_nodes(self):
         from .mesh import side_set_nodes
         lv = self.p.levels[self.p.fine]
-        out = {}
-        for sid in self.clamp:
-            out[sid] = side_set_nodes(self.p.mesh, lv.dofmap, [sid])
-        return out
+        return {sid: side_set_nodes(self.p.mesh, lv.dofmap, [sid]) for sid in self.clamp}
 
     def bc_values(self, load: float) -> np.ndarray:
         """DMPlexInsertBoundaryValues at `time = loadIncrement` (matops.c:70-72)."""
@@ -396,8 +350,7 @@ class NewtonPMG:
                 # 1 / diagonal; constrained rows come out of the masked operator as zeros and stay zero (CeedVectorReciprocal
                 # leaves zeros alone): residuals and corrections are zero there anyway.  No trip through the host.
                 w["dinv"].reciprocal()
-                if hasattr(w["dinv"], "t"):
-                    self._touched(w["dinv"])
+                w["dinv"].touched()
             mask = self.p.levels[lv].mask != 0
             # The start vector of the eigenvalue estimate is drawn once per level; no BLAS on the host (a threaded BLAS
             # call leaves its worker pool spinning, which starves a CPU-quota'd process for ~0.1 s a call).
@@ -415,14 +368,7 @@ class NewtonPMG:
             # largest eigenvalue of D^-1 A: 10 steps of Jacobi-preconditioned CG on the noisy right-hand side and
             # the largest eigenvalue of its Lanczos tridiagonal -- what KSPChebyshevEstEig does (elasticity.c:546-549).
             # (A plain power iteration from the same vector was 2x low after 12 steps on the config-3 mesh.)
-            alphas, betas = self._lanczos_host(lv, 10) if (self.halos and not self.rhalos) else self._lanczos_device(lv, 10)
-            k = len(alphas)
-            T = np.zeros((max(k, 1), max(k, 1)))
-            for j in range(k):
-                T[j, j] = 1.0 / alphas[j] + (betas[j - 1] / alphas[j - 1] if j else 0.0)
-                if j + 1 < k:
-                    T[j, j + 1] = T[j + 1, j] = np.sqrt(max(betas[j], 0.0)) / alphas[j]
-            self.emax[lv] = float(np.linalg.eigvalsh(T).max()) if k else 1.0
+            self.emax[lv] = lanczos_emax(*(self._lanczos_host(lv, 10) if (self.halos and not self.rhalos) else self._lanczos_device(lv, 10)))
 
     def _lanczos_host(self, lv, steps):
         """CG coefficients with every dot product read on the host (several ranks: the dots are all-reduced)."""
@@ -447,43 +393,10 @@ class NewtonPMG:
         return alphas, betas
 
     def _lanczos_device(self, lv, steps):
-        """The same recurrence with its scalars kept on the device (CeedXVectorDotTo / CeedXScalarDivide /
-        CeedXVectorAXPBYScalars): one read of the 2 * steps coefficients at the end instead of 2 * steps + 1 host round
-        trips.  Scalar slots: 0 / 3 rz of the even / odd steps, 1 pAp; 8 + 2 j alpha_j, 9 + 2 j beta_j."""
-        w, lib, chk = self.w[lv], self.L.lib, self.L.chk
-        r, z, pv, Ap = w["r"], w["z"], w["d"], w["t"]
-        if self._scal is None:
-            self._scal = self.ceed.vector(8 + 2 * 16)
-        sc = self._scal
-        sc.set_value(0.0)
-        self.copy(r, self._x0[lv])
-        self.minv(lv, z, r); self.copy(pv, z)
-        one, neg = C.c_double(1.0), C.c_double(-1.0)
-        wv = self.weights[lv].h if self.weights[lv] is not None else None      # several ranks: every dof counts once
-        many = bool(self.rhalos)
-
-        def dot_to(a, b, slot):
-            chk(lib.CeedXVectorDotTo(a.h, b.h, wv, sc.h, slot))
-            if many:                 # summed over the ranks where it lies: the scalar never leaves the device
-                chk(lib.CeedXCommAllReduce(self.ceed.h, sc.h, slot, 1))
-        dot_to(r, z, 0)
-        for j in range(steps):
-            rz, rz_new, ja, jb = (0, 3, 8 + 2 * j, 9 + 2 * j) if j % 2 == 0 else (3, 0, 8 + 2 * j, 9 + 2 * j)
-            self.A(lv, pv, Ap)
-            dot_to(pv, Ap, 1)
-            chk(lib.CeedXScalarDivide(sc.h, ja, rz, 1, one))                           # alpha_j = rz / pAp (0 on breakdown)
-            chk(lib.CeedXVectorAXPBYScalars(r.h, sc.h, ja, neg, Ap.h, -1, one))         # r -= alpha Ap
-            self.minv(lv, z, r)
-            dot_to(r, z, rz_new)
-            chk(lib.CeedXScalarDivide(sc.h, jb, rz_new, rz, one))                       # beta_j = rz_new / rz
-            chk(lib.CeedXVectorAXPBYScalars(pv.h, sc.h, -1, one, z.h, jb, one))         # p = z + beta p
-        v = sc.to_numpy()
-        alphas, betas = [], []
-        for j in range(steps):
-            if not (v[8 + 2 * j] > 0.0) or not np.isfinite(v[9 + 2 * j]):
-                break
-            alphas.append(float(v[8 + 2 * j])); betas.append(float(v[9 + 2 * j]))
-        return alphas, betas
+        """The same recurrence, scalars kept on the device; several ranks: every dof counts once, the library sums the dots."""
+        w = self.w[lv]
+        return lanczos_device(self.ceed, lambda x, y: self.A(lv, x, y), lambda z, r: self.minv(lv, z, r), self._x0[lv],
+                              w["r"], w["z"], w["d"], w["t"], steps, weight=self.weights[lv], all_reduce=bool(self.rhalos))
 
     def chebyshev(self, lv, b, x, its, zero_guess, lmin_frac=0.1):
         """Chebyshev iteration on D^-1 A with bounds [0.1, 1.1] x emax (KSPChebyshevEstEigSet(0,0.1,0,1.1)).  As KSPCHEBYSHEV does, the
@@ -491,39 +404,25 @@ class NewtonPMG:
         applied to x, and the step reads b, dinv, d, x and writes d, x -- no residual vector is read or written (round 5: 48 instead of
         56 B per dof in the step; the two are equal in exact arithmetic)."""
         w = self.w[lv]
-        lmin, lmax = lmin_frac * self.emax[lv], 1.1 * self.emax[lv]
-        theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
-        sigma = theta / delta
-        rho = 1.0 / sigma
         d, t = w["d"], w["t"]
-        step = self.L.lib.CeedXVectorChebyshevStep
-        fused = self.L.lib.CeedXOperatorApplyChebyshev
         op = self._fused_op(lv)
-
-        def one_pb(c1, c2, have_x):
-            """d = c1 B (b - A x) + c2 d;  x (+)= d with the inverted nodal blocks B: the apply, then the block step (the fused
-            epilogue is a lane-per-dof kernel and has no block form)"""
-            if have_x:
-                self.A(lv, x, t)
-            cd.chebyshev_step_pointblock(x, d, None, b, t if have_x else None, w["pb"], c1, c2, not have_x)
 
         def one(c1, c2, have_x):
             """d = c1 dinv (b - A x) + c2 d;  x (+)= d   (have_x False: x = 0, no apply)"""
-            if self._pb:
-                one_pb(c1, c2, have_x)
+            if self._pb:              # the inverted nodal blocks for dinv: the apply, then the block step (the fused epilogue is a
+                if have_x:            # lane-per-dof kernel and has no block form)
+                    self.A(lv, x, t)
+                cd.chebyshev_step_pointblock(x, d, None, b, t if have_x else None, w["pb"], c1, c2, not have_x)
             elif not have_x:
-                self.L.chk(step(x.h, d.h, None, b.h, None, w["dinv"].h, C.c_double(c1), C.c_double(c2), 1))
+                x.chebyshev_step(d, None, b, None, w["dinv"], c1, c2, True)
             elif op is not None:      # the apply and the step in one: A x is consumed where it is formed
-                self.L.chk(fused(op.h, x.h, t.h, x.h, d.h, None, b.h, w["dinv"].h, C.c_double(c1), C.c_double(c2), 0))
+                op.apply_chebyshev(x, t, x, d, None, b, w["dinv"], c1, c2)
                 self.stats.jacobian_applies += 1
             else:
                 self.A(lv, x, t)
-                self.L.chk(step(x.h, d.h, None, b.h, t.h, w["dinv"].h, C.c_double(c1), C.c_double(c2), 0))
-        one(1.0 / theta, 0.0, not zero_guess)
-        for k in range(1, its):
-            rho_new = 1.0 / (2.0 * sigma - rho)
-            one(2.0 * rho_new / delta, rho_new * rho, True)
-            rho = rho_new
+                x.chebyshev_step(d, None, b, t, w["dinv"], c1, c2, False)
+        for k, (c1, c2) in enumerate(chebyshev_coefficients(self.emax[lv], lmin_frac, its)):
+            one(c1, c2, k > 0 or not zero_guess)
 
     def coarse_solve(self, b, x):
         """Jacobi-preconditioned CG on the coarsest operator (stands in for GAMG on the FD-coloured matrix)."""
@@ -554,7 +453,7 @@ class NewtonPMG:
         lf = 1.0 / self.amg_smooth_ratio
         self.chebyshev(0, b, x, self.amg_smooth_its, True, lf)
         self.A(0, x, w["t"])
-        self.waxpby(w["z"], 1.0, b, -1.0, w["t"])                          # residual
+        w["z"].waxpby(1.0, b, -1.0, w["t"])                                # residual
         amg.restrict(w["z"])
         amg.solve_coarsest()
         amg.prolong(w["z"])
@@ -591,7 +490,6 @@ class NewtonPMG:
 
     def _autotune_vcycle(self, r, z, reps=2):
         """Pick (fused consumers?, replayed graph?) by timing the V-cycle in every combination left open ("auto")."""
-        import time
         top = self.nlev - 1
         keep = (self.stats.jacobian_applies, self.stats.coarse_its, self.stats.coarse_spmv)
         fuses = (True, False) if (self._auto_fuse and self._fused_op(top) is not None) else (self.fuse_epilogue,)

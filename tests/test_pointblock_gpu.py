@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from ceedpetscsolid_amd import ceed as cd
+from ceedpetscsolid_amd.krylov import chebyshev_coefficients
 from ceedpetscsolid_amd.mesh import load_mesh_npz
 from ceedpetscsolid_amd.solid import SolidProblem
 from ceedpetscsolid_amd.solver import NewtonPMG
@@ -158,17 +159,10 @@ def test_chebyshev_sweep_with_blocks_against_numpy(oracle, gpu):
     got = xv.to_numpy()
     # the same recurrence (solver.py::chebyshev) with the oracle's matrix, NumPy block inverses and the solver's own emax
     mult = lambda r: np.einsum("nij,nj->ni", Binv, r.reshape(-1, 3)).reshape(-1)
-    lmin, lmax = 0.1 * s.emax[top], 1.1 * s.emax[top]
-    theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
-    sigma = theta / delta
-    rho = 1.0 / sigma
-    d = (1.0 / theta) * mult(b)
-    x = d.copy()
-    for _ in range(1, 3):
-        rho_new = 1.0 / (2.0 * sigma - rho)
-        d = (2.0 * rho_new / delta) * mult(b - A @ x) + (rho_new * rho) * d
+    x = d = np.zeros(n)
+    for c1, c2 in chebyshev_coefficients(s.emax[top], 0.1, 3):
+        d = c1 * mult(b - A @ x) + c2 * d
         x = x + d
-        rho = rho_new
     err = np.abs(got - x).max() / np.abs(x).max()
     print(f"3 Chebyshev steps with blocks, emax {s.emax[top]:.4f}: device vs NumPy recurrence {err:.2e}")
     assert err <= 1e-9 and np.abs(x).max() > 0
