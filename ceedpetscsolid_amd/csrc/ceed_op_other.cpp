@@ -172,9 +172,12 @@ int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CeedQFunction qf = op->qf;
   OpField &u = op->in[0], &en = op->out[0];
   if (!in || in->length < u.rstr->lsize || !out || out->length < en.rstr->lsize) return ceed_error("displacement / energy vector too short");
+  CeedVector qd = op->in[op->i_qdata].vec;
+  if (!is_passive(qd)) return ceed_error("qdata needs a passive vector");
+  if ((size_t)qd->length < (size_t)u.rstr->nelem * 10 * u.basis->Q1d * u.basis->Q1d * u.basis->Q1d) return ceed_error("qdata vector too short");
   EnergyOpArgs a{};
   double *pu, *py, *pq;
-  CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
+  CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(qd, false, &pq));
   a.off_u = u.rstr->d_offsets; a.u = pu; a.off_e = en.rstr->d_offsets; a.y = py; a.qdata = pq;
   a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
   const int kd = qf->kind;
@@ -204,7 +207,10 @@ int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
   a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
   if (a.mode != 2) {
-    CHK(vec_dev(op->in[1].vec, false, &pq)); a.qdata = pq;
+    CeedVector qd = op->in[1].vec;
+    if (!is_passive(qd)) return ceed_error("qdata needs a passive vector");
+    if ((size_t)qd->length < (size_t)a.nelem * 10 * a.Q * a.Q * a.Q) return ceed_error("qdata vector too short");
+    CHK(vec_dev(qd, false, &pq)); a.qdata = pq;
     a.Pout = o.basis->P1d;
     memcpy(a.bu, o.basis->interp1d.data(), sizeof(double) * o.basis->interp1d.size());
     if (!qf->ctx) return ceed_error("QFunction '%s' needs its context", qf->name.c_str());

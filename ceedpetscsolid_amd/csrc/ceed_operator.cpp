@@ -228,7 +228,7 @@ int op_plan(CeedOperator op) {
     if (!is_disp(u)) return unsupported("displacement field");
     const int P = u.basis->P1d, Q = u.basis->Q1d;
     if (!nodes_fit(u)) return unsupported("restriction element size is not P^3");
-    if (!is_qdata(qd, Q)) return unsupported("qdata must be strided 10 x Q^3");
+    if (!is_qdata(qd, Q) || qd.rstr->nelem != u.rstr->nelem) return unsupported("qdata must be strided 10 x Q^3");
     if (energy) {
       if (!is_offsets(o.rstr) || o.rstr->ncomp != 1 || o.rstr->nelem != u.rstr->nelem || o.basis == CEED_BASIS_COLLOCATED ||
           !nodes_fit(o) || o.basis->Q1d != Q || o.basis->P1d != P)
@@ -251,7 +251,7 @@ int op_plan(CeedOperator op) {
     const int Q = x.basis->Q1d;
     if (force) {
       if (qf->in[1].emode != CEED_EVAL_NONE || qf->in[1].size != 10 || qf->out[0].emode != CEED_EVAL_INTERP) return unsupported("forcing takes qdata NONE and gives force INTERP");
-      if (!is_qdata(op->in[1], Q)) return unsupported("qdata must be strided 10 x Q^3");
+      if (!is_qdata(op->in[1], Q) || op->in[1].rstr->nelem != x.rstr->nelem) return unsupported("qdata must be strided 10 x Q^3");
       if (o.basis == CEED_BASIS_COLLOCATED || o.basis->Q1d != Q || !nodes_fit(o)) return unsupported("force basis must share the quadrature of the coordinate basis");
       op->i_qdata = 1;
     } else {

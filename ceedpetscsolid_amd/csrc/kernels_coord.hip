@@ -111,11 +111,11 @@ CPS_DEV double log1p_series4_e(double x) {  // hyperSS.h:43-55
 }
 CPS_DEV double log1p_series4_shifted_e(double x) {  // hyperFS.h:45-67
   const double left = sqrt(2.) / 2 - 1, right = sqrt(2.) - 1;
-  double sum = 0;
+  double sum = 0;   // half the result, as in the reference: a shift moves log(1 + x) by log 2
   if (x < left) { sum -= log(2.) / 2; x = 1 + 2 * x; }
   else if (right < x) { sum += log(2.) / 2; x = (x - 1) / 2; }
   const double y = x / (2. + x), y2 = y * y;
-  return sum + 2. * (y + y2 * y / 3. + y2 * y2 * y / 5. + y2 * y2 * y2 * y / 7.);
+  return 2. * (sum + y + y2 * y / 3. + y2 * y2 * y / 5. + y2 * y2 * y2 * y / 7.);
 }
 // model 0: LinElasEnergy (linElas.h:285-370), 1: HyperSSEnergy (hyperSS.h:326-412), 2: HyperFSEnergy
 // (hyperFS.h:469-553), restated as written (including the `strain_vol * mu` term of the first two)

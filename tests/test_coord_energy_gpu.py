@@ -1,0 +1,347 @@
+"""The set-up and post-processing kernels (csrc/kernels_coord.hip: k_coord_op behind apply_coord, k_energy_op behind apply_energy) at
+every shape they take, device against oracle on identical inputs and both against plain numpy.
+
+k_coord_op serves SetupConstantForce, SetupMMSForce and MMSTrueSoln, k_energy_op the three *Energy and the three *Diagnostic
+QFunctions; both take P and Q from 2 to 8 at run time, on a block of max(P^3, Q^3) threads rounded up to 64.  The shapes here are the
+ones at which such a kernel can be wrong and the one shape of test_gpu_parity.py (a swept cylinder at P = Q = 4) cannot tell:
+  * every P = 2..8 with Q = P, P + 1, P + 2 (Q <= 8): a basis table read with the wrong leading dimension, or transposed, computes the
+    same thing at P = Q; 8 live threads of 64 (Q = 2), 125 of 128 (Q = 5), 512 of 512 (Q = 8, the launch bound);
+  * a mesh with every vertex moved -- neither affine nor swept, so all nine entries of dXdx are non-zero and a wrong index of one shows
+    -- of 8 elements (the centre node summed from 8, face nodes from 2 and 4) and of one element (nothing shared);
+  * the three branches of the finite-strain log series, each shown from the reference to have run;
+  * caller-chosen numberings, CeedOperatorApplyAdd, and an overwriting apply into a pre-filled, longer vector.
+
+Tolerances are the project's own: 1e-10 relative to the oracle in the 2-norm and in the max norm (one wrong entry of one element moves
+the max norm by order one), 1e-12 for the closed forms, which are asserted for the device AND for the oracle.  Both kernels sum shared
+nodes with atomics: nothing here asserts that two device runs agree bitwise.  With CPS_COORD_ENERGY_REPORT=<file> the worst figure per
+kernel, mode or model, and Q is written there."""
+import os
+import time
+
+import numpy as np
+import pytest
+
+from ceedpetscsolid_amd.mesh import box_mesh
+from ceedpetscsolid_amd.postprocess import DIAG_FIELDS, Diagnostics, StrainEnergy
+from ceedpetscsolid_amd.solid import SolidProblem
+from _numbering import NUMBERINGS, PRESET, UNREAD, problem_under, referenced
+from test_gpu_parity import _forcing_and_true_operator, distorted_box
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10          # device against oracle, 2-norm and max norm
+TOL_STATE = 1e-12    # closed forms, device and oracle alike
+# two device applies of one operator differ by the order of the atomic node sums only: at most 8 terms a node, so 7 roundings of the sum
+# of their magnitudes, which (same-sized terms) is within a small multiple of the vector's largest entry -- 1e-13 leaves a factor 100
+TOL_REORDER = 1e-13
+
+PHYSICS = {"linElas": "LinElas", "hyperSS": "HyperSS", "hyperFS": "HyperFS"}
+COORD_KERNEL = {"const": "coord_op<SetupConstantForce>", "mms": "coord_op<SetupMMSForce>", "true": "coord_op<MMSTrueSoln>"}
+DIRECTION = np.array([0.3, -1.0, 2.0])            # the constant forcing _forcing_and_true_operator sets
+PQ = [(P, Q) for P in range(2, 9) for Q in (P, P + 1, P + 2) if Q <= 8]
+MESHES = {"eight": lambda: distorted_box(2, 2, 2, seed=3, amp=0.2),      # every vertex moved: neither affine nor swept
+          "one": lambda: distorted_box(1, 1, 1, seed=3, amp=0.2)}
+STRETCH = 0.1                                     # u = STRETCH * x: grad u = STRETCH * I exactly, on any mesh (det C - 1 = 0.77: the right-hand shift)
+LEFT, RIGHT = np.sqrt(2.0) / 2 - 1, np.sqrt(2.0) - 1      # the range shifts of log1p_series_shifted (hyperFS.h:45-67), in det C - 1
+
+
+def energy_kernel(physics):
+    return f"energy_op<{PHYSICS[physics]}Energy>"
+
+
+def diagnostic_kernel(physics):
+    return f"diagnostic_op<{PHYSICS[physics]}Diagnostic>"
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the record of a run
+# --------------------------------------------------------------------------------------------------------------------------------
+class Record:
+    def __init__(self):
+        self.oracle, self.closed, self.t0 = {}, {}, time.time()
+
+    def write(self, path):
+        with open(path, "w") as f:
+            f.write(f"coord / energy kernels (tests/test_coord_energy_gpu.py), {time.time() - self.t0:.1f} s from the first test of the file to the last\n")
+            f.write("device against the oracle, worst relative error over meshes, P, numberings, add / overwrite: 2-norm | max norm (bar 1e-10)\n")
+            for (kernel, Q), (e2, einf) in sorted(self.oracle.items()):
+                f.write(f"  {kernel:36s} Q={Q}  {e2:.2e} | {einf:.2e}\n")
+            f.write("closed forms in plain numpy, worst relative error: 2-norm | max norm (bar 1e-12)\n")
+            for (what, who, Q), (e2, einf) in sorted(self.closed.items()):
+                f.write(f"  {what:36s} {who:6s} Q={Q}  {e2:.2e} | {einf:.2e}\n")
+
+
+RECORD = Record()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report():
+    RECORD.t0 = time.time()
+    yield
+    path = os.environ.get("CPS_COORD_ENERGY_REPORT")
+    if path:
+        RECORD.write(path)
+
+
+def errors(got, want):
+    got, want = np.atleast_1d(np.asarray(got, dtype=np.float64)), np.atleast_1d(np.asarray(want, dtype=np.float64))
+    assert got.shape == want.shape and np.isfinite(got).all() and np.isfinite(want).all()
+    n2, ninf = np.linalg.norm(want), np.abs(want).max()
+    assert n2 > 0
+    return np.linalg.norm(got - want) / n2, np.abs(got - want).max() / ninf
+
+
+def _hold(table, key, what, got, want, tol):
+    e2, einf = errors(got, want)
+    w = table.setdefault(key, [0.0, 0.0])
+    w[0], w[1] = max(w[0], e2), max(w[1], einf)
+    print(f"  {' '.join(map(str, key))} {what}: {e2:.2e} | {einf:.2e}")
+    assert e2 <= tol and einf <= tol, (key, what, e2, einf)
+
+
+def hold(kernel, Q, what, got, want):
+    """the device's `got` against the oracle's `want`"""
+    _hold(RECORD.oracle, (kernel, Q), what, got, want, TOL)
+
+
+def closed(what, who, Q, got, want):
+    """`got` of backend `who` against the closed form `want`"""
+    _hold(RECORD.closed, (what, who, Q), "", got, want, TOL_STATE)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# problems and operators
+# --------------------------------------------------------------------------------------------------------------------------------
+WHO = ("oracle", "device")
+
+
+def problems(oracle, gpu, mesh, P, Q, physics, E=2.0):
+    return [SolidProblem(c, mesh, P - 1, physics, nu=0.3, E=E, bc_sides=[1], multigrid="none", qextra=Q - P) for c in (oracle, gpu)]
+
+
+def vec(c, arr):
+    return c.vector(arr.size).set_array(arr)
+
+
+def multiplicity(dm):
+    """elements holding each node, counted in numpy"""
+    return np.bincount(dm.elem_nodes.ravel(), minlength=dm.nnodes).astype(np.float64)
+
+
+def true_solution(X):
+    """manufacturedTrue.h"""
+    x, y, z = X[:, 0], X[:, 1], X[:, 2]
+    return 1e-8 * np.stack([np.exp(2 * x) * np.sin(3 * y) * np.cos(4 * z), np.exp(3 * y) * np.sin(4 * z) * np.cos(2 * x),
+                            np.exp(4 * z) * np.sin(2 * x) * np.cos(3 * y)], axis=1)
+
+
+def applied(op, vin, n, kernel=None):
+    """op applied to vin, overwriting a vector pre-filled with PRESET; with `kernel` the name the device must report"""
+    Y = op.ceed.vector(n).set_value(PRESET)
+    op.apply(vin, Y)
+    if kernel is not None:
+        assert op.kernel_name == kernel, (op.kernel_name, kernel)
+    out = Y.to_numpy()
+    Y.destroy()
+    return out
+
+
+def coord_both(probs, kind):
+    """(oracle's, device's) output of the forcing / true-solution operator `kind`"""
+    return [applied(_forcing_and_true_operator(p.ceed, p, kind), p.xcoord, p.lsize(), COORD_KERNEL[kind] if who == "device" else None)
+            for who, p in zip(WHO, probs)]
+
+
+def energy_both(probs, physics, u):
+    out = []
+    for who, p in zip(WHO, probs):
+        se = StrainEnergy(p, physics)
+        out.append(applied(se.op, vec(p.ceed, u), se.nnodes, energy_kernel(physics) if who == "device" else None))
+        se.destroy()
+    return out
+
+
+def diagnostics_both(probs, physics, us):
+    """per displacement of `us`: (oracle's, device's) dloc, [nnodes][8], BEFORE the multiplicity division"""
+    out = [[] for _ in us]
+    for who, p in zip(WHO, probs):
+        d = Diagnostics(p, physics)
+        for k, u in enumerate(us):
+            out[k].append(applied(d.op, vec(p.ceed, u), 8 * d.nnodes, diagnostic_kernel(physics) if who == "device" else None).reshape(-1, 8))
+    return out
+
+
+def destroy(probs):
+    for p in probs:
+        p.destroy()
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# every shape
+# --------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P,Q", PQ, ids=[f"P{P}-Q{Q}" for P, Q in PQ])
+@pytest.mark.parametrize("meshname", list(MESHES))
+def test_strain_energy_and_forcing_at_every_P_and_Q(oracle, gpu, meshname, P, Q):
+    mesh = MESHES[meshname]()
+    for physics in PHYSICS:
+        probs = problems(oracle, gpu, mesh, P, Q, physics)
+        assert probs[1].Q == Q and probs[1].levels[-1].degree + 1 == P
+        want, got = energy_both(probs, physics, probs[0].smooth_state(0.1))
+        hold(energy_kernel(physics), Q, f"{meshname} P={P} eloc", got, want)
+        hold(energy_kernel(physics), Q, f"{meshname} P={P} strain energy", got.sum(), want.sum())
+        if physics == "linElas":            # the forcing the reference's MMS case takes (linElas.h); the constant one has no physics
+            volume = probs[0].qdata.to_numpy().reshape(mesh.nelem, 10, Q ** 3)[:, 0, :].sum()       # sum of w det J
+            for kind in ("const", "mms"):
+                want, got = coord_both(probs, kind)
+                hold(COORD_KERNEL[kind], Q, f"{meshname} P={P}", got, want)
+                if kind == "const":         # INTERP^T is a partition of unity: the nodal forces sum to direction x volume
+                    for who, f in zip(WHO, (want, got)):
+                        closed("sum of the constant force", who, Q, f.reshape(-1, 3).sum(axis=0), DIRECTION * volume)
+        destroy(probs)
+
+
+@pytest.mark.parametrize("P", range(2, 9))
+@pytest.mark.parametrize("meshname", list(MESHES))
+def test_true_solution_and_diagnostics_at_every_P(oracle, gpu, meshname, P):
+    """Collocated on the GLL points: Q = P."""
+    mesh = MESHES[meshname]()
+    for physics in PHYSICS:
+        probs = problems(oracle, gpu, mesh, P, P, physics)
+        dm = probs[0].levels[-1].dofmap
+        mult = multiplicity(dm)
+        if physics == "linElas":
+            want, got = coord_both(probs, "true")
+            hold(COORD_KERNEL["true"], P, f"{meshname}", got, want)
+            for who, t in zip(WHO, (want, got)):
+                closed("true solution x multiplicity", who, P, t.reshape(-1, 3), mult[:, None] * true_solution(dm.node_coords))
+        u, stretch = probs[0].smooth_state(0.1), STRETCH * dm.node_coords.reshape(-1)
+        (want, got), (swant, sgot) = diagnostics_both(probs, physics, [u, stretch])
+        for k, field in enumerate(DIAG_FIELDS):          # each column by itself: pressure and energy density are orders above the displacement
+            hold(diagnostic_kernel(physics), P, f"{meshname} {field}", got[:, k], want[:, k])
+            hold(diagnostic_kernel(physics), P, f"{meshname} stretch {field}", sgot[:, k], swant[:, k])
+        det_J = (1 + STRETCH) ** 3 if physics == "hyperFS" else 1 + 3 * STRETCH
+        for who, d, s in zip(WHO, (want, got), (swant, sgot)):
+            closed("diagnostic displacement = input", who, P, d[:, :3] / mult[:, None], u.reshape(-1, 3))
+            closed(f"det_J of u = {STRETCH} x, {physics}", who, P, s[:, 6] / mult, np.full(dm.nnodes, det_J))
+        destroy(probs)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the branches of the energy kernel's log series (kernels_coord.hip holds its own copy of it)
+# --------------------------------------------------------------------------------------------------------------------------------
+def det_c_minus_1(p, u):
+    """det C - 1 at every quadrature point of problem `p` (the oracle's) under displacement u, in numpy from the oracle's q-data and
+    basis tables: grad u = sum_m du/dxi_m dXdx[m][.], C = F^T F."""
+    lv = p.levels[-1]
+    B, G = lv.basisu.interp1d, lv.basisu.grad1d                       # [Q][P]
+    Pn, ne = lv.degree + 1, p.mesh.nelem
+    U = u.reshape(-1, 3)[lv.dofmap.elem_nodes].reshape(ne, Pn, Pn, Pn, 3)      # [e][z][y][x][component]
+    dU = np.stack([np.einsum("kc,jb,ia,ecbav->ekjiv", *tabs, U) for tabs in ((B, B, G), (B, G, B), (G, B, B))], axis=-1)   # [..][v][m]
+    dXdx = p.qdata.to_numpy().reshape(ne, 10, -1)[:, 1:, :].reshape(ne, 3, 3, -1)          # [e][m][k][q]
+    g = np.einsum("eqvm,emkq->eqvk", dU.reshape(ne, -1, 3, 3), dXdx)
+    return np.linalg.det(np.eye(3) + g) ** 2 - 1
+
+
+BRANCHES = [(-0.25, "left"), (-0.06, "left"), (-0.05, "middle"), (0.059, "middle"), (0.06, "right"), (0.3, "right")]
+
+
+def on_its_side(x, branch):
+    return np.all(x < LEFT) if branch == "left" else (np.all(x > RIGHT) if branch == "right" else np.all((x >= LEFT) & (x <= RIGHT)))
+
+
+@pytest.mark.parametrize("s,branch", BRANCHES, ids=[f"s={s}-{b}" for s, b in BRANCHES])
+def test_log_series_branches_of_the_energy_kernel(oracle, gpu, s, branch):
+    """u = s x plus a small smooth part (grad u no multiple of the identity) takes det C - 1 = (1 + s)^6 - 1 to either side of both
+    range shifts of the finite-strain series, closely; that every point IS on the intended side is read from the oracle: its det_J
+    column at the nodes (the diagnostic kernel's points) and its q-data and tables at the Gauss points (the energy kernel's).  The
+    same six for hyperSS, whose series has no branch: sv = 3 s is at its largest in the suite."""
+    mesh = box_mesh(2, 2, 2)
+    for physics in ("hyperFS", "hyperSS"):
+        probs = problems(oracle, gpu, mesh, 3, 3, physics, E=1.0)
+        dm = probs[0].levels[-1].dofmap
+        u = s * dm.node_coords.reshape(-1) + probs[0].smooth_state(1e-3)
+        (want, got), = diagnostics_both(probs, physics, [u])
+        if physics == "hyperFS":
+            J = want[:, 6] / multiplicity(dm)
+            at_gauss = det_c_minus_1(probs[0], u)
+            print(f"  s={s}: det C - 1 in [{(J * J - 1).min():.4f}, {(J * J - 1).max():.4f}] at the nodes, [{at_gauss.min():.4f}, {at_gauss.max():.4f}] at the Gauss points")
+            assert abs((J * J - 1).mean() - ((1 + s) ** 6 - 1)) < 1e-3
+            assert on_its_side(J * J - 1, branch) and on_its_side(at_gauss, branch), (s, branch)
+        for k, field in enumerate(DIAG_FIELDS):
+            hold(diagnostic_kernel(physics), 3, f"s={s} {field}", got[:, k], want[:, k])
+        want, got = energy_both(probs, physics, u)
+        hold(energy_kernel(physics), 3, f"s={s} eloc", got, want)
+        hold(energy_kernel(physics), 3, f"s={s} strain energy", got.sum(), want.sum())
+        destroy(probs)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# caller-chosen numberings; add and overwrite
+# --------------------------------------------------------------------------------------------------------------------------------
+def operators(p, physics):
+    """kind -> (operator, its input, length of its output, values per node, kernel, Q) of the four operator kinds on problem p"""
+    c, lv = p.ceed, p.levels[-1]
+    u = p.smooth_state(0.1)
+    u[~referenced(lv.dofmap)] = UNREAD                       # entries of nodes no element holds: nothing may read them
+    X = vec(c, u)
+    se, d = StrainEnergy(p, physics), Diagnostics(p, physics)
+    return {"energy": (se.op, X, se.nnodes, 1, energy_kernel(physics), p.Q),
+            "diagnostic": (d.op, X, 8 * d.nnodes, 8, diagnostic_kernel(physics), lv.degree + 1),
+            "const": (_forcing_and_true_operator(c, p, "const"), p.xcoord, p.lsize(), 3, COORD_KERNEL["const"], p.Q),
+            "mms": (_forcing_and_true_operator(c, p, "mms"), p.xcoord, p.lsize(), 3, COORD_KERNEL["mms"], p.Q),
+            "true": (_forcing_and_true_operator(c, p, "true"), p.xcoord, p.lsize(), 3, COORD_KERNEL["true"], lv.degree + 1)}
+
+
+@pytest.mark.parametrize("numbering", ["permuted", "gaps"])
+def test_under_a_caller_chosen_numbering(oracle, gpu, monkeypatch, numbering):
+    """The restrictions of all four operator kinds come from dofmap.offsets() (postprocess.py): the 8-element mesh at (P, Q) = (3, 4)
+    under two numberings.  Under `gaps` the entries of nodes no element holds are exactly what the oracle leaves there."""
+    mesh = MESHES["eight"]()
+    for physics in PHYSICS:
+        probs = [problem_under(monkeypatch, NUMBERINGS[numbering], c, mesh, 2, physics, [1], multigrid="none", qextra=1) for c in (oracle, gpu)]
+        dm = probs[0].levels[-1].dofmap
+        ops = [operators(p, physics) for p in probs]
+        for kind in ops[0] if physics == "linElas" else ("energy", "diagnostic"):
+            (opo, xo, n, per_node, kernel, Q), (opg, xg) = ops[0][kind], ops[1][kind][:2]
+            want, got = applied(opo, xo, n), applied(opg, xg, n, kernel)
+            held = referenced(dm, per_node)
+            assert held.all() == (numbering != "gaps")
+            assert np.array_equal(got[~held], want[~held]) and not np.any(want[~held] == PRESET)
+            for k in range(per_node if kind == "diagnostic" else 1):       # the diagnostic columns one by one
+                cols = slice(k, None, per_node) if kind == "diagnostic" else slice(None)
+                hold(kernel, Q, f"{numbering} {DIAG_FIELDS[k] if kind == 'diagnostic' else ''}", got[cols], want[cols])
+        destroy(probs)
+
+
+@pytest.mark.parametrize("kind", ["energy", "diagnostic", "mms", "true"])
+def test_add_and_overwrite(oracle, gpu, kind):
+    """CeedOperatorApply into a vector pre-filled and two entries longer than the L-size equals the apply into a fresh vector of the
+    L-size, its tail what the oracle leaves there; CeedOperatorApplyAdd onto a drawn y0 equals y0 + the overwriting result."""
+    probs = problems(oracle, gpu, MESHES["eight"](), 3, 4, "hyperFS")
+    ops = [operators(p, "hyperFS")[kind] for p in probs]
+    n, per_node, kernel, Q = ops[0][2:]
+    res = []
+    for p, (op, X, *_) in zip(probs, ops):
+        fresh, longer = p.ceed.vector(n), p.ceed.vector(n + 2).set_value(PRESET)
+        op.apply(X, fresh)
+        op.apply(X, longer)
+        res.append([fresh.to_numpy(), longer.to_numpy()])
+    size = np.abs(res[0][0].reshape(-1, per_node)).max(axis=0)                         # y0 of the result's size, component by component:
+    y0 = np.random.default_rng(11).uniform(-1, 1, n + 2) * np.resize(size, n + 2)      # the sum shows both
+    for r, p, (op, X, *_) in zip(res, probs, ops):
+        Y = vec(p.ceed, y0)
+        op.apply_add(X, Y)
+        assert p.ceed is oracle or op.kernel_name == kernel
+        r.append(Y.to_numpy())
+    (fo, lo, ao), (fg, lg, ag) = res
+    for k in range(per_node):              # component by component: the diagnostic columns are orders apart
+        cols = slice(k, n, per_node)
+        hold(kernel, Q, f"fresh [{k}]", fg[cols], fo[cols])
+        hold(kernel, Q, f"pre-filled [{k}]", lg[cols], lo[cols])
+        hold(kernel, Q, f"add [{k}]", ag[cols], ao[cols])
+    assert np.array_equal(lg[n:], lo[n:]) and np.array_equal(ag[n:], ao[n:]) and np.array_equal(ao[n:], y0[n:])
+    for what, a, b in (("pre-filled against fresh", lg[:n], fg), ("add against y0 + fresh", ag[:n], y0[:n] + fg)):
+        e2, einf = errors(a, b)
+        print(f"  device {what}: {e2:.2e} | {einf:.2e}")
+        assert e2 <= TOL_REORDER and einf <= TOL_REORDER, (what, e2, einf)
+    destroy(probs)

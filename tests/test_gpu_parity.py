@@ -1118,10 +1118,9 @@ def test_direct_interior_stores_equal_the_assembled_path(gpu, product_lib):
             assert np.array_equal(a, b)
 
 
-def _forcing_and_true(c, p, kind):
-    """opSetupForce / opTrue as the reference wires them (setuplibceed.c:555-583, 608-636)."""
+def _forcing_and_true_operator(c, p, kind):
+    """opSetupForce / opTrue as the reference wires them (setuplibceed.c:555-583, 608-636); applied to p.xcoord."""
     lv = p.levels[p.fine]
-    n = p.lsize()
     if kind == "true":
         qf = c.qfunction("MMSTrueSoln", source="qfunctions/manufacturedTrue.h:MMSTrueSoln")
         qf.add_input("x", 3, cd.EVAL_INTERP).add_output("true_soln", 3, cd.EVAL_NONE)
@@ -1143,8 +1142,12 @@ def _forcing_and_true(c, p, kind):
         op.set_field("x", p.Erestrictx, p.basisx, "active")
         op.set_field("qdata", p.Erestrictqdi, None, p.qdata)
         op.set_field("force", lv.Erestrictu, lv.basisu, "active")
-    F = c.vector(n)
-    op.apply(p.xcoord, F)
+    return op
+
+
+def _forcing_and_true(c, p, kind):
+    F = c.vector(p.lsize())
+    _forcing_and_true_operator(c, p, kind).apply(p.xcoord, F)
     return F.to_numpy()
 
 

@@ -4,8 +4,9 @@ the kernel families is a loud error" (DESIGN 1), pinned message by message.
 Every graph is built through ceed.py on a 2 x 1 x 1 box at P = 2, Q = 2 (the transfers: P_c = 2, P_f = 3).  Per kernel family one valid
 graph is applied once -- the family accepts it -- and each defective twin differs from it in ONE thing and must raise CeedError with the
 message of the check that thing violates: every distinct message of op_plan, and every disjunct of its shape checks (strided or not,
-ncomp, compstride, elemsize, collocated basis or not, nelem of the fused family's qdata, missing / superfluous state field, field order).
-A refused graph launches nothing.  Then the refusals the entry points make themselves (masks, overlap split, diagonals, epilogue applies,
+ncomp, compstride, elemsize, collocated basis or not, nelem of every family's qdata, missing / superfluous state field, field order).
+A refused graph launches nothing.  Neither does an energy, diagnostic or forcing operator whose qdata VECTOR is shorter than its elements
+need (apply_energy / apply_coord, ceed_op_other.cpp).  Then the refusals the entry points make themselves (masks, overlap split, diagonals, epilogue applies,
 split-phase applies, the state kernel; composite operators), and one replay of a recorded apply whose Dirichlet flag arrays were replaced
 under it (the operator's device arrays leave through ceed_retire).
 
@@ -70,6 +71,7 @@ def o(gpu):
     s.rs_off = c.elem_restriction(2, 8, 9, 1, 144, np.arange(16, dtype=np.int32) * 9)
     s.rs_e27 = c.strided_restriction(2, 27, 9, 486)
     s.rs_nc10 = s.rq
+    s.qdata_short = c.vector(159).set_value(0.125)                      # one entry short of 2 elements x 10 x Q^3
     return s
 
 
@@ -334,6 +336,10 @@ REFUSED = [
     ("true", put("outs", 0, MODE, INTERP), OUTSIDE + "true solution is collocated on the points of the coordinate basis"),
     ("true", put("outs", 0, BASIS, "bu"), OUTSIDE + "true solution is collocated on the points"),
     ("true", put("outs", 0, RSTR, "rf"), OUTSIDE + "true solution is collocated on the points"),
+    # --- qdata of fewer elements than the active field (behind the rest: the ids above stay what they were)
+    ("energy", put("ins", 1, RSTR, "rq_ne1"), OUTSIDE + QDATA),
+    ("diagnostic", put("ins", 2, RSTR, "rq_ne1"), OUTSIDE + QDATA),
+    ("force", put("ins", 1, RSTR, "rq_ne1"), OUTSIDE + QDATA),
 ]
 
 
@@ -348,6 +354,26 @@ def test_a_graph_with_one_defect_is_refused_with_the_message_of_its_check(o, qda
     with pytest.raises(cd.CeedError, match=message):
         op.apply(vin, vout)
     assert np.array_equal(vout.to_numpy(), before)          # nothing was launched
+    op.destroy(); qf.destroy()
+
+
+# (valid graph, its qdata input): the kernels read nelem * 10 * Q^3 entries of the passive vector, whatever its length
+SHORT_QDATA = [("energy", 1), ("diagnostic", 2), ("force", 1)]
+
+
+@pytest.mark.parametrize("name,i", SHORT_QDATA, ids=[n for n, _ in SHORT_QDATA])
+def test_a_qdata_vector_shorter_than_the_elements_need_is_refused(o, qdata, name, i):
+    g = GRAPHS[name]()
+    put("ins", i, VEC, "qdata_short")(g)                    # the graph is the valid one: op_plan accepts it
+    op, qf = build(o, g)
+    vin, vout = vectors(o, g)
+    vout.set_value(-7.0)
+    with pytest.raises(cd.CeedError, match="qdata vector too short"):
+        op.apply(vin, vout)
+    assert np.all(vout.to_numpy() == -7.0)                  # refused before the output was zeroed: nothing was launched
+    with pytest.raises(cd.CeedError, match="qdata vector too short"):
+        op.apply_add(vin, vout)
+    assert np.all(vout.to_numpy() == -7.0)
     op.destroy(); qf.destroy()
 
 
