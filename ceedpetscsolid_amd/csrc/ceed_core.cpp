@@ -91,13 +91,13 @@ extern "C" int CeedInit(const char *resource, Ceed *ceed) {
 void ceed_ref(Ceed c) { c->refcount++; }
 int (*g_rccl_comm_destroy)(void *) = nullptr;   // set when RCCL is bound (ceed_halo.cpp)
 static void ceed_free_parked(Ceed c) {
-  for (double *p : c->evec_parked) (void)hipFree(p);
-  for (void *p : c->parked_misc) (void)hipFree(p);
-  c->evec_parked.clear(); c->parked_misc.clear();
+  for (void *p : c->parked) (void)hipFree(p);
+  c->parked.clear();
 }
+// the one exit of a device array (DevArray::release): parked while recorded nodes may still read it, else freed behind the stream
 void ceed_retire(Ceed c, void *p) {
   if (!p) return;
-  if (c->capturing || c->live_graphs > 0) c->parked_misc.push_back(p);
+  if (c->capturing || c->live_graphs > 0) c->parked.push_back(p);
   else { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
 }
 void ceed_unref(Ceed c) {
@@ -109,15 +109,13 @@ void ceed_unref(Ceed c) {
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   if (c->capture_stream) (void)hipStreamDestroy(c->capture_stream);
   if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-  if (c->evec) (void)hipFree(c->evec);
+  c->evec.release();   // (while the Ceed is whole: no graph is left, so this is the free itself)
   ceed_free_parked(c);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   for (hipEvent_t ev : c->ev_seg) if (ev) (void)hipEventDestroy(ev);
-  if (c->d_scalar) (void)hipFree(c->d_scalar);
   if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-  if (c->d_pb_bad) (void)hipFree(c->d_pb_bad);
-  delete c;
+  delete c;            // (d_scalar and d_pb_bad are bound to no Ceed: freed directly with it)
 }
 int ceed_need_side_stream(Ceed c) {
   if (c->side_stream) return 0;
@@ -147,14 +145,14 @@ extern "C" int CeedXSynchronize(Ceed ceed) {
 extern "C" int CeedXClockProbe(Ceed ceed, int spin_us, double *ghz) {
   if (ceed->capturing) return ceed_error("CeedXClockProbe during graph capture");
   if (spin_us < 1 || spin_us > 1000000) return ceed_error("CeedXClockProbe: 1 us ... 1 s");
-  hipStream_t ps = nullptr;
-  long long *d = nullptr, h[2] = {0, 0};
-  HIPCHK(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
-  HIPCHK(hipMalloc((void **)&d, 2 * sizeof(long long)));
-  HIPCHK(launch_clock_probe(d, spin_us, ps));
-  HIPCHK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ps));
-  HIPCHK(hipStreamSynchronize(ps));
-  (void)hipFree(d); (void)hipStreamDestroy(ps);
+  struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) (void)hipStreamDestroy(s); } } ps;
+  DevArray<long long> d;     // (bound to no Ceed: freed directly, on every way out)
+  long long h[2] = {0, 0};
+  HIPCHK(hipStreamCreateWithFlags(&ps.s, hipStreamNonBlocking));
+  CHK(d.alloc(nullptr, 2));
+  HIPCHK(launch_clock_probe(d.get(), spin_us, ps.s));
+  HIPCHK(hipMemcpyAsync(h, d.get(), sizeof h, hipMemcpyDeviceToHost, ps.s));
+  HIPCHK(hipStreamSynchronize(ps.s));
   *ghz = h[1] > 0 ? (double)h[0] / ((double)h[1] * 10.0) : 0.;     // cycles / (ticks x 10 ns) = GHz
   return 0;
 }
@@ -201,8 +199,8 @@ extern "C" int CeedXGraphEndCapture(Ceed ceed, CeedXGraph *graph) {
 // 0: the recording still describes its vectors; 1: a qdata vector's geometry provenance was dropped; 2: a stored state's derived state
 static int graph_stale(CeedXGraph G) {
   for (const GraphDep &d : G->deps) {
-    if (d.geo && d.v->geo != d.geo) return 1;
-    if (d.derived && !(d.v->derived_valid && d.v->derived == d.derived)) return 2;
+    if (d.geo && d.v->geo.get() != d.geo) return 1;
+    if (d.derived && !(d.v->derived_valid && d.v->derived.get() == d.derived)) return 2;
   }
   return 0;
 }
@@ -239,22 +237,16 @@ extern "C" int CeedXGraphDestroy(CeedXGraph *graph) {
 void vec_drop_geo(CeedVector v) {   // = "the vector is being written"
   v->version++;
   v->derived_valid = false;
-  // retired, not freed: a recorded graph may hold these pointers in its kernel arguments (it refuses to replay --
-  // CeedXGraphLaunch checks its GraphDeps -- but its nodes must never point at freed memory)
-  ceed_retire(v->ceed, v->geo); ceed_retire(v->ceed, v->geo_aff); ceed_retire(v->ceed, v->geo_swept);
-  v->geo = v->geo_aff = v->geo_swept = nullptr; v->geo_nelem = v->geo_Q = 0;
+  // (a recorded graph may hold these pointers in its kernel arguments: it refuses to replay -- CeedXGraphLaunch checks its
+  // GraphDeps -- and, the arrays being DevArrays, its nodes never point at freed memory)
+  v->geo.release(); v->geo_aff.release(); v->geo_swept.release();
+  v->geo_nelem = v->geo_Q = 0;
 }
 
 int ceed_need_evec(Ceed c, size_t len) {
-  if (c->evec_len >= len) return 0;
-  if (c->evec) {
-    if (c->capturing || c->live_graphs > 0) c->evec_parked.push_back(c->evec);   // recorded nodes still point at it
-    else { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->evec)); }
-    c->evec = nullptr; c->evec_len = 0;
-  }
-  HIPCHK(hipMalloc((void **)&c->evec, sizeof(double) * len));
-  c->evec_len = len;
-  return 0;
+  if (c->evec.size() >= len) return 0;
+  c->evec.release();             // (parked if recorded nodes still point at it)
+  return c->evec.alloc(c, len);
 }
 
 // ---------------------------------------------------------------------------
@@ -393,10 +385,10 @@ extern "C" int CeedVectorDestroy(CeedVector *vec) {
   *vec = nullptr;
   if (v == CEED_VECTOR_ACTIVE || v == CEED_VECTOR_NONE) return 0;
   if (--v->refcount > 0) return 0;
-  vec_drop_host(v); vec_drop_dev(v); vec_drop_geo(v);
-  ceed_retire(v->ceed, v->derived);
-  ceed_unref(v->ceed);
-  delete v;
+  vec_drop_host(v); vec_drop_dev(v);
+  Ceed c = v->ceed;
+  delete v;            // (before the reference goes: the provenance arrays retire into a Ceed that still exists)
+  ceed_unref(c);
   return 0;
 }
 
@@ -476,12 +468,12 @@ extern "C" int CeedXVectorPointBlockInvert(CeedVector blocks, int *n_bad) {
   double *pb;
   CHK(vec_dev(blocks, true, &pb));
   if (n_bad) {
-    if (!c->d_pb_bad) HIPCHK(hipMalloc((void **)&c->d_pb_bad, sizeof(int)));
-    HIPCHK(hipMemsetAsync(c->d_pb_bad, 0, sizeof(int), c->stream));
+    if (!c->d_pb_bad) CHK(c->d_pb_bad.alloc(nullptr, 1));
+    HIPCHK(hipMemsetAsync(c->d_pb_bad.get(), 0, sizeof(int), c->stream));
   }
-  HIPCHK(launch_pb_invert(pb, (size_t)blocks->length / 9, n_bad ? c->d_pb_bad : nullptr, c->stream));
+  HIPCHK(launch_pb_invert(pb, (size_t)blocks->length / 9, n_bad ? c->d_pb_bad.get() : nullptr, c->stream));
   if (n_bad) {
-    HIPCHK(hipMemcpyAsync(n_bad, c->d_pb_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(n_bad, c->d_pb_bad.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return 0;
@@ -529,9 +521,9 @@ extern "C" int CeedXVectorDot(CeedVector x, CeedVector y, CeedVector weight, dou
   if (weight && weight != CEED_VECTOR_NONE) CHK(vec_dev(weight, false, &pw));
   hipStream_t s = x->ceed->stream;
   if (x->ceed->capturing) return ceed_error("CeedXVectorDot during graph capture (it returns a host value)");
-  if (!x->ceed->d_scalar) HIPCHK(hipMalloc((void **)&x->ceed->d_scalar, sizeof(double) * (1 + 2048)));  // result + per-block partials
+  if (!x->ceed->d_scalar) CHK(x->ceed->d_scalar.alloc(nullptr, 1 + 2048));  // result + per-block partials
   if (!x->ceed->h_scalar) HIPCHK(hipHostMalloc((void **)&x->ceed->h_scalar, sizeof(double), hipHostMallocDefault));
-  dres = x->ceed->d_scalar;
+  dres = x->ceed->d_scalar.get();
   HIPCHK(launch_dot(px, py, pw, (size_t)x->length, dres, s));
   HIPCHK(hipMemcpyAsync(x->ceed->h_scalar, dres, sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -549,9 +541,9 @@ extern "C" int CeedXVectorDotTo(CeedVector x, CeedVector y, CeedVector weight, C
   if (weight && weight != CEED_VECTOR_NONE) CHK(vec_dev(weight, false, &pw));
   if (!x->ceed->d_scalar) {
     if (x->ceed->capturing) return ceed_error("CeedXVectorDotTo: take one dot product before recording (scratch allocation)");
-    HIPCHK(hipMalloc((void **)&x->ceed->d_scalar, sizeof(double) * (1 + 2048)));
+    CHK(x->ceed->d_scalar.alloc(nullptr, 1 + 2048));
   }
-  HIPCHK(launch_dot(px, py, pw, (size_t)x->length, x->ceed->d_scalar, x->ceed->stream, ps + idx));
+  HIPCHK(launch_dot(px, py, pw, (size_t)x->length, x->ceed->d_scalar.get(), x->ceed->stream, ps + idx));
   return 0;
 }
 extern "C" int CeedXScalarDivide(CeedVector scalars, CeedInt dst, CeedInt num, CeedInt den, double scale) {

@@ -9,24 +9,39 @@ using namespace cps;
 struct CeedXCsr_private {
   Ceed ceed = nullptr;
   int nrows = 0, ncols = 0, nnz = 0, ncoo = 0, n_unit = 0;
-  uint32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_slotptr = nullptr, *d_perm = nullptr, *d_unit_slot = nullptr,
-           *d_diag_slot = nullptr;
-  double *d_vals = nullptr;
+  DevArray<uint32_t> d_rowptr, d_cols, d_slotptr, d_perm, d_unit_slot, d_diag_slot;
+  DevArray<double> d_vals;
   // values = product of two other matrices' values on this pattern (CeedXCsrCreateProduct / CeedXCsrUpdate)
   CeedXCsr src = nullptr, src2 = nullptr;
-  double *d_gj = nullptr;
-  int *d_info = nullptr;
+  DevArray<double> d_gj;
+  DevArray<int> d_info;
   bool dense = false;       // full pattern, columns ascending: vals is a row-major nrows x nrows matrix
   int max_row = 0;          // longest row of the pattern (products: chooses the kernel of CeedXCsrUpdate)
-  uint32_t *d_row_block = nullptr;   // CSR-stream runs of CeedXCsrApply (launch_csr_spmv_stream), cut at the first apply
+  DevArray<uint32_t> d_row_block;    // CSR-stream runs of CeedXCsrApply (launch_csr_spmv_stream), cut at the first apply
   int n_row_blocks = 0;
   int refs = 1;             // an operand is kept alive by the products formed from it
   std::vector<int> h_rowptr, h_cols;      // host copy of the pattern (operand of CeedXCsrCreateProduct)
 };
-template <class T>
-static int csr_upload(uint32_t **dst, const std::vector<T> &v) {
-  HIPCHK(hipMalloc((void **)dst, sizeof(uint32_t) * (v.size() ? v.size() : 1)));
-  if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice));
+// what a Create function returns when a step after `new` failed: nothing of the half-built matrix survives
+static int csr_fail(CeedXCsr A, int ierr) { (void)CeedXCsrDestroy(&A); return ierr; }
+// A matrix on the pattern (rp, cl): the pattern and the diagonal's slots uploaded, the values allocated -- `vals`, or zeros.
+static int csr_new(Ceed ceed, int nrows, int ncols, const std::vector<uint32_t> &rp, const std::vector<uint32_t> &cl,
+                   const std::vector<uint32_t> &diag, const double *vals, CeedXCsr *out) {
+  CeedXCsr A = new CeedXCsr_private;
+  A->ceed = ceed; ceed_ref(ceed);
+  const size_t nnz = cl.size();
+  A->nrows = nrows; A->ncols = ncols; A->nnz = (int)nnz;
+  A->h_rowptr.assign(rp.begin(), rp.end()); A->h_cols.assign(cl.begin(), cl.end());
+  auto fill = [&]() -> int {
+    CHK(A->d_rowptr.upload(ceed, rp)); CHK(A->d_cols.upload(ceed, cl)); CHK(A->d_diag_slot.upload(ceed, diag));
+    if (vals && nnz) return A->d_vals.upload(ceed, vals, nnz);
+    CHK(A->d_vals.alloc(ceed, nnz));
+    HIPCHK(hipMemset(A->d_vals.get(), 0, sizeof(double) * (nnz ? nnz : 1)));
+    return 0;
+  };
+  const int ierr = fill();
+  if (ierr) return csr_fail(A, ierr);
+  *out = A;
   return 0;
 }
 extern "C" int CeedXCsrCreate(Ceed ceed, CeedInt nrows, const CeedInt *rowptr, const CeedInt *cols, CeedInt ncoo,
@@ -60,20 +75,19 @@ extern "C" int CeedXCsrCreate(Ceed ceed, CeedInt nrows, const CeedInt *rowptr, c
       return ceed_error("CeedXCsrCreate: unit row %d has no diagonal entry in the pattern", unit_rows[i]);
     unit.push_back(diag[unit_rows[i]]);
   }
-  CeedXCsr A = new CeedXCsr_private;
-  A->ceed = ceed; ceed_ref(ceed);
-  A->nrows = nrows; A->ncols = nrows; A->nnz = nnz; A->ncoo = ncoo; A->n_unit = n_unit;
+  CeedXCsr A = nullptr;
+  CHK(csr_new(ceed, nrows, nrows, rp, cl, diag, nullptr, &A));
+  A->ncoo = ncoo; A->n_unit = n_unit;
   {  // a full pattern with ascending columns may be inverted in place (CeedXCsrInvertDenseSPD): the summed coarsest level of a distributed hierarchy
     bool dense = (long long)nnz == (long long)nrows * nrows && nrows > 0;
     for (int r = 0; dense && r < nrows; r++)
       for (int k = rowptr[r]; k < rowptr[r + 1]; k++) if (cols[k] != k - rowptr[r]) { dense = false; break; }
     A->dense = dense;
   }
-  A->h_rowptr.assign(rowptr, rowptr + nrows + 1); A->h_cols.assign(cols, cols + nnz);
-  CHK(csr_upload(&A->d_rowptr, rp)); CHK(csr_upload(&A->d_cols, cl)); CHK(csr_upload(&A->d_slotptr, slotptr));
-  CHK(csr_upload(&A->d_perm, perm)); CHK(csr_upload(&A->d_unit_slot, unit)); CHK(csr_upload(&A->d_diag_slot, diag));
-  HIPCHK(hipMalloc((void **)&A->d_vals, sizeof(double) * (nnz ? nnz : 1)));
-  HIPCHK(hipMemset(A->d_vals, 0, sizeof(double) * (nnz ? nnz : 1)));
+  int ierr = A->d_slotptr.upload(ceed, slotptr);
+  if (!ierr) ierr = A->d_perm.upload(ceed, perm);
+  if (!ierr) ierr = A->d_unit_slot.upload(ceed, unit);
+  if (ierr) return csr_fail(A, ierr);
   *csr = A;
   return 0;
 }
@@ -81,7 +95,7 @@ extern "C" int CeedXCsrAssemble(CeedXCsr A, CeedVector coo_values) {
   if (coo_values->length < A->ncoo) return ceed_error("CeedXCsrAssemble: %d COO values, %d expected", coo_values->length, A->ncoo);
   double *pc;
   CHK(vec_dev(coo_values, false, &pc));
-  HIPCHK(launch_csr_sum(A->d_slotptr, A->d_perm, pc, A->d_vals, A->nnz, A->d_unit_slot, A->n_unit, A->ceed->stream));
+  HIPCHK(launch_csr_sum(A->d_slotptr.get(), A->d_perm.get(), pc, A->d_vals.get(), A->nnz, A->d_unit_slot.get(), A->n_unit, A->ceed->stream));
   return 0;
 }
 // runs of consecutive rows for the CSR-stream SpMV: at most 2048 entries and 256 rows each; a longer row alone
@@ -98,7 +112,7 @@ static int csr_row_blocks(CeedXCsr A) {
     r = r1;
   }
   A->n_row_blocks = (int)rb.size() - 1;
-  CHK(csr_upload(&A->d_row_block, rb));
+  CHK(A->d_row_block.upload(A->ceed, rb));
   return 0;
 }
 extern "C" int CeedXCsrApply(CeedXCsr A, CeedVector x, CeedVector y) {
@@ -107,14 +121,14 @@ extern "C" int CeedXCsrApply(CeedXCsr A, CeedVector x, CeedVector y) {
   double *px, *py;
   CHK(vec_dev(x, false, &px)); CHK(vec_dev(y, true, &py));
   CHK(csr_row_blocks(A));
-  HIPCHK(launch_csr_spmv_stream(A->d_row_block, A->n_row_blocks, A->d_rowptr, A->d_cols, A->d_vals, px, py, A->ceed->stream));
+  HIPCHK(launch_csr_spmv_stream(A->d_row_block.get(), A->n_row_blocks, A->d_rowptr.get(), A->d_cols.get(), A->d_vals.get(), px, py, A->ceed->stream));
   return 0;
 }
 extern "C" int CeedXCsrGetDiagonal(CeedXCsr A, CeedVector d) {
   if (d->length < A->nrows) return ceed_error("CeedXCsrGetDiagonal: vector shorter than the matrix");
   double *pd;
   CHK(vec_dev(d, true, &pd));
-  HIPCHK(launch_csr_diag(A->d_diag_slot, A->d_vals, pd, A->nrows, A->ceed->stream));
+  HIPCHK(launch_csr_diag(A->d_diag_slot.get(), A->d_vals.get(), pd, A->nrows, A->ceed->stream));
   return 0;
 }
 // Rectangular matrix with fixed values (prolongation / restriction of the aggregation hierarchy), or a pattern whose
@@ -134,14 +148,9 @@ extern "C" int CeedXCsrCreateRect(Ceed ceed, CeedInt nrows, CeedInt ncols, const
   std::vector<uint32_t> rp(rowptr, rowptr + nrows + 1), cl(cols, cols + nnz), diag((size_t)nrows, 0xFFFFFFFFu);
   for (int r = 0; r < nrows; r++)
     for (int k = rowptr[r]; k < rowptr[r + 1]; k++) if (cols[k] == r) diag[r] = (uint32_t)k;
-  CeedXCsr A = new CeedXCsr_private;
-  A->ceed = ceed; ceed_ref(ceed);
-  A->nrows = nrows; A->ncols = ncols; A->nnz = nnz; A->dense = dense;
-  A->h_rowptr.assign(rowptr, rowptr + nrows + 1); A->h_cols.assign(cols, cols + nnz);
-  CHK(csr_upload(&A->d_rowptr, rp)); CHK(csr_upload(&A->d_cols, cl)); CHK(csr_upload(&A->d_diag_slot, diag));
-  HIPCHK(hipMalloc((void **)&A->d_vals, sizeof(double) * (nnz ? nnz : 1)));
-  if (vals && nnz) HIPCHK(hipMemcpy(A->d_vals, vals, sizeof(double) * nnz, hipMemcpyHostToDevice));
-  else HIPCHK(hipMemset(A->d_vals, 0, sizeof(double) * (nnz ? nnz : 1)));
+  CeedXCsr A = nullptr;
+  CHK(csr_new(ceed, nrows, ncols, rp, cl, diag, vals, &A));
+  A->dense = dense;
   *csr = A;
   return 0;
 }
@@ -203,17 +212,12 @@ extern "C" int CeedXCsrCreateProduct(CeedXCsr Lm, CeedXCsr Rm, int variable, int
       std::vector<uint32_t>().swap(pt.cl); std::vector<uint32_t>().swap(pt.len);
     }
   }
-  const int nnz = (int)cl.size();
   std::vector<uint32_t> diag((size_t)nrows, 0xFFFFFFFFu);
   for (int r = 0; r < nrows; r++)
     for (uint32_t k = rp[r]; k < rp[r + 1]; k++) if ((int)cl[k] == r) diag[r] = k;
-  CeedXCsr A = new CeedXCsr_private;
-  A->ceed = Lm->ceed; ceed_ref(A->ceed);
-  A->nrows = nrows; A->ncols = ncols; A->nnz = nnz; A->dense = dense != 0;
-  A->h_rowptr.assign(rp.begin(), rp.end()); A->h_cols.assign(cl.begin(), cl.end());
-  CHK(csr_upload(&A->d_rowptr, rp)); CHK(csr_upload(&A->d_cols, cl)); CHK(csr_upload(&A->d_diag_slot, diag));
-  HIPCHK(hipMalloc((void **)&A->d_vals, sizeof(double) * (nnz ? nnz : 1)));
-  HIPCHK(hipMemset(A->d_vals, 0, sizeof(double) * (nnz ? nnz : 1)));
+  CeedXCsr A = nullptr;
+  CHK(csr_new(Lm->ceed, nrows, ncols, rp, cl, diag, nullptr, &A));
+  A->dense = dense != 0;
   for (int r = 0; r < nrows; r++) A->max_row = std::max(A->max_row, (int)(rp[(size_t)r + 1] - rp[(size_t)r]));
   A->src = Lm; Lm->refs++;
   A->src2 = Rm; Rm->refs++;
@@ -231,7 +235,8 @@ extern "C" int CeedXCsrGetPattern(CeedXCsr A, CeedInt *nrows, CeedInt *ncols, Ce
 extern "C" int CeedXCsrUpdate(CeedXCsr A) {
   if (!A->src || !A->src2) return ceed_error("CeedXCsrUpdate: not a product (CeedXCsrCreateProduct)");
   CeedXCsr Lm = A->src, Rm = A->src2;
-  HIPCHK(launch_csr_spgemm(Lm->d_rowptr, Lm->d_cols, Lm->d_vals, Rm->d_rowptr, Rm->d_cols, Rm->d_vals, A->d_rowptr, A->d_cols, A->d_vals,
+  HIPCHK(launch_csr_spgemm(Lm->d_rowptr.get(), Lm->d_cols.get(), Lm->d_vals.get(), Rm->d_rowptr.get(), Rm->d_cols.get(), Rm->d_vals.get(),
+                           A->d_rowptr.get(), A->d_cols.get(), A->d_vals.get(),
                            A->nrows, A->ceed->stream, A->dense ? A->ncols : 0, A->max_row));
   return 0;
 }
@@ -239,7 +244,7 @@ extern "C" int CeedXCsrGetValues(CeedXCsr A, CeedVector v) {
   if (v->length < A->nnz) return ceed_error("CeedXCsrGetValues: vector of %d for %d entries", v->length, A->nnz);
   double *pv;
   CHK(vec_dev(v, true, &pv));
-  if (A->nnz) HIPCHK(hipMemcpyAsync(pv, A->d_vals, sizeof(double) * A->nnz, hipMemcpyDeviceToDevice, A->ceed->stream));
+  if (A->nnz) HIPCHK(hipMemcpyAsync(pv, A->d_vals.get(), sizeof(double) * A->nnz, hipMemcpyDeviceToDevice, A->ceed->stream));
   return 0;
 }
 // In-place inverse of a matrix with a FULL pattern (every row holds columns 0..n-1 in order) and symmetric positive
@@ -247,14 +252,12 @@ extern "C" int CeedXCsrGetValues(CeedXCsr A, CeedVector v) {
 extern "C" int CeedXCsrInvertDenseSPD(CeedXCsr A) {
   if (!A->dense) return ceed_error("CeedXCsrInvertDenseSPD: the pattern is not a full square one with ascending columns");
   if (A->ceed->capturing) return ceed_error("CeedXCsrInvertDenseSPD cannot be recorded into a graph (it reports a status to the host)");
-  if (!A->d_gj) {
-    HIPCHK(hipMalloc((void **)&A->d_gj, sizeof(double) * 32 * 32));
-    HIPCHK(hipMalloc((void **)&A->d_info, sizeof(int)));
-  }
-  HIPCHK(hipMemsetAsync(A->d_info, 0, sizeof(int), A->ceed->stream));
-  HIPCHK(launch_dense_spd_inverse(A->d_vals, A->nrows, A->d_gj, A->d_info, A->ceed->stream));
+  if (!A->d_gj) CHK(A->d_gj.alloc(A->ceed, 32 * 32));
+  if (!A->d_info) CHK(A->d_info.alloc(A->ceed, 1));
+  HIPCHK(hipMemsetAsync(A->d_info.get(), 0, sizeof(int), A->ceed->stream));
+  HIPCHK(launch_dense_spd_inverse(A->d_vals.get(), A->nrows, A->d_gj.get(), A->d_info.get(), A->ceed->stream));
   int info = 0;
-  HIPCHK(hipMemcpyAsync(&info, A->d_info, sizeof(int), hipMemcpyDeviceToHost, A->ceed->stream));
+  HIPCHK(hipMemcpyAsync(&info, A->d_info.get(), sizeof(int), hipMemcpyDeviceToHost, A->ceed->stream));
   HIPCHK(hipStreamSynchronize(A->ceed->stream));
   if (info) return ceed_error("CeedXCsrInvertDenseSPD: pivot %d is not positive: the matrix is not positive definite", info - 1);
   return 0;
@@ -264,14 +267,10 @@ extern "C" int CeedXCsrDestroy(CeedXCsr *csr) {
   CeedXCsr A = *csr;
   *csr = nullptr;
   if (--A->refs > 0) return 0;        // still the source of another matrix: freed with the last of those
-  (void)hipStreamSynchronize(A->ceed->stream);
-  for (uint32_t *p : {A->d_rowptr, A->d_cols, A->d_slotptr, A->d_perm, A->d_unit_slot, A->d_diag_slot, A->d_row_block})
-    if (p) (void)hipFree(p);
-  for (double *p : {A->d_vals, A->d_gj}) if (p) (void)hipFree(p);
-  if (A->d_info) (void)hipFree(A->d_info);
   CeedXCsr src = A->src, src2 = A->src2;
-  ceed_unref(A->ceed);
-  delete A;
+  Ceed c = A->ceed;
+  delete A;            // (before the reference goes: its arrays retire into a Ceed that still exists)
+  ceed_unref(c);
   if (src) (void)CeedXCsrDestroy(&src);
   if (src2) (void)CeedXCsrDestroy(&src2);
   return 0;

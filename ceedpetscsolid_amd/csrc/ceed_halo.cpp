@@ -117,14 +117,11 @@ extern "C" int CeedXCommAllReduce(Ceed ceed, CeedVector v, CeedInt first, CeedIn
 }
 
 static void halo_free(CeedXHalo H) {
-  if (H->d_idx) (void)hipFree(H->d_idx);
-  if (H->send) (void)hipFree(H->send);
-  if (H->recv) (void)hipFree(H->recv);
-  for (uint32_t *p : {H->d_dst, H->d_uptr, H->d_uslot}) if (p) (void)hipFree(p);
   if (H->packed) (void)hipEventDestroy(H->packed);
   if (H->arrived) (void)hipEventDestroy(H->arrived);
-  ceed_unref(H->ceed);
-  delete H;
+  Ceed c = H->ceed;
+  delete H;            // (before the reference goes: its arrays retire into a Ceed that still exists)
+  ceed_unref(c);
 }
 static int halo_build(CeedXHalo H, CeedInt nneigh, const int *neigh_rank, const CeedInt *count, const CeedInt *const *index) {
   Ceed ceed = H->ceed;
@@ -154,14 +151,8 @@ static int halo_build(CeedXHalo H, CeedInt nneigh, const int *neigh_rank, const 
   uptr.push_back((uint32_t)uslot.size());
   if (dst.empty()) uptr.assign(1, 0u);
   H->ndst = (int)dst.size();
-  auto up = [](uint32_t **d, const std::vector<uint32_t> &v) -> int {
-    HIPCHK(hipMalloc((void **)d, sizeof(uint32_t) * (v.size() ? v.size() : 1)));
-    if (!v.empty()) HIPCHK(hipMemcpy(*d, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice));
-    return 0;
-  };
-  CHK(up(&H->d_idx, idx)); CHK(up(&H->d_dst, dst)); CHK(up(&H->d_uptr, uptr)); CHK(up(&H->d_uslot, uslot));
-  HIPCHK(hipMalloc((void **)&H->send, sizeof(double) * (idx.size() ? idx.size() : 1)));
-  HIPCHK(hipMalloc((void **)&H->recv, sizeof(double) * (idx.size() ? idx.size() : 1)));
+  CHK(H->d_idx.upload(ceed, idx)); CHK(H->d_dst.upload(ceed, dst)); CHK(H->d_uptr.upload(ceed, uptr)); CHK(H->d_uslot.upload(ceed, uslot));
+  CHK(H->send.alloc(ceed, idx.size())); CHK(H->recv.alloc(ceed, idx.size()));
   HIPCHK(hipEventCreateWithFlags(&H->packed, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&H->arrived, hipEventDisableTiming));
   return 0;
@@ -192,7 +183,7 @@ extern "C" int CeedXHaloCreate(Ceed ceed, CeedInt nneigh, const int *neigh_rank,
 //    and whoever needs the arrivals waits for it.
 int halo_pack_and_send(CeedXHalo H, const double *py, hipStream_t pack_stream) {
   Ceed c = H->ceed;
-  HIPCHK(launch_halo_pack(H->d_idx, H->total, py, H->send, pack_stream));
+  HIPCHK(launch_halo_pack(H->d_idx.get(), H->total, py, H->send.get(), pack_stream));
   return halo_send(H, pack_stream);
 }
 // the RCCL group alone: the send buffer has been filled on `pack_stream` (by k_halo_pack or by the rows' launch, HaloPackFold)
@@ -216,8 +207,8 @@ int halo_send(CeedXHalo H, hipStream_t pack_stream) {
   }
   RCCLCHK(g_rccl.GroupStart());
   for (HaloNeighbour &nb : H->nb) {
-    RCCLCHK(g_rccl.Send(H->send + nb.offset, (size_t)nb.n, RCCL_FLOAT64, nb.rank, c->comm, cs));
-    RCCLCHK(g_rccl.Recv(H->recv + nb.offset, (size_t)nb.n, RCCL_FLOAT64, nb.rank, c->comm, cs));
+    RCCLCHK(g_rccl.Send(H->send.get() + nb.offset, (size_t)nb.n, RCCL_FLOAT64, nb.rank, c->comm, cs));
+    RCCLCHK(g_rccl.Recv(H->recv.get() + nb.offset, (size_t)nb.n, RCCL_FLOAT64, nb.rank, c->comm, cs));
   }
   RCCLCHK(g_rccl.GroupEnd());
   HIPCHK(hipEventRecord(H->arrived, cs));
@@ -228,7 +219,7 @@ int halo_wait_arrivals(CeedXHalo H, hipStream_t s) {
   if (H->arrived_on != s) HIPCHK(hipStreamWaitEvent(s, H->arrived, 0));     // (the same stream: already in order)
   return 0;
 }
-HaloUnpackArgs halo_unpack_args(CeedXHalo H) { return HaloUnpackArgs{H->d_dst, H->d_uptr, H->d_uslot, H->recv, H->ndst}; }
+HaloUnpackArgs halo_unpack_args(CeedXHalo H) { return HaloUnpackArgs{H->d_dst.get(), H->d_uptr.get(), H->d_uslot.get(), H->recv.get(), H->ndst}; }
 // Start: pack on the Ceed's stream, then the RCCL group on the communicator's stream -- the Ceed's stream is free for
 // the interior elements meanwhile (CeedXOperatorApplyPhase 1).
 extern "C" int CeedXHaloStart(CeedXHalo H, CeedVector y) {

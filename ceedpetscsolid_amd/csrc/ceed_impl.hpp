@@ -1,6 +1,8 @@
 // ceed_impl.hpp -- private object layouts and helpers shared by the host-side sources of the MI355X backend
 // (ceed_core.cpp: Ceed, vectors, graphs; ceed_basis.cpp; ceed_restriction.cpp; ceed_qfunction.cpp; the operators: ceed_operator.cpp
 // with ceed_op_fused.cpp and ceed_op_other.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
+// Every device array one of these objects owns is a DevArray (dev_array.hpp): allocated under the object's Ceed, gone with the member,
+// through ceed_retire.  The one exception is a vector's host / device mirrors, which may be borrowed (ceed_core.cpp).
 // Nothing here is part of the ABI: include/ceed.h is.
 #pragma once
 #include <ceed.h>
@@ -12,9 +14,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "dev_array.hpp"
 #include "kernels.hpp"
 
 // ---------------------------------------------------------------------------
@@ -69,14 +73,12 @@ struct Ceed_private {
   int device = 0;
   CeedOptions opt;
   // scratch E-vector shared by the operators of this Ceed (applies are serialised on `stream`)
-  double *evec = nullptr;
-  size_t evec_len = 0;
+  DevArray<double> evec;
   // A recorded hipGraph has the scratch pointer of its capture time baked into its kernel nodes.  When the scratch has
   // to grow while a graph of this Ceed is alive (or is being recorded), the old buffer is PARKED, not freed: replays of
   // the older graphs keep a valid scratch of the size they were recorded with.  Parked buffers go when the last graph
-  // goes.  The same holds for re-ordered transpose maps and flag arrays that are replaced (parked_misc).
-  std::vector<double *> evec_parked;
-  std::vector<void *> parked_misc;
+  // goes.  The same holds for every other device array of an object of this Ceed (ceed_retire, the exit of DevArray).
+  std::vector<void *> parked;
   int live_graphs = 0;
   hipStream_t side_stream = nullptr;          // second chain of a pipelined apply; phase 1 of a split-phase apply
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -85,9 +87,9 @@ struct Ceed_private {
   void *comm = nullptr;
   int comm_rank = 0, comm_size = 1;
   hipStream_t comm_stream = nullptr;
-  double *d_scalar = nullptr;   // device scalar for reductions (1 + 2048 doubles)
+  DevArray<double> d_scalar;    // device scalar for reductions (1 + 2048 doubles)
   double *h_scalar = nullptr;   // pinned host landing slot for it (pageable targets make the runtime stage + pin per copy)
-  int *d_pb_bad = nullptr;      // device counter of CeedXVectorPointBlockInvert (bad pivots), allocated when first asked for
+  DevArray<int> d_pb_bad;       // device counter of CeedXVectorPointBlockInvert (bad pivots), allocated when first asked for
   // hipGraph capture (CeedXGraphBeginCapture): device work is recorded on `capture_stream`
   hipStream_t capture_stream = nullptr, saved_stream = nullptr;
   bool capturing = false;
@@ -112,17 +114,16 @@ struct CeedVector_private {
   // provenance of a qdata vector: written by the SetupGeo operator from trilinear elements whose map coefficients
   // are kept here ([nelem][GEO_NCOEF], device).  The fused kernels then recompute the geometric factors instead of
   // reading them (FusedGradArgs::geo).  Dropped by any other write to the vector.
-  double *geo = nullptr;
-  double *geo_aff = nullptr;   // set when EVERY element is affine: [nelem][GEO_NAFF] constant factors (FusedGradArgs::geo_aff)
-  double *geo_swept = nullptr; // set when every element is swept along the reference direction geo_axis (FusedGradArgs::geo_swept)
+  DevArray<double> geo;
+  DevArray<double> geo_aff;    // set when EVERY element is affine: [nelem][GEO_NAFF] constant factors (FusedGradArgs::geo_aff)
+  DevArray<double> geo_swept;  // set when every element is swept along the reference direction geo_axis (FusedGradArgs::geo_swept)
   int geo_axis = 0;
   int geo_nelem = 0, geo_Q = 0;
   double geo_qref[cps::MAXN1D] = {0}, geo_qwt[cps::MAXN1D] = {0};
   // provenance of a stored-state vector (grad u): written by this backend's HyperFSF kernel, which left the DERIVED state of
   // the tangent ([nelem][10][Q^3]: F^-1, lambda ln J - mu) beside it; HyperFSdF then reads that instead (QF_HYPERFS_DF_DS).
   // Any other write to the vector invalidates it (the buffer is kept for the next residual evaluation).
-  double *derived = nullptr;
-  size_t derived_len = 0;
+  DevArray<double> derived;
   bool derived_valid = false;
   int derived_nelem = 0, derived_Q3 = 0;
   double derived_nu = 0., derived_E = 0.;   // the material the derived state was formed with
@@ -131,24 +132,12 @@ struct CeedVector_private {
 // Transpose map of an offsets restriction: distinct node offsets and, per node, the E-vector
 // positions (e*elemsize + n) of its contributors in element order.  Rows [0, nprio) are the
 // "priority" nodes when the map was built with a priority mask (split-phase apply).
-void ceed_retire(Ceed c, void *p);   // (see the helpers below)
 struct CsrMap {
   bool built = false, full_cover = false;
   int nnodes = 0, nprio = 0, nskipped = 0;
   std::vector<uint32_t> h_node_off, h_rowptr, h_cols;   // host copies (the re-ordered maps are derived from them)
-  uint32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_node_off = nullptr;
-  cps::NodeMap view() const { return cps::NodeMap{d_rowptr, d_cols, d_node_off, nnodes, 0}; }
-  void release() {
-    if (d_rowptr) (void)hipFree(d_rowptr);
-    if (d_cols) (void)hipFree(d_cols);
-    if (d_node_off) (void)hipFree(d_node_off);
-    d_rowptr = d_cols = d_node_off = nullptr; built = false;
-  }
-  // the same for a map recorded launches may have read (an operator's own split map): the arrays leave through ceed_retire
-  void release(Ceed c) {
-    ceed_retire(c, d_rowptr); ceed_retire(c, d_cols); ceed_retire(c, d_node_off);
-    d_rowptr = d_cols = d_node_off = nullptr; built = false;
-  }
+  DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
+  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nnodes, 0}; }
 };
 
 // The transpose map re-ordered for the PIPELINED assembly: the apply is cut into segments of consecutive elements, one
@@ -160,8 +149,8 @@ struct PipeMap {
   const void *base = nullptr;              // the CsrMap it was derived from
   std::vector<int> elem_bound, row_bound;  // nseg + 1 each
   std::vector<uint32_t> h_node_off;        // re-ordered (for the per-operator Dirichlet flags)
-  uint32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_node_off = nullptr;
-  cps::NodeMap view() const { return cps::NodeMap{d_rowptr, d_cols, d_node_off, nrows, 0}; }
+  DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
+  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nrows, 0}; }
 };
 
 struct CeedElemRestriction_private {
@@ -171,14 +160,14 @@ struct CeedElemRestriction_private {
   bool strided = false, backend_strides = true;
   CeedInt strides[3] = {0, 0, 0};
   std::vector<CeedInt> h_offsets;
-  uint32_t *d_offsets = nullptr;  // plain (unflagged)
+  DevArray<uint32_t> d_offsets;   // plain (unflagged)
   CsrMap csr;              // default map (nodes in ascending offset order), built on first use
   CsrMap csr_shell;        // the same without the element-interior nodes (FusedGradArgs::direct)
   // pipelined maps, one per (base map, group size, persistent waves, segments asked for): never replaced once built, so
   // recorded graphs and alternating operators (different Q on one restriction) keep valid pointers
-  std::vector<PipeMap *> pipes;
+  std::vector<std::unique_ptr<PipeMap>> pipes;
   int interior_private = 0;  // 0: not checked yet; 1: every element-interior node has one contributor; -1: not so
-  uint32_t *d_int_off = nullptr;   // node offsets of the element-interior nodes, elements in order, int_per_elem each (direct-store mode:
+  DevArray<uint32_t> d_int_off;    // node offsets of the element-interior nodes, elements in order, int_per_elem each (direct-store mode:
   int int_per_elem = 0;            // the epilogue kernels read those nodes' values from y -- build_interior_list)
 };
 
@@ -226,14 +215,15 @@ struct CeedOperator_private {
   bool kernel_fused = false;          // CeedXOperatorGetKernelName then adds how the geometric factors were obtained (kernel_name_full)
   std::string kernel_name_full;
   int geo_mode = 0;                   // last fused launch: 0 qdata read, 1 recomputed per point, 2 affine elements, 3 swept elements
-  // Dirichlet flags.  Every device array of an operator that a launch may have read leaves through ceed_retire (op_free_flags)
-  uint32_t *d_off_flagged_in = nullptr, *d_off_flagged_out = nullptr;  // same array unless transfer
-  unsigned char *d_node_flags = nullptr;        // per node of the restriction's transpose map
-  unsigned char *d_node_flags_ovl = nullptr;    // per node of the operator's own (priority-first) map
-  unsigned char *d_node_flags_shell = nullptr;  // per node of the restriction's shell map (direct-store mode)
-  std::vector<std::pair<const PipeMap *, unsigned char *>> pipe_flags;   // per row of a pipelined map of the restriction
+  // Dirichlet flags (op_free_flags drops them all)
+  DevArray<uint32_t> d_off_flagged;             // the offsets with the flag bits of their nodes: the active restriction's; of a transfer, the
+                                                // COARSE side's (input of a prolongation, output of a restriction) -- one array either way
+  DevArray<unsigned char> d_node_flags;         // per node of the restriction's transpose map
+  DevArray<unsigned char> d_node_flags_ovl;     // per node of the operator's own (priority-first) map
+  DevArray<unsigned char> d_node_flags_shell;   // per node of the restriction's shell map (direct-store mode)
+  std::vector<std::pair<const PipeMap *, DevArray<unsigned char>>> pipe_flags;   // per row of a pipelined map of the restriction
   // pack of a halo exchange folded into the rows' launch: per (transpose map, halo) the rows' send slots (HaloPackFold)
-  struct PackFold { const CsrMap *M; CeedXHalo H; long serial; uint32_t *d_ptr, *d_slot; bool ok; };
+  struct PackFold { const CsrMap *M; CeedXHalo H; long serial; DevArray<uint32_t> d_ptr, d_slot; bool ok; };
   std::vector<PackFold> pack_folds;
   std::vector<unsigned char> h_mask;      // copy of the output mask (node flags are derived lazily)
   int mask_mode = 0;
@@ -241,10 +231,9 @@ struct CeedOperator_private {
   CeedVector scale = nullptr;
   // transfer operators in OWNER form (ceed_op_other.cpp: transfer_owner_map, transfer_weights)
   std::vector<unsigned char> h_mask_fine;  // the fine side's Dirichlet mask (empty: none)
-  uint32_t *d_own_f = nullptr;             // [nelem][Pf^3] offset | flags of the fine nodes each element owns
+  DevArray<uint32_t> d_own_f;              // [nelem][Pf^3] offset | flags of the fine nodes each element owns
   bool own_full_cover = false;             // every entry of the fine L-vector has an owner
-  double *d_w = nullptr;                   // scale x local multiplicity per fine dof
-  size_t w_len = 0;
+  DevArray<double> d_w;                    // scale x local multiplicity per fine dof
   bool w_ready = false, w_unit = false;    // w_unit: every covered weight is 1 -- the kernels read none
   CeedVector w_scale = nullptr;            // the scale vector and its version the weights were formed from
   uint64_t w_version = 0;
@@ -266,8 +255,6 @@ struct CeedOperator_private {
 // ---------------------------------------------------------------------------
 void ceed_ref(Ceed c);
 void ceed_unref(Ceed c);
-// park a device allocation that recorded graph nodes may still read; freed with the last graph (or at once if none)
-void ceed_retire(Ceed c, void *p);
 int ceed_need_evec(Ceed c, size_t len);
 int ceed_need_side_stream(Ceed c);
 int dev_zero(Ceed c, double *p, size_t n);
@@ -289,12 +276,12 @@ struct CeedXHalo_private {
   long serial = 0;                   // unique per halo ever created (caches keyed by a halo check it, not just the address)
   std::vector<HaloNeighbour> nb;     // slices [offset, offset + n) of the send / receive buffers
   int total = 0;                     // entries over all neighbours
-  uint32_t *d_idx = nullptr;         // [total] L-vector entry of every slot (pack)
+  DevArray<uint32_t> d_idx;          // [total] L-vector entry of every slot (pack)
   std::vector<uint32_t> h_idx;       // host copy (the operators fold the pack into their rows' launch from it)
-  double *send = nullptr, *recv = nullptr;
+  DevArray<double> send, recv;
   // arrivals by destination: distinct entries, and per entry its slots in neighbour-list order (unpack-add)
   int ndst = 0;
-  uint32_t *d_dst = nullptr, *d_uptr = nullptr, *d_uslot = nullptr;
+  DevArray<uint32_t> d_dst, d_uptr, d_uslot;
   hipEvent_t packed = nullptr, arrived = nullptr;
   hipStream_t arrived_on = nullptr;  // the stream the last exchange's receives were issued on (its `arrived` event too)
   bool in_flight = false;

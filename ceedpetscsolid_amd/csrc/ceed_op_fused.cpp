@@ -36,13 +36,11 @@ struct FusedApply {
   const CsrMap *M = nullptr;               // the transpose map of this apply (restriction's, shell, or the operator's split map)
   const unsigned char *flags = nullptr;    // Dirichlet flags per row of M (null: none)
 };
-static unsigned char *make_row_flags(CeedOperator op, CeedElemRestriction r, const std::vector<uint32_t> &node_off, int *err) {
+// the Dirichlet flags of the operator's mask in the row order of a transpose map
+static int make_row_flags(CeedOperator op, CeedElemRestriction r, const std::vector<uint32_t> &node_off, DevArray<unsigned char> &d) {
   std::vector<unsigned char> fl(node_off.size(), 0);
   for (size_t i = 0; i < node_off.size(); i++) fl[i] = (unsigned char)node_flag_bits(op->h_mask.data(), node_off[i], r);
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, fl.size() ? fl.size() : 1) != hipSuccess ||
-      hipMemcpy(d, fl.data(), fl.size(), hipMemcpyHostToDevice) != hipSuccess) { *err = ceed_error("device allocation of the Dirichlet row flags failed"); return nullptr; }
-  return d;
+  return d.upload(op->ceed, fl);
 }
 // vectors, tables, geometry provenance, physics, transpose map, flags, scratch: the launch arguments of this apply
 static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool add, bool split, FusedApply &F) {
@@ -62,7 +60,7 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
   CHK(vec_dev(in, false, &px));
   CHK(vec_dev(out, true, &F.py));
   CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
-  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : r->d_offsets;
+  a.offsets = op->d_off_flagged ? op->d_off_flagged.get() : r->d_offsets.get();
   a.x = px; a.y = F.py; a.qdata = pq;
   CHK(read_phys(qf, &a.nu, &a.E));
   const int Q3 = ai.basis->Q1d * ai.basis->Q1d * ai.basis->Q1d;
@@ -73,8 +71,8 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     if (qf->kind == QF_HYPERFS_DF && c->opt.derived_state && pencil_derived_state(ai.basis->Q1d) && sv->derived_valid && sv->derived_nelem == r->nelem && sv->derived_Q3 == Q3 &&
         sv->derived_nu == a.nu && sv->derived_E == a.E) {
       F.qfkind = QF_HYPERFS_DF_DS;
-      a.state_in = sv->derived;
-      if (c->capturing) capture_dep(c, GraphDep{sv, nullptr, sv->derived});
+      a.state_in = sv->derived.get();
+      if (c->capturing) capture_dep(c, GraphDep{sv, nullptr, sv->derived.get()});
     }
   }
   if (op->o_state >= 0) {
@@ -83,14 +81,11 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     CHK(vec_dev(sv, true, &ps)); a.state_out = ps;  // every point is overwritten (and the derived state invalidated)
     if (qf->kind == QF_HYPERFS_F && c->opt.derived_state && pencil_derived_state(ai.basis->Q1d) && !split) {
       const size_t need = (size_t)r->nelem * 10 * Q3;
-      if (sv->derived_len < need) {
+      if (sv->derived.size() < need) {
         if (c->capturing) return ceed_error("evaluate the residual once before recording (derived-state buffer)");
-        ceed_retire(c, sv->derived);
-        sv->derived = nullptr; sv->derived_len = 0;
-        HIPCHK(hipMalloc((void **)&sv->derived, sizeof(double) * need));
-        sv->derived_len = need;
+        CHK(sv->derived.alloc(c, need));
       }
-      a.state_out2 = sv->derived;
+      a.state_out2 = sv->derived.get();
       F.derived_for = sv;
     }
   }
@@ -102,11 +97,11 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     for (int i = 0; same_rule && i < ai.basis->Q1d; i++)
       same_rule = qv->geo_qref[i] == ai.basis->qref1d[i] && qv->geo_qwt[i] == ai.basis->qweight1d[i];
     if (same_rule && c->opt.recompute_geo) {
-      a.geo = qv->geo;
-      a.geo_aff = qv->geo_aff;
-      a.geo_swept = qv->geo_swept; a.geo_axis = qv->geo_axis;
+      a.geo = qv->geo.get();
+      a.geo_aff = qv->geo_aff.get();
+      a.geo_swept = qv->geo_swept.get(); a.geo_axis = qv->geo_axis;
       for (int i = 0; i < ai.basis->Q1d; i++) { a.qref[i] = qv->geo_qref[i]; a.qwt[i] = qv->geo_qwt[i]; }
-      if (c->capturing) capture_dep(c, GraphDep{qv, qv->geo, nullptr});
+      if (c->capturing) capture_dep(c, GraphDep{qv, qv->geo.get(), nullptr});
     }
   }
   lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
@@ -118,7 +113,7 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
   F.direct = !add && c->opt.direct_interior && rstr_interior_private(r, ai.basis->P1d);
   a.direct = F.direct ? 1 : 0;
   // atomic-free, deterministic scatter: element results -> E-vector -> per-node sums
-  unsigned char **flagsp;
+  DevArray<unsigned char> *flagsp;
   if (split) {
     F.M = &op->ovl_csr; flagsp = &op->d_node_flags_ovl;
     if ((F.M->nskipped > 0) != F.direct) return ceed_error("split-phase map and direct-store mode disagree");
@@ -130,15 +125,11 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     CHK(build_csr(r, r->csr, nullptr));
     F.M = &r->csr; flagsp = &op->d_node_flags;
   }
-  if (!*flagsp && !op->h_mask.empty()) {
-    int err = 0;
-    *flagsp = make_row_flags(op, r, F.M->h_node_off, &err);
-    if (err) return err;
-  }
-  F.flags = (op->mask_mode & 2) ? *flagsp : nullptr;
+  if (!*flagsp && !op->h_mask.empty()) CHK(make_row_flags(op, r, F.M->h_node_off, *flagsp));
+  F.flags = (op->mask_mode & 2) ? flagsp->get() : nullptr;
   a.evec_stride = 3 * (F.direct ? element_shell_size(ai.basis->P1d) : r->elemsize);
   CHK(ceed_need_evec(c, (size_t)r->nelem * std::max((size_t)3 * (size_t)r->elemsize, (size_t)a.evec_stride)));   // (an aligned shell block may exceed P^3 records at small P)
-  a.evec = c->evec;
+  a.evec = c->evec.get();
   if (F.derived_for) {   // this (whole) residual apply also writes the tangent's derived state beside grad u: valid from here on in stream order
     CeedVector sv = F.derived_for;
     sv->derived_valid = true; sv->derived_nelem = r->nelem; sv->derived_Q3 = Q3;
@@ -168,8 +159,8 @@ static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s
 // Built once per (map, halo); not ok (-> the separate pack kernel) if an entry of the halo is no row of the map.
 static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const CsrMap *M, CeedXHalo H, HaloPackFold *out, bool *ok) {
   for (auto &pf : op->pack_folds)
-    if (pf.M == M && pf.H == H && pf.serial == H->serial) { *ok = pf.ok; *out = HaloPackFold{pf.d_ptr, pf.d_slot, H->send}; return 0; }
-  CeedOperator_private::PackFold pf{M, H, H->serial, nullptr, nullptr, false};
+    if (pf.M == M && pf.H == H && pf.serial == H->serial) { *ok = pf.ok; *out = HaloPackFold{pf.d_ptr.get(), pf.d_slot.get(), H->send.get()}; return 0; }
+  CeedOperator_private::PackFold pf{M, H, H->serial, {}, {}, false};
   if (op->ceed->capturing) { *ok = false; return 0; }     // cold while recording: the separate pack kernel
   const int nn = M->nnodes;
   bool good = r->ncomp == 3 && r->compstride == 1 && (size_t)H->total < (1u << 30);
@@ -193,14 +184,11 @@ static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const CsrMap *M
     }
   }
   if (good) {
-    HIPCHK(hipMalloc((void **)&pf.d_ptr, sizeof(uint32_t) * ptr.size()));
-    HIPCHK(hipMalloc((void **)&pf.d_slot, sizeof(uint32_t) * slot.size()));
-    HIPCHK(hipMemcpy(pf.d_ptr, ptr.data(), sizeof(uint32_t) * ptr.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pf.d_slot, slot.data(), sizeof(uint32_t) * slot.size(), hipMemcpyHostToDevice));
+    CHK(pf.d_ptr.upload(op->ceed, ptr)); CHK(pf.d_slot.upload(op->ceed, slot));
     pf.ok = true;
   }
-  op->pack_folds.push_back(pf);
-  *ok = pf.ok; *out = HaloPackFold{pf.d_ptr, pf.d_slot, H->send};
+  *ok = pf.ok; *out = HaloPackFold{pf.d_ptr.get(), pf.d_slot.get(), H->send.get()};
+  op->pack_folds.push_back(std::move(pf));
   return 0;
 }
 
@@ -231,14 +219,13 @@ static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM) {
   Ceed c = op->ceed;
   const unsigned char *fl = nullptr;
   if ((op->mask_mode & 2) && !op->h_mask.empty()) {   // Dirichlet flags in this map's row order (made once per map)
-    for (auto &pf : op->pipe_flags) if (pf.first == PM) fl = pf.second;
+    for (auto &pf : op->pipe_flags) if (pf.first == PM) fl = pf.second.get();
     if (!fl) {
       if (c->capturing) return ceed_error("apply the operator once before recording (Dirichlet flags of the pipelined map)");
-      int err = 0;
-      unsigned char *d = make_row_flags(op, F.r, PM->h_node_off, &err);
-      if (err) return err;
-      op->pipe_flags.emplace_back(PM, d);
-      fl = d;
+      DevArray<unsigned char> d;
+      CHK(make_row_flags(op, F.r, PM->h_node_off, d));
+      fl = d.get();
+      op->pipe_flags.emplace_back(PM, std::move(d));
     }
   }
   const int nseg = PM->nseg;
@@ -356,7 +343,7 @@ static int apply_fused_epilogue(CeedOperator op, CeedVector in, CeedVector t, Ep
   // replayed, pipelined 6.10 eager / 6.83 replayed (profiles/r05_ab_experiments.txt item 10).
   set_launch_info(op, 1, 1, 1, F.r->nelem);
   CHK(fused_launch(op, F, 0, F.r->nelem, 0, s));
-  ep.int_off = nint ? F.r->d_int_off : nullptr;
+  ep.int_off = nint ? F.r->d_int_off.get() : nullptr;
   ep.n_int = F.r->nelem * nint;
   HIPCHK(launch_assemble_epi(M->view(), F.flags, F.a.evec, ep, s));
   op->launches++;
@@ -430,9 +417,10 @@ extern "C" int CeedXOperatorSetOverlapSplit(CeedOperator op, CeedInt n_leading_e
                                             CeedInt lsize) {
   CHK(need_fused(op, "overlap split", Kind::either));
   CeedElemRestriction r = op->in[op->i_active].rstr;
-  op->ovl_csr.release(op->ceed);     // (recorded graphs may still read the split map and its flags)
+  op->ovl_csr = CsrMap();     // a map not built, its counts and host copies reset with it (every reader asks `built` first); recorded
+                              // graphs may still read the old split map and its flags: both are DevArrays
   op->ovl_halo_checked = 0;
-  ceed_retire(op->ceed, op->d_node_flags_ovl); op->d_node_flags_ovl = nullptr;
+  op->d_node_flags_ovl.release();
   op->ovl_lead = 0;
   if (!priority) return 0;
   if (lsize < r->lsize || n_leading_elems < 0 || n_leading_elems > r->nelem) return ceed_error("bad overlap split arguments");
@@ -540,16 +528,16 @@ static int assemble_diagonal(CeedOperator op, CeedVector assembled, int width) {
   CHK(vec_dev(assembled, true, &pd));
   CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
   if (op->i_state >= 0) CHK(vec_dev(op->in[op->i_state].vec, false, &ps));
-  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : r->d_offsets;
+  a.offsets = op->d_off_flagged ? op->d_off_flagged.get() : r->d_offsets.get();
   a.qdata = pq; a.state_in = ps; a.nelem = r->nelem;
   // one form for both widths: without flagged offsets the plain ones carry no flag bits, so the kernels read "nothing masked" either way
-  a.mask_in = (op->d_off_flagged_in && (op->mask_mode & 1)) ? 1 : 0; a.mask_out = (op->d_off_flagged_in && (op->mask_mode & 2)) ? 1 : 0;
+  a.mask_in = (op->d_off_flagged && (op->mask_mode & 1)) ? 1 : 0; a.mask_out = (op->d_off_flagged && (op->mask_mode & 2)) ? 1 : 0;
   CHK(read_phys(op->qf, &a.nu, &a.E));
   lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
   CHK(dev_zero(op->ceed, pd, (size_t)assembled->length));
   CHK(build_csr(r, r->csr, nullptr));
   CHK(ceed_need_evec(op->ceed, (size_t)r->nelem * r->elemsize * 3 * width));
-  a.evec = op->ceed->evec;
+  a.evec = op->ceed->evec.get();
   const char *kname = "";
   hipError_t e = (width == 3 ? launch_pbdiag : launch_diag)(ai.basis->P1d, ai.basis->Q1d, op->qf->kind, op->tables, a, s, &kname);
   if (no_kernel(e, kname)) return ceed_error("no %s kernel for P=%d Q=%d %s", who, ai.basis->P1d, ai.basis->Q1d, op->qf->name.c_str());
@@ -587,7 +575,7 @@ extern "C" int CeedXOperatorApplyState(CeedOperator op, CeedVector u) {
   CHK(vec_dev(u, false, &px));
   CHK(vec_dev(qv, false, &pq));
   CHK(vec_dev(sv, true, &ps));
-  a.offsets = op->d_off_flagged_in ? op->d_off_flagged_in : r->d_offsets;
+  a.offsets = op->d_off_flagged ? op->d_off_flagged.get() : r->d_offsets.get();
   a.x = px; a.qdata = pq; a.state_out = ps; a.nelem = r->nelem; a.mask_in = (op->mask_mode & 1) ? 1 : 0;
   const char *kname = "";
   {

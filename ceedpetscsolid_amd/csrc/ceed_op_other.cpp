@@ -23,21 +23,18 @@ static int transfer_owner_map(CeedOperator op, CeedElemRestriction rf) {
     own[i] = o | ((mk.empty() ? 0u : node_flag_bits(mk.data(), o, rf)) << OFF_FLAG_SHIFT);
   }
   op->own_full_cover = distinct * 3 == (size_t)rf->lsize;
-  HIPCHK(hipMalloc((void **)&op->d_own_f, sizeof(uint32_t) * own.size()));
-  HIPCHK(hipMemcpy(op->d_own_f, own.data(), sizeof(uint32_t) * own.size(), hipMemcpyHostToDevice));
-  return 0;
+  return op->d_own_f.upload(c, own);
 }
 // Set-up time only (never while recording): `n` counters on the device, zeroed, counted into by `count` on the Ceed's stream,
 // and read back into h[0 .. n).
 template <class Count>
 static int count_on_device(Ceed c, int n, int *h, Count count) {
-  int *d_cnt = nullptr;
-  HIPCHK(hipMalloc((void **)&d_cnt, n * sizeof(int)));
-  HIPCHK(hipMemsetAsync(d_cnt, 0, n * sizeof(int), c->stream));
-  CHK(count(d_cnt));
-  HIPCHK(hipMemcpyAsync(h, d_cnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  DevArray<int> d_cnt;     // (bound to no Ceed: freed directly on every way out, behind the synchronisation below or an error)
+  CHK(d_cnt.alloc(nullptr, (size_t)n));
+  HIPCHK(hipMemsetAsync(d_cnt.get(), 0, n * sizeof(int), c->stream));
+  CHK(count(d_cnt.get()));
+  HIPCHK(hipMemcpyAsync(h, d_cnt.get(), n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  (void)hipFree(d_cnt);
   return 0;
 }
 // w = (fine-side scale, CeedXOperatorSetFineScale, or 1) x (local multiplicity of the fine restriction) per fine dof; *w = null
@@ -47,28 +44,24 @@ static int transfer_weights(CeedOperator op, CeedElemRestriction rf, const doubl
   Ceed c = op->ceed;
   CeedVector sc = op->scale;
   const uint64_t ver = sc ? sc->version : 0;
-  if (op->w_ready && op->w_scale == sc && op->w_version == ver) { *w = op->w_unit ? nullptr : op->d_w; return 0; }
+  if (op->w_ready && op->w_scale == sc && op->w_version == ver) { *w = op->w_unit ? nullptr : op->d_w.get(); return 0; }
   if (c->capturing)
     return ceed_error("transfer operator during graph capture: its fine-side scale was written since the last apply (or this is the first); "
                       "apply the operator once before recording");
   double *psc = nullptr;
   if (sc) CHK(vec_dev(sc, false, &psc));
   const size_t n = (size_t)rf->lsize;
-  if (op->w_len < n) {
-    ceed_retire(c, op->d_w); op->d_w = nullptr; op->w_len = 0;
-    HIPCHK(hipMalloc((void **)&op->d_w, sizeof(double) * (n ? n : 1)));
-    op->w_len = n;
-  }
+  if (op->d_w.size() < n) CHK(op->d_w.alloc(c, n));
   int cnt = 1;
   CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) {
-    CHK(dev_zero(c, op->d_w, n));
-    HIPCHK(launch_multiplicity(rf->d_offsets, rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w, c->stream));
-    HIPCHK(launch_transfer_weights(op->d_w, psc, n, d_cnt, c->stream));
+    CHK(dev_zero(c, op->d_w.get(), n));
+    HIPCHK(launch_multiplicity(rf->d_offsets.get(), rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w.get(), c->stream));
+    HIPCHK(launch_transfer_weights(op->d_w.get(), psc, n, d_cnt, c->stream));
     return 0;
   }));
   op->w_unit = cnt == 0; op->w_scale = sc; op->w_version = ver; op->w_ready = true;
-  if (op->w_unit) { ceed_retire(c, op->d_w); op->d_w = nullptr; op->w_len = 0; }     // (not needed again until the scale is rewritten: 8 B per fine dof given back)
-  *w = op->w_unit ? nullptr : op->d_w;
+  if (op->w_unit) op->d_w.release();     // (not needed again until the scale is rewritten: 8 B per fine dof given back)
+  *w = op->w_unit ? nullptr : op->d_w.get();
   return 0;
 }
 int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add) {
@@ -87,9 +80,8 @@ int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CHK(transfer_owner_map(op, rf));
   CHK(transfer_weights(op, rf, &a.w_f));
   // the coarse side's flagged offsets: the input side of a prolongation, the output side of a restriction
-  const uint32_t *fc = pro ? op->d_off_flagged_in : op->d_off_flagged_out;
-  a.off_c = fc ? fc : rc->d_offsets;
-  a.own_f = op->d_own_f;
+  a.off_c = op->d_off_flagged ? op->d_off_flagged.get() : rc->d_offsets.get();
+  a.own_f = op->d_own_f.get();
   a.x = px; a.y = py; a.nelem = rc->nelem; a.add = add ? 1 : 0;
   const int m_in = (op->mask_mode & 1) ? 1 : 0, m_out = (op->mask_mode & 2) ? 1 : 0;
   a.mask_c = pro ? m_in : m_out; a.mask_f = pro ? m_out : m_in;
@@ -101,7 +93,7 @@ int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add) {
     // element order over the coarse restriction's transpose map (masked entries travel as zeros)
     CHK(build_csr(rc, rc->csr, nullptr));
     CHK(ceed_need_evec(op->ceed, (size_t)rc->nelem * rc->ncomp * rc->elemsize));
-    a.evec = op->ceed->evec;
+    a.evec = op->ceed->evec.get();
     if (!add && !rc->csr.full_cover) CHK(dev_zero(op->ceed, py, (size_t)out->length));
   }
   TimerScope ts(op, s);
@@ -123,26 +115,26 @@ static int geo_provenance(CeedOperator op, CeedVector out, const uint32_t *off_x
   Ceed c = op->ceed;
   hipStream_t s = c->stream;
   CeedBasis xb = op->in[0].basis;
-  HIPCHK(hipMalloc((void **)&out->geo, sizeof(double) * GEO_NCOEF * (size_t)nelem));
-  HIPCHK(launch_geo_coeffs(off_x, px, out->geo, nelem, s));
+  CHK(out->geo.alloc(c, GEO_NCOEF * (size_t)nelem));
+  HIPCHK(launch_geo_coeffs(off_x, px, out->geo.get(), nelem, s));
   out->geo_nelem = nelem; out->geo_Q = xb->Q1d;
   if (c->opt.affine_geo) {   // all elements affine (box meshes)?  then dXdx and det J are per-ELEMENT constants
     int cnt = 1;
-    HIPCHK(hipMalloc((void **)&out->geo_aff, sizeof(double) * GEO_NAFF * (size_t)nelem));
-    CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) { HIPCHK(launch_geo_affine(out->geo, out->geo_aff, nelem, d_cnt, s)); return 0; }));
-    if (cnt != 0) { (void)hipFree(out->geo_aff); out->geo_aff = nullptr; }   // a mixed mesh takes the general recompute everywhere
+    CHK(out->geo_aff.alloc(c, GEO_NAFF * (size_t)nelem));
+    CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) { HIPCHK(launch_geo_affine(out->geo.get(), out->geo_aff.get(), nelem, d_cnt, s)); return 0; }));
+    if (cnt != 0) out->geo_aff.release();   // a mixed mesh takes the general recompute everywhere
   }
   if (!out->geo_aff && c->opt.swept_geo) {   // every element swept along ONE reference direction (extruded meshes)?
     int cnt[4] = {0, 0, 0, 1};
-    HIPCHK(hipMalloc((void **)&out->geo_swept, sizeof(double) * GEO_NSWEPT * (size_t)nelem));
+    CHK(out->geo_swept.alloc(c, GEO_NSWEPT * (size_t)nelem));
     CHK(count_on_device(c, 4, cnt, [&](int *d_cnt) {     // count: every direction an element qualifies for
-      HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, d_cnt, -1, s));
+      HIPCHK(launch_geo_swept(out->geo.get(), out->geo_swept.get(), nelem, d_cnt, -1, s));
       return 0;
     }));
     int axis = -1;
     for (int d = 2; d >= 0; d--) if (cnt[d] == nelem) axis = d;      // a direction ALL elements share
-    if (axis < 0) { (void)hipFree(out->geo_swept); out->geo_swept = nullptr; }   // no common direction or general hexes: the general recompute
-    else { HIPCHK(launch_geo_swept(out->geo, out->geo_swept, nelem, nullptr, axis, s)); out->geo_axis = axis; }
+    if (axis < 0) out->geo_swept.release();   // no common direction or general hexes: the general recompute
+    else { HIPCHK(launch_geo_swept(out->geo.get(), out->geo_swept.get(), nelem, nullptr, axis, s)); out->geo_axis = axis; }
   }
   for (int i = 0; i < xb->Q1d && i < MAXN1D; i++) { out->geo_qref[i] = xb->qref1d[i]; out->geo_qwt[i] = xb->qweight1d[i]; }
   return 0;
@@ -155,7 +147,7 @@ int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out) {
   double *px, *pq;
   CHK(vec_dev(in, false, &px));
   CHK(vec_dev(out, true, &pq));
-  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.qdata = pq; a.nelem = x.rstr->nelem;
+  a.off_x = x.rstr->d_offsets.get(); a.xcoord = px; a.qdata = pq; a.nelem = x.rstr->nelem;
   if ((size_t)out->length < (size_t)a.nelem * 10 * x.basis->Q1d * x.basis->Q1d * x.basis->Q1d) return ceed_error("qdata vector too short");
   TimerScope ts(op, s);
   const char *kname = "";
@@ -165,7 +157,10 @@ int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out) {
   op->launches++;
   set_kernel_name(op, kname, false);
   // the elements are trilinear (op_plan takes no other coordinates): keep the map coefficients with the qdata vector
-  if (op->ceed->opt.recompute_geo && !op->ceed->capturing) CHK(geo_provenance(op, out, a.off_x, px, a.nelem));
+  if (op->ceed->opt.recompute_geo && !op->ceed->capturing) {
+    const int ierr = geo_provenance(op, out, a.off_x, px, a.nelem);
+    if (ierr) { vec_drop_geo(out); return ierr; }      // no half-built provenance: the vector reads as plain qdata
+  }
   return 0;
 }
 int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
@@ -178,7 +173,7 @@ int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   EnergyOpArgs a{};
   double *pu, *py, *pq;
   CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(qd, false, &pq));
-  a.off_u = u.rstr->d_offsets; a.u = pu; a.off_e = en.rstr->d_offsets; a.y = py; a.qdata = pq;
+  a.off_u = u.rstr->d_offsets.get(); a.u = pu; a.off_e = en.rstr->d_offsets.get(); a.y = py; a.qdata = pq;
   a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
   const int kd = qf->kind;
   a.diag = (kd == QF_DIAG_LINELAS || kd == QF_DIAG_HYPERSS || kd == QF_DIAG_HYPERFS) ? 1 : 0;
@@ -203,7 +198,7 @@ int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CoordOpArgs a{};
   double *px, *py, *pq = nullptr;
   CHK(vec_dev(in, false, &px)); CHK(vec_dev(out, true, &py));
-  a.off_x = x.rstr->d_offsets; a.xcoord = px; a.off_u = o.rstr->d_offsets; a.y = py;
+  a.off_x = x.rstr->d_offsets.get(); a.xcoord = px; a.off_u = o.rstr->d_offsets.get(); a.y = py;
   a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
   a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
   if (a.mode != 2) {

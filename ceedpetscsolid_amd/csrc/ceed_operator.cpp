@@ -53,13 +53,10 @@ extern "C" int CeedOperatorSetField(CeedOperator op, const char *name, CeedElemR
   op->plan = PLAN_NONE;
   return 0;
 }
-// everything derived from the Dirichlet mask: recorded graphs may still read the arrays, so each leaves through ceed_retire
+// everything derived from the Dirichlet mask (recorded graphs may still read the arrays: they are DevArrays)
 static void op_free_flags(CeedOperator o) {
-  auto retire = [&](auto *&p) { ceed_retire(o->ceed, p); p = nullptr; };
-  if (o->d_off_flagged_out == o->d_off_flagged_in) o->d_off_flagged_out = nullptr;     // one array unless the operator is a transfer
-  retire(o->d_off_flagged_in); retire(o->d_off_flagged_out); retire(o->d_own_f);
-  retire(o->d_node_flags); retire(o->d_node_flags_ovl); retire(o->d_node_flags_shell);
-  for (auto &pf : o->pipe_flags) ceed_retire(o->ceed, pf.second);
+  o->d_off_flagged.release(); o->d_own_f.release();
+  o->d_node_flags.release(); o->d_node_flags_ovl.release(); o->d_node_flags_shell.release();
   o->pipe_flags.clear(); o->h_mask.clear(); o->h_mask_fine.clear();
   o->mask_mode = 0;
 }
@@ -78,14 +75,11 @@ extern "C" int CeedOperatorDestroy(CeedOperator *op) {
       }
     CeedQFunctionDestroy(&o->qf);
   }
-  op_free_flags(o);
-  for (auto &pf : o->pack_folds) { ceed_retire(o->ceed, pf.d_ptr); ceed_retire(o->ceed, pf.d_slot); }
-  o->ovl_csr.release(o->ceed);
-  ceed_retire(o->ceed, o->d_w);
   CeedVectorDestroy(&o->scale);
   for (auto &ev : o->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-  ceed_unref(o->ceed);
-  delete o;
+  Ceed c = o->ceed;
+  delete o;            // (before the reference goes: its arrays and its split map retire into a Ceed that still exists)
+  ceed_unref(c);
   return 0;
 }
 
@@ -307,16 +301,14 @@ extern "C" int CeedXOperatorGetKernelName(CeedOperator op, const char **name) {
   return 0;
 }
 
-static int make_flagged(CeedElemRestriction r, const unsigned char *mask, CeedInt lsize, uint32_t **dev) {
+static int make_flagged(CeedElemRestriction r, const unsigned char *mask, CeedInt lsize, DevArray<uint32_t> &dev) {
   if (lsize < r->lsize) return ceed_error("Dirichlet mask shorter than the L-vector");
   std::vector<uint32_t> fl(r->h_offsets.size());
   for (size_t i = 0; i < fl.size(); i++) {
     const uint32_t o = (uint32_t)r->h_offsets[i];
     fl[i] = o | (node_flag_bits(mask, o, r) << OFF_FLAG_SHIFT);
   }
-  HIPCHK(hipMalloc((void **)dev, sizeof(uint32_t) * (fl.size() ? fl.size() : 1)));
-  HIPCHK(hipMemcpy(*dev, fl.data(), sizeof(uint32_t) * fl.size(), hipMemcpyHostToDevice));
-  return 0;
+  return dev.upload(r->ceed, fl);
 }
 // mode: 1 = masked entries read as zero, 2 = masked rows dropped, 3 = both (default for mode 0)
 extern "C" int CeedXOperatorSetDirichletMaskMode(CeedOperator op, CeedMemType mtype, const unsigned char *mask,
@@ -327,16 +319,15 @@ extern "C" int CeedXOperatorSetDirichletMaskMode(CeedOperator op, CeedMemType mt
   if (!mask && !mask_out) return 0;
   if (mtype != CEED_MEM_HOST) return ceed_error("pass the Dirichlet mask in host memory (it is folded into the offsets once)");
   if (op->plan == PLAN_FUSED_GRAD) {
-    CHK(make_flagged(op->in[op->i_active].rstr, mask, lsize, &op->d_off_flagged_in));
-    op->d_off_flagged_out = op->d_off_flagged_in;
+    CHK(make_flagged(op->in[op->i_active].rstr, mask, lsize, op->d_off_flagged));
     op->h_mask.assign(mask, mask + lsize);
   } else if (op->plan == PLAN_PROLONG || op->plan == PLAN_RESTRICT) {
     if (!mask || !mask_out) return ceed_error("transfer operators need the input-side and the output-side mask");
     // the COARSE side's flags ride in its offsets (input of a prolongation, output of a restriction); the FINE side's in the
     // owner map (transfer_owner_map), rebuilt at the next apply
     const bool pro = op->plan == PLAN_PROLONG;
-    if (pro) CHK(make_flagged(op->in[0].rstr, mask, lsize, &op->d_off_flagged_in));
-    else CHK(make_flagged(op->out[0].rstr, mask_out, lsize_out, &op->d_off_flagged_out));
+    if (pro) CHK(make_flagged(op->in[0].rstr, mask, lsize, op->d_off_flagged));
+    else CHK(make_flagged(op->out[0].rstr, mask_out, lsize_out, op->d_off_flagged));
     CeedElemRestriction rf = pro ? op->out[0].rstr : op->in[0].rstr;
     if ((pro ? lsize_out : lsize) < rf->lsize) return ceed_error("Dirichlet mask shorter than the L-vector");
     const unsigned char *mf = pro ? mask_out : mask;

@@ -20,8 +20,9 @@ extern "C" int CeedElemRestrictionCreate(Ceed ceed, CeedInt nelem, CeedInt elems
   r->ceed = ceed; ceed_ref(ceed);
   r->nelem = nelem; r->elemsize = elemsize; r->ncomp = ncomp; r->compstride = compstride; r->lsize = lsize;
   r->h_offsets.assign(offsets, offsets + n);
-  HIPCHK(hipMalloc((void **)&r->d_offsets, sizeof(uint32_t) * (n ? n : 1)));
-  HIPCHK(hipMemcpy(r->d_offsets, offsets, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  static_assert(sizeof(CeedInt) == sizeof(uint32_t), "the offsets are uploaded as they are (checked non-negative above)");
+  const int ierr = r->d_offsets.upload(ceed, (const uint32_t *)offsets, n);
+  if (ierr) { (void)CeedElemRestrictionDestroy(&r); return ierr; }
   *rstr = r;
   return 0;
 }
@@ -38,8 +39,10 @@ extern "C" int CeedElemRestrictionCreateStrided(Ceed ceed, CeedInt nelem, CeedIn
   if (r->backend_strides) { r->strides[0] = 1; r->strides[1] = elemsize; r->strides[2] = elemsize * ncomp; }
   else {
     memcpy(r->strides, strides, sizeof r->strides);
-    if (!(strides[0] == 1 && strides[1] == elemsize && strides[2] == elemsize * ncomp))
+    if (!(strides[0] == 1 && strides[1] == elemsize && strides[2] == elemsize * ncomp)) {
+      (void)CeedElemRestrictionDestroy(&r);
       return ceed_error("only the [elem][comp][node] strided layout is supported on /gpu/hip/mi355x");
+    }
   }
   *rstr = r;
   return 0;
@@ -61,14 +64,14 @@ extern "C" int CeedElemRestrictionApply(CeedElemRestriction r, CeedTransposeMode
     else HIPCHK(launch_axpby(pv, 1., pu, 1., n, s));
     return 0;
   }
-  if (tmode == CEED_NOTRANSPOSE) HIPCHK(launch_rstr_gather(r->d_offsets, r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
-  else HIPCHK(launch_rstr_scatter_add(r->d_offsets, r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
+  if (tmode == CEED_NOTRANSPOSE) HIPCHK(launch_rstr_gather(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
+  else HIPCHK(launch_rstr_scatter_add(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
   return 0;
 }
 extern "C" int CeedElemRestrictionGetMultiplicity(CeedElemRestriction r, CeedVector mult) {
   if (r->strided) return CeedVectorSetValue(mult, 1.);
   CHK(CeedVectorSetValue(mult, 0.));
-  HIPCHK(launch_multiplicity(r->d_offsets, r->nelem, r->elemsize, r->ncomp, r->compstride, mult->d, r->ceed->stream));
+  HIPCHK(launch_multiplicity(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, mult->d, r->ceed->stream));
   return 0;
 }
 extern "C" int CeedElemRestrictionDestroy(CeedElemRestriction *rstr) {
@@ -77,16 +80,9 @@ extern "C" int CeedElemRestrictionDestroy(CeedElemRestriction *rstr) {
   *rstr = nullptr;
   if (r == CEED_ELEMRESTRICTION_NONE) return 0;
   if (--r->refcount > 0) return 0;
-  if (r->d_offsets) (void)hipFree(r->d_offsets);
-  if (r->d_int_off) (void)hipFree(r->d_int_off);
-  r->csr.release();
-  r->csr_shell.release();
-  for (PipeMap *p : r->pipes) {
-    for (uint32_t *q : {p->d_rowptr, p->d_cols, p->d_node_off}) if (q) (void)hipFree(q);
-    delete p;
-  }
-  ceed_unref(r->ceed);
-  delete r;
+  Ceed c = r->ceed;
+  delete r;            // (before the reference goes: its arrays and maps retire into a Ceed that still exists)
+  ceed_unref(c);
   return 0;
 }
 
@@ -134,12 +130,7 @@ int build_csr(CeedElemRestriction r, CsrMap &M, const unsigned char *prio, int s
   M.nnodes = nn;
   // every L-vector entry is written by the assembly (or, for the skipped nodes, by the fused kernel)
   M.full_cover = ((size_t)nn + (size_t)M.nskipped) * (size_t)r->ncomp == (size_t)r->lsize;
-  HIPCHK(hipMalloc((void **)&M.d_rowptr, sizeof(uint32_t) * (nn + 1)));
-  HIPCHK(hipMalloc((void **)&M.d_cols, sizeof(uint32_t) * cols.size()));
-  HIPCHK(hipMalloc((void **)&M.d_node_off, sizeof(uint32_t) * (nn ? nn : 1)));
-  HIPCHK(hipMemcpy(M.d_rowptr, rowptr.data(), sizeof(uint32_t) * (nn + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(M.d_cols, cols.data(), sizeof(uint32_t) * cols.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(M.d_node_off, M.h_node_off.data(), sizeof(uint32_t) * nn, hipMemcpyHostToDevice));
+  CHK(M.d_rowptr.upload(r->ceed, rowptr)); CHK(M.d_cols.upload(r->ceed, cols)); CHK(M.d_node_off.upload(r->ceed, M.h_node_off));
   M.built = true;
   return 0;
 }
@@ -170,8 +161,7 @@ int build_interior_list(CeedElemRestriction r, int P) {
   for (CeedInt e = 0; e < r->nelem; e++)
     for (int n = 0; n < r->elemsize; n++)
       if (node_is_element_interior(n, P)) lst[k++] = (uint32_t)r->h_offsets[(size_t)e * r->elemsize + n];
-  HIPCHK(hipMalloc((void **)&r->d_int_off, sizeof(uint32_t) * (lst.size() ? lst.size() : 1)));
-  HIPCHK(hipMemcpy(r->d_int_off, lst.data(), sizeof(uint32_t) * lst.size(), hipMemcpyHostToDevice));
+  CHK(r->d_int_off.upload(r->ceed, lst));
   r->int_per_elem = m;
   return 0;
 }
@@ -182,8 +172,8 @@ int build_interior_list(CeedElemRestriction r, int P) {
 // Maps are cached per restriction and never replaced: a recorded graph, or a second operator with another quadrature on
 // the same restriction, keeps valid pointers.  A launch too small to pipeline gets a map with nseg = 1 and NO copies.
 int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int req_seg_in, int waves, int mb, PipeMap **out) {
-  for (PipeMap *p : r->pipes)
-    if (p->E == E && p->req_seg == req_seg_in && p->waves == waves && p->mb == mb && p->base == (const void *)&M) { *out = p; return 0; }
+  for (auto &p : r->pipes)
+    if (p->E == E && p->req_seg == req_seg_in && p->waves == waves && p->mb == mb && p->base == (const void *)&M) { *out = p.get(); return 0; }
   const CeedOptions &opt = r->ceed->opt;
   int req_seg = req_seg_in;
   const int ngroups = (r->nelem + E - 1) / E;
@@ -202,10 +192,10 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   else if (req_seg == 0) req_seg = std::max(2, std::min(16, (int)((double)r->nelem * per_elem * 24. / (1e6 * std::max(mb, 1)) + 0.5)));
   int nseg = min_rounds > 0 ? std::max(1, std::min(req_seg, ngroups / (min_rounds * std::max(waves, 1)))) : std::min(req_seg, std::max(1, ngroups));
   if (nseg >= 2 && r->ceed->capturing) { *out = nullptr; return 0; }   // cold map while recording: the caller takes the serial path (its map exists)
-  PipeMap *Gp = new PipeMap;
+  std::unique_ptr<PipeMap> Gp(new PipeMap);     // (dropped with its arrays by an error return below)
   PipeMap &G = *Gp;
   G.E = E; G.req_seg = req_seg_in; G.waves = waves; G.mb = mb; G.base = (const void *)&M;
-  if (nseg < 2) { G.nseg = 1; G.built = true; r->pipes.push_back(Gp); *out = Gp; return 0; }
+  if (nseg < 2) { G.nseg = 1; G.built = true; *out = Gp.get(); r->pipes.push_back(std::move(Gp)); return 0; }
   // Boundaries are laid out FROM THE END in whole rounds of the waves: the last segment (whose rows are summed with nothing
   // to hide behind) is `last_rounds` rounds, the others share the rest equally in whole rounds, and the odd remainder of the
   // mesh lands in the FIRST segment, where the next fused kernel fills the chip behind its ragged last round.  (Four rounds:
@@ -255,14 +245,9 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
     no2[j] = G.h_node_off[j] = M.h_node_off[i];
   }
   G.nrows = nn;
-  auto up = [](uint32_t **dst, const std::vector<uint32_t> &v) -> int {
-    HIPCHK(hipMalloc((void **)dst, sizeof(uint32_t) * (v.size() ? v.size() : 1)));
-    if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice));
-    return 0;
-  };
-  CHK(up(&G.d_rowptr, rp2)); CHK(up(&G.d_cols, cols2)); CHK(up(&G.d_node_off, no2));
+  CHK(G.d_rowptr.upload(r->ceed, rp2)); CHK(G.d_cols.upload(r->ceed, cols2)); CHK(G.d_node_off.upload(r->ceed, no2));
   G.built = true;
-  r->pipes.push_back(Gp);
-  *out = Gp;
+  *out = Gp.get();
+  r->pipes.push_back(std::move(Gp));
   return 0;
 }

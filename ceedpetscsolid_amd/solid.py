@@ -376,6 +376,8 @@ class SolidProblem:
         return smooth_displacement(self.levels[self.fine].dofmap.node_coords, amplitude, origin, span)
 
     def destroy(self):
+        """Destroys every object of the problem; an object the caller has destroyed already holds a null handle, which is skipped
+        (tests/test_object_lifetime_gpu.py takes operators and restrictions away first)."""
         for lv in self.levels:
             for o in (lv.opJacob, lv.opProlong, lv.opRestrict, lv.qfJacob, lv.Erestrictu, lv.basisu, lv.basisCtoF,
                       lv.xceed, lv.yceed, lv.multinv):
