@@ -25,6 +25,7 @@ from ceedpetscsolid_amd.mesh import box_mesh
 from ceedpetscsolid_amd.postprocess import DIAG_FIELDS, Diagnostics, StrainEnergy
 from ceedpetscsolid_amd.solid import SolidProblem
 from _numbering import NUMBERINGS, PRESET, UNREAD, problem_under, referenced
+from _physics_states import STRETCHES as BRANCHES, det_c_minus_1, errors, on_its_side
 from test_gpu_parity import _forcing_and_true_operator, distorted_box
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,6 @@ PQ = [(P, Q) for P in range(2, 9) for Q in (P, P + 1, P + 2) if Q <= 8]
 MESHES = {"eight": lambda: distorted_box(2, 2, 2, seed=3, amp=0.2),      # every vertex moved: neither affine nor swept
           "one": lambda: distorted_box(1, 1, 1, seed=3, amp=0.2)}
 STRETCH = 0.1                                     # u = STRETCH * x: grad u = STRETCH * I exactly, on any mesh (det C - 1 = 0.77: the right-hand shift)
-LEFT, RIGHT = np.sqrt(2.0) / 2 - 1, np.sqrt(2.0) - 1      # the range shifts of log1p_series_shifted (hyperFS.h:45-67), in det C - 1
 
 
 def energy_kernel(physics):
@@ -81,14 +81,6 @@ def report():
     path = os.environ.get("CPS_COORD_ENERGY_REPORT")
     if path:
         RECORD.write(path)
-
-
-def errors(got, want):
-    got, want = np.atleast_1d(np.asarray(got, dtype=np.float64)), np.atleast_1d(np.asarray(want, dtype=np.float64))
-    assert got.shape == want.shape and np.isfinite(got).all() and np.isfinite(want).all()
-    n2, ninf = np.linalg.norm(want), np.abs(want).max()
-    assert n2 > 0
-    return np.linalg.norm(got - want) / n2, np.abs(got - want).max() / ninf
 
 
 def _hold(table, key, what, got, want, tol):
@@ -229,26 +221,6 @@ def test_true_solution_and_diagnostics_at_every_P(oracle, gpu, meshname, P):
 # --------------------------------------------------------------------------------------------------------------------------------
 # the branches of the energy kernel's log series (kernels_coord.hip holds its own copy of it)
 # --------------------------------------------------------------------------------------------------------------------------------
-def det_c_minus_1(p, u):
-    """det C - 1 at every quadrature point of problem `p` (the oracle's) under displacement u, in numpy from the oracle's q-data and
-    basis tables: grad u = sum_m du/dxi_m dXdx[m][.], C = F^T F."""
-    lv = p.levels[-1]
-    B, G = lv.basisu.interp1d, lv.basisu.grad1d                       # [Q][P]
-    Pn, ne = lv.degree + 1, p.mesh.nelem
-    U = u.reshape(-1, 3)[lv.dofmap.elem_nodes].reshape(ne, Pn, Pn, Pn, 3)      # [e][z][y][x][component]
-    dU = np.stack([np.einsum("kc,jb,ia,ecbav->ekjiv", *tabs, U) for tabs in ((B, B, G), (B, G, B), (G, B, B))], axis=-1)   # [..][v][m]
-    dXdx = p.qdata.to_numpy().reshape(ne, 10, -1)[:, 1:, :].reshape(ne, 3, 3, -1)          # [e][m][k][q]
-    g = np.einsum("eqvm,emkq->eqvk", dU.reshape(ne, -1, 3, 3), dXdx)
-    return np.linalg.det(np.eye(3) + g) ** 2 - 1
-
-
-BRANCHES = [(-0.25, "left"), (-0.06, "left"), (-0.05, "middle"), (0.059, "middle"), (0.06, "right"), (0.3, "right")]
-
-
-def on_its_side(x, branch):
-    return np.all(x < LEFT) if branch == "left" else (np.all(x > RIGHT) if branch == "right" else np.all((x >= LEFT) & (x <= RIGHT)))
-
-
 @pytest.mark.parametrize("s,branch", BRANCHES, ids=[f"s={s}-{b}" for s, b in BRANCHES])
 def test_log_series_branches_of_the_energy_kernel(oracle, gpu, s, branch):
     """u = s x plus a small smooth part (grad u no multiple of the identity) takes det C - 1 = (1 + s)^6 - 1 to either side of both
