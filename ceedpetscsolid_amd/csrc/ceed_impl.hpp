@@ -3,6 +3,7 @@
 // with ceed_op_fused.cpp and ceed_op_other.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
 // Every device array one of these objects owns is a DevArray (dev_array.hpp): allocated under the object's Ceed, gone with the member,
 // through ceed_retire.  The one exception is a vector's host / device mirrors, which may be borrowed (ceed_core.cpp).
+// Every transpose map is a RowMap (CsrMap, PipeMap); an operator keeps its Dirichlet flags per RowMap in ONE cache (row_flags).
 // Nothing here is part of the ABI: include/ceed.h is.
 #pragma once
 #include <ceed.h>
@@ -129,28 +130,30 @@ struct CeedVector_private {
   double derived_nu = 0., derived_E = 0.;   // the material the derived state was formed with
 };
 
+// The rows of a transpose map as k_assemble reads them: per row a node offset and the E-vector positions of the node's contributors in
+// element order.  Whatever only sums or flags rows (assemble_rows, make_row_flags, get_pack_fold) takes this.
+struct RowMap {
+  std::vector<uint32_t> h_node_off;        // host copy (the Dirichlet flags and the pack folds of an operator are derived from it)
+  DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
+  int nrows = 0;
+  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nrows, 0}; }
+};
 // Transpose map of an offsets restriction: distinct node offsets and, per node, the E-vector
 // positions (e*elemsize + n) of its contributors in element order.  Rows [0, nprio) are the
 // "priority" nodes when the map was built with a priority mask (split-phase apply).
-struct CsrMap {
+struct CsrMap : RowMap {
   bool built = false, full_cover = false;
-  int nnodes = 0, nprio = 0, nskipped = 0;
-  std::vector<uint32_t> h_node_off, h_rowptr, h_cols;   // host copies (the re-ordered maps are derived from them)
-  DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
-  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nnodes, 0}; }
+  int nprio = 0, nskipped = 0;
+  std::vector<uint32_t> h_rowptr, h_cols;  // host copies (the re-ordered maps are derived from them)
 };
-
 // The transpose map re-ordered for the PIPELINED assembly: the apply is cut into segments of consecutive elements, one
 // launch of the fused kernel each; a row (node) belongs to the segment of its LAST contributor, rows are sorted by segment,
 // and the rows of segment k are summed by their own k_assemble launch beside the fused kernel of segment k + 1.
-struct PipeMap {
-  bool built = false;
-  int nseg = 0, req_seg = 0, E = 0, waves = 0, nrows = 0, mb = 0;
-  const void *base = nullptr;              // the CsrMap it was derived from
-  std::vector<int> elem_bound, row_bound;  // nseg + 1 each
-  std::vector<uint32_t> h_node_off;        // re-ordered (for the per-operator Dirichlet flags)
-  DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
-  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nrows, 0}; }
+struct PipeMap : RowMap {
+  int E = 0, req_seg = 0, waves = 0, mb = 0;   // the key (get_pipe), with ...
+  const CsrMap *base = nullptr;                // ... the map it was derived from
+  int nseg = 0;                                // 1: too small to pipeline, no rows
+  std::vector<int> elem_bound, row_bound;      // nseg + 1 each
 };
 
 struct CeedElemRestriction_private {
@@ -218,12 +221,9 @@ struct CeedOperator_private {
   // Dirichlet flags (op_free_flags drops them all)
   DevArray<uint32_t> d_off_flagged;             // the offsets with the flag bits of their nodes: the active restriction's; of a transfer, the
                                                 // COARSE side's (input of a prolongation, output of a restriction) -- one array either way
-  DevArray<unsigned char> d_node_flags;         // per node of the restriction's transpose map
-  DevArray<unsigned char> d_node_flags_ovl;     // per node of the operator's own (priority-first) map
-  DevArray<unsigned char> d_node_flags_shell;   // per node of the restriction's shell map (direct-store mode)
-  std::vector<std::pair<const PipeMap *, DevArray<unsigned char>>> pipe_flags;   // per row of a pipelined map of the restriction
+  std::vector<std::pair<const RowMap *, DevArray<unsigned char>>> row_flags;   // per row of every map this operator has summed under its mask (op_row_flags)
   // pack of a halo exchange folded into the rows' launch: per (transpose map, halo) the rows' send slots (HaloPackFold)
-  struct PackFold { const CsrMap *M; CeedXHalo H; long serial; DevArray<uint32_t> d_ptr, d_slot; bool ok; };
+  struct PackFold { const RowMap *M; CeedXHalo H; long serial; DevArray<uint32_t> d_ptr, d_slot; bool ok; };
   std::vector<PackFold> pack_folds;
   std::vector<unsigned char> h_mask;      // copy of the output mask (node flags are derived lazily)
   int mask_mode = 0;

@@ -34,13 +34,27 @@ struct FusedApply {
   CeedVector derived_for = nullptr;        // residual applies: the state vector whose derived state this apply writes
   double *py = nullptr;
   const CsrMap *M = nullptr;               // the transpose map of this apply (restriction's, shell, or the operator's split map)
-  const unsigned char *flags = nullptr;    // Dirichlet flags per row of M (null: none)
+  const RowMap *rows = nullptr;            // the rows it sums: M's, or (apply_fused) those of M's pipelined re-ordering
+  const unsigned char *flags = nullptr;    // Dirichlet flags per row of `rows` (null: none)
 };
 // the Dirichlet flags of the operator's mask in the row order of a transpose map
-static int make_row_flags(CeedOperator op, CeedElemRestriction r, const std::vector<uint32_t> &node_off, DevArray<unsigned char> &d) {
-  std::vector<unsigned char> fl(node_off.size(), 0);
-  for (size_t i = 0; i < node_off.size(); i++) fl[i] = (unsigned char)node_flag_bits(op->h_mask.data(), node_off[i], r);
+static int make_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, DevArray<unsigned char> &d) {
+  std::vector<unsigned char> fl(M.h_node_off.size(), 0);
+  for (size_t i = 0; i < fl.size(); i++) fl[i] = (unsigned char)node_flag_bits(op->h_mask.data(), M.h_node_off[i], r);
   return d.upload(op->ceed, fl);
+}
+// The same as an apply reads them (*flags null: no mask, or none on the output side): ONE cache per operator, keyed by the map.  Like
+// every lazily built array of this layer they are made by an eager apply only, never while a graph is recorded.
+static int op_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, const unsigned char **flags) {
+  *flags = nullptr;
+  if (op->h_mask.empty() || !(op->mask_mode & 2)) return 0;
+  for (auto &e : op->row_flags) if (e.first == &M) { *flags = e.second.get(); return 0; }
+  if (op->ceed->capturing) return ceed_error("apply the operator once before recording (Dirichlet row flags)");
+  DevArray<unsigned char> d;
+  CHK(make_row_flags(op, r, M, d));
+  *flags = d.get();
+  op->row_flags.emplace_back(&M, std::move(d));
+  return 0;
 }
 // vectors, tables, geometry provenance, physics, transpose map, flags, scratch: the launch arguments of this apply
 static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool add, bool split, FusedApply &F) {
@@ -105,7 +119,6 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     }
   }
   lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
-  a.waves_per_cu = c->opt.pencil_waves;
   if (split && (add || op->ovl_lead <= 0 || !op->ovl_csr.built))
     return ceed_error("split-phase apply needs CeedXOperatorSetOverlapSplit and overwrite mode");
   a.elem_begin = 0; a.nelem = r->nelem;
@@ -113,20 +126,19 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
   F.direct = !add && c->opt.direct_interior && rstr_interior_private(r, ai.basis->P1d);
   a.direct = F.direct ? 1 : 0;
   // atomic-free, deterministic scatter: element results -> E-vector -> per-node sums
-  DevArray<unsigned char> *flagsp;
   if (split) {
-    F.M = &op->ovl_csr; flagsp = &op->d_node_flags_ovl;
+    F.M = &op->ovl_csr;
     if ((F.M->nskipped > 0) != F.direct) return ceed_error("split-phase map and direct-store mode disagree");
   } else if (F.direct) {
     CHK(build_csr(r, r->csr_shell, nullptr, ai.basis->P1d));
     CHK(build_interior_list(r, ai.basis->P1d));
-    F.M = &r->csr_shell; flagsp = &op->d_node_flags_shell;
+    F.M = &r->csr_shell;
   } else {
     CHK(build_csr(r, r->csr, nullptr));
-    F.M = &r->csr; flagsp = &op->d_node_flags;
+    F.M = &r->csr;
   }
-  if (!*flagsp && !op->h_mask.empty()) CHK(make_row_flags(op, r, F.M->h_node_off, *flagsp));
-  F.flags = (op->mask_mode & 2) ? flagsp->get() : nullptr;
+  F.rows = F.M;
+  CHK(op_row_flags(op, r, *F.rows, &F.flags));
   a.evec_stride = 3 * (F.direct ? element_shell_size(ai.basis->P1d) : r->elemsize);
   CHK(ceed_need_evec(c, (size_t)r->nelem * std::max((size_t)3 * (size_t)r->elemsize, (size_t)a.evec_stride)));   // (an aligned shell block may exceed P^3 records at small P)
   a.evec = c->evec.get();
@@ -140,29 +152,30 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
 // one launch of the fused kernel over elements [e0, e0 + ne); its name and how it obtained the geometric factors stay on the operator
 static int fused_launch(CeedOperator op, const FusedApply &F, int e0, int ne, int wave_groups, hipStream_t s) {
   FusedGradArgs ak = F.a;
-  ak.elem_begin = e0; ak.nelem = ne; ak.wave_groups = wave_groups;
+  ak.elem_begin = e0; ak.nelem = ne;
   const char *kname = "";
-  hipError_t e = launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, ak, s, &kname);
+  hipError_t e = launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, ak, FusedLaunch{wave_groups, op->ceed->opt.pencil_waves}, s, &kname);
   if (no_kernel(e, kname))
     return ceed_error("no fused kernel instantiated for P=%d Q=%d QFunction %s", F.b->P1d, F.b->Q1d, op->qf->name.c_str());
   HIPCHK(e);
   set_kernel_name(op, kname, true);
-  op->geo_mode = F.a.geo_aff && F.a.geo ? 2 : (F.a.geo_swept && F.a.geo ? 3 : (F.a.geo ? 1 : 0));
+  op->geo_mode = fused_geo_mode(F.a);
   return 0;
 }
+// rows [row0, row0 + nrows) of the apply's row map summed into y: the one k_assemble launch of the serial, split-phase and pipelined forms
 static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s, const HaloUnpackArgs *un = nullptr,
                          const HaloPackFold *pk = nullptr) {
-  HIPCHK(launch_assemble(F.M->view().rows(row0, nrows), F.flags, F.a.evec, F.py, F.add ? 1 : 0, s, un, pk));
+  HIPCHK(launch_assemble(F.rows->view().rows(row0, nrows), F.flags, F.a.evec, F.py, F.add ? 1 : 0, s, un, pk));
   return 0;
 }
 // The pack of halo H folded into the launch that sums the rows of map M: per row the send slots of its node's entries.
 // Built once per (map, halo); not ok (-> the separate pack kernel) if an entry of the halo is no row of the map.
-static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const CsrMap *M, CeedXHalo H, HaloPackFold *out, bool *ok) {
+static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const RowMap *M, CeedXHalo H, HaloPackFold *out, bool *ok) {
   for (auto &pf : op->pack_folds)
     if (pf.M == M && pf.H == H && pf.serial == H->serial) { *ok = pf.ok; *out = HaloPackFold{pf.d_ptr.get(), pf.d_slot.get(), H->send.get()}; return 0; }
   CeedOperator_private::PackFold pf{M, H, H->serial, {}, {}, false};
   if (op->ceed->capturing) { *ok = false; return 0; }     // cold while recording: the separate pack kernel
-  const int nn = M->nnodes;
+  const int nn = M->nrows;
   bool good = r->ncomp == 3 && r->compstride == 1 && (size_t)H->total < (1u << 30);
   std::vector<uint32_t> ptr((size_t)nn + 1, 0u), slot((size_t)(H->total ? H->total : 1));
   if (good) {
@@ -215,19 +228,8 @@ static int seg_event(Ceed c, int k, hipEvent_t *ev) {
 // segment k + 1 sits in the other queue and fills the chip as the waves of segment k retire (no kernel boundary between
 // fused kernels), every k_assemble but the last runs beside a fused kernel.  Every row is summed in contributor order by
 // one thread, whatever the segment: bitwise the serial result.
-static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM) {
+static int apply_pipelined(CeedOperator op, const FusedApply &F, const PipeMap *PM) {
   Ceed c = op->ceed;
-  const unsigned char *fl = nullptr;
-  if ((op->mask_mode & 2) && !op->h_mask.empty()) {   // Dirichlet flags in this map's row order (made once per map)
-    for (auto &pf : op->pipe_flags) if (pf.first == PM) fl = pf.second.get();
-    if (!fl) {
-      if (c->capturing) return ceed_error("apply the operator once before recording (Dirichlet flags of the pipelined map)");
-      DevArray<unsigned char> d;
-      CHK(make_row_flags(op, F.r, PM->h_node_off, d));
-      fl = d.get();
-      op->pipe_flags.emplace_back(PM, std::move(d));
-    }
-  }
   const int nseg = PM->nseg;
   set_launch_info(op, nseg, 2, nseg, PM->elem_bound[nseg] - PM->elem_bound[nseg - 1]);
   CHK(side_fork(c));
@@ -240,22 +242,17 @@ static int apply_pipelined(CeedOperator op, const FusedApply &F, PipeMap *PM) {
     CHK(seg_event(c, k, &ev));
     HIPCHK(hipEventRecord(ev, sk));
     if (k >= 1) HIPCHK(hipStreamWaitEvent(sk, ev_before, 0));
-    const int r0 = PM->row_bound[k], nr = PM->row_bound[k + 1] - r0;
-    HIPCHK(launch_assemble(PM->view().rows(r0, nr), fl, F.a.evec, F.py, 0, sk));
+    CHK(assemble_rows(F, PM->row_bound[k], PM->row_bound[k + 1] - PM->row_bound[k], sk));
   }
   return side_join(c);
 }
 
 // The segments of the pipelined form for a whole apply (get_pipe): from the persistent waves of a full launch of THIS kernel
-// (LDS-limited from Q = 6 on), the E-vector records per element and the MB of E-vector per segment.  *PM null or of one
-// segment: the serial form.
+// (pencil_waves_per_cu: LDS-limited from Q = 6 on), the E-vector records per element and the MB of E-vector per segment.  *PM null or
+// of one segment: the serial form.
 static int choose_pipe(CeedOperator op, const FusedApply &F, PipeMap **PM) {
   Ceed c = op->ceed;
-  int waves = 0;
-  FusedGradArgs aq = F.a;
-  aq.query_waves = &waves;
-  const char *nm = "";
-  HIPCHK(launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, aq, c->stream, &nm));
+  const int waves = device_cu_count() * (c->opt.pencil_waves > 0 ? c->opt.pencil_waves : pencil_waves_per_cu(F.b->Q1d));
   if (waves <= 0) return ceed_error("pipelined assembly: no persistent-wave count for P=%d Q=%d", F.b->P1d, F.b->Q1d);
   const int per_elem = F.direct ? element_shell_size(F.b->P1d) : F.r->elemsize;
   const bool fs = F.qfkind == QF_HYPERFS_DF || F.qfkind == QF_HYPERFS_DF_DS || F.qfkind == QF_HYPERFS_F;
@@ -279,47 +276,41 @@ int apply_fused(CeedOperator op, CeedVector in, CeedVector out, bool add, CeedXH
   hipStream_t s = c->stream;
   FusedApply F;
   CHK(fused_prepare(op, in, out, add, false, F));
-  const CsrMap *M = F.M;
-  if (!add && !M->full_cover) CHK(dev_zero(c, F.py, (size_t)out->length));
-  TimerScope ts(op, s);
-  // pipelined assembly: whole applies in overwrite mode, large enough for two segments
+  // pipelined assembly: whole applies in overwrite mode, large enough for two segments -- the rows summed are then the pipelined map's
   PipeMap *PM = nullptr;
   if (c->opt.pipe_segments != 0 && !add) CHK(choose_pipe(op, F, &PM));
+  if (PM && PM->nseg >= 2) { F.rows = PM; CHK(op_row_flags(op, F.r, *PM, &F.flags)); } else PM = nullptr;
+  if (!add && !F.M->full_cover) CHK(dev_zero(c, F.py, (size_t)out->length));
+  TimerScope ts(op, s);
   bool folded = false;
-  if (PM && PM->nseg >= 2) CHK(apply_pipelined(op, F, PM));
+  if (PM) CHK(apply_pipelined(op, F, PM));
   else {
     set_launch_info(op, 1, 1, 1, F.r->nelem);
     CHK(fused_launch(op, F, 0, F.r->nelem, 0, s));
     HaloPackFold pk{nullptr, nullptr, nullptr};
-    if (H && c->opt.fold_pack) CHK(get_pack_fold(op, F.r, M, H, &pk, &folded));
-    CHK(assemble_rows(F, 0, M->nnodes, s, nullptr, folded ? &pk : nullptr));   // timed together with the fused kernel: the launches ARE the operator apply
+    if (H && c->opt.fold_pack) CHK(get_pack_fold(op, F.r, F.M, H, &pk, &folded));
+    CHK(assemble_rows(F, 0, F.M->nrows, s, nullptr, folded ? &pk : nullptr));   // timed together with the fused kernel: the launches ARE the operator apply
   }
   if (H) CHK(halo_sum_behind(H, F.py, folded, s));
   op->launches++;
   return 0;
 }
 
-// The two halves of a split-phase apply (CeedXOperatorApplyPhase), one after the other on the Ceed's stream: the leading elements and
-// the priority rows they alone contribute to, then the other elements and the other rows.
-static int fused_phase(CeedOperator op, const FusedApply &F, int e0, int ne, int row0, int nrows) {
+// One half of a split-phase apply (CeedXOperatorApplyPhase) on the Ceed's stream: phase 0 the leading elements and the priority rows they
+// alone contribute to, phase 1 the other elements and the other rows.
+static int apply_fused_phase(CeedOperator op, CeedVector in, CeedVector out, int phase) {
   hipStream_t s = op->ceed->stream;
+  FusedApply F;
+  CHK(fused_prepare(op, in, out, false, true, F));
+  if (phase == 0 && !F.M->full_cover) CHK(dev_zero(op->ceed, F.py, (size_t)out->length));
+  const int e0 = phase ? op->ovl_lead : 0, ne = phase ? F.r->nelem - op->ovl_lead : op->ovl_lead;
+  const int row0 = phase ? F.M->nprio : 0, nrows = phase ? F.M->nrows - F.M->nprio : F.M->nprio;
   TimerScope ts(op, s);
   CHK(fused_launch(op, F, e0, ne, 0, s));
   CHK(assemble_rows(F, row0, nrows, s));
   set_launch_info(op, 1, 1, 1, ne);
   op->launches++;
   return 0;
-}
-static int apply_fused_phase0(CeedOperator op, CeedVector in, CeedVector out) {
-  FusedApply F;
-  CHK(fused_prepare(op, in, out, false, true, F));
-  if (!F.M->full_cover) CHK(dev_zero(op->ceed, F.py, (size_t)out->length));
-  return fused_phase(op, F, 0, op->ovl_lead, 0, F.M->nprio);
-}
-static int apply_fused_phase1(CeedOperator op, CeedVector in, CeedVector out) {
-  FusedApply F;
-  CHK(fused_prepare(op, in, out, false, true, F));
-  return fused_phase(op, F, op->ovl_lead, F.r->nelem - op->ovl_lead, F.M->nprio, F.M->nnodes - F.M->nprio);
 }
 
 // The apply with its consumer fused behind it (CeedXOperatorApplyChebyshev / ApplyResidual): the launches of a whole apply in
@@ -361,8 +352,6 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
   hipStream_t s = c->stream;
   FusedApply F;
   CHK(fused_prepare(op, in, out, false, true, F));
-  if (H->in_flight) return ceed_error("CeedXOperatorApplyWithHalo: an exchange is already in flight");
-  if (out->length < H->lsize_min) return ceed_error("CeedXOperatorApplyWithHalo: vector shorter than the halo's indices");
   const CsrMap *M = F.M;
   const int lead = op->ovl_lead, rest = F.r->nelem - lead;
   // Contract of this form: the arrivals are added by the SAME launch that overwrites the non-priority rows, and
@@ -388,7 +377,7 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
     CHK(halo_pack_and_send(H, F.py, s));
     CHK(fused_launch(op, F, lead, rest, 0, s));
     CHK(halo_wait_arrivals(H, s));
-    CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s, &un));
+    CHK(assemble_rows(F, M->nprio, M->nrows - M->nprio, s, &un));
     op->launches++;
     return 0;
   }
@@ -403,7 +392,7 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
   CHK(halo_pack_and_send(H, F.py, s));
   HIPCHK(hipStreamWaitEvent(s1, lead_done, 0));
   CHK(halo_wait_arrivals(H, s1));
-  CHK(assemble_rows(F, M->nprio, M->nnodes - M->nprio, s1, &un));
+  CHK(assemble_rows(F, M->nprio, M->nrows - M->nprio, s1, &un));
   CHK(side_join(c));
   op->launches++;
   return 0;
@@ -420,7 +409,8 @@ extern "C" int CeedXOperatorSetOverlapSplit(CeedOperator op, CeedInt n_leading_e
   op->ovl_csr = CsrMap();     // a map not built, its counts and host copies reset with it (every reader asks `built` first); recorded
                               // graphs may still read the old split map and its flags: both are DevArrays
   op->ovl_halo_checked = 0;
-  op->d_node_flags_ovl.release();
+  op->row_flags.erase(std::remove_if(op->row_flags.begin(), op->row_flags.end(), [&](const auto &e) { return e.first == &op->ovl_csr; }),
+                      op->row_flags.end());     // (same address, new content)
   op->ovl_lead = 0;
   if (!priority) return 0;
   if (lsize < r->lsize || n_leading_elems < 0 || n_leading_elems > r->nelem) return ceed_error("bad overlap split arguments");
@@ -437,7 +427,7 @@ extern "C" int CeedXOperatorSetOverlapSplit(CeedOperator op, CeedInt n_leading_e
 extern "C" int CeedXOperatorApplyPhase(CeedOperator op, CeedVector in, CeedVector out, int phase) {
   CHK(need_fused(op, "split-phase apply", Kind::either));
   if (phase != 0 && phase != 1) return ceed_error("bad split-phase apply");
-  return phase == 0 ? apply_fused_phase0(op, in, out) : apply_fused_phase1(op, in, out);
+  return apply_fused_phase(op, in, out, phase);
 }
 
 // The split-phase apply and the interface sum of its output in ONE call: phase 0, the exchange started, phase 1 beside it,
@@ -445,21 +435,19 @@ extern "C" int CeedXOperatorApplyPhase(CeedOperator op, CeedVector in, CeedVecto
 extern "C" int CeedXOperatorApplyWithHalo(CeedOperator op, CeedVector in, CeedVector out, CeedXHalo halo) {
   CHK(need_fused(op, "split-phase apply", Kind::any));
   if (!halo || halo->nb.empty()) return CeedOperatorApply(op, in, out, CEED_REQUEST_IMMEDIATE);
-  // Default (CeedOptions::ovl_mode 0): the whole apply, then pack / RCCL group / unpack-add, IN ORDER on the Ceed's stream.
-  // Measured on the emulated rank 3 of 8 (DESIGN.md 5): 13 200 hexes at p = 4 -- split-phase on two streams 119 us, split-phase on
-  // one stream 112 us, whole apply + exchange through the communicator's stream 120 us; a hand-over between two streams costs
-  // more than the exchange it would hide.
-  // (while a graph is recorded always this form: RCCL's calls record correctly only in order on the capturing stream)
-  if (op->plan == PLAN_FUSED_GRAD && (op->ceed->opt.ovl_mode == 0 || op->ceed->capturing || op->ovl_lead <= 0 || !op->ovl_csr.built)) {
-    if (halo->in_flight) return ceed_error("CeedXOperatorApplyWithHalo: an exchange is already in flight");
-    if (out->length < halo->lsize_min) return ceed_error("CeedXOperatorApplyWithHalo: vector shorter than the halo's indices");
-    return apply_fused(op, in, out, false, halo);
-  }
   if (op->plan != PLAN_FUSED_GRAD) {
     CHK(CeedOperatorApply(op, in, out, CEED_REQUEST_IMMEDIATE));
     CHK(CeedXHaloStart(halo, out));
     return CeedXHaloFinish(halo, out);
   }
+  if (halo->in_flight) return ceed_error("CeedXOperatorApplyWithHalo: an exchange is already in flight");
+  if (is_passive(out) && out->length < halo->lsize_min) return ceed_error("CeedXOperatorApplyWithHalo: vector shorter than the halo's indices");
+  // Default (CeedOptions::ovl_mode 0): the whole apply, then pack / RCCL group / unpack-add, IN ORDER on the Ceed's stream.
+  // Measured on the emulated rank 3 of 8 (DESIGN.md 5): 13 200 hexes at p = 4 -- split-phase on two streams 119 us, split-phase on
+  // one stream 112 us, whole apply + exchange through the communicator's stream 120 us; a hand-over between two streams costs
+  // more than the exchange it would hide.
+  // (while a graph is recorded always this form: RCCL's calls record correctly only in order on the capturing stream)
+  if (op->ceed->opt.ovl_mode == 0 || op->ceed->capturing || op->ovl_lead <= 0 || !op->ovl_csr.built) return apply_fused(op, in, out, false, halo);
   return apply_fused_with_halo(op, in, out, halo);
 }
 

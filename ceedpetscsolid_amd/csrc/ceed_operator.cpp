@@ -56,8 +56,7 @@ extern "C" int CeedOperatorSetField(CeedOperator op, const char *name, CeedElemR
 // everything derived from the Dirichlet mask (recorded graphs may still read the arrays: they are DevArrays)
 static void op_free_flags(CeedOperator o) {
   o->d_off_flagged.release(); o->d_own_f.release();
-  o->d_node_flags.release(); o->d_node_flags_ovl.release(); o->d_node_flags_shell.release();
-  o->pipe_flags.clear(); o->h_mask.clear(); o->h_mask_fine.clear();
+  o->row_flags.clear(); o->h_mask.clear(); o->h_mask_fine.clear();
   o->mask_mode = 0;
 }
 extern "C" int CeedOperatorDestroy(CeedOperator *op) {

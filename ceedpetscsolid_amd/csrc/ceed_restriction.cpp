@@ -127,7 +127,7 @@ int build_csr(CeedElemRestriction r, CsrMap &M, const unsigned char *prio, int s
     const size_t e = i / (size_t)r->elemsize; const int ln = (int)(i % (size_t)r->elemsize);
     cols[cursor[sl]++] = skipP > 0 ? (uint32_t)(e * (size_t)element_shell_size(skipP) + (size_t)node_shell_rank(ln, skipP)) : (uint32_t)i;
   }
-  M.nnodes = nn;
+  M.nrows = nn;
   // every L-vector entry is written by the assembly (or, for the skipped nodes, by the fused kernel)
   M.full_cover = ((size_t)nn + (size_t)M.nskipped) * (size_t)r->ncomp == (size_t)r->lsize;
   CHK(M.d_rowptr.upload(r->ceed, rowptr)); CHK(M.d_cols.upload(r->ceed, cols)); CHK(M.d_node_off.upload(r->ceed, M.h_node_off));
@@ -173,7 +173,7 @@ int build_interior_list(CeedElemRestriction r, int P) {
 // the same restriction, keeps valid pointers.  A launch too small to pipeline gets a map with nseg = 1 and NO copies.
 int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int req_seg_in, int waves, int mb, PipeMap **out) {
   for (auto &p : r->pipes)
-    if (p->E == E && p->req_seg == req_seg_in && p->waves == waves && p->mb == mb && p->base == (const void *)&M) { *out = p.get(); return 0; }
+    if (p->E == E && p->req_seg == req_seg_in && p->waves == waves && p->mb == mb && p->base == &M) { *out = p.get(); return 0; }
   const CeedOptions &opt = r->ceed->opt;
   int req_seg = req_seg_in;
   const int ngroups = (r->nelem + E - 1) / E;
@@ -194,8 +194,8 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   if (nseg >= 2 && r->ceed->capturing) { *out = nullptr; return 0; }   // cold map while recording: the caller takes the serial path (its map exists)
   std::unique_ptr<PipeMap> Gp(new PipeMap);     // (dropped with its arrays by an error return below)
   PipeMap &G = *Gp;
-  G.E = E; G.req_seg = req_seg_in; G.waves = waves; G.mb = mb; G.base = (const void *)&M;
-  if (nseg < 2) { G.nseg = 1; G.built = true; *out = Gp.get(); r->pipes.push_back(std::move(Gp)); return 0; }
+  G.E = E; G.req_seg = req_seg_in; G.waves = waves; G.mb = mb; G.base = &M;
+  if (nseg < 2) { G.nseg = 1; *out = Gp.get(); r->pipes.push_back(std::move(Gp)); return 0; }
   // Boundaries are laid out FROM THE END in whole rounds of the waves: the last segment (whose rows are summed with nothing
   // to hide behind) is `last_rounds` rounds, the others share the rest equally in whole rounds, and the odd remainder of the
   // mesh lands in the FIRST segment, where the next fused kernel fills the chip behind its ragged last round.  (Four rounds:
@@ -223,7 +223,7 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   G.elem_bound.push_back(r->nelem);
   nseg = (int)G.elem_bound.size() - 1;
   G.nseg = nseg;
-  const int nn = M.nnodes;
+  const int nn = M.nrows;
   const std::vector<uint32_t> &rowptr = M.h_rowptr, &cols = M.h_cols;
   std::vector<int> seg((size_t)nn);
   std::vector<uint32_t> cnt((size_t)nseg + 1, 0u);
@@ -246,7 +246,6 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   }
   G.nrows = nn;
   CHK(G.d_rowptr.upload(r->ceed, rp2)); CHK(G.d_cols.upload(r->ceed, cols2)); CHK(G.d_node_off.upload(r->ceed, no2));
-  G.built = true;
   *out = Gp.get();
   r->pipes.push_back(std::move(Gp));
   return 0;

@@ -267,8 +267,6 @@ CPS_DEV void pencil_pass(ktab_t table, const ldsp_t (&addr)[R], int lane, int nt
   } else pencil_pass_impl<NIN, NOUT, LD, TR, SB, SRC, DST, SGN, EO, R>(table, addr, lane, ntask);
 }
 
-constexpr int PENCIL_MINW = 2;   // waves per SIMD the register allocation is held to (256 VGPRs), at every Q (a Q = 5 value of its
-                                 // own: profiles/r05_ab_experiments.txt item 13)
 constexpr int PENCIL_NSET = 2;   // q-point register sets: 2 = every round's data is requested two rounds ahead
                                  // (198 VGPRs with the hyperFS tangent; 1 set: 4-6 % slower; 3 sets: no gain; profiles/r04_ab_experiments.txt
                                  // item 10).  Q >= 6: two sets as well since round 4.  Rounds 1-3 had ONE (a second set pushed the hyperFS
@@ -458,7 +456,7 @@ __global__ __launch_bounds__(64, PENCIL_MINW) void k_fused_pencil(const BasisTab
 
 #ifdef CPS_PHASE_TIMING
   int ph_iter = 0;
-  long long *const ph_buf = (long long *)a.query_waves;
+  long long *const ph_buf = a.phase_buf;
 #endif
   for (;;) {
     CPS_PH(0);
@@ -804,40 +802,31 @@ __global__ __launch_bounds__(64, PENCIL_MINW) void k_fused_pencil(const BasisTab
   }
 }
 
-template <int P, int Q> constexpr int pencil_waves_per_cu() {
-  constexpr int by_lds = (160 * 1024) / PencilGeom<P, Q>::LDS_BYTES;
-  return by_lds < 1 ? 1 : (by_lds > 4 * PENCIL_MINW ? 4 * PENCIL_MINW : by_lds);  // 8 waves per CU = 2 per SIMD at <= 256 VGPRs
-}
-
-// Launch shape.  Default: a PERSISTENT grid -- as many one-wave workgroups as the device holds at once (CUs x waves per
-// CU), each walking its strided list of groups with the next group's data requested a group ahead.  `a.wave_groups` > 0
-// (host-side hint, small launches): every wave is given at most that many groups instead and the grid grows accordingly
-// (rounded to whole XCD sets) -- workgroups beyond the resident set are dispatched as earlier ones retire, which balances
-// a launch of a few rounds and gives co-scheduled kernels (the halo exchange's) a slot at every retirement.
+// Launch shape.  Default: a PERSISTENT grid -- as many one-wave workgroups as the device holds at once (CUs x waves per CU), each walking
+// its strided list of groups with the next group's data requested a group ahead.  `l.wave_groups` > 0 (small launches): the grid grows
+// instead (rounded to whole XCD sets) -- workgroups beyond the resident set are dispatched as earlier ones retire, which balances a launch
+// of a few rounds and gives co-scheduled kernels (the halo exchange's) a slot at every retirement.
 template <int P, int Q, int QF>
-hipError_t launch_fused_pencil_t(const BasisTables &t, const FusedGradArgs &a_in, hipStream_t s) {
-  using G = PencilGeom<P, Q>;
-  if (a_in.nelem <= 0 && !a_in.query_waves) return hipSuccess;
-  const int ngroups = (a_in.nelem + G::E - 1) / G::E;
-  const int ncu = device_cu_count();
+hipError_t launch_fused_pencil_t(const BasisTables &t, const FusedGradArgs &a_in, FusedLaunch l, hipStream_t s) {
+  static_assert(PencilGeom<P, Q>::LDS_BYTES == pencil_lds_bytes(Q), "the host sizes the persistent grid from pencil_lds_bytes (kernels.hpp)");
+  if (a_in.nelem <= 0) return hipSuccess;
+  const int ngroups = (a_in.nelem + pencil_group_elems(Q) - 1) / pencil_group_elems(Q), ncu = device_cu_count();
   if (ncu <= 0) return hipErrorUnknown;
-  const int resident = ncu * (a_in.waves_per_cu > 0 ? a_in.waves_per_cu : pencil_waves_per_cu<P, Q>());
-  if (a_in.query_waves) { *a_in.query_waves = resident; return hipSuccess; }
-#ifdef CPS_PHASE_TIMING   // (diagnostic build) the time-stamp buffer rides in the query pointer, which a real launch does not use
+#ifdef CPS_PHASE_TIMING   // (diagnostic build) the time-stamp buffer rides behind the arguments
   FusedGradArgs a = a_in;
-  if (const char *e = getenv("CEED_MI355X_PHASE_BUF")) a.query_waves = (int *)strtoull(e, nullptr, 0);
+  if (const char *e = getenv("CEED_MI355X_PHASE_BUF")) a.phase_buf = (long long *)strtoull(e, nullptr, 0);
 #else
   const FusedGradArgs &a = a_in;
 #endif
-  int grid = resident;
-  if (a.wave_groups > 0) grid = ((ngroups + a.wave_groups - 1) / a.wave_groups + 7) / 8 * 8;
+  int grid = l.wave_groups > 0 ? ((ngroups + l.wave_groups - 1) / l.wave_groups + 7) / 8 * 8 : ncu * (l.waves_per_cu > 0 ? l.waves_per_cu : pencil_waves_per_cu(Q));
   // (A persistent grid SHRUNK so that every wave gets the same number of groups -- 1 650 waves x 4 groups instead of 2 048 x 3.2 at
   // 13 200 hexes -- was measured in round 3: 3 ... 14 % slower at every size from 5 500 to 99 000 hexes.  More waves in flight beat an
   // even finish: profiles/r03_ab_experiments.txt item 11.)
   if (grid > ngroups) grid = ngroups;
-  if (a.geo && a.geo_aff) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 2>), dim3(grid), dim3(64), 0, s, t, a);
-  else if (a.geo && a.geo_swept) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 3>), dim3(grid), dim3(64), 0, s, t, a);
-  else if (a.geo) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 1>), dim3(grid), dim3(64), 0, s, t, a);
+  const int geo = fused_geo_mode(a);
+  if (geo == 2) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 2>), dim3(grid), dim3(64), 0, s, t, a);
+  else if (geo == 3) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 3>), dim3(grid), dim3(64), 0, s, t, a);
+  else if (geo == 1) hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 1>), dim3(grid), dim3(64), 0, s, t, a);
   else hipLaunchKernelGGL((k_fused_pencil<P, Q, QF, 0>), dim3(grid), dim3(64), 0, s, t, a);
   return hipGetLastError();
 }

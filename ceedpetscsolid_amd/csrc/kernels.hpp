@@ -91,11 +91,16 @@ struct FusedGradArgs {
                                // host) are stored straight into y and skip the E-vector round trip; the E-vector then is
                                // [elem][shell node][3] and the transpose map handed to launch_assemble() holds the shell
                                // nodes only, its columns being positions e * element_shell_size(P) + rank
-  // ---- host side only (behind everything the kernels read) ----
-  int wave_groups;            // > 0: every wave is given at most this many groups (grid = groups / wave_groups) instead of
-                               // the persistent grid (launch_fused_pencil_t)
-  int waves_per_cu;           // > 0: persistent waves per CU (tuning hook CEED_MI355X_PENCIL_WAVES)
-  int *query_waves;           // if set, the launcher stores the number of persistent waves a full launch has and launches nothing
+#ifdef CPS_PHASE_TIMING       // (diagnostic build only) the time-stamp buffer, filled in by the launcher from CEED_MI355X_PHASE_BUF
+  long long *phase_buf;
+#endif
+};
+// how a launch obtains the geometric factors (k_fused_pencil's GEO): 0 qdata read, 1 recomputed per point, 2 affine, 3 swept elements
+static inline int fused_geo_mode(const FusedGradArgs &a) { return !a.geo ? 0 : (a.geo_aff ? 2 : (a.geo_swept ? 3 : 1)); }
+// the launch shape of the fused kernel (launch_fused_pencil_t): host side only, none of it reaches the kernel
+struct FusedLaunch {
+  int wave_groups;    // > 0: every wave is given at most this many groups (grid = groups / wave_groups) instead of the persistent grid
+  int waves_per_cu;   // > 0: persistent waves per CU (tuning hook CEED_MI355X_PENCIL_WAVES) instead of pencil_waves_per_cu(Q)
 };
 hipError_t launch_clock_probe(long long *out /* device: shader cycles, 100 MHz ticks */, int spin_us, hipStream_t s);
 // compute units of the current device (one device per process: cached)
@@ -199,8 +204,7 @@ struct StateArgs {
 // Each returns hipSuccess or the launch error; `name` receives a static string
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
-hipError_t launch_fused_grad(int P, int Q, int qf, const BasisTables &t, const FusedGradArgs &a,
-                             hipStream_t s, const char **name);
+hipError_t launch_fused_grad(int P, int Q, int qf, const BasisTables &t, const FusedGradArgs &a, FusedLaunch l, hipStream_t s, const char **name);
 hipError_t launch_transfer(int Pc, int Pf, bool prolong, const BasisTables &t, const TransferArgs &a,
                            hipStream_t s, const char **name);
 hipError_t launch_setup_geo(int Q, const BasisTables &t, const SetupGeoArgs &a, hipStream_t s,
@@ -217,9 +221,16 @@ constexpr int pencil_inst_parts(int Q) { return Q == 8 ? 4 : (Q == 7 ? 2 : 1); }
 // lanes and the 9 Q^3-double LDS slab per element
 // (Q = 5: two; one element per wave was 8-25 % slower, profiles/r03_ab_experiments.txt item 12)
 constexpr int pencil_group_elems(int Q) { return Q <= 2 ? 8 : (Q <= 4 ? 4 : (Q == 5 ? 2 : 1)); }
+// LDS of one wave: PencilGeom<P, Q>::LDS_BYTES, as the launcher asserts.  No P in it: the persistent waves a CU holds -- what its 160 KB of LDS
+// take, at most the 4 x PENCIL_MINW the registers allow -- depend on Q alone, and the host sizes a full launch itself (choose_pipe).
+constexpr int PENCIL_MINW = 2;   // waves per SIMD the register allocation is held to (256 VGPRs), at every Q (a Q = 5 value of its own: profiles/r05_ab_experiments.txt item 13)
+constexpr int pencil_lds_bytes(int Q) { return (pencil_group_elems(Q) * (9 * Q * Q * Q + (Q == 5 ? 5 : 1) + GEO_NCOEF) + 2 * Q) * 8; }
+constexpr int pencil_waves_per_cu(int Q) {   // 1 ... 4 x PENCIL_MINW: 8 waves per CU = 2 per SIMD at <= 256 VGPRs
+  const int by_lds = (160 * 1024) / pencil_lds_bytes(Q); return by_lds < 1 ? 1 : (by_lds > 4 * PENCIL_MINW ? 4 * PENCIL_MINW : by_lds);
+}
 
 // The transpose map of a restriction as the kernels read it: rows [row0, row0 + nnodes) of rowptr / node_off, the contributors
-// of row r being cols[rowptr[r] .. rowptr[r + 1]).  Made from a CsrMap or a PipeMap by their view() (ceed_impl.hpp).
+// of row r being cols[rowptr[r] .. rowptr[r + 1]).  Made by RowMap::view() (ceed_impl.hpp) of whichever map the apply sums.
 struct NodeMap {
   const uint32_t *rowptr, *cols, *node_off;
   int nnodes, row0;

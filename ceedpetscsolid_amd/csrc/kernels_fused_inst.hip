@@ -29,7 +29,7 @@ namespace cps {
   if constexpr ((CPS_Q - (Pv)) % pencil_inst_parts(CPS_Q) == PART) {                \
     if (P == Pv && qf == QFv) {                                                     \
       *name = "fused_grad<P=" #Pv ",Q=" CPS_STR(CPS_Q) "," QFname ">/pencil";       \
-      return launch_fused_pencil_t<Pv, CPS_Q, QFv>(t, a, s);                        \
+      return launch_fused_pencil_t<Pv, CPS_Q, QFv>(t, a, l, s);                     \
     }                                                                               \
   }
 // The derived-state tangent is instantiated where it measured a gain: Q >= 6 (one element per wave; -2.6 ... -3.1 % on config 5's
@@ -54,7 +54,7 @@ namespace cps {
   }
 
 template <int PART>
-static hipError_t dispatch_part(int P, int qf, const BasisTables &t, const FusedGradArgs &a, hipStream_t s, const char **name) {
+static hipError_t dispatch_part(int P, int qf, const BasisTables &t, const FusedGradArgs &a, FusedLaunch l, hipStream_t s, const char **name) {
   CPS_JACOBIANS(CPS_Q)
   CPS_RESIDUALS(CPS_Q)
   // (degrees 6 and 7: the uniform ladders, cloptions.c:195-225 -- every degree below the fine one is a level)
@@ -63,9 +63,9 @@ static hipError_t dispatch_part(int P, int qf, const BasisTables &t, const Fused
 }
 
 hipError_t CPS_CAT(CPS_CAT(CPS_CAT(launch_fused_grad_q, CPS_Q), p), CPS_PART)(int P, int qf, const BasisTables &t, const FusedGradArgs &a,
-                                                                              hipStream_t s, const char **name) {
+                                                                              FusedLaunch l, hipStream_t s, const char **name) {
   static_assert(CPS_PART >= 0 && CPS_PART < pencil_inst_parts(CPS_Q), "part of this quadrature size");
-  return dispatch_part<CPS_PART>(P, qf, t, a, s, name);
+  return dispatch_part<CPS_PART>(P, qf, t, a, l, s, name);
 }
 
 }  // namespace cps
