@@ -85,6 +85,8 @@ extern "C" int CeedInit(const char *resource, Ceed *ceed) {
   o.comm_priority = env_int("CEED_MI355X_COMM_PRIO", o.comm_priority);
   o.comm_inline = env_int("CEED_MI355X_COMM_INLINE", o.comm_inline);
   o.fold_pack = env_int("CEED_MI355X_FOLD_PACK", o.fold_pack);
+  o.row_code = !env_is("CEED_MI355X_ROWMAP", "plain");
+  o.row_code_max = std::max(0, env_int("CEED_MI355X_ROWCODE_MAX", o.row_code_max));
   *ceed = c;
   return 0;
 }

@@ -57,6 +57,9 @@ struct CeedOptions {
   int fold_pack = 1;             // CEED_MI355X_FOLD_PACK=0: the exchange's pack as a launch of its own (A/B)
   int comm_inline = 1;           // CEED_MI355X_COMM_INLINE=0: the exchange's sends / receives on a stream of their own (see halo_pack_and_send)
   int comm_priority = 0;         // CEED_MI355X_COMM_PRIO=1: the exchange on a highest-priority stream -- measured 4x SLOWER (see CeedXCommInit)
+  // the shared-node sum's A/B lever (it retires once the records of profiles/assemble_row_code.txt are confirmed)
+  bool row_code = true;          // CEED_MI355X_ROWMAP=plain: k_assemble walks rowptr / cols for every row (no stencil code is built)
+  int row_code_max = 4096;       // CEED_MI355X_ROWCODE_MAX: stencils a map's table may hold; rows beyond it keep rowptr / cols
 };
 
 // ---------------------------------------------------------------------------
@@ -136,7 +139,16 @@ struct RowMap {
   std::vector<uint32_t> h_node_off;        // host copy (the Dirichlet flags and the pack folds of an operator are derived from it)
   DevArray<uint32_t> d_rowptr, d_cols, d_node_off;
   int nrows = 0;
-  cps::NodeMap view() const { return cps::NodeMap{d_rowptr.get(), d_cols.get(), d_node_off.get(), nrows, 0}; }
+  // the stencil code of the rows (row_code.hpp; upload_row_code, made with the arrays above: never while a graph is recorded) --
+  // rowptr and cols stay: escape rows, the point-block sum and the segment rule of get_pipe read them
+  DevArray<uint32_t> d_pos0, d_stencil;
+  DevArray<uint16_t> d_sid;
+  int nstencils = 0, nescape = 0;
+  cps::NodeMap view() const {
+    cps::NodeMap m{d_rowptr.get(), d_cols.get(), d_node_off.get(), nrows, 0};
+    m.pos0 = d_pos0.get(); m.sid = d_sid.get(); m.stencil = d_stencil.get();
+    return m;
+  }
 };
 // Transpose map of an offsets restriction: distinct node offsets and, per node, the E-vector
 // positions (e*elemsize + n) of its contributors in element order.  Rows [0, nprio) are the
@@ -265,6 +277,7 @@ void vec_drop_geo(CeedVector v);
 
 // restriction maps (ceed_restriction.cpp)
 int build_csr(CeedElemRestriction r, CsrMap &M, const unsigned char *prio, int skipP = 0);
+int upload_row_code(Ceed c, RowMap &M, const std::vector<uint32_t> &rowptr, const std::vector<uint32_t> &cols);
 bool rstr_interior_private(CeedElemRestriction r, int P);
 int build_interior_list(CeedElemRestriction r, int P);
 int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int req_seg, int waves, int mb_per_segment, PipeMap **out);

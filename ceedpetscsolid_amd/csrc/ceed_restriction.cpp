@@ -2,6 +2,7 @@
 // scatter is built on (set-up time, host).  Reference: CreateRestrictionPlex -> CeedElemRestrictionCreate
 // (src/setuplibceed.c:194-240), CeedElemRestrictionCreateStrided with CEED_STRIDES_BACKEND (:304-318).
 #include "ceed_impl.hpp"
+#include "row_code.hpp"
 
 using namespace cps;
 
@@ -86,6 +87,18 @@ extern "C" int CeedElemRestrictionDestroy(CeedElemRestriction *rstr) {
   return 0;
 }
 
+// The stencil code of a map's rows beside the arrays it was made from (row_code.hpp), under the options of the map's Ceed.  Called where a
+// RowMap gets its arrays, so never while a graph is recorded.
+int upload_row_code(Ceed c, RowMap &M, const std::vector<uint32_t> &rowptr, const std::vector<uint32_t> &cols) {
+  if (!c->opt.row_code) return 0;
+  const RowCode code = row_code_encode(rowptr, cols, c->opt.row_code_max);
+  static_assert(sizeof(RowStencil) == 8 * sizeof(uint32_t), "a stencil is uploaded as eight words");
+  CHK(M.d_pos0.upload(c, code.pos0)); CHK(M.d_sid.upload(c, code.sid));
+  CHK(M.d_stencil.upload(c, (const uint32_t *)code.table.data(), code.table.size() * 8));
+  M.nstencils = (int)code.table.size(); M.nescape = (int)code.nescape;
+  return 0;
+}
+
 // Build a transpose map (setup time, host): counting sort over the L-vector.  With `prio`
 // (one byte per L-vector entry, tested at each node's component-0 offset) the flagged nodes
 // come first.
@@ -131,6 +144,7 @@ int build_csr(CeedElemRestriction r, CsrMap &M, const unsigned char *prio, int s
   // every L-vector entry is written by the assembly (or, for the skipped nodes, by the fused kernel)
   M.full_cover = ((size_t)nn + (size_t)M.nskipped) * (size_t)r->ncomp == (size_t)r->lsize;
   CHK(M.d_rowptr.upload(r->ceed, rowptr)); CHK(M.d_cols.upload(r->ceed, cols)); CHK(M.d_node_off.upload(r->ceed, M.h_node_off));
+  CHK(upload_row_code(r->ceed, M, rowptr, cols));
   M.built = true;
   return 0;
 }
@@ -246,6 +260,7 @@ int get_pipe(CeedElemRestriction r, const CsrMap &M, int E, int per_elem, int re
   }
   G.nrows = nn;
   CHK(G.d_rowptr.upload(r->ceed, rp2)); CHK(G.d_cols.upload(r->ceed, cols2)); CHK(G.d_node_off.upload(r->ceed, no2));
+  CHK(upload_row_code(r->ceed, G, rp2, cols2));
   *out = Gp.get();
   r->pipes.push_back(std::move(Gp));
   return 0;

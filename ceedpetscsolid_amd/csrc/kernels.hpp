@@ -231,10 +231,15 @@ constexpr int pencil_waves_per_cu(int Q) {   // 1 ... 4 x PENCIL_MINW: 8 waves p
 
 // The transpose map of a restriction as the kernels read it: rows [row0, row0 + nnodes) of rowptr / node_off, the contributors
 // of row r being cols[rowptr[r] .. rowptr[r + 1]).  Made by RowMap::view() (ceed_impl.hpp) of whichever map the apply sums.
+// The STENCIL CODE of the same rows (row_code.hpp), read by k_assemble and k_assemble_epi in place of rowptr / cols where `sid` is set:
+// contributor j of row r at pos0[r] + distance j of stencil sid[r]; rows with the escape id take rowptr / cols.
 struct NodeMap {
   const uint32_t *rowptr, *cols, *node_off;
   int nnodes, row0;
-  NodeMap rows(int first, int n) const { return NodeMap{rowptr, cols, node_off, n, first}; }
+  const uint32_t *pos0 = nullptr;
+  const uint16_t *sid = nullptr;
+  const uint32_t *stencil = nullptr;     // [stencils][8]: RowStencil
+  NodeMap rows(int first, int n) const { NodeMap m = *this; m.row0 = first; m.nnodes = n; return m; }
 };
 // Deterministic, atomic-free E^T (kernels_assemble.hip): y[node_off[r] + c] (+)= sum over the node's contributors, in element
 // order, of E[3 * cols[k] + c] (cols[k] = e * P3 + n).  `flags` (one byte per node of the whole map, bit c = component c constrained) may be null.

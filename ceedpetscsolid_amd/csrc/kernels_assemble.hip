@@ -22,9 +22,10 @@ __global__ void k_rstr(const uint32_t *off, size_t total, int elemsize, int ncom
 // consecutive 24-byte rows, so the three strided 8-byte accesses of a wave cover whole cache lines.
 // Workgroups [nb_rows, gridDim.x) -- present only with `un.n` > 0 -- add the arrivals of a halo exchange instead
 // (HaloUnpackArgs: different entries of y than any row of this launch).
+// With the stencil code of the rows (rc.sid set) a row is summed by node_sum3_coded.
 __global__ void k_assemble(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off,
                            const unsigned char *flags, const double *evec, double *y, int nnodes, int add, int nb_rows,
-                           const HaloUnpackArgs un, const HaloPackFold pk) {
+                           const HaloUnpackArgs un, const HaloPackFold pk, const RowCodeView rc) {
   // (no wave priority of its own: the row sums at priority 3 beside a fused kernel measured +2 %, profiles/r03_ab_experiments.txt item 15c)
   if ((int)blockIdx.x >= nb_rows) {
     halo_unpack_add(un, y, ((int)blockIdx.x - nb_rows) * blockDim.x + threadIdx.x, ((int)gridDim.x - nb_rows) * blockDim.x);
@@ -32,7 +33,8 @@ __global__ void k_assemble(const uint32_t *rowptr, const uint32_t *cols, const u
   }
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nnodes; r += nb_rows * blockDim.x) {
     double a0 = 0., a1 = 0., a2 = 0.;
-    node_sum3(rowptr, cols, evec, r, a0, a1, a2);
+    if (rc.sid) node_sum3_coded(rc, rowptr, cols, evec, r, a0, a1, a2);
+    else node_sum3(rowptr, cols, evec, r, a0, a1, a2);
     const unsigned fl = flags ? flags[r] : 0u;
     double *dst = y + (node_off[r] & OFF_MASK);
     if (fl & 1u) a0 = 0.;
@@ -57,7 +59,7 @@ __global__ void k_assemble(const uint32_t *rowptr, const uint32_t *cols, const u
 // summed only after the last element that holds its node has finished (pipelined form: rows belong to the segment of their LAST
 // contributor), and no later element gathers it.
 __global__ void k_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, const unsigned char *flags,
-                               const double *evec, int nnodes, int nb_rows, const EpilogueArgs ep) {
+                               const double *evec, int nnodes, int nb_rows, const EpilogueArgs ep, const RowCodeView rc) {
   if ((int)blockIdx.x >= nb_rows) {
     const size_t n = (size_t)ep.n_int * 3;
     for (size_t u = ((size_t)blockIdx.x - nb_rows) * blockDim.x + threadIdx.x; u < n; u += ((size_t)gridDim.x - nb_rows) * blockDim.x) {
@@ -98,7 +100,8 @@ __global__ void k_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, con
     }
     double a0 = 0., a1 = 0., a2 = 0.;
     if (live) {
-      node_sum3(rowptr, cols, evec, r, a0, a1, a2);
+      if (rc.sid) node_sum3_coded(rc, rowptr, cols, evec, r, a0, a1, a2);
+      else node_sum3(rowptr, cols, evec, r, a0, a1, a2);
       const unsigned fl = flags ? flags[r] : 0u;
       if (fl & 1u) a0 = 0.;
       if (fl & 2u) a1 = 0.;
@@ -115,13 +118,17 @@ __global__ void k_assemble_epi(const uint32_t *rowptr, const uint32_t *cols, con
     }
   }
 }
+// the stencil code of the rows of a launch (null: none was built, every row takes rowptr / cols)
+static RowCodeView row_code_view(const NodeMap &m) {
+  return m.sid ? RowCodeView{m.pos0 + m.row0, m.sid + m.row0, m.stencil} : RowCodeView{nullptr, nullptr, nullptr};
+}
 hipError_t launch_assemble_epi(const NodeMap &m, const unsigned char *flags, const double *evec, const EpilogueArgs &ep, hipStream_t s) {
   if (m.nnodes <= 0 && ep.n_int <= 0) return hipSuccess;
   constexpr int AB = 256;
   const unsigned nb_rows = (unsigned)((std::max(m.nnodes, 0) + AB - 1) / AB);
   const unsigned nb_int = (unsigned)std::min<size_t>(((size_t)std::max(ep.n_int, 0) * 3 + AB - 1) / AB, 4096);
   hipLaunchKernelGGL(k_assemble_epi, dim3(nb_rows + nb_int), dim3(AB), 0, s, m.rowptr + m.row0, m.cols, m.node_off + m.row0,
-                     flags ? flags + m.row0 : nullptr, evec, m.nnodes, (int)nb_rows, ep);
+                     flags ? flags + m.row0 : nullptr, evec, m.nnodes, (int)nb_rows, ep, row_code_view(m));
   return hipGetLastError();
 }
 hipError_t launch_assemble(const NodeMap &m, const unsigned char *flags, const double *evec, double *y, int add, hipStream_t s,
@@ -134,7 +141,8 @@ hipError_t launch_assemble(const NodeMap &m, const unsigned char *flags, const d
   hipLaunchKernelGGL(k_assemble, dim3(nb_rows + nb_un), dim3(AB), 0, s, m.rowptr + m.row0, m.cols, m.node_off + m.row0,
                      flags ? flags + m.row0 : nullptr, evec, y, m.nnodes, add, (int)nb_rows,
                      unpack ? *unpack : HaloUnpackArgs{nullptr, nullptr, nullptr, nullptr, 0},
-                     pack ? HaloPackFold{pack->ptr + m.row0, pack->slot, pack->send} : HaloPackFold{nullptr, nullptr, nullptr});
+                     pack ? HaloPackFold{pack->ptr + m.row0, pack->slot, pack->send} : HaloPackFold{nullptr, nullptr, nullptr},
+                     row_code_view(m));
   return hipGetLastError();
 }
 
