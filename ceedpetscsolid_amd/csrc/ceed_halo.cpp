@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 
 #include "ceed_impl.hpp"
+#include "index_maps.hpp"
 
 using namespace cps;
 
@@ -139,19 +140,9 @@ static int halo_build(CeedXHalo H, CeedInt nneigh, const int *neigh_rank, const 
   }
   H->total = (int)idx.size();
   H->h_idx = idx;
-  // arrivals by destination entry, each entry's slots in neighbour-list order (slots ascend with the neighbour)
-  std::vector<uint32_t> order(idx.size());
-  for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return idx[a] < idx[b]; });
-  std::vector<uint32_t> dst, uptr(1, 0u), uslot;
-  for (size_t i = 0; i < order.size(); i++) {
-    if (i == 0 || idx[order[i]] != idx[order[i - 1]]) { if (i) uptr.push_back((uint32_t)uslot.size()); dst.push_back(idx[order[i]]); }
-    uslot.push_back(order[i]);
-  }
-  uptr.push_back((uint32_t)uslot.size());
-  if (dst.empty()) uptr.assign(1, 0u);
-  H->ndst = (int)dst.size();
-  CHK(H->d_idx.upload(ceed, idx)); CHK(H->d_dst.upload(ceed, dst)); CHK(H->d_uptr.upload(ceed, uptr)); CHK(H->d_uslot.upload(ceed, uslot));
+  const HaloArrivals A = halo_arrivals(idx);     // arrivals by destination entry (index_maps.hpp)
+  H->ndst = (int)A.dst.size();
+  CHK(H->d_idx.upload(ceed, idx)); CHK(H->d_dst.upload(ceed, A.dst)); CHK(H->d_uptr.upload(ceed, A.uptr)); CHK(H->d_uslot.upload(ceed, A.uslot));
   CHK(H->send.alloc(ceed, idx.size())); CHK(H->recv.alloc(ceed, idx.size()));
   HIPCHK(hipEventCreateWithFlags(&H->packed, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&H->arrived, hipEventDisableTiming));

@@ -134,7 +134,7 @@ struct CeedVector_private {
 };
 
 // The rows of a transpose map as k_assemble reads them: per row a node offset and the E-vector positions of the node's contributors in
-// element order.  Whatever only sums or flags rows (assemble_rows, make_row_flags, get_pack_fold) takes this.
+// element order.  Whatever only sums or flags rows (assemble_rows, op_row_flags, get_pack_fold) takes this.
 struct RowMap {
   std::vector<uint32_t> h_node_off;        // host copy (the Dirichlet flags and the pack folds of an operator are derived from it)
   DevArray<uint32_t> d_rowptr, d_cols, d_node_off;

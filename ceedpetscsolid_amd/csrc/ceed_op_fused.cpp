@@ -37,21 +37,15 @@ struct FusedApply {
   const RowMap *rows = nullptr;            // the rows it sums: M's, or (apply_fused) those of M's pipelined re-ordering
   const unsigned char *flags = nullptr;    // Dirichlet flags per row of `rows` (null: none)
 };
-// the Dirichlet flags of the operator's mask in the row order of a transpose map
-static int make_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, DevArray<unsigned char> &d) {
-  std::vector<unsigned char> fl(M.h_node_off.size(), 0);
-  for (size_t i = 0; i < fl.size(); i++) fl[i] = (unsigned char)node_flag_bits(op->h_mask.data(), M.h_node_off[i], r);
-  return d.upload(op->ceed, fl);
-}
-// The same as an apply reads them (*flags null: no mask, or none on the output side): ONE cache per operator, keyed by the map.  Like
-// every lazily built array of this layer they are made by an eager apply only, never while a graph is recorded.
+// The Dirichlet flags of the operator's mask in the row order of a transpose map (index_maps.hpp: row_flag_bits) as an apply reads them
+// (*flags null: no mask, or none on the output side): ONE cache per operator, keyed by the map.  Like every lazily built array of this layer they are made by an eager apply only, never while a graph is recorded.
 static int op_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, const unsigned char **flags) {
   *flags = nullptr;
   if (op->h_mask.empty() || !(op->mask_mode & 2)) return 0;
   for (auto &e : op->row_flags) if (e.first == &M) { *flags = e.second.get(); return 0; }
   if (op->ceed->capturing) return ceed_error("apply the operator once before recording (Dirichlet row flags)");
   DevArray<unsigned char> d;
-  CHK(make_row_flags(op, r, M, d));
+  CHK(d.upload(op->ceed, row_flag_bits(M.h_node_off, op->h_mask.data(), r->ncomp, r->compstride)));
   *flags = d.get();
   op->row_flags.emplace_back(&M, std::move(d));
   return 0;
@@ -168,36 +162,16 @@ static int assemble_rows(const FusedApply &F, int row0, int nrows, hipStream_t s
   HIPCHK(launch_assemble(F.rows->view().rows(row0, nrows), F.flags, F.a.evec, F.py, F.add ? 1 : 0, s, un, pk));
   return 0;
 }
-// The pack of halo H folded into the launch that sums the rows of map M: per row the send slots of its node's entries.
-// Built once per (map, halo); not ok (-> the separate pack kernel) if an entry of the halo is no row of the map.
+// The pack of halo H folded into the launch that sums the rows of map M: per row the send slots of its node's entries (index_maps.hpp:
+// pack_fold).  Built once per (map, halo); not ok (-> the separate pack kernel) if an entry of the halo is no row of the map.
 static int get_pack_fold(CeedOperator op, CeedElemRestriction r, const RowMap *M, CeedXHalo H, HaloPackFold *out, bool *ok) {
   for (auto &pf : op->pack_folds)
     if (pf.M == M && pf.H == H && pf.serial == H->serial) { *ok = pf.ok; *out = HaloPackFold{pf.d_ptr.get(), pf.d_slot.get(), H->send.get()}; return 0; }
   CeedOperator_private::PackFold pf{M, H, H->serial, {}, {}, false};
   if (op->ceed->capturing) { *ok = false; return 0; }     // cold while recording: the separate pack kernel
-  const int nn = M->nrows;
-  bool good = r->ncomp == 3 && r->compstride == 1 && (size_t)H->total < (1u << 30);
-  std::vector<uint32_t> ptr((size_t)nn + 1, 0u), slot((size_t)(H->total ? H->total : 1));
-  if (good) {
-    // row of a node offset: the map's rows are distinct node offsets (ascending within each priority class): look up by sort
-    std::vector<std::pair<uint32_t, uint32_t>> rows((size_t)nn);
-    for (int i = 0; i < nn; i++) rows[(size_t)i] = {M->h_node_off[(size_t)i], (uint32_t)i};
-    std::sort(rows.begin(), rows.end());
-    std::vector<uint32_t> row_of((size_t)H->total);
-    for (int k = 0; k < H->total && good; k++) {
-      const uint32_t d = H->h_idx[(size_t)k], node = d - d % 3;
-      auto it = std::lower_bound(rows.begin(), rows.end(), std::make_pair(node, 0u));
-      if (it == rows.end() || it->first != node) good = false;
-      else { row_of[(size_t)k] = it->second; ptr[(size_t)it->second + 1]++; }
-    }
-    if (good) {
-      for (int i = 0; i < nn; i++) ptr[(size_t)i + 1] += ptr[(size_t)i];
-      std::vector<uint32_t> cur(ptr.begin(), ptr.end() - 1);
-      for (int k = 0; k < H->total; k++) slot[cur[row_of[(size_t)k]]++] = (uint32_t)k | ((H->h_idx[(size_t)k] % 3u) << 30);
-    }
-  }
-  if (good) {
-    CHK(pf.d_ptr.upload(op->ceed, ptr)); CHK(pf.d_slot.upload(op->ceed, slot));
+  const PackFoldLists L = pack_fold(M->h_node_off, H->h_idx, r->ncomp, r->compstride);
+  if (L.ok) {
+    CHK(pf.d_ptr.upload(op->ceed, L.ptr)); CHK(pf.d_slot.upload(op->ceed, L.slot));
     pf.ok = true;
   }
   *ok = pf.ok; *out = HaloPackFold{pf.d_ptr.get(), pf.d_slot.get(), H->send.get()};
@@ -358,12 +332,10 @@ static int apply_fused_with_halo(CeedOperator op, CeedVector in, CeedVector out,
   // the exchange starts when only the priority rows are complete -- so every entry of the halo must lie on a priority row of
   // the split map.  Checked once per (operator, halo) on the host.
   if (op->ovl_halo_checked != H->serial) {
-    std::vector<uint32_t> prio(M->h_node_off.begin(), M->h_node_off.begin() + M->nprio);
-    std::sort(prio.begin(), prio.end());
-    for (uint32_t d : H->h_idx)
-      if (!std::binary_search(prio.begin(), prio.end(), d - d % 3u))
-        return ceed_error("CeedXOperatorApplyWithHalo: entry %u of the halo is not on a priority node of the operator's overlap split "
-                          "(CeedXOperatorSetOverlapSplit): its partial sum would be exchanged before it is complete", d);
+    const long k = halo_entry_off_priority(M->h_node_off, M->nprio, H->h_idx);
+    if (k >= 0)
+      return ceed_error("CeedXOperatorApplyWithHalo: entry %u of the halo is not on a priority node of the operator's overlap split "
+                        "(CeedXOperatorSetOverlapSplit): its partial sum would be exchanged before it is complete", H->h_idx[(size_t)k]);
     op->ovl_halo_checked = H->serial;
   }
   if (!M->full_cover) CHK(dev_zero(c, F.py, (size_t)out->length));
@@ -415,10 +387,8 @@ extern "C" int CeedXOperatorSetOverlapSplit(CeedOperator op, CeedInt n_leading_e
   if (!priority) return 0;
   if (lsize < r->lsize || n_leading_elems < 0 || n_leading_elems > r->nelem) return ceed_error("bad overlap split arguments");
   // check the contract: every contributor of a priority node is a leading element
-  const size_t es = (size_t)r->elemsize;
-  for (size_t i = 0; i < r->h_offsets.size(); i++)
-    if (priority[(size_t)r->h_offsets[i]] && i / es >= (size_t)n_leading_elems)
-      return ceed_error("element %zu touches a priority node but is not among the %d leading elements", i / es, n_leading_elems);
+  const long bad = overlap_split_violation(r->h_offsets, r->elemsize, priority, n_leading_elems);
+  if (bad >= 0) return ceed_error("element %zu touches a priority node but is not among the %d leading elements", (size_t)bad, n_leading_elems);
   const int P1 = op->in[op->i_active].basis->P1d;
   CHK(build_csr(r, op->ovl_csr, priority, (op->ceed->opt.direct_interior && rstr_interior_private(r, P1)) ? P1 : 0));
   op->ovl_lead = n_leading_elems;

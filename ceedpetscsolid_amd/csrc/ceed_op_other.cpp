@@ -5,25 +5,14 @@
 using namespace cps;
 
 // The transfer operators in OWNER form (kernels_transfer.hip, k_transfer).
-// own_f[e][n] = offset | fine-side Dirichlet flags if element e is the FIRST (in element order) to hold fine node n, else
-// 0xFFFFFFFF.  Set-up time, host; rebuilt when the operator's mask changes.
+// The owner map of the fine side (index_maps.hpp: owner_map), with the fine-side Dirichlet flags.  Set-up time, host; rebuilt when the
+// operator's mask changes.
 static int transfer_owner_map(CeedOperator op, CeedElemRestriction rf) {
   if (op->d_own_f) return 0;
   Ceed c = op->ceed;
   if (c->capturing) return ceed_error("first apply of a transfer operator during graph capture: apply it once before recording");
-  const size_t n = rf->h_offsets.size();
-  std::vector<uint32_t> own(n ? n : 1);
-  std::vector<unsigned char> seen((size_t)rf->lsize, 0);
   const std::vector<unsigned char> &mk = op->h_mask_fine;
-  size_t distinct = 0;
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t o = (uint32_t)rf->h_offsets[i];
-    if (seen[o]) { own[i] = 0xFFFFFFFFu; continue; }
-    seen[o] = 1; distinct++;
-    own[i] = o | ((mk.empty() ? 0u : node_flag_bits(mk.data(), o, rf)) << OFF_FLAG_SHIFT);
-  }
-  op->own_full_cover = distinct * 3 == (size_t)rf->lsize;
-  return op->d_own_f.upload(c, own);
+  return op->d_own_f.upload(c, owner_map(rf->h_offsets, rf->lsize, mk.empty() ? nullptr : mk.data(), rf->ncomp, rf->compstride, &op->own_full_cover));
 }
 // Set-up time only (never while recording): `n` counters on the device, zeroed, counted into by `count` on the Ceed's stream,
 // and read back into h[0 .. n).

@@ -302,12 +302,7 @@ extern "C" int CeedXOperatorGetKernelName(CeedOperator op, const char **name) {
 
 static int make_flagged(CeedElemRestriction r, const unsigned char *mask, CeedInt lsize, DevArray<uint32_t> &dev) {
   if (lsize < r->lsize) return ceed_error("Dirichlet mask shorter than the L-vector");
-  std::vector<uint32_t> fl(r->h_offsets.size());
-  for (size_t i = 0; i < fl.size(); i++) {
-    const uint32_t o = (uint32_t)r->h_offsets[i];
-    fl[i] = o | (node_flag_bits(mask, o, r) << OFF_FLAG_SHIFT);
-  }
-  return dev.upload(r->ceed, fl);
+  return dev.upload(r->ceed, flagged_offsets(r->h_offsets, mask, r->ncomp, r->compstride));
 }
 // mode: 1 = masked entries read as zero, 2 = masked rows dropped, 3 = both (default for mode 0)
 extern "C" int CeedXOperatorSetDirichletMaskMode(CeedOperator op, CeedMemType mtype, const unsigned char *mask,

@@ -2,6 +2,7 @@
 // residual / Jacobian family), ceed_op_other.cpp (transfers, SetupGeo, coordinate and energy operators).  Private, like ceed_impl.hpp.
 #pragma once
 #include "ceed_impl.hpp"
+#include "index_maps.hpp"
 
 // the launches of one apply between two events on its stream, while the operator is timed (CeedXOperatorSetTiming)
 struct TimerScope {
@@ -34,12 +35,6 @@ static inline void set_kernel_name(CeedOperator op, const char *name, bool fused
 static inline bool no_kernel(hipError_t e, const char *kname) { return e == hipErrorInvalidValue && !*kname; }
 // a vector of its own: neither missing nor one of the two sentinels
 static inline bool is_passive(CeedVector v) { return v && v != CEED_VECTOR_NONE && v != CEED_VECTOR_ACTIVE; }
-// the Dirichlet flag bits of the node at `offset` of restriction r: bit c set where component c is masked
-static inline uint32_t node_flag_bits(const unsigned char *mask, uint32_t offset, CeedElemRestriction r) {
-  uint32_t f = 0;
-  for (int c = 0; c < r->ncomp && c < 3; c++) if (mask[(size_t)offset + (size_t)c * r->compstride]) f |= 1u << c;
-  return f;
-}
 static inline int read_phys(CeedQFunction qf, double *nu, double *E) {
   // The reference passes sizeof(pointer) as the context size at setuplibceed.c:826; the
   // context is the 16-byte {nu, E} struct behind the pointer (elasticity.h:33-36).

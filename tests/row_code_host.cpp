@@ -2,15 +2,16 @@
 // under the address and undefined-behaviour sanitizers and run as a child process.  Every map is encoded and decoded again; the decoded
 // (rowptr, cols) must be the map itself, entry for entry.
 //   boxes 2x2x2 and 3x3x3 at P = 2, 3, 5: the whole map (columns e * P^3 + n) and the shell map of the direct-store mode (interior nodes
-//     left out, columns e * shell size + shell rank), both built the way build_csr builds them;
+//     left out, columns e * shell size + shell rank), both built by the library's transpose_map (csrc/index_maps.hpp);
 //   a map with a 12-contributor row and one with a contributor BEFORE its row's first: escape rows;
 //   an empty map; rows without contributors;
 //   a table limit of 4 (coded and escape rows side by side: half the shell rows of the 3x3x3 box at P = 5 escape) and of 0 (all escape).
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
-#include "kernels.hpp"
+#include "index_maps.hpp"
 #include "row_code.hpp"
 
 using namespace cps;
@@ -21,35 +22,19 @@ static int g_fail = 0;
 struct Map { std::vector<uint32_t> rowptr, cols; };
 
 // the transpose map of an n x n x n box of degree P - 1 (nodes numbered lexicographically over the box), rows in ascending node order,
-// a row's contributors in element order -- ceed_restriction.cpp's build_csr, with its `skipP`
+// a row's contributors in element order: the offsets made here, the map by the library's own transpose_map (index_maps.hpp), with its `skipP`
 static Map box_map(int n, int P, bool shell) {
   const int N = n * (P - 1) + 1, P3 = P * P * P, nelem = n * n * n;
-  std::vector<uint32_t> off((size_t)nelem * P3);
+  std::vector<int> off((size_t)nelem * P3);
   for (int ez = 0, e = 0; ez < n; ez++)
     for (int ey = 0; ey < n; ey++)
       for (int ex = 0; ex < n; ex++, e++)
         for (int k = 0, l = 0; k < P; k++)
           for (int j = 0; j < P; j++)
             for (int i = 0; i < P; i++, l++)
-              off[(size_t)e * P3 + l] = (uint32_t)(((ez * (P - 1) + k) * N + ey * (P - 1) + j) * N + ex * (P - 1) + i);
-  const size_t nnodes = (size_t)N * N * N;
-  std::vector<uint32_t> cnt(nnodes, 0u);
-  for (size_t i = 0; i < off.size(); i++)
-    if (!(shell && node_is_element_interior((int)(i % P3), P))) cnt[off[i]]++;
-  Map M;
-  std::vector<uint32_t> slot(nnodes, 0xFFFFFFFFu);
-  M.rowptr.push_back(0u);
-  for (size_t o = 0; o < nnodes; o++)
-    if (cnt[o]) { slot[o] = (uint32_t)M.rowptr.size() - 1; M.rowptr.push_back(M.rowptr.back() + cnt[o]); }
-  std::vector<uint32_t> cur(M.rowptr.begin(), M.rowptr.end() - 1);
-  M.cols.assign(M.rowptr.back(), 0u);
-  for (size_t i = 0; i < off.size(); i++) {
-    const int l = (int)(i % P3);
-    if (shell && node_is_element_interior(l, P)) continue;
-    const size_t e = i / P3;
-    M.cols[cur[slot[off[i]]]++] = shell ? (uint32_t)(e * element_shell_size(P) + node_shell_rank(l, P)) : (uint32_t)i;
-  }
-  return M;
+              off[(size_t)e * P3 + l] = ((ez * (P - 1) + k) * N + ey * (P - 1) + j) * N + ex * (P - 1) + i;
+  TransposeMap T = transpose_map(off, N * N * N, P3, 1, nullptr, shell ? P : 0);
+  return Map{std::move(T.rowptr), std::move(T.cols)};
 }
 
 // encode, decode, compare; returns the code for the caller's own checks
