@@ -76,7 +76,9 @@ class CeedLib:
     # declared CEED_EXTERN_OPTIONAL in include/ceed.h: the product library exports them, another backend of the ABI (the CPU oracle) may
     # not -- the callers look them up (``has``) and otherwise take the portable form built from the entry points above
     OPTIONAL = ["CeedXOperatorApplyState", "CeedOperatorLinearAssemblePointBlockDiagonal", "CeedXVectorPointBlockInvert",
-                "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock"]
+                "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock",
+                "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
+                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -314,6 +316,47 @@ class Csr:
     def destroy(self):
         if self.h:
             self.L.lib.CeedXCsrDestroy(C.byref(self.h))
+            self.h = None
+
+
+SURFACE_TRACTION, SURFACE_PRESSURE = 0, 1
+
+
+class SurfaceLoadHandle:
+    """CeedXSurfaceLoad*: traction, follower pressure and its tangent on a list of element faces, on the device.  CEED_EXTERN_OPTIONAL:
+    only where the library has ``CeedXSurfaceLoadCreate``; surface.py's SurfaceLoad takes its portable NumPy form otherwise."""
+
+    def __init__(self, ceed: "Ceed", P: int, Q: int, offsets, lsize: int):
+        self.L, self._ceed = ceed.L, ceed
+        if not self.L.has("CeedXSurfaceLoadCreate"):
+            raise CeedError(f"{self.L.path} has no CeedXSurfaceLoadCreate: use the portable form (surface.SurfaceLoad)")
+        self.h = C.c_void_p()
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, P * P)
+        self.nface = off.shape[0]
+        self.L.chk(self.L.lib.CeedXSurfaceLoadCreate(ceed.h, c_int(self.nface), c_int(P), c_int(Q), off.ctypes.data_as(c_int_p),
+                                                     c_int(lsize), C.byref(self.h)))
+
+    def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        self.L.chk(self.L.lib.CeedXSurfaceLoadSetDirichletMask(self.h, MEM_HOST, None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                               c_int(0 if m is None else m.size)))
+
+    def apply_add(self, kind: int, coef, scale: float, X: "Vector", u: Optional["Vector"], y: "Vector"):   # y += scale g
+        cf = (C.c_double * 3)(*[float(v) for v in coef])
+        self.L.chk(self.L.lib.CeedXSurfaceLoadApplyAdd(self.h, int(kind), cf, C.c_double(scale), X.h, _h(u), y.h))
+
+    def apply_tangent_add(self, p: float, scale: float, X: "Vector", u: Optional["Vector"], du: "Vector", y: "Vector"):   # y += scale p T(u) du
+        self.L.chk(self.L.lib.CeedXSurfaceLoadApplyTangentAdd(self.h, C.c_double(p), C.c_double(scale), X.h, _h(u), du.h, y.h))
+
+    @property
+    def kernel_name(self) -> str:
+        s = C.c_char_p()
+        self.L.chk(self.L.lib.CeedXSurfaceLoadGetKernelName(self.h, C.byref(s)))
+        return s.value.decode() if s.value else ""
+
+    def destroy(self):
+        if self.h:
+            self.L.lib.CeedXSurfaceLoadDestroy(C.byref(self.h))
             self.h = None
 
 

@@ -182,6 +182,12 @@ inline std::vector<uint32_t> flagged_offsets(const std::vector<int> &offsets, co
   }
   return fl;
 }
+// the offsets of the faces of a surface load (three interlaced components per node) as its kernel reads them: the flag bits of their
+// nodes in the top bits under a mask, plain without one (`mask` null)
+inline std::vector<uint32_t> face_offsets(const std::vector<int> &offsets, const unsigned char *mask) {
+  if (mask) return flagged_offsets(offsets, mask, 3, 1);
+  return std::vector<uint32_t>(offsets.begin(), offsets.end());
+}
 // the Dirichlet flags of a mask in the row order of a transpose map
 inline std::vector<unsigned char> row_flag_bits(const std::vector<uint32_t> &node_off, const unsigned char *mask, int ncomp, int compstride) {
   std::vector<unsigned char> fl(node_off.size(), 0);

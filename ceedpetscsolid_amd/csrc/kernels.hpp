@@ -272,6 +272,26 @@ struct EpilogueArgs {
 };
 hipError_t launch_assemble_epi(const NodeMap &m, const unsigned char *flags, const double *evec, const EpilogueArgs &ep, hipStream_t s);
 
+// Surface loads on element faces (kernels_surface.hip, k_surface): per face the P^2 nodal values of one of three geometric vectors,
+//   traction  g_a = int N_a t |X_xi x X_eta|,   pressure  g_a = int N_a (x_xi x x_eta),   tangent  T du |_a = int N_a (du_xi x x_eta + x_xi x du_eta),
+// x = X + u, (xi, eta) the two in-face directions (xi fastest in the face's node list) with X_xi x X_eta pointing out of the body.
+enum SurfaceKind : int { SURF_TRACTION = 0, SURF_PRESSURE = 1, SURF_TANGENT = 2 };
+struct SurfaceArgs {
+  const uint32_t *offsets;  // [nface][P^2] component-0 L-offsets, the Dirichlet flags of their nodes in the top bits
+  const double *X;          // node coordinates, an L-vector interlaced [node][3]
+  const double *u;          // displacement (pressure, tangent) or null: the reference configuration; read as it is (boundary values)
+  const double *du;         // tangent: the variation; flagged components read as zero
+  double *evec;             // face results [face][P^2][3], plain coalesced stores; launch_surface_sum() adds them into y
+  int nface, kind;
+  double coef[3];           // scale x t (traction); scale x p in coef[0] (pressure, tangent)
+};
+// hipErrorInvalidValue with *name left empty when (P, Q) is not instantiated: P = 2 .. 8, Q = P .. min(P + 2, 8)
+hipError_t launch_surface(int P, int Q, const BasisTables &t, const SurfaceArgs &a, hipStream_t s, const char **name);
+bool surface_instantiated(int P, int Q);
+// y[node_off[r] + c] += the sum of row r's face contributions in face order (node_sum3), one read-modify-write per row of the face
+// transpose map; components flagged in `flags` (a byte per row, may be null) are skipped, rows off the faces are never touched
+hipError_t launch_surface_sum(const NodeMap &m, const unsigned char *flags, const double *evec, double *y, hipStream_t s);
+
 // Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.
 struct CoordOpArgs {
   const uint32_t *off_x;   // [nelem][8] coordinate restriction

@@ -390,6 +390,30 @@ def side_set_nodes(mesh: HexMesh, dm: DofMap, side_ids) -> np.ndarray:
     return np.unique(np.concatenate(out)) if out else np.zeros(0, dtype=np.int64)
 
 
+# _local_face_nodes lists a face's nodes with its SECOND in-face direction fastest: (y, z) on the x-faces, (x, z) on the y-faces, (x, y) on
+# the z-faces.  With xi the fastest and eta the other direction, X_xi x X_eta of a right-handed element is then z x y = -x, z x x = +y and
+# y x x = -z: outward on the local faces 0 (x-), 3 (y+), 4 (z-), inward on 1, 2, 5, whose lists are transposed.
+_FACE_FLIP = (False, True, True, False, False, True)
+
+
+def side_set_faces(mesh: HexMesh, dm: DofMap, side_ids) -> np.ndarray:
+    """(nface, P^2) node ids of the faces of the given side sets, xi fastest, (xi, eta) ordered so that X_xi x X_eta points out of the
+    body (elements are right-handed, ``_fix_orientation``: the order depends on the local face alone).  Faces come in side-set
+    order, then element order."""
+    P = dm.P
+    loc = []
+    for f in range(6):
+        n = _local_face_nodes(P, f).reshape(P, P)
+        loc.append((n.T if _FACE_FLIP[f] else n).ravel())
+    loc = np.stack(loc)                                               # (6, P^2) local nodes of every local face
+    out = []
+    for sid in side_ids:
+        fs = np.asarray(mesh.side_sets[sid], dtype=np.int64).reshape(-1, 2)
+        fs = fs[np.argsort(fs[:, 0], kind="stable")]
+        out.append(dm.elem_nodes[fs[:, 0][:, None], loc[fs[:, 1]]].astype(np.int64))
+    return np.concatenate(out, axis=0) if out else np.zeros((0, P * P), dtype=np.int64)
+
+
 def boundary_nodes(mesh: HexMesh, dm: DofMap) -> np.ndarray:
     """Nodes on faces that belong to exactly one element of this (sub-)mesh: the whole
     boundary -- the "marker" label of -test mode (setupdm.c:160-170) -- and, on a

@@ -116,6 +116,8 @@ class SolidProblem:
         if coarse_quadrature not in ("fine", "own"):
             raise ValueError(f"coarse_quadrature must be 'fine' or 'own', not {coarse_quadrature!r}")
         self.coarse_quadrature, self.qextra = coarse_quadrature, qextra
+        self.bc_sides = [] if bc_all_boundary else [int(s) for s in (bc_sides or [])]      # the clamped side sets (surface loads refuse them)
+        self.bc_all_boundary = bool(bc_all_boundary)
         self._state_scratch = None
         self._pb_asm = {}                                # level -> AssembledLevel of the portable point-block diagonal
         self.phys = np.array([nu, E], dtype=np.float64)  # Physics {nu, E}

@@ -76,10 +76,21 @@ class NewtonPMG:
                  coarse: str = "cg", coarse_cheb_its: int = 40, coarse_cheb_ratio: float = 100.0, graph: bool = False,
                  amg_smooth_its: int = 3, amg_smooth_ratio: float = 10.0, amg_max_coarse_dofs: int = 1500, amg_coarse_cycles: int = 1,
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
-                 line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi"):
+                 line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi",
+                 traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full"):
         """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
-        set but absent here are held at zero."""
+        set but absent here are held at zero.
+        Surface loads (surface.py; one rank, and never on a clamped side set):
+        ``traction``: {side_set_id: (tx, ty, tz)} -- a dead load per unit REFERENCE area acting on the body in the direction t, scaled by
+        the load fraction like the body force; evaluated once and folded into the load vector.
+        ``pressure``: {side_set_id: p} -- a pressure on the CURRENT surface, p > 0 pushing on the body, scaled by the load fraction;
+        evaluated in every residual, R = F_int(u) - load (f + sum_s g_s^traction) + load sum_s p_s g_s^pressure(u).
+        ``pressure_tangent``: "full" adds load sum_s p_s T_s(u) to the Jacobian of the OUTER Krylov iteration (the V-cycle, its
+        smoothers, diagonals and eigenvalue estimates do not see it: the preconditioner is the volume operator's); "none" omits it
+        (modified Newton).  T(u) is symmetric only on the variations that vanish on the rim of the loaded surface: a closed surface, or
+        a patch whose rim is clamped (a tube with clamped ends).  The outer CG assumes a symmetric operator; a follower pressure on a
+        patch with a free rim is the caller's responsibility, as with any non-conservative load."""
         self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
         # smoother: what the Chebyshev iteration of every p-multigrid level, its eigenvalue estimate and the Jacobi-preconditioned
         # coarse CG are preconditioned with -- "jacobi" (default, the reference: PCJACOBI on GetDiag_Ceed) or "pbjacobi": the inverted
@@ -99,6 +110,10 @@ class NewtonPMG:
         if smoother == "pbjacobi" and many:
             raise ValueError("smoother='pbjacobi' is not provided with a halo (several ranks): the nodal blocks of the interface nodes "
                              "are not summed over the ranks")
+        if many and (traction or pressure):
+            # partial face sums at the interface nodes would need the exchange between the add and its consumer
+            raise ValueError("surface loads (traction=, pressure=) are not provided with a halo (several ranks): the face sums of the "
+                             "interface nodes are not summed over the ranks")
         if many and single and len(prob.levels) > 1:
             raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
         if many and len(halo) != len(prob.levels):
@@ -207,12 +222,62 @@ class NewtonPMG:
         self.load = 1.0
         self.stats = SolveStats()
         self._bc_nodes = self._collect_bc_nodes()
+        self._setup_surface_loads(traction, pressure, pressure_tangent)
         if self.amg is not None:
             # setup, not solve: aggregates, prolongation and the product patterns from the Jacobian of the undeformed state
             self.U.set_value(0.0)
             self.p.form_residual(self.U, self.R)
             self.asm.assemble()
             self.amg.build()
+
+    # ---- surface loads (surface.py) -----------------------------------------------------------
+    def _setup_surface_loads(self, traction, pressure, pressure_tangent):
+        """With no surface load given nothing here runs beyond the argument checks, and no solve takes a new path."""
+        if pressure_tangent not in ("full", "none"):
+            raise ValueError(f"pressure_tangent must be 'full' or 'none', not {pressure_tangent!r}")
+        self.pressure_tangent = pressure_tangent
+        self.pressure_loads = []                     # (SurfaceLoad, p) per loaded side set
+        self.surface_loads = []                      # every SurfaceLoad made here (destroy_surface_loads)
+        if not traction and not pressure:
+            return
+        from .mesh import side_set_nodes
+        from .surface import SurfaceLoad
+        prob, lv = self.p, self.p.levels[self.p.fine]
+        for sid in list(traction or {}) + list(pressure or {}):
+            if sid not in prob.mesh.side_sets:
+                raise ValueError(f"surface load on side set {sid}: the mesh has no such side set")
+            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
+            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
+                raise ValueError(f"surface load on side set {sid}, which is one of the problem's Dirichlet side sets")
+        n, top = prob.lsize(), self.nlev - 1
+        make = lambda sid: SurfaceLoad(self.ceed, prob.mesh, lv.dofmap, [sid], Q=prob.Q, mask=lv.mask)
+        for sid, t in (traction or {}).items():
+            t = np.asarray(t, dtype=np.float64).reshape(-1)
+            if t.size != 3:
+                raise ValueError(f"traction on side set {sid}: three components expected")
+            if self.fv is None:
+                self.fv = self._vec(n, top)
+            sl = make(sid)
+            sl.traction_add(t, 1.0, self.fv)         # masked rows are never written: fv stays zero on the constrained dofs
+            self.surface_loads.append(sl)
+        for sid, pval in (pressure or {}).items():
+            sl = make(sid)
+            self.pressure_loads.append((sl, float(pval)))
+            self.surface_loads.append(sl)
+
+    def destroy_surface_loads(self):
+        for sl in self.surface_loads:
+            sl.destroy()
+        self.surface_loads, self.pressure_loads = [], []
+
+    def A_outer(self, lv, x, y):
+        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x, u the state of the last
+        residual evaluation (Xloc: free part + boundary values).  Masked entries of x read as zero and masked rows are not written,
+        as in the volume operator."""
+        self.A(lv, x, y)
+        if self.pressure_tangent == "full":
+            for sl, pval in self.pressure_loads:
+                sl.tangent_add(pval, self.load, self.Xloc, x, y)
 
     # ---- vector helpers ---------------------------------------------------------------------
     def axpby(self, y, a, x, b):
@@ -325,6 +390,8 @@ class NewtonPMG:
         self._halo_sum(self.nlev - 1, R)
         if self.fv is not None:
             self.axpby(R, -self.load, self.fv, 1.0)
+        for sl, pval in self.pressure_loads:           # follower pressure on the current surface (constrained rows are not written)
+            sl.pressure_add(pval, self.load, self.Xloc, R)
         self.stats.residual_evals += 1
 
     # ---- multigrid preconditioner ---------------------------------------------------------------
@@ -573,8 +640,9 @@ class NewtonPMG:
         its = 0
         if rz0 <= 0.0:
             return 0
+        apply_A = self.A_outer if self.pressure_loads else self.A
         for its in range(1, 500):
-            self.A(fine, p, Ap)
+            apply_A(fine, p, Ap)
             alpha = rz / self.dot(p, Ap, True)
             self.axpby(x, alpha, p, 1.0); self.axpby(r, -alpha, Ap, 1.0)
             r_zold = self.dot(r, z, True)                    # r_new . z_old, taken BEFORE the preconditioner overwrites z (no copy of z)

@@ -378,6 +378,54 @@ CEED_EXTERN_OPTIONAL int CeedXVectorPointBlockMult(CeedVector w, CeedVector bloc
 /* Recordable into a CeedXGraph like the scalar step.                          */
 CEED_EXTERN_OPTIONAL int CeedXVectorChebyshevStepPointBlock(CeedVector x, CeedVector d, CeedVector r /* or NULL */,
     CeedVector b, CeedVector t /* or NULL */, CeedVector blocks, double c1, double c2, int assign_x);
+/* OPTIONAL entry points: surface loads on a list of element faces (a union of */
+/* side sets): a dead traction, a pressure that follows the deforming surface  */
+/* and that pressure's exact tangent.  (The reference has no surface loads:    */
+/* no call site is cited.)  A caller looks them up and, where they are absent, */
+/* integrates over the faces itself (ceedpetscsolid_amd/surface.py).           */
+/* A face has the P x P face nodes of its element, N_a their tensor Lagrange   */
+/* functions on the Gauss-Lobatto points, (xi, eta) its two reference          */
+/* directions -- xi runs fastest in the face's node list -- ordered by the     */
+/* caller so that X_xi x X_eta points out of the body.  X are the node         */
+/* coordinates, x = X + u the current position, the quadrature Q x Q Gauss     */
+/* points.  Three geometric vectors; signs and load factors are the caller's:  */
+/*   traction:  g_a      = int N_a t |X_xi x X_eta| dxi deta                   */
+/*              (t a constant 3-vector, per unit REFERENCE area)               */
+/*   pressure:  g_a(u)   = int N_a (x_xi x x_eta) dxi deta                     */
+/*              (area-weighted current outward normal; quadratic in u)         */
+/*   tangent:   T(u) du |_a = int N_a (du_xi x x_eta + x_xi x du_eta) dxi deta */
+/*              (the derivative of g(u) in the direction du)                   */
+/* The face results are summed per node in face order: bit-reproducible.       */
+/*   Create: offsets[nface][P*P] are the component-0 L-offsets of the face     */
+/*     nodes (three interlaced components per node, so multiples of 3 with     */
+/*     offset + 2 < lsize), xi fastest; copied.  (P, Q) must be instantiated:  */
+/*     P = 2..8, Q = P..min(P+2, 8).  nface = 0 is legal: every apply is then  */
+/*     a no-op.                                                                */
+/*   SetDirichletMask: the byte mask of CeedXOperatorSetDirichletMaskMode      */
+/*     (host memory, copied; NULL clears).  Masked rows of y are never         */
+/*     written and masked entries of du read as zero; u is read as it is (it   */
+/*     carries the boundary values).                                           */
+/*   ApplyAdd: y += scale * g.  Traction: coef = t, u is ignored.  Pressure:   */
+/*     g is multiplied by coef[0]; u = NULL is the reference configuration.    */
+/*   ApplyTangentAdd: y += scale * p * T(u) du.                                */
+/* Both applies check the vector lengths against lsize before anything is      */
+/* launched, run on the Ceed's stream, and can be recorded in a CeedXGraph     */
+/* after one eager apply (the first builds the faces' transpose map).  Rows of */
+/* y that lie on no face are never touched.                                    */
+typedef struct CeedXSurfaceLoad_private *CeedXSurfaceLoad;
+#define CEED_X_SURFACE_TRACTION 0
+#define CEED_X_SURFACE_PRESSURE 1
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadCreate(Ceed ceed, CeedInt nface, CeedInt P, CeedInt Q,
+    const CeedInt *offsets, CeedInt lsize, CeedXSurfaceLoad *sl);
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadSetDirichletMask(CeedXSurfaceLoad sl, CeedMemType mtype,
+    const unsigned char *mask, CeedInt lsize);
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadApplyAdd(CeedXSurfaceLoad sl, int kind, const CeedScalar coef[3],
+    CeedScalar scale, CeedVector X, CeedVector u /* or NULL */, CeedVector y);
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadApplyTangentAdd(CeedXSurfaceLoad sl, CeedScalar p, CeedScalar scale,
+    CeedVector X, CeedVector u /* or NULL */, CeedVector du, CeedVector y);
+/* Instantiation of the last launch, e.g. "surface<P=3,Q=3>" (empty before).   */
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadGetKernelName(CeedXSurfaceLoad sl, const char **name);
+CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadDestroy(CeedXSurfaceLoad *sl);
 /* Assembled sparse operator on L-vectors: the coarse level of the multigrid. */
 /* The reference builds it by finite-difference colouring of the p=1 operator */
 /* (misc.c:151-183, elasticity.c:457-483) and hands it to GAMG; here the      */
