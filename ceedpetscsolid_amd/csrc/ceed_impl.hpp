@@ -224,7 +224,7 @@ struct CeedOperator_private {
   // lowering (op_plan)
   int plan = PLAN_NONE;
   int i_active = -1, i_qdata = -1, i_state = -1, i_weight = -1, o_active = -1, o_state = -1, o_qdata = -1;
-  cps::BasisTables tables;
+  cps::BasisTables tables{};
   double eo[6][cps::EO_TAB];          // even-odd forms of the six 1-D products (fused operators with pencil_even_odd(Q))
   std::string kernel_name;            // instantiation of the last launch (set_kernel_name), and whether that was a fused kernel:
   bool kernel_fused = false;          // CeedXOperatorGetKernelName then adds how the geometric factors were obtained (kernel_name_full)

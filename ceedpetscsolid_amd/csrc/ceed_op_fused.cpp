@@ -13,12 +13,6 @@ static void capture_dep(Ceed c, const GraphDep &d) {
   d.v->refcount++;      // held from here: the vector may be destroyed by its creator before the recording ends
   c->capture_deps.push_back(d);
 }
-static void lame_constants(double nu, double E, double *lambda, double *TwoMu) {
-  // hyperSS.h:79-81 / hyperFS.h:164-167, evaluated once per apply on the host
-  *TwoMu = E / (1 + nu);
-  const double Kbulk = E / (3 * (1 - 2 * nu));
-  *lambda = (3 * Kbulk - *TwoMu) / 3;
-}
 // how the last apply was launched (CeedXOperatorGetLaunchInfo)
 static void set_launch_info(CeedOperator op, int segments, int streams, int assemble_launches, int last_segment_elems) {
   op->launch_info[0] = segments; op->launch_info[1] = streams; op->launch_info[2] = assemble_launches; op->launch_info[3] = last_segment_elems;

@@ -42,9 +42,10 @@ static int transfer_weights(CeedOperator op, CeedElemRestriction rf, const doubl
   const size_t n = (size_t)rf->lsize;
   if (op->d_w.size() < n) CHK(op->d_w.alloc(c, n));
   int cnt = 1;
+  CHK(build_csr(rf, rf->csr, nullptr));
   CHK(count_on_device(c, 1, &cnt, [&](int *d_cnt) {
     CHK(dev_zero(c, op->d_w.get(), n));
-    HIPCHK(launch_multiplicity(rf->d_offsets.get(), rf->nelem, rf->elemsize, rf->ncomp, rf->compstride, op->d_w.get(), c->stream));
+    HIPCHK(launch_multiplicity(rf->csr.view(), rf->ncomp, rf->compstride, op->d_w.get(), c->stream));
     HIPCHK(launch_transfer_weights(op->d_w.get(), psc, n, d_cnt, c->stream));
     return 0;
   }));
@@ -152,6 +153,22 @@ int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out) {
   }
   return 0;
 }
+// The element results of an energy / coordinate operator, stored by its kernel in the E-layout of the output restriction `r`, summed into
+// `out` per node in element order (k_rstr_transpose).  prepare: the map, the scratch and -- overwrite mode -- zeros wherever the sum
+// does not store (entries no element holds, the tail of a longer vector); finish: the sum, after the kernel.
+static int cold_sum_prepare(CeedOperator op, CeedElemRestriction r, CeedVector out, double *py, bool add, double **evec) {
+  CHK(build_csr(r, r->csr, nullptr));
+  CHK(ceed_need_evec(op->ceed, (size_t)r->nelem * r->ncomp * r->elemsize));
+  *evec = op->ceed->evec.get();
+  if (!add && (!r->csr.full_cover || out->length > r->lsize)) CHK(dev_zero(op->ceed, py, (size_t)out->length));
+  return 0;
+}
+static int cold_sum_finish(CeedOperator op, CeedElemRestriction r, const double *evec, double *py, bool add, const char *kname) {
+  HIPCHK(launch_rstr_transpose(r->csr.view(), r->elemsize, r->ncomp, r->compstride, evec, py, add ? 1 : 0, op->ceed->stream));
+  set_kernel_name(op, kname, false);
+  op->launches++;
+  return 0;
+}
 int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CeedQFunction qf = op->qf;
   OpField &u = op->in[0], &en = op->out[0];
@@ -162,23 +179,20 @@ int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   EnergyOpArgs a{};
   double *pu, *py, *pq;
   CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(qd, false, &pq));
-  a.off_u = u.rstr->d_offsets.get(); a.u = pu; a.off_e = en.rstr->d_offsets.get(); a.y = py; a.qdata = pq;
+  a.off_u = u.rstr->d_offsets.get(); a.u = pu; a.qdata = pq;
   a.nelem = u.rstr->nelem; a.Q = u.basis->Q1d; a.P = u.basis->P1d;
+  if (a.Q > MAXN1D || a.P > MAXN1D) return ceed_error("energy operator: Q=%d / P=%d outside the supported range", a.Q, a.P);
   const int kd = qf->kind;
   a.diag = (kd == QF_DIAG_LINELAS || kd == QF_DIAG_HYPERSS || kd == QF_DIAG_HYPERFS) ? 1 : 0;
   a.model = (kd == QF_ENERGY_LINELAS || kd == QF_DIAG_LINELAS) ? 0 : ((kd == QF_ENERGY_HYPERSS || kd == QF_DIAG_HYPERSS) ? 1 : 2);
-  CHK(read_phys(qf, &a.nu, &a.E));
-  memcpy(a.interp, u.basis->interp1d.data(), sizeof(double) * u.basis->interp1d.size());
-  memcpy(a.grad, u.basis->grad1d.data(), sizeof(double) * u.basis->grad1d.size());
-  if (!a.diag) memcpy(a.interp_e, en.basis->interp1d.data(), sizeof(double) * en.basis->interp1d.size());
-  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-  hipError_t e = launch_energy_op(a, op->ceed->stream);
-  if (e == hipErrorInvalidValue) return ceed_error("energy operator: Q=%d / P=%d outside the supported range", a.Q, a.P);
-  HIPCHK(e);
-  set_kernel_name(op, a.diag ? (a.model == 0 ? "diagnostic_op<LinElasDiagnostic>" : (a.model == 1 ? "diagnostic_op<HyperSSDiagnostic>" : "diagnostic_op<HyperFSDiagnostic>"))
-                  : (a.model == 0 ? "energy_op<LinElasEnergy>" : (a.model == 1 ? "energy_op<HyperSSEnergy>" : "energy_op<HyperFSEnergy>")), false);
-  op->launches++;
-  return 0;
+  double nu, E;
+  CHK(read_phys(qf, &nu, &E));
+  lame_constants(nu, E, &a.lambda, &a.TwoMu);
+  CHK(cold_sum_prepare(op, en.rstr, out, py, add, &a.evec));
+  HIPCHK(launch_energy_op(op->tables, a, op->ceed->stream));
+  return cold_sum_finish(op, en.rstr, a.evec, py, add,
+                         a.diag ? (a.model == 0 ? "diagnostic_op<LinElasDiagnostic>" : (a.model == 1 ? "diagnostic_op<HyperSSDiagnostic>" : "diagnostic_op<HyperFSDiagnostic>"))
+                                : (a.model == 0 ? "energy_op<LinElasEnergy>" : (a.model == 1 ? "energy_op<HyperSSEnergy>" : "energy_op<HyperFSEnergy>")));
 }
 int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CeedQFunction qf = op->qf;
@@ -187,30 +201,26 @@ int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CoordOpArgs a{};
   double *px, *py, *pq = nullptr;
   CHK(vec_dev(in, false, &px)); CHK(vec_dev(out, true, &py));
-  a.off_x = x.rstr->d_offsets.get(); a.xcoord = px; a.off_u = o.rstr->d_offsets.get(); a.y = py;
+  a.off_x = x.rstr->d_offsets.get(); a.xcoord = px;
   a.nelem = x.rstr->nelem; a.Q = x.basis->Q1d;
   a.mode = qf->kind == QF_CONST_FORCE ? 0 : (qf->kind == QF_MMS_FORCE ? 1 : 2);
+  a.Pout = a.mode == 2 ? a.Q : o.basis->P1d;
+  if (a.Q > MAXN1D || a.Pout > MAXN1D) return ceed_error("coordinate operator: Q=%d / P=%d outside the supported range", a.Q, a.Pout);
   if (a.mode != 2) {
     CeedVector qd = op->in[1].vec;
     if (!is_passive(qd)) return ceed_error("qdata needs a passive vector");
     if ((size_t)qd->length < (size_t)a.nelem * 10 * a.Q * a.Q * a.Q) return ceed_error("qdata vector too short");
     CHK(vec_dev(qd, false, &pq)); a.qdata = pq;
-    a.Pout = o.basis->P1d;
-    memcpy(a.bu, o.basis->interp1d.data(), sizeof(double) * o.basis->interp1d.size());
     if (!qf->ctx) return ceed_error("QFunction '%s' needs its context", qf->name.c_str());
     const double *cx = (const double *)qf->ctx;   // pointer pass-through: forcing vector (3) or Physics {nu, E} (setuplibceed.c:563-566)
-    for (int i = 0; i < (a.mode == 0 ? 3 : 2); i++) a.ctx[i] = cx[i];
-  } else {
-    a.Pout = a.Q;
+    if (a.mode == 0) for (int i = 0; i < 3; i++) a.ctx[i] = cx[i];
+    else lame_constants(cx[0], cx[1], &a.lambda, &a.TwoMu);
   }
   memcpy(a.bx, x.basis->interp1d.data(), sizeof(double) * x.basis->interp1d.size());
-  if (!add) CHK(dev_zero(op->ceed, py, (size_t)out->length));
-  hipError_t e = launch_coord_op(a, op->ceed->stream);
-  if (e == hipErrorInvalidValue) return ceed_error("coordinate operator: Q=%d / P=%d outside the supported range", a.Q, a.Pout);
-  HIPCHK(e);
-  set_kernel_name(op, a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>"), false);
-  op->launches++;
-  return 0;
+  CHK(cold_sum_prepare(op, o.rstr, out, py, add, &a.evec));
+  HIPCHK(launch_coord_op(op->tables, a, op->ceed->stream));
+  return cold_sum_finish(op, o.rstr, a.evec, py, add,
+                         a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>"));
 }
 // Fine-side multiplicity scale of the transfer operators (matops.c:149,176); NULL clears.
 extern "C" int CeedXOperatorSetFineScale(CeedOperator op, CeedVector scale) {

@@ -223,13 +223,15 @@ int op_plan(CeedOperator op) {
     if (!nodes_fit(u)) return unsupported("restriction element size is not P^3");
     if (!is_qdata(qd, Q) || qd.rstr->nelem != u.rstr->nelem) return unsupported("qdata must be strided 10 x Q^3");
     if (energy) {
+      // (the same points: the kernel takes INTERP^T of the energy basis from the displacement basis's table, compared entry by entry)
       if (!is_offsets(o.rstr) || o.rstr->ncomp != 1 || o.rstr->nelem != u.rstr->nelem || o.basis == CEED_BASIS_COLLOCATED ||
-          !nodes_fit(o) || o.basis->Q1d != Q || o.basis->P1d != P)
+          !nodes_fit(o) || o.basis->Q1d != Q || o.basis->P1d != P || o.basis->interp1d != u.basis->interp1d)
         return unsupported("energy field must be a 1-component field on the displacement's nodes and points");
     } else if (!is_offsets(o.rstr) || o.rstr->ncomp != 8 || o.rstr->compstride != 1 || o.rstr->nelem != u.rstr->nelem ||
                o.rstr->elemsize != cube(Q) || o.basis != CEED_BASIS_COLLOCATED)
       return unsupported("diagnostic field must be 8 interlaced components collocated with the points");
     op->i_active = 0; op->i_qdata = (int)nin - 1; op->o_active = 0;
+    fill_tables(op->tables, u.basis);
     op->plan = PLAN_ENERGY;
     return 0;
   }
@@ -247,6 +249,7 @@ int op_plan(CeedOperator op) {
       if (!is_qdata(op->in[1], Q) || op->in[1].rstr->nelem != x.rstr->nelem) return unsupported("qdata must be strided 10 x Q^3");
       if (o.basis == CEED_BASIS_COLLOCATED || o.basis->Q1d != Q || !nodes_fit(o)) return unsupported("force basis must share the quadrature of the coordinate basis");
       op->i_qdata = 1;
+      fill_tables(op->tables, o.basis);
     } else {
       if (qf->out[0].emode != CEED_EVAL_NONE || o.basis != CEED_BASIS_COLLOCATED || o.rstr->elemsize != cube(Q)) return unsupported("true solution is collocated on the points of the coordinate basis");
     }

@@ -43,4 +43,10 @@ static inline int read_phys(CeedQFunction qf, double *nu, double *E) {
   *nu = p[0]; *E = p[1];
   return 0;
 }
+static inline void lame_constants(double nu, double E, double *lambda, double *TwoMu) {
+  // hyperSS.h:79-81 / hyperFS.h:164-167, evaluated once per apply on the host
+  *TwoMu = E / (1 + nu);
+  const double Kbulk = E / (3 * (1 - 2 * nu));
+  *lambda = (3 * Kbulk - *TwoMu) / 3;
+}
 #pragma GCC visibility pop

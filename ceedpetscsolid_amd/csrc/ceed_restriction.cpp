@@ -57,23 +57,31 @@ extern "C" int CeedElemRestrictionCreateVector(CeedElemRestriction r, CeedVector
 extern "C" int CeedElemRestrictionApply(CeedElemRestriction r, CeedTransposeMode tmode, CeedVector u,
                                         CeedVector ru, CeedRequest *) {
   hipStream_t s = r->ceed->stream;
+  const size_t esize = (size_t)r->nelem * r->elemsize * r->ncomp;
+  CeedVector lv = tmode == CEED_NOTRANSPOSE ? u : ru, ev = tmode == CEED_NOTRANSPOSE ? ru : u;
+  if (lv->length < r->lsize || (size_t)ev->length < esize) return ceed_error("restriction apply: L- or E-vector too short");
   double *pu, *pv;
   CHK(vec_dev(u, false, &pu));
   CHK(vec_dev(ru, true, &pv));
   if (r->strided) {  // identity layout: E == L
-    const size_t n = (size_t)r->nelem * r->elemsize * r->ncomp;
-    if (tmode == CEED_NOTRANSPOSE) HIPCHK(hipMemcpyAsync(pv, pu, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    else HIPCHK(launch_axpby(pv, 1., pu, 1., n, s));
+    if (tmode == CEED_NOTRANSPOSE) HIPCHK(hipMemcpyAsync(pv, pu, esize * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else HIPCHK(launch_axpby(pv, 1., pu, 1., esize, s));
     return 0;
   }
   if (tmode == CEED_NOTRANSPOSE) HIPCHK(launch_rstr_gather(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
-  else HIPCHK(launch_rstr_scatter_add(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, pu, pv, s));
+  else if (r->nelem > 0) {   // v += E^T u: per row of the transpose map the contributors in element order, then one add
+    CHK(build_csr(r, r->csr, nullptr));
+    HIPCHK(launch_rstr_transpose(r->csr.view(), r->elemsize, r->ncomp, r->compstride, pu, pv, 1, s));
+  }
   return 0;
 }
 extern "C" int CeedElemRestrictionGetMultiplicity(CeedElemRestriction r, CeedVector mult) {
   if (r->strided) return CeedVectorSetValue(mult, 1.);
-  CHK(CeedVectorSetValue(mult, 0.));
-  HIPCHK(launch_multiplicity(r->d_offsets.get(), r->nelem, r->elemsize, r->ncomp, r->compstride, mult->d, r->ceed->stream));
+  if (mult->length < r->lsize) return ceed_error("multiplicity vector shorter than the L-size");
+  CHK(CeedVectorSetValue(mult, 0.));      // (entries no element holds stay zero)
+  if (r->nelem <= 0) return 0;
+  CHK(build_csr(r, r->csr, nullptr));
+  HIPCHK(launch_multiplicity(r->csr.view(), r->ncomp, r->compstride, mult->d, r->ceed->stream));
   return 0;
 }
 extern "C" int CeedElemRestrictionDestroy(CeedElemRestriction *rstr) {

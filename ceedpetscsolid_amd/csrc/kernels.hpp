@@ -292,34 +292,33 @@ bool surface_instantiated(int P, int Q);
 // transpose map; components flagged in `flags` (a byte per row, may be null) are skipped, rows off the faces are never touched
 hipError_t launch_surface_sum(const NodeMap &m, const unsigned char *flags, const double *evec, double *y, hipStream_t s);
 
-// Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.
+// Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.  The 1-D tables of the output
+// (displacement) basis come by value (BasisTables, forcing only); the element results go to `evec` in the E-layout [elem][3][Pout^3] of the
+// output restriction, whose transpose (launch_rstr_transpose) sums them into the L-vector.
 struct CoordOpArgs {
   const uint32_t *off_x;   // [nelem][8] coordinate restriction
   const double *xcoord;    // interlaced [vertex][3]
-  const uint32_t *off_u;   // [nelem][Pout^3] displacement restriction
-  double *y;               // output L-vector, pre-zeroed, accumulated over the elements
+  double *evec;            // element results, [nelem][3][Pout^3]
   const double *qdata;     // [nelem][10][Q^3] (forcing) or null (true solution)
   int nelem, Q, Pout, mode;  // mode 0: SetupConstantForce, 1: SetupMMSForce, 2: MMSTrueSoln
-  double ctx[3];           // direction | (nu, E)
+  double ctx[3];           // direction (mode 0)
+  double lambda, TwoMu;    // mode 1: the Lame constants of (nu, E), formed on the host (lame_constants)
   double bx[MAXN1D * 2];   // coordinate basis interp1d, Q x 2
-  double bu[MAXN1D * MAXN1D];  // displacement basis interp1d, Q x Pout (forcing only)
 };
-hipError_t launch_coord_op(const CoordOpArgs &a, hipStream_t s);
-// Strain-energy operator (kernels_coord.hip): opEnergy of setuplibceed.c:651-670.
+hipError_t launch_coord_op(const BasisTables &t, const CoordOpArgs &a, hipStream_t s);
+// Strain-energy operator (kernels_coord.hip): opEnergy of setuplibceed.c:651-670.  The tables are the displacement basis's, which the
+// energy basis shares (op_plan compares them).
 struct EnergyOpArgs {
   const uint32_t *off_u;   // [nelem][P^3] displacement restriction (3 interlaced components)
   const double *u;         // displacement L-vector
-  const uint32_t *off_e;   // [nelem][P^3] energy restriction (1 component)
-  double *y;               // energy L-vector, pre-zeroed
+  double *evec;            // element results: [nelem][1][P^3] (energy) or [nelem][8][Q^3] (diagnostic), E-layout of the output restriction
   const double *qdata;     // [nelem][10][Q^3]
   int nelem, Q, P, model;  // model 0: LinElas, 1: HyperSS, 2: HyperFS
   int diag;                // 0: *Energy -> 1 component through INTERP^T; 1: *Diagnostic (opDiagnostic, setuplibceed.c:712-737)
-                           // -> 8 components collocated with the points, off_e then is the [nelem][Q^3] diagnostic restriction
-  double nu, E;
-  double interp[MAXN1D * MAXN1D], grad[MAXN1D * MAXN1D];  // displacement basis, Q x P
-  double interp_e[MAXN1D * MAXN1D];                        // energy basis, Q x P
+                           // -> 8 components collocated with the points
+  double nu, E, lambda, TwoMu;
 };
-hipError_t launch_energy_op(const EnergyOpArgs &a, hipStream_t s);
+hipError_t launch_energy_op(const BasisTables &t, const EnergyOpArgs &a, hipStream_t s);
 
 // Interface-dof halo exchange (CeedXHalo*, the L-vector sum of src/matops.c:57 across GPUs).  ONE launch packs the entries
 // of all neighbour lists into the (contiguous) send buffer; ONE launch adds all arrivals: a thread per distinct destination
@@ -354,10 +353,10 @@ hipError_t launch_masked_copy(double *dst, const double *src, const unsigned cha
                               hipStream_t s);  // dst = mask ? 0 : src
 hipError_t launch_rstr_gather(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
                               const double *l, double *e, hipStream_t s);
-hipError_t launch_rstr_scatter_add(const uint32_t *off, int nelem, int elemsize, int ncomp,
-                                   int compstride, const double *e, double *l, hipStream_t s);
-hipError_t launch_multiplicity(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
-                               double *l, hipStream_t s);
+// v += E^T u (add) or v = E^T u (store; entries no element holds are left) for the E-layout [elem][comp][node], and the number of
+// contributors of every entry some element holds: a lane per (row of the restriction's transpose map, component), no atomics
+hipError_t launch_rstr_transpose(const NodeMap &m, int elemsize, int ncomp, int compstride, const double *e, double *l, int add, hipStream_t s);
+hipError_t launch_multiplicity(const NodeMap &m, int ncomp, int compstride, double *l, hipStream_t s);
 hipError_t launch_dot(const double *x, const double *y, const double *w, size_t n, double *result_dev,
                       hipStream_t s, double *out = nullptr);  // result_dev[0] (and *out) = sum w_i x_i y_i (w may be null), reproducibly; result_dev: 1 + 2048 doubles
 hipError_t launch_scalar_div(double *sc, int dst, int num, int den, double scale, hipStream_t s);

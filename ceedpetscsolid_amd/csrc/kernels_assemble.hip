@@ -1,20 +1,41 @@
-// kernels_assemble.hip -- the restriction and its deterministic transpose: the plain gather / scatter-add (k_rstr), the per-node sum
-// in element order (k_assemble), the same sum with a consumer behind it (k_assemble_epi), and the halo pack / unpack-add that the
-// interface sum of several GPUs puts around it.  The sums themselves are kernel_node_sum.hpp's.
+// kernels_assemble.hip -- the restriction and its deterministic transpose: the plain gather (k_rstr) and its ordered transpose for
+// the libCEED E-layout (k_rstr_transpose, k_multiplicity), the per-node sum in element order of the interlaced E-vector (k_assemble), the
+// same sum with a consumer behind it (k_assemble_epi), and the halo pack / unpack-add that the interface sum of several GPUs puts around
+// it.  The sums of the interlaced E-vector are kernel_node_sum.hpp's.
 #include <algorithm>
 #include "kernel_node_sum.hpp"
 
 namespace cps {
 
 // E-layout [e][c][n]
-__global__ void k_rstr(const uint32_t *off, size_t total, int elemsize, int ncomp, int compstride,
-                       const double *src, double *dst, int mode) {
+__global__ void k_rstr(const uint32_t *off, size_t total, int elemsize, int ncomp, int compstride, const double *l, double *e) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t n = i % elemsize, ec = i / elemsize, c = ec % ncomp, e = ec / ncomp;
-    const size_t li = (size_t)(off[e * elemsize + n] & OFF_MASK) + c * (size_t)compstride;
-    if (mode == 0) dst[i] = src[li];
-    else if (mode == 1) atomic_add_f64(dst + li, src[i]);
-    else atomic_add_f64(dst + li, 1.0);
+    const size_t n = i % elemsize, ec = i / elemsize, c = ec % ncomp, el = ec / ncomp;
+    e[i] = l[(size_t)(off[el * elemsize + n] & OFF_MASK) + c * (size_t)compstride];
+  }
+}
+// The transpose of the same layout, for any ncomp / compstride / elemsize (cold path: CeedElemRestrictionApply(CEED_TRANSPOSE) and the
+// set-up / post-processing operators).  One lane per (row r of the restriction's transpose map, component c): the row's contributors
+// cols[k] = e * elemsize + n, in element order, are summed into a register; then ONE add (or, with add == 0, a store) goes to the
+// row's entry -- the rows of a map own disjoint entries of y, as k_assemble's do.
+__global__ void k_rstr_transpose(const uint32_t *rowptr, const uint32_t *cols, const uint32_t *node_off, size_t total, int elemsize,
+                                 int ncomp, int compstride, const double *evec, double *y, int add) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / ncomp, c = i % ncomp;
+    double sum = 0.;
+    for (uint32_t k = rowptr[r]; k < rowptr[r + 1]; k++) {
+      const size_t e = cols[k] / (uint32_t)elemsize, n = cols[k] % (uint32_t)elemsize;
+      sum += evec[(e * ncomp + c) * elemsize + n];
+    }
+    double *dst = y + (node_off[r] & OFF_MASK) + c * (size_t)compstride;
+    *dst = add ? *dst + sum : sum;
+  }
+}
+// the contributors of every row, counted: the entries of nodes no element holds are not written
+__global__ void k_multiplicity(const uint32_t *rowptr, const uint32_t *node_off, size_t total, int ncomp, int compstride, double *y) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / ncomp, c = i % ncomp;
+    y[(node_off[r] & OFF_MASK) + c * (size_t)compstride] = (double)(rowptr[r + 1] - rowptr[r]);
   }
 }
 // One lane per L-node.  The E-vector is interlaced [elem][node][3] like the L-vector: a contributor is
@@ -159,22 +180,18 @@ hipError_t launch_halo_unpack_add(const HaloUnpackArgs &u, double *y, hipStream_
   return launch_stream(k_halo_unpack_add, (size_t)std::max(u.n, 0), s, u, y);
 }
 
-static hipError_t rstr(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
-                       const double *src, double *dst, int mode, hipStream_t s) {
-  const size_t total = (size_t)nelem * elemsize * ncomp;
-  return launch_stream(k_rstr, total, s, off, total, elemsize, ncomp, compstride, src, dst, mode);
-}
 hipError_t launch_rstr_gather(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
                               const double *l, double *e, hipStream_t s) {
-  return rstr(off, nelem, elemsize, ncomp, compstride, l, e, 0, s);
+  const size_t total = (size_t)nelem * elemsize * ncomp;
+  return launch_stream(k_rstr, total, s, off, total, elemsize, ncomp, compstride, l, e);
 }
-hipError_t launch_rstr_scatter_add(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
-                                   const double *e, double *l, hipStream_t s) {
-  return rstr(off, nelem, elemsize, ncomp, compstride, e, l, 1, s);
+hipError_t launch_rstr_transpose(const NodeMap &m, int elemsize, int ncomp, int compstride, const double *e, double *l, int add, hipStream_t s) {
+  const size_t total = (size_t)std::max(m.nnodes, 0) * ncomp;
+  return launch_stream(k_rstr_transpose, total, s, m.rowptr + m.row0, m.cols, m.node_off + m.row0, total, elemsize, ncomp, compstride, e, l, add);
 }
-hipError_t launch_multiplicity(const uint32_t *off, int nelem, int elemsize, int ncomp, int compstride,
-                               double *l, hipStream_t s) {
-  return rstr(off, nelem, elemsize, ncomp, compstride, nullptr, l, 2, s);
+hipError_t launch_multiplicity(const NodeMap &m, int ncomp, int compstride, double *l, hipStream_t s) {
+  const size_t total = (size_t)std::max(m.nnodes, 0) * ncomp;
+  return launch_stream(k_multiplicity, total, s, m.rowptr + m.row0, m.node_off + m.row0, total, ncomp, compstride, l);
 }
 
 }  // namespace cps

@@ -25,11 +25,6 @@ template <int Q> struct Geom {
   static constexpr int BLOCK = TPE * EPB;
 };
 
-CPS_DEV void atomic_add_f64(double *p, double v) {
-  // hardware f64 atomic (global_atomic_add_f64); no CAS loop
-  unsafeAtomicAdd(p, v);
-}
-
 // The streaming kernels (HBM-bound, grid-stride): 256 lanes per workgroup, at most 2048 workgroups; nothing is launched for n = 0.
 static inline dim3 stream_grid(size_t n) {
   size_t b = (n + 255) / 256;

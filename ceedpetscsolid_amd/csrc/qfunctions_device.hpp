@@ -165,10 +165,9 @@ CPS_DEV double log1p_series4_shifted(double x) {  // hyperFS.h:45-67
 // 0:(0,0) 1:(1,1) 2:(2,2) 3:(1,2) 4:(0,2) 5:(0,1)
 #define CPS_SYM(w, a, b) ((a) == (b) ? w[a] : w[6 - (a) - (b)])
 struct FSState { double S[6], Ci[6], llnj; };
-// S in the reference's cancellation-free form llnj C^-1 + mu C^-1 E2 (the residual's; the tangent is qf_hyperfs_df)
-CPS_DEV void fs_state(double lambda, double mu, const double g[3][3], FSState &s) {  // hyperFS.h:85-142
+// E2 = 2 E = grad u + grad u^T + grad u^T grad u, the Green-Lagrange strain twice (hyperFS.h:89-97)
+CPS_DEV void green_strain2(const double g[3][3], double E2[6]) {
   constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
-  double E2[6];
 #pragma unroll
   for (int m = 0; m < 6; m++) {
     double t = g[J[m]][K[m]] + g[K[m]][J[m]];
@@ -176,10 +175,19 @@ CPS_DEV void fs_state(double lambda, double mu, const double g[3][3], FSState &s
     for (int n = 0; n < 3; n++) t += g[n][J[m]] * g[n][K[m]];
     E2[m] = t;
   }
-  const double detCm1 =  // hyperFS.h:72-80
-      E2[0] * (E2[1] * E2[2] - E2[3] * E2[3]) + E2[5] * (E2[4] * E2[3] - E2[5] * E2[2]) +
-      E2[4] * (E2[5] * E2[3] - E2[4] * E2[1]) + E2[0] + E2[1] + E2[2] + E2[0] * E2[1] +
-      E2[0] * E2[2] + E2[1] * E2[2] - E2[5] * E2[5] - E2[4] * E2[4] - E2[3] * E2[3];
+}
+// det C - 1 = J^2 - 1 of C = I + E2, expanded so that nothing cancels at small strain (hyperFS.h:72-80)
+CPS_DEV double det_c_minus_1(const double E2[6]) {
+  return E2[0] * (E2[1] * E2[2] - E2[3] * E2[3]) + E2[5] * (E2[4] * E2[3] - E2[5] * E2[2]) +
+         E2[4] * (E2[5] * E2[3] - E2[4] * E2[1]) + E2[0] + E2[1] + E2[2] + E2[0] * E2[1] +
+         E2[0] * E2[2] + E2[1] * E2[2] - E2[5] * E2[5] - E2[4] * E2[4] - E2[3] * E2[3];
+}
+// S in the reference's cancellation-free form llnj C^-1 + mu C^-1 E2 (the residual's; the tangent is qf_hyperfs_df)
+CPS_DEV void fs_state(double lambda, double mu, const double g[3][3], FSState &s) {  // hyperFS.h:85-142
+  constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
+  double E2[6];
+  green_strain2(g, E2);
+  const double detCm1 = det_c_minus_1(E2);
   const double C00 = 1 + E2[0], C11 = 1 + E2[1], C22 = 1 + E2[2], C12 = E2[3], C02 = E2[4], C01 = E2[5];
   const double A[6] = {C11 * C22 - C12 * C12, C00 * C22 - C02 * C02, C00 * C11 - C01 * C01,
                        C02 * C01 - C00 * C12, C01 * C12 - C02 * C11, C02 * C12 - C01 * C22};

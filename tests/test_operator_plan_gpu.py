@@ -8,7 +8,8 @@ ncomp, compstride, elemsize, collocated basis or not, nelem of every family's qd
 A refused graph launches nothing.  Neither does an energy, diagnostic or forcing operator whose qdata VECTOR is shorter than its elements
 need (apply_energy / apply_coord, ceed_op_other.cpp).  Then the refusals the entry points make themselves (masks, overlap split, diagonals, epilogue applies,
 split-phase applies, the state kernel; composite operators), and one replay of a recorded apply whose Dirichlet flag arrays were replaced
-under it (the operator's device arrays leave through ceed_retire).
+under it (the operator's device arrays leave through ceed_retire), and a forcing operator whose FIRST apply is recorded: refused, its output
+restriction's transpose map being built on the host; after one eager apply the recording replays to the bits of the eager result.
 
 Two branches of op_plan the binding cannot reach are left out:
   * "the basis tables are not centro-symmetric": every basis comes from CeedBasisCreateTensorH1Lagrange, whose tables are;
@@ -465,6 +466,45 @@ def test_a_recorded_apply_replays_after_its_mask_was_set_again(o, qdata):
         Y.set_value(-7.0)
         graph.launch()
         assert np.array_equal(Y.to_numpy(), eager)
+    finally:
+        graph.destroy()
+    op.destroy()
+
+
+FIRST_APPLY = "first apply of an operator during graph capture: its restriction's transpose map is built on the host; apply the operator once before recording"
+
+
+def _force_on_a_fresh_restriction(o):
+    """the valid forcing graph with an output restriction of its own: no operator has built its transpose map"""
+    cells = np.array([[(e + a) + 3 * b + 6 * k for k in (0, 1) for b in (0, 1) for a in (0, 1)] for e in (0, 1)], dtype=np.int32)
+    o.ru_fresh = o.c.elem_restriction(2, 8, 3, 1, 36, cells * 3)
+    g = g_force()
+    put("outs", 0, RSTR, "ru_fresh")(g)
+    return build(o, g)[0], o.c.vector(36)
+
+
+def test_a_first_apply_of_a_forcing_operator_is_refused_while_recording(o, qdata):
+    op, Y = _force_on_a_fresh_restriction(o)
+    Y.set_value(-7.0)
+    with pytest.raises(cd.CeedError, match=FIRST_APPLY):
+        o.c.capture(lambda: op.apply(o.x, Y))
+    assert np.all(Y.to_numpy() == -7.0)                      # nothing was recorded or launched
+    op.apply(o.x, Y)                                         # the Ceed records no longer: an eager apply goes through
+    assert np.any(Y.to_numpy() != 0.0)
+    op.destroy()
+
+
+def test_a_forcing_operator_applied_once_records_and_replays_to_the_bit(o, qdata):
+    op, Y = _force_on_a_fresh_restriction(o)
+    op.apply(o.x, Y)
+    eager = Y.to_numpy()
+    assert np.any(eager != 0.0)
+    graph = o.c.capture(lambda: op.apply(o.x, Y))
+    try:
+        for _ in range(2):
+            Y.set_value(-7.0)
+            graph.launch()
+            assert np.array_equal(Y.to_numpy(), eager)
     finally:
         graph.destroy()
     op.destroy()
