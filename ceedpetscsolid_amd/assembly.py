@@ -28,7 +28,9 @@ from .solid import SolidProblem
 
 
 class AssembledLevel:
-    def __init__(self, prob: SolidProblem, level: int = 0):
+    def __init__(self, prob: SolidProblem, level: int = 0, mass_coef=None):
+        """``mass_coef`` (dynamics.py): the matrix is that of K + mass_coef M -- the level's mass operator (mass.py) on the same
+        element-discontinuous restriction is added to every unit-vector apply.  None: nothing of it exists."""
         self.p, self.level = prob, level
         c = self.ceed = prob.ceed
         lv = prob.levels[level]
@@ -52,6 +54,10 @@ class AssembledLevel:
         self.op.set_field("deltadv", self.rstr, lv.basisu, "active")      # (fine Q) unless coarse_quadrature="own"
         if prob.info["state"]:
             self.op.set_field("gradu", lv.ErestrictGradui, None, lv.gradu)
+        self.mass = self._mass_cols = None
+        if mass_coef is not None:
+            from .mass import MassOperator
+            self.mass = MassOperator(prob, level, mass_coef, rstr=self.rstr, offsets=eoff)
         # --- unit vectors and the COO value buffer: entry [j][e][n][c] = K_e[(n,c), j] -----------------
         self.units = []
         for j in range(self.nd):
@@ -100,7 +106,19 @@ class AssembledLevel:
                                   for j in range(self.nd)]
         for j in range(self.nd):
             self.op.apply(self.units[j], self._cols_out[j])
+            if self.mass is not None:
+                self._add_mass_column(j)
         self.csr.assemble(self.coo)
+
+    def _add_mass_column(self, j: int):
+        """Column j of every element's mass_coef M_e added to the column of K_e just written."""
+        if not self.mass.portable:
+            self.mass.apply_add(self.units[j], self._cols_out[j])
+            return
+        if self._mass_cols is None:         # host memory borrowed by the outputs: added in place; M does not change, so formed once
+            self._mass_cols = [self.mass.apply_host(self.units[k].to_numpy()) for k in range(self.nd)]
+        nloc = self.ne * self.nd
+        self._coo_host[j * nloc:(j + 1) * nloc] += self._mass_cols[j]
 
     def apply(self, x: cd.Vector, y: cd.Vector):
         self.csr.apply(x, y)
@@ -109,5 +127,7 @@ class AssembledLevel:
         self.csr.diagonal(d)
 
     def destroy(self):
+        if self.mass is not None:
+            self.mass.destroy()
         for o in [self.csr, self.op, self.qf, self.rstr, self.coo] + ([self.coo_local] if self.coo_local is not self.coo else []) + self.units + (self._cols_out or []):
             o.destroy()

@@ -78,7 +78,7 @@ class CeedLib:
     OPTIONAL = ["CeedXOperatorApplyState", "CeedOperatorLinearAssemblePointBlockDiagonal", "CeedXVectorPointBlockInvert",
                 "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock",
                 "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
-                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy"]
+                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -397,6 +397,14 @@ class Ceed:
         m = C.c_int()
         self.L.chk(self.L.lib.CeedGetPreferredMemType(self.h, C.byref(m)))
         return m.value
+
+    def has_qfunction(self, name: str) -> bool:
+        """Does the library have a device functor for the QFunction ``name`` (CeedXHasQFunction)?  False where it lacks the entry point."""
+        if not self.L.has("CeedXHasQFunction"):
+            return False
+        r = C.c_int(0)
+        self.L.chk(self.L.lib.CeedXHasQFunction(self.h, name.encode(), C.byref(r)))
+        return bool(r.value)
 
     def set_stream(self, hip_stream: int):
         self.L.chk(self.L.lib.CeedXSetStream(self.h, C.c_void_p(hip_stream)))

@@ -1,6 +1,6 @@
 // ceed_impl.hpp -- private object layouts and helpers shared by the host-side sources of the MI355X backend
 // (ceed_core.cpp: Ceed, vectors, graphs; ceed_basis.cpp; ceed_restriction.cpp; ceed_qfunction.cpp; the operators: ceed_operator.cpp
-// with ceed_op_fused.cpp and ceed_op_other.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
+// with ceed_op_fused.cpp, ceed_op_other.cpp and ceed_op_mass.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
 // Every device array one of these objects owns is a DevArray (dev_array.hpp): allocated under the object's Ceed, gone with the member,
 // through ceed_retire.  The one exception is a vector's host / device mirrors, which may be borrowed (ceed_core.cpp).
 // Every transpose map is a RowMap (CsrMap, PipeMap); an operator keeps its Dirichlet flags per RowMap in ONE cache (row_flags).
@@ -210,7 +210,7 @@ struct CeedQFunction_private {
 
 struct OpField { bool set = false; CeedElemRestriction rstr = nullptr; CeedBasis basis = nullptr; CeedVector vec = nullptr; };
 
-enum PlanKind { PLAN_NONE = 0, PLAN_FUSED_GRAD, PLAN_SETUP_GEO, PLAN_PROLONG, PLAN_RESTRICT, PLAN_COORD, PLAN_ENERGY };
+enum PlanKind { PLAN_NONE = 0, PLAN_FUSED_GRAD, PLAN_SETUP_GEO, PLAN_PROLONG, PLAN_RESTRICT, PLAN_COORD, PLAN_ENERGY, PLAN_MASS };
 
 struct CeedXHalo_private;
 
@@ -225,6 +225,7 @@ struct CeedOperator_private {
   int plan = PLAN_NONE;
   int i_active = -1, i_qdata = -1, i_state = -1, i_weight = -1, o_active = -1, o_state = -1, o_qdata = -1;
   cps::BasisTables tables{};
+  cps::BasisTables tables_sq{};       // PLAN_MASS: `interp` squared entry by entry, the table of the mass diagonal
   double eo[6][cps::EO_TAB];          // even-odd forms of the six 1-D products (fused operators with pencil_even_odd(Q))
   std::string kernel_name;            // instantiation of the last launch (set_kernel_name), and whether that was a fused kernel:
   bool kernel_fused = false;          // CeedXOperatorGetKernelName then adds how the geometric factors were obtained (kernel_name_full)

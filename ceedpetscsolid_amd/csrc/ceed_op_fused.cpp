@@ -33,7 +33,7 @@ struct FusedApply {
 };
 // The Dirichlet flags of the operator's mask in the row order of a transpose map (index_maps.hpp: row_flag_bits) as an apply reads them
 // (*flags null: no mask, or none on the output side): ONE cache per operator, keyed by the map.  Like every lazily built array of this layer they are made by an eager apply only, never while a graph is recorded.
-static int op_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, const unsigned char **flags) {
+int op_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, const unsigned char **flags) {
   *flags = nullptr;
   if (op->h_mask.empty() || !(op->mask_mode & 2)) return 0;
   for (auto &e : op->row_flags) if (e.first == &M) { *flags = e.second.get(); return 0; }
@@ -468,6 +468,13 @@ extern "C" int CeedXOperatorApplyResidual(CeedOperator op, CeedVector in, CeedVe
 // (launch_pb_assemble: the destination of node offset o is 3 o, which the three-value kernel cannot address).
 static int assemble_diagonal(CeedOperator op, CeedVector assembled, int width) {
   const char *who = width == 3 ? "point-block diagonal" : "diagonal";
+  if (!op->composite) {
+    CHK(op_plan(op));
+    if (op->plan == PLAN_MASS)
+      return width == 3 ? ceed_error("point-block diagonal assembly is not provided for the mass operator: its nodal blocks are its scalar "
+                                     "diagonal times the identity (CeedOperatorLinearAssembleDiagonal)")
+                        : mass_diagonal(op, assembled);
+  }
   CHK(need_fused(op, (std::string(who) + " assembly").c_str(), Kind::jacobian));
   OpField &ai = op->in[op->i_active];
   CeedElemRestriction r = ai.rstr;

@@ -11,9 +11,10 @@
 //   prolong    : Identity, INTERP in -> NONE out                (:857-862)
 //   restrict   : Identity, NONE in  -> INTERP out               (:849-854)
 //   coord / energy : forcing, MMS, strain energy, diagnostics   (:555-737)
+//   mass       : INTERP active in, NONE qdata, INTERP active out (no call site in the reference: the elastodynamic solve, dynamics.py)
 //
 // There is NO host fallback: a graph outside these families or a QFunction without a device functor (ceed_qfunction.cpp) is a loud
-// error.  The families' applies: ceed_op_fused.cpp (fused_grad, with its diagonals and the state kernel), ceed_op_other.cpp (the rest).
+// error.  The families' applies: ceed_op_fused.cpp (fused_grad, with its diagonals and the state kernel), ceed_op_other.cpp (the rest but the mass operator: ceed_op_mass.cpp).
 #include "ceed_operator.hpp"
 
 using namespace cps;
@@ -257,6 +258,29 @@ int op_plan(CeedOperator op) {
     op->plan = PLAN_COORD;
     return 0;
   }
+  if (k == QF_MASS) {
+    // (u INTERP active (3), qdata NONE (10)) -> v INTERP active (3): v = c qdata[0] u
+    if (qf->in.size() != 2 || qf->out.size() != 1) return unsupported("Mass takes (u, qdata) -> v");
+    const QFField &fu = qf->in[0], &fq = qf->in[1], &fv = qf->out[0];
+    if (fu.emode != CEED_EVAL_INTERP || fu.size != 3 || fq.emode != CEED_EVAL_NONE || fq.size != 10 || fv.emode != CEED_EVAL_INTERP || fv.size != 3 ||
+        op->in[0].vec != CEED_VECTOR_ACTIVE || op->out[0].vec != CEED_VECTOR_ACTIVE)
+      return unsupported("Mass eval modes must be INTERP(3) active, NONE(10) -> INTERP(3) active");
+    OpField &ai = op->in[0], &ao = op->out[0], &qd = op->in[1];
+    if (!is_offsets(ai.rstr) || ai.rstr != ao.rstr || ai.basis != ao.basis || ai.basis == CEED_BASIS_COLLOCATED)
+      return unsupported("active input and output must share one offsets restriction and one basis");
+    if (!is_disp(ai)) return unsupported("active fields must be 3 interlaced components");
+    CeedBasis b = ai.basis;
+    const int P = b->P1d, Q = b->Q1d;
+    if (!nodes_fit(ai)) return unsupported("restriction element size is not P^3");
+    if (!is_qdata(qd, Q) || qd.rstr->nelem != ai.rstr->nelem) return unsupported("qdata must be a strided 10 x Q^3 field");
+    if (P > Q) return unsupported("the mass kernel needs P <= Q");
+    fill_tables(op->tables, b);
+    op->tables_sq = op->tables;
+    for (double &v : op->tables_sq.interp) v *= v;
+    op->i_active = 0; op->i_qdata = 1; op->o_active = 0;
+    op->plan = PLAN_MASS;
+    return 0;
+  }
   return unsupported("no kernel family");
 }
 
@@ -280,6 +304,7 @@ static int op_apply_single(CeedOperator op, CeedVector in, CeedVector out, bool 
   case PLAN_RESTRICT: return apply_transfer(op, in, out, add);
   case PLAN_ENERGY: return apply_energy(op, in, out, add);
   case PLAN_COORD: return apply_coord(op, in, out, add);
+  case PLAN_MASS: return apply_mass(op, in, out, add);
   default: return ceed_error("operator has no plan");
   }
 }
@@ -315,7 +340,7 @@ extern "C" int CeedXOperatorSetDirichletMaskMode(CeedOperator op, CeedMemType mt
   op_free_flags(op);
   if (!mask && !mask_out) return 0;
   if (mtype != CEED_MEM_HOST) return ceed_error("pass the Dirichlet mask in host memory (it is folded into the offsets once)");
-  if (op->plan == PLAN_FUSED_GRAD) {
+  if (op->plan == PLAN_FUSED_GRAD || op->plan == PLAN_MASS) {
     CHK(make_flagged(op->in[op->i_active].rstr, mask, lsize, op->d_off_flagged));
     op->h_mask.assign(mask, mask + lsize);
   } else if (op->plan == PLAN_PROLONG || op->plan == PLAN_RESTRICT) {

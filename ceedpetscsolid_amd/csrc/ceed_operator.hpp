@@ -1,5 +1,6 @@
 // ceed_operator.hpp -- what the operator sources share: ceed_operator.cpp (the object, op_plan, the dispatch), ceed_op_fused.cpp (the
-// residual / Jacobian family), ceed_op_other.cpp (transfers, SetupGeo, coordinate and energy operators).  Private, like ceed_impl.hpp.
+// residual / Jacobian family), ceed_op_other.cpp (transfers, SetupGeo, coordinate and energy operators), ceed_op_mass.cpp (the mass
+// operator).  Private, like ceed_impl.hpp.
 #pragma once
 #include "ceed_impl.hpp"
 #include "index_maps.hpp"
@@ -28,6 +29,12 @@ int apply_transfer(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out);
 int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add);
+int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add);
+// CeedOperatorLinearAssembleDiagonal of a PLAN_MASS operator (overwrites `assembled`; masked rows are zero)
+int mass_diagonal(CeedOperator op, CeedVector assembled);
+// The Dirichlet flags of the operator's mask in the row order of a transpose map, as an apply hands them to launch_assemble (*flags
+// null: no mask, or none on the output side); one cache per operator, filled by an eager apply only (ceed_op_fused.cpp).
+int op_row_flags(CeedOperator op, CeedElemRestriction r, const RowMap &M, const unsigned char **flags);
 
 // fused: a launch of the fused kernel, whose name CeedXOperatorGetKernelName completes with how the geometric factors were obtained
 static inline void set_kernel_name(CeedOperator op, const char *name, bool fused) { op->kernel_name = name; op->kernel_fused = fused; }

@@ -11,7 +11,7 @@ static int resolve_qf(const std::string &name) {
       {"HyperFSdF", QF_HYPERFS_DF},  {"SetupConstantForce", QF_CONST_FORCE}, {"SetupMMSForce", QF_MMS_FORCE},
       {"MMSTrueSoln", QF_MMS_TRUE},  {"LinElasEnergy", QF_ENERGY_LINELAS}, {"HyperSSEnergy", QF_ENERGY_HYPERSS},
       {"HyperFSEnergy", QF_ENERGY_HYPERFS}, {"LinElasDiagnostic", QF_DIAG_LINELAS}, {"HyperSSDiagnostic", QF_DIAG_HYPERSS},
-      {"HyperFSDiagnostic", QF_DIAG_HYPERFS},
+      {"HyperFSDiagnostic", QF_DIAG_HYPERFS}, {"Mass", QF_MASS},
   };
   for (auto &t : tab) if (name == t.n) return t.k;
   return QF_NONE;
@@ -29,6 +29,14 @@ extern "C" int CeedQFunctionCreateInterior(Ceed ceed, CeedInt, CeedQFunctionUser
   q->ceed = ceed; ceed_ref(ceed);
   q->f = f; q->source = src; q->name = name; q->kind = kind;
   *qf = q;
+  return 0;
+}
+// does `name` (the part after ':' of a source string, or the whole of it) select a device functor?
+extern "C" int CeedXHasQFunction(Ceed, const char *name, int *has) {
+  if (!name || !has) return ceed_error("CeedXHasQFunction: name and result required");
+  std::string n = name;
+  const size_t colon = n.rfind(':');
+  *has = resolve_qf(colon == std::string::npos ? n : n.substr(colon + 1)) != QF_NONE ? 1 : 0;
   return 0;
 }
 extern "C" int CeedQFunctionCreateIdentity(Ceed ceed, CeedInt size, CeedEvalMode inmode, CeedEvalMode outmode,

@@ -24,6 +24,7 @@ enum QFKind : int {
   QF_DIAG_HYPERSS,
   QF_DIAG_HYPERFS,
   QF_HYPERFS_DF_DS,   // HyperFSdF reading the DERIVED state (F^-1, lambda ln J - mu) the residual kernel wrote beside grad u
+  QF_MASS,            // v = c qdata[0] u: the mass operator of the elastodynamic solve (kernels_mass.hip)
 };
 
 constexpr int MAXN1D = 8;  // largest P or Q supported by the kernel tables
@@ -201,6 +202,18 @@ struct StateArgs {
   int mask_in;              // honour the Dirichlet flags on the gather (constrained entries read as zero)
 };
 
+// The mass operator and its diagonal (kernels_mass.hip, k_mass): v = coef B^T (w det J) B u on 3 interlaced components.
+struct MassArgs {
+  const uint32_t *offsets;  // [nelem][P^3] (flagged)
+  const double *x;          // the input L-vector, interlaced [node][3] (apply; the diagonal reads none)
+  const double *qdata;      // [nelem][10][Q^3]: component 0 (w det J) is the only one read
+  double *evec;             // element results [elem][P^3][3], plain coalesced stores; launch_assemble() sums them per node in element order
+  int nelem;
+  int mask_in;              // apply: flagged components of the input read as zero
+  int mask_out;             // diagonal: flagged rows are stored as zeros (the apply leaves its masked rows to launch_assemble's row flags)
+  double coef;              // the QFunction context c, read by the host at every apply
+};
+
 // Each returns hipSuccess or the launch error; `name` receives a static string
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
@@ -213,6 +226,8 @@ hipError_t launch_diag(int P, int Q, int qf, const BasisTables &t, const DiagArg
                        const char **name);
 hipError_t launch_state_at_points(int Pf, int Qc, const BasisTables &t, const StateArgs &a, hipStream_t s,
                                   const char **name);
+// diag: `t.interp` holds the entry-wise SQUARED table; names "mass<P,Q>" / "mass_diag<P,Q>"; the pairs of CPS_DIAG_PQ (kernel_diag_sf.hpp)
+hipError_t launch_mass(int P, int Q, bool diag, const BasisTables &t, const MassArgs &a, hipStream_t s, const char **name);
 
 // The instantiations of one quadrature size are compiled as pencil_inst_parts(Q) objects (kernels_fused_inst.hip, -DCPS_PART=<k>): the kernels
 // with (Q - P) % parts == k -- the Q = 8 object alone took 72 s of a 90 s build.  csrc/Makefile lists the same parts.

@@ -1,0 +1,233 @@
+"""Elastodynamics: implicit Newmark time stepping on top of the Newton - CG - p-multigrid solve (solver.py).
+
+The semi-discrete equations, with the sign and load conventions of ``solver.NewtonPMG`` (R = F_int - load (f + tractions) + load
+sum_s p_s g_s^pressure, a pressure p > 0 pushing on the body),
+
+    rho M a_{n+1} + F_int(u_{n+1}) = load(t_{n+1}) (f + tractions) - load(t_{n+1}) sum_s p_s g_s^pressure(u_{n+1})
+
+are closed by Newmark's update (beta = 1/4, gamma = 1/2: the average-acceleration rule, unconditionally stable and energy-conserving
+for a linear material):
+
+    a_{n+1} = a0 (u_{n+1} - u_n) - a2 v_n - a3 a_n,     a0 = 1 / (beta dt^2),  a2 = 1 / (beta dt),  a3 = 1 / (2 beta) - 1
+    v_{n+1} = v_n + dt ((1 - gamma) a_n + gamma a_{n+1})
+
+u, v, a are L-vectors WITH the boundary values (clamp values follow load(t) as they follow the load fraction of a quasi-static solve;
+the formulas above then give the clamped nodes the velocity and acceleration of that motion).  Every step is a Newton solve for
+u_{n+1} with the residual above and the effective tangent K + a0 rho M on every multigrid level: ``A`` is the parent's apply followed by
+the level's mass operator (mass.py) in add mode; the smoother's diagonal is diag K + a0 rho diag M; an assembled coarse level
+(``coarse="assembled"`` / ``"amg"``) carries a0 rho M in its element matrices, so the p = 1 matrix and the aggregation hierarchy under
+it are those of the effective operator.  The consumers fused into the Jacobian apply's epilogue have no mass term, so the two-pass
+forms are used throughout (``_fused_op`` is None; same bits).  dt is fixed per solver object: a recorded V-cycle keeps the
+coefficient a0 rho it was recorded with.
+
+Refused: ``smoother="pbjacobi"`` (the nodal blocks of M are not built) and a halo with several ranks (the mass operator's interface sums
+were never run there).
+"""
+from __future__ import annotations
+
+import time
+from typing import Callable, Optional, Union
+
+import numpy as np
+
+from .mass import MassOperator
+from .solid import SolidProblem
+from .solver import NewtonPMG, SolveStats
+
+
+class NewmarkPMG(NewtonPMG):
+    def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, **kw):
+        if not (density > 0.0 and dt > 0.0 and beta > 0.0):
+            raise ValueError("density, dt and beta must be positive")
+        if kw.get("smoother", "jacobi") == "pbjacobi":
+            raise ValueError("NewmarkPMG: smoother='pbjacobi' is not provided: the 3 x 3 nodal blocks of the mass operator are not built")
+        halo = kw.get("halo")
+        if halo is not None:
+            hl = halo if isinstance(halo, (list, tuple)) else [halo]
+            if hl[-1].world > 1:
+                raise ValueError("NewmarkPMG is not provided with a halo (several ranks): the mass operator's sums at the interface nodes "
+                                 "have not been run over several ranks")
+        if kw.get("line_search", "cp") == "cp-petsc":
+            raise ValueError("NewmarkPMG: line_search must be 'cp' or 'full'")
+        self.density, self.dt, self.beta, self.gamma = float(density), float(dt), float(beta), float(gamma)
+        self.a0, self.a2, self.a3 = 1.0 / (beta * dt * dt), 1.0 / (beta * dt), 1.0 / (2.0 * beta) - 1.0
+        self._asm_kwargs = {"mass_coef": self.a0 * self.density}
+        # the tangent's mass term per level (read by A and _get_diag, which the parent's constructor may already call)
+        self.mass = [MassOperator(prob, lv, self.a0 * self.density) for lv in range(len(prob.levels))]
+        self._mdiag = {}
+        super().__init__(prob, **kw)
+        n, top = prob.lsize(), self.nlev - 1
+        self.mass_res = MassOperator(prob, prob.fine, self.density, mask_mode=2)      # the residual's: reads the boundary values
+        self.xn, self.vn, self.an, self._pred, self._acc, self._mt = (self._vec(n, top) for _ in range(6))
+        self.t = 0.0
+        self.last_rnorm = 0.0
+        self._load_fn: Callable[[float], float] = lambda t: 1.0
+        self._started = False
+
+    # ---- the effective operator K + a0 rho M --------------------------------------------------------------------------------
+    def A(self, lv, x, y):
+        super().A(lv, x, y)
+        if not (lv == 0 and self.asm is not None):     # (the assembled level holds its mass term in the matrix)
+            self.mass[lv].apply_add(x, y)
+
+    def _fused_op(self, lv):
+        return None
+
+    def _get_diag(self, lv, d):
+        super()._get_diag(lv, d)
+        if lv not in self._mdiag:                # M does not change: its diagonal is formed once per level
+            m = self._vec(self.p.lsize(lv), lv)
+            self.mass[lv].diagonal(m)
+            self._mdiag[lv] = m
+        d.axpby(1.0, self._mdiag[lv], 1.0)
+
+    # ---- residual with the inertia term ----------------------------------------------------------------------------------------
+    def residual(self, U, R):
+        """R = F_int(x) - load f (+ pressure) + rho M (a0 x + pred), x = U + boundary values, pred = -(a0 x_n + a2 v_n + a3 a_n)."""
+        super().residual(U, R)
+        self._acc.waxpby(self.a0, self.Xloc, 1.0, self._pred)
+        self.mass_res.apply_add(self._acc, R)
+
+    def kinetic_energy(self) -> float:
+        """1/2 v . rho M v over the free rows."""
+        self.mass_res.apply(self.vn, self._mt)
+        return 0.5 * self.dot(self.vn, self._mt, True)
+
+    # ---- start ---------------------------------------------------------------------------------------------------------------
+    def set_initial(self, u0=None, v0=None, load: Union[float, Callable[[float], float]] = 1.0):
+        """State at t = 0: displacement u0 and velocity v0 (host L-vectors; None: zero) on the free dofs, the boundary values of
+        load(0) on the others, and a_0 = (rho M)^-1 (load f - F_int(u_0) - pressure terms) on the free dofs by Jacobi-preconditioned CG
+        on the mass operator (its condition number is O(1))."""
+        self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+        n = self.p.lsize()
+        free = self.free
+        self.t = 0.0
+        self.load = float(self._load_fn(0.0))
+        self._set(self.bcv, self.bc_values(self.load))
+        self._set(self.U, (np.zeros(n) if u0 is None else np.asarray(u0, dtype=np.float64).reshape(-1)[:n]) * free)
+        self._set(self.vn, (np.zeros(n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)[:n]) * free)
+        NewtonPMG.residual(self, self.U, self.R)         # the static residual (no inertia); also Xloc = U + boundary values
+        self.copy(self.xn, self.Xloc)
+        self.axpby(self.Rtry, -1.0, self.R, 0.0)
+        self._mass_solve(self.Rtry, self.an)             # a_0 = -(rho M)^-1 R_static
+        self._started = True
+
+    def _mass_solve(self, b, x, rtol: float = 1e-13, maxit: int = 200):
+        """x = (rho M)^-1 b on the free dofs: Jacobi-preconditioned CG with the fine level's tangent mass operator at coefficient rho."""
+        top = self.nlev - 1
+        M = self.mass[top]
+        M.set_coef(self.density)
+        w = self.w[top]
+        r, z, d, t, dinv = w["r"], w["z"], w["d"], w["t"], w["x"]
+        M.diagonal(dinv)
+        dinv.reciprocal()
+        x.set_value(0.0)
+        self.copy(r, b)
+        z.pointwise_mult(r, dinv); self.copy(d, z)
+        rz = rz0 = self.dot(r, z, True)
+        for _ in range(maxit):
+            if rz0 <= 0.0:
+                break
+            M.apply(d, t)
+            alpha = rz / self.dot(d, t, True)
+            self.axpby(x, alpha, d, 1.0); self.axpby(r, -alpha, t, 1.0)
+            z.pointwise_mult(r, dinv)
+            rz_new = self.dot(r, z, True)
+            if rz_new <= rtol ** 2 * rz0:
+                break
+            self.axpby(d, 1.0, z, rz_new / rz)
+            rz = rz_new
+        M.set_coef(self.a0 * self.density)
+
+    # ---- one step ------------------------------------------------------------------------------------------------------------
+    def step(self) -> SolveStats:
+        """Advance (u, v, a) from t to t + dt; returns this step's SolveStats (``history``: (step count, Newton iteration, Krylov
+        iterations, line-search step, |R|) per Newton iteration)."""
+        if not self._started:
+            self.set_initial()
+        st = self.stats = SolveStats()
+        t0 = time.perf_counter()
+        self.t += self.dt
+        self.load = float(self._load_fn(self.t))
+        self._set(self.bcv, self.bc_values(self.load))
+        # pred = -(a0 x_n + a2 v_n + a3 a_n)
+        self._pred.waxpby(-self.a0, self.xn, -self.a2, self.vn)
+        self.axpby(self._pred, -self.a3, self.an, 1.0)
+        self.residual(self.U, self.R)                    # the start of the iteration: u_n on the free dofs
+        rnorm0 = rnorm = np.sqrt(self.dot(self.R, self.R, True))
+        st.initial_residuals.append(rnorm0)
+        if self.verbose:
+            print(f"t = {self.t:.6g}: |R| = {rnorm0:.6e}")
+        for it in range(self.snes_maxit):
+            if rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50:
+                break
+            self.setup_preconditioner()
+            self.record_preconditioner(self.w[self.nlev - 1]["b"], self.kz)
+            self.axpby(self.Rtry, -1.0, self.R, 0.0)
+            k = self.fcg(self.Rtry, self.dU, self.ksp_rtol)
+            st.ksp_its += k
+            lam = self._line_search()
+            self.axpby(self.U, lam, self.dU, 1.0)
+            self.residual(self.U, self.R)                # also refreshes the stored state and Xloc
+            rnorm = np.sqrt(self.dot(self.R, self.R, True))
+            st.newton_its += 1
+            st.history.append((1, it + 1, k, lam, rnorm))
+            if self.verbose:
+                print(f"   newton {it + 1:2d}: ksp its {k:3d}  lambda {lam:.4f}  |R| = {rnorm:.6e}")
+        st.converged = bool(np.isfinite(rnorm) and (rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50))
+        st.increments = 1
+        self.last_rnorm = float(rnorm)
+        # a_{n+1} = a0 x_{n+1} + pred;  v_{n+1} = v_n + dt ((1 - gamma) a_n + gamma a_{n+1});  Xloc is x_{n+1} (the last residual's)
+        self._acc.waxpby(self.a0, self.Xloc, 1.0, self._pred)
+        self.axpby(self.vn, self.dt * (1.0 - self.gamma), self.an, 1.0)
+        self.axpby(self.vn, self.dt * self.gamma, self._acc, 1.0)
+        self.copy(self.an, self._acc)
+        self.copy(self.xn, self.Xloc)
+        self.ceed.synchronize()
+        st.seconds = time.perf_counter() - t0
+        if self._pc_graph is not None:
+            self._pc_graph.destroy()
+            self._pc_graph = None
+        return st
+
+    def _line_search(self) -> float:
+        """The parent's critical-point secant search on phi(l) = dU . R(U + l dU) ("cp"), or l = 1 ("full")."""
+        lam, lam_old = 1.0, 0.0
+        if self.line_search == "full":
+            return lam
+        phi_old = self.dot(self.dU, self.R, True)
+        for _ in range(3):
+            self.copy(self.Utry, self.U); self.axpby(self.Utry, lam, self.dU, 1.0)
+            self.residual(self.Utry, self.Rtry)
+            phi = self.dot(self.dU, self.Rtry, True)
+            if abs(phi) <= 1e-8 * abs(phi_old) or abs(phi - phi_old) < 1e-300:
+                break
+            lam_new = lam - phi * (lam - lam_old) / (phi - phi_old)
+            if not np.isfinite(lam_new) or abs(lam_new - lam) < 1e-8 or lam_new <= 0.0 or lam_new > 10.0:
+                break
+            lam_old, phi_old, lam = lam, phi, lam_new
+        return lam
+
+    def run(self, nsteps: int, load: Union[float, Callable[[float], float], None] = None) -> dict:
+        """``nsteps`` steps from the current state (``set_initial`` first; ``load`` given here replaces its load function).  Returns the
+        history: per step t, |u| and max |u| over the free dofs, the kinetic energy 1/2 v . rho M v, Newton and Krylov counts, the last
+        Newton residual norm and whether the step converged."""
+        if load is not None:
+            self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+        if not self._started:
+            self.set_initial(load=self._load_fn)
+        h = {k: [] for k in ("t", "norm_u", "max_u", "kinetic", "newton_its", "ksp_its", "rnorm", "converged")}
+        for _ in range(nsteps):
+            st = self.step()
+            u = self.U.to_numpy()
+            h["t"].append(self.t); h["norm_u"].append(float(np.sqrt(np.square(u).sum()))); h["max_u"].append(float(np.abs(u).max()))
+            h["kinetic"].append(self.kinetic_energy())
+            h["newton_its"].append(st.newton_its); h["ksp_its"].append(st.ksp_its)
+            h["rnorm"].append(self.last_rnorm); h["converged"].append(st.converged)
+            if not st.converged:
+                break
+        return h
+
+    def destroy_mass(self):
+        for m in self.mass + [self.mass_res]:
+            m.destroy()

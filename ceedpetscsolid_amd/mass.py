@@ -1,0 +1,146 @@
+"""The mass operator of the elastodynamic solve: y = c B^T (w det J) B x on the three displacement components of a multigrid level.
+
+    (M x)_a,c = c sum_e sum_q N_a(q) w_q det J_e(q) sum_b N_b(q) x_b,c
+
+N the tensor Lagrange functions of the level's basis (P nodes per direction on the Gauss-Lobatto points), the quadrature the level's own
+(``lv.basisu``: Q Gauss points per direction, Q >= P, exact for the products N_a N_b on affine elements), w det J component 0 of the
+level's quadrature data, c a coefficient (the density, or a0 x density in the effective tangent K + a0 M of ``dynamics.NewmarkPMG``).
+
+On the device this is the library's operator graph of the QFunction ``Mass`` (include/ceed.h; csrc/kernels_mass.hip): u INTERP active,
+qdata NONE passive, v INTERP active, the coefficient in the context.  Where the library has no functor of that name
+(``Ceed.has_qfunction``: the CPU oracle), or with ``portable=True``, the same sums are formed in NumPy: plain ``einsum`` in float64 with
+the 1-D table of ``lv.basisu`` and component 0 of the quadrature data read back once, element contributions added in element order.  The
+portable form is the device tests' yardstick, as the surface loads' is.
+
+Dirichlet mask (the level's, unless a restriction of the caller's is given): masked entries of x read as zero (``mask_mode`` 3, the
+tangent's form) or as they are (``mask_mode`` 2, the residual's form: x carries the boundary values); masked rows of y are stored as
+zeros by ``apply`` and left alone by ``apply_add``; the diagonal is zero there.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import ceed as cd
+from .solid import SolidProblem
+
+
+class MassOperator:
+    def __init__(self, prob: SolidProblem, level: int, coef: float, portable: Optional[bool] = None,
+                 rstr: Optional[cd.ElemRestriction] = None, offsets=None, mask_mode: int = 3):
+        """``rstr`` / ``offsets``: a restriction of the caller's on the level's elements and nodes-per-element (and its component-0
+        offsets, [nelem][P^3], for the portable form) in place of the level's own -- the element-discontinuous one of
+        ``assembly.AssembledLevel``; no mask is applied then."""
+        c = self.ceed = prob.ceed
+        self.L = c.L
+        lv = self.lv = prob.levels[level]
+        self.P, self.Q, self.ne = lv.degree + 1, lv.Q, prob.mesh.nelem
+        self.coef = float(coef)
+        if mask_mode not in (2, 3):
+            raise ValueError(f"mask_mode must be 2 (rows dropped) or 3 (rows dropped, input read as zero), not {mask_mode!r}")
+        self.mask_mode = mask_mode
+        own = rstr is None
+        self.rstr = lv.Erestrictu if own else rstr
+        self.lsize = lv.dofmap.lsize if own else int(rstr.lsize)
+        off = lv.dofmap.offsets() if own else offsets
+        if off is None:
+            raise ValueError("a restriction of the caller's needs its offsets too")
+        self.offsets = np.asarray(off, dtype=np.int64).reshape(self.ne, self.P ** 3)
+        self.mask = (np.asarray(lv.mask).reshape(-1)[:self.lsize] != 0) if own and prob.fused_bc else None
+        self.portable = (not c.has_qfunction("Mass")) if portable is None else bool(portable)
+        self._B = self._W = None
+        self.qf = self.op = None
+        if not self.portable:
+            self.qf = c.qfunction("Mass", source="qfunctions/mass.h:Mass")
+            self.qf.add_input("u", 3, cd.EVAL_INTERP).add_input("qdata", 10, cd.EVAL_NONE).add_output("v", 3, cd.EVAL_INTERP)
+            self.qf.set_context([self.coef])
+            self.op = c.operator(self.qf)
+            self.op.set_field("u", self.rstr, lv.basisu, "active")
+            self.op.set_field("qdata", lv.Erestrictqdi, None, lv.qdata)
+            self.op.set_field("v", self.rstr, lv.basisu, "active")
+            if self.mask is not None:
+                self.op.set_dirichlet_mask_mode(self.mask.astype(np.uint8), None, mask_mode)
+
+    @property
+    def kernel_name(self) -> str:
+        return "portable" if self.op is None else self.op.kernel_name
+
+    def set_coef(self, coef: float):
+        """The coefficient of the next applies (the context is borrowed and re-read; a recorded apply keeps the value it was made with)."""
+        self.coef = float(coef)
+        if self.qf is not None:
+            self.qf._ctx[0] = self.coef
+
+    # ---- the portable form: NumPy on host arrays ---------------------------------------------------------------------------
+    def _tables(self):
+        if self._B is None:
+            Q = self.Q
+            self._B = self.lv.basisu.interp1d                                                   # [q][p]
+            self._W = self.lv.qdata.to_numpy().reshape(self.ne, 10, Q, Q, Q)[:, 0].copy()       # w det J, [e][kk][b][a]
+        return self._B, self._W
+
+    def _sum(self, ve: np.ndarray) -> np.ndarray:
+        """Element results [e][n][3] added into an L-vector in element order."""
+        out = np.zeros((self.lsize // 3 + 1, 3))
+        np.add.at(out, (self.offsets // 3).reshape(-1), ve.reshape(-1, 3))
+        return out.reshape(-1)[:self.lsize]
+
+    def apply_host(self, x) -> np.ndarray:
+        """M x as an L-vector (NumPy); masked rows are NOT dropped here (``apply`` / ``apply_add`` do)."""
+        B, W = self._tables()
+        P = self.P
+        x = np.asarray(x, dtype=np.float64).reshape(-1)[:self.lsize]
+        if self.mask is not None and self.mask_mode & 1:
+            x = np.where(self.mask, 0.0, x)
+        xp = np.concatenate([x, np.zeros(3)])
+        ue = xp[(self.offsets[:, :, None] + np.arange(3)).reshape(-1)].reshape(self.ne, P, P, P, 3)      # [e][k][j][i][c]
+        uq = np.einsum("ai,bj,dk,ekjic->edbac", B, B, B, ue)
+        vq = uq * (self.coef * W)[..., None]
+        return self._sum(np.einsum("ai,bj,dk,edbac->ekjic", B, B, B, vq).reshape(self.ne, P ** 3, 3))
+
+    def diagonal_host(self) -> np.ndarray:
+        B, W = self._tables()
+        B2 = B * B
+        de = np.einsum("ai,bj,dk,edba->ekji", B2, B2, B2, self.coef * W).reshape(self.ne, self.P ** 3)
+        d = self._sum(np.repeat(de[:, :, None], 3, axis=2))
+        if self.mask is not None:
+            d[self.mask] = 0.0
+        return d
+
+    def _store_host(self, y: cd.Vector, r: np.ndarray, add: bool):
+        v = y.to_numpy().copy() if add else np.zeros(y.n)
+        if self.mask is not None:
+            r = np.where(self.mask, 0.0, r)
+        v[:self.lsize] += r
+        y.fill(v)
+
+    # ---- on vectors of the Ceed ----------------------------------------------------------------------------------------------
+    def apply(self, x: cd.Vector, y: cd.Vector):
+        """y = M x (masked rows zero)."""
+        if self.op is not None:
+            self.op.apply(x, y)
+        else:
+            self._store_host(y, self.apply_host(x.to_numpy()), False)
+
+    def apply_add(self, x: cd.Vector, y: cd.Vector):
+        """y += M x (masked rows and everything beyond the L-size left alone)."""
+        if self.op is not None:
+            self.op.apply_add(x, y)
+        else:
+            self._store_host(y, self.apply_host(x.to_numpy()), True)
+
+    def diagonal(self, d: cd.Vector):
+        """d = diag M: c sum_q N_a(q)^2 w det J(q), the same for the three components; zero on masked rows."""
+        if self.op is not None:
+            self.op.assemble_diagonal(d)
+        else:
+            v = np.zeros(d.n)
+            v[:self.lsize] = self.diagonal_host()
+            d.fill(v)
+
+    def destroy(self):
+        for o in (self.op, self.qf):
+            if o is not None:
+                o.destroy()
+        self.op = self.qf = None

@@ -71,6 +71,8 @@ class SolveStats:
 
 
 class NewtonPMG:
+    _asm_kwargs: dict = {}          # keywords of the assembled coarse level (dynamics.NewmarkPMG: its mass term); none here
+
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None,
                  halo=None, rccl="auto", lead_elements: int = 0, smooth_its: int = 3, coarse_rtol: float = 1e-3, coarse_maxit: int = 200,
                  coarse: str = "cg", coarse_cheb_its: int = 40, coarse_cheb_ratio: float = 100.0, graph: bool = False,
@@ -165,7 +167,7 @@ class NewtonPMG:
             # "local product, then the interface sum" like the matrix-free levels); with "amg" the first transfer of the aggregation
             # hierarchy is distributed over the ranks and everything under it is small and replicated (amg.py, round 5; rounds 3-4
             # all-gathered all element matrices and replicated the whole level)
-            self.asm = AssembledLevel(prob, 0)
+            self.asm = AssembledLevel(prob, 0, **self._asm_kwargs)
             if coarse == "amg":
                 from .amg import AggregationAMG
                 self.amg = AggregationAMG(self.asm, verbose=verbose, max_coarse_dofs=amg_max_coarse_dofs,
@@ -412,7 +414,7 @@ class NewtonPMG:
                 if n_bad:
                     raise RuntimeError(f"smoother='pbjacobi': {n_bad} nodal blocks of level {lv} have a non-positive or non-finite pivot")
             else:
-                self.p.get_diag(lv, w["dinv"])
+                self._get_diag(lv, w["dinv"])
                 self._halo_sum(lv, w["dinv"])
                 # 1 / diagonal; constrained rows come out of the masked operator as zeros and stay zero (CeedVectorReciprocal
                 # leaves zeros alone): residuals and corrections are zero there anyway.  No trip through the host.
@@ -436,6 +438,10 @@ class NewtonPMG:
             # the largest eigenvalue of its Lanczos tridiagonal -- what KSPChebyshevEstEig does (elasticity.c:546-549).
             # (A plain power iteration from the same vector was 2x low after 12 steps on the config-3 mesh.)
             self.emax[lv] = lanczos_emax(*(self._lanczos_host(lv, 10) if (self.halos and not self.rhalos) else self._lanczos_device(lv, 10)))
+
+    def _get_diag(self, lv, d):
+        """The diagonal of level lv's operator (a subclass with more terms in its operator adds theirs)."""
+        self.p.get_diag(lv, d)
 
     def _lanczos_host(self, lv, steps):
         """CG coefficients with every dot product read on the host (several ranks: the dots are all-reduced)."""

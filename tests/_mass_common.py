@@ -1,0 +1,103 @@
+"""What the CPU and the device tests of the mass operator and the Newmark solve share: dense matrices from unit-vector applies, the
+generalised eigenproblem, and the two solver checks (the exact discrete solution of the average-acceleration rule on an eigenvector;
+the recomputed dynamic residual of a finite-strain run).  The same code runs on the CPU oracle and on the device."""
+import numpy as np
+
+from ceedpetscsolid_amd.dynamics import NewmarkPMG
+from ceedpetscsolid_amd.mass import MassOperator
+from ceedpetscsolid_amd.mesh import box_mesh
+from ceedpetscsolid_amd.solid import SolidProblem
+
+E, NU, RHO = 1.0, 0.3, 1.5
+
+
+def dense_from_applies(ceed, n, apply, cols):
+    """Columns ``cols`` of the n x n matrix of ``apply(x, y)``."""
+    X, Y = ceed.vector(n), ceed.vector(n)
+    A = np.zeros((n, len(cols)))
+    for k, j in enumerate(cols):
+        e = np.zeros(n)
+        e[j] = 1.0
+        X.set_array(e)
+        apply(X, Y)
+        A[:, k] = Y.to_numpy()
+    X.destroy(); Y.destroy()
+    return A
+
+
+def dense_K_M(ceed, prob, density):
+    """(K, M, free): stiffness of the undeformed state and density x mass, free-free blocks, of the fine level."""
+    lv = prob.levels[prob.fine]
+    n = prob.lsize()
+    free = np.nonzero(lv.mask == 0)[0]
+    K = dense_from_applies(ceed, n, lambda x, y: prob.apply_jacobian(prob.fine, x, y), free)[free]
+    mop = MassOperator(prob, prob.fine, density)
+    M = dense_from_applies(ceed, n, mop.apply, free)[free]
+    mop.destroy()
+    return K, M, free
+
+
+def lowest_mode(K, M):
+    """(omega, phi) of the lowest mode of K phi = omega^2 M phi: Cholesky of M, then eigh."""
+    L = np.linalg.cholesky(0.5 * (M + M.T))
+    A = np.linalg.solve(L, np.linalg.solve(L, 0.5 * (K + K.T)).T).T
+    w2, Y = np.linalg.eigh(0.5 * (A + A.T))
+    return float(np.sqrt(w2[0])), np.linalg.solve(L.T, Y[:, 0])
+
+
+def eigenvector_run(ceed, nsteps=40, steps_per_period=20, **solver_kw):
+    """A 2 x 1 x 1 box, p = 2, linElas, the end x = 0 clamped, released from its lowest mode with beta = 1/4, gamma = 1/2: the scheme's
+    exact solution is u_n = phi cos(n theta), theta = 2 atan(omega dt / 2).  Returns (worst |u_n - exact| / |phi|, worst relative
+    energy drift, the bound 10 nsteps cond(K + a0 M) 1e-10, theta, the theta measured from u_1 . M phi)."""
+    prob = SolidProblem(ceed, box_mesh(2, 1, 1), 2, "linElas", nu=NU, E=E, bc_sides=[6])
+    K, M, free = dense_K_M(ceed, prob, RHO)
+    w, phi = lowest_mode(K, M)
+    phi *= 0.01 / np.abs(phi).max()
+    dt = 2.0 * np.pi / w / steps_per_period
+    theta = 2.0 * np.arctan(0.5 * w * dt)
+    sol = NewmarkPMG(prob, RHO, dt, ksp_rtol=1e-10, snes_rtol=1e-10, **solver_kw)
+    bound = 10.0 * nsteps * np.linalg.cond(K + sol.a0 * M) * 1e-10
+    u0 = np.zeros(prob.lsize())
+    u0[free] = phi
+    sol.set_initial(u0=u0)
+    energy = lambda: 0.5 * (sol.vn.to_numpy()[free] @ M @ sol.vn.to_numpy()[free]) + 0.5 * (sol.xn.to_numpy()[free] @ K @ sol.xn.to_numpy()[free])
+    e0 = energy()
+    worst_u = worst_e = 0.0
+    theta_meas = None
+    for n in range(1, nsteps + 1):
+        st = sol.step()
+        assert st.converged, (n, st.history)
+        u = sol.U.to_numpy()[free]
+        if n == 1:
+            theta_meas = float(np.arccos(np.clip((u @ M @ phi) / (phi @ M @ phi), -1.0, 1.0)))
+        worst_u = max(worst_u, np.linalg.norm(u - phi * np.cos(n * theta)) / np.linalg.norm(phi))
+        worst_e = max(worst_e, abs(energy() - e0) / e0)
+    sol.destroy_mass()
+    prob.destroy()
+    return worst_u, worst_e, bound, theta, theta_meas
+
+
+def hyperfs_run(ceed, mesh, nsteps, dt=0.4, **solver_kw):
+    """hyperFS, p = 2, side 1 clamped, a body force switched on at t = 0.  After every step the dynamic residual
+    F_int(u) + rho M a - load f on the free dofs, recomputed here from the solver's (u, a) with the portable mass operator, is compared
+    with the last Newton residual norm.  Returns (solver, [(recomputed norm, last Newton norm)], per-step stats)."""
+    prob = SolidProblem(ceed, mesh, 2, "hyperFS", nu=NU, E=E, bc_sides=[1])
+    n = prob.lsize()
+    lv = prob.levels[prob.fine]
+    free = lv.mask == 0
+    force = np.tile([0.002, 0.0, 0.001], n // 3)          # nodal forces: the tip moves by about half the body's size in five steps (finite strain)
+    sol = NewmarkPMG(prob, RHO, dt, forcing=force, snes_rtol=1e-10, **solver_kw)
+    ref = MassOperator(prob, prob.fine, RHO, portable=True, mask_mode=2)
+    sol.set_initial()
+    X, Y = ceed.vector(n), ceed.vector(n)
+    out, stats = [], []
+    for _ in range(nsteps):
+        st = sol.step()
+        assert st.converged, st.history
+        stats.append(st)
+        X.set_array(sol.xn.to_numpy())
+        prob.form_residual(X, Y)                                  # F_int, constrained rows dropped
+        r = Y.to_numpy() + ref.apply_host(sol.an.to_numpy()) - sol.load * force
+        out.append((float(np.linalg.norm(r[free])), sol.last_rnorm))
+    X.destroy(); Y.destroy()
+    return sol, prob, out, stats

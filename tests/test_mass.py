@@ -1,0 +1,172 @@
+"""The mass operator's portable form (mass.py) and the Newmark solve (dynamics.py) on the CPU oracle: integrals with closed forms, the
+algebra of the operator, and the time stepping against the exact discrete solution."""
+import numpy as np
+import pytest
+
+from _mass_common import E, NU, RHO, dense_from_applies, eigenvector_run, hyperfs_run
+from ceedpetscsolid_amd.assembly import AssembledLevel
+from ceedpetscsolid_amd.dynamics import NewmarkPMG
+from ceedpetscsolid_amd.mass import MassOperator
+from ceedpetscsolid_amd.mesh import box_mesh, hollow_cylinder_mesh
+from ceedpetscsolid_amd.solid import SolidProblem
+from ceedpetscsolid_amd.solver import NewtonPMG
+
+
+def component_field(n, c):
+    x = np.zeros((n // 3, 3))
+    x[:, c] = 1.0
+    return x.reshape(-1)
+
+
+def test_oracle_takes_the_portable_form(oracle):
+    assert not oracle.has_qfunction("Mass")
+    prob = SolidProblem(oracle, box_mesh(1, 1, 1), 1, "linElas", nu=NU, E=E, multigrid="none")
+    m = MassOperator(prob, 0, 1.0)
+    assert m.portable and m.kernel_name == "portable"
+    prob.destroy()
+
+
+@pytest.mark.parametrize("shape", ["box", "cylinder"])
+def test_total_mass_is_density_times_volume(oracle, shape):
+    mesh = box_mesh(2, 1, 2) if shape == "box" else hollow_cylinder_mesh(1, 8, 2, z0=-1.0, z1=1.0)
+    prob = SolidProblem(oracle, mesh, 3, "linElas", nu=NU, E=E, multigrid="none")
+    n = prob.lsize()
+    vol = prob.qdata.to_numpy().reshape(mesh.nelem, 10, -1)[:, 0].sum()
+    if shape == "box":
+        assert abs(vol - 1.0) < 1e-13
+    else:            # the ring's cross-section is an octagonal one: between the inscribed and the exact annulus
+        assert 0.85 * np.pi * 0.75 * 2.0 < vol < np.pi * 0.75 * 2.0
+    m = MassOperator(prob, 0, RHO)
+    X, Y = oracle.vector(n), oracle.vector(n)
+    for c in range(3):
+        X.set_array(component_field(n, c))
+        m.apply(X, Y)
+        y = Y.to_numpy().reshape(-1, 3)
+        assert abs(y[:, c].sum() - RHO * vol) <= 1e-13 * RHO * vol
+        assert np.abs(np.delete(y, c, axis=1)).max() == 0.0
+    prob.destroy()
+
+
+def test_quadratic_form_is_the_integral_of_u_squared(oracle):
+    """u = (x^2 y, y^2 z^2, 1 + x z) on the unit cube, degree <= 2 per direction, p = 2: Q = 3 Gauss points integrate |u|^2 exactly.
+    int |u|^2 = 1/15 + 1/25 + (1 + 1/2 + 1/9)."""
+    prob = SolidProblem(oracle, box_mesh(2, 1, 1), 2, "linElas", nu=NU, E=E, multigrid="none")
+    X = prob.levels[0].dofmap.node_coords
+    u = np.stack([X[:, 0] ** 2 * X[:, 1], X[:, 1] ** 2 * X[:, 2] ** 2, 1.0 + X[:, 0] * X[:, 2]], axis=1).reshape(-1)
+    m = MassOperator(prob, 0, RHO)
+    exact = RHO * (1.0 / 15 + 1.0 / 25 + 1.0 + 0.5 + 1.0 / 9)
+    assert abs(u @ m.apply_host(u) - exact) <= 1e-13 * exact
+    prob.destroy()
+
+
+def test_symmetry_positive_diagonal_and_diagonal_entry_point(oracle):
+    prob = SolidProblem(oracle, hollow_cylinder_mesh(1, 4, 1, z0=0.0, z1=1.0), 2, "linElas", nu=NU, E=E, bc_sides=[998], qextra=1)
+    n = prob.lsize()
+    m = MassOperator(prob, prob.fine, RHO)
+    M = dense_from_applies(oracle, n, m.apply, range(n))
+    assert np.abs(M - M.T).max() <= 1e-15 * np.abs(M).max()
+    mask = prob.levels[prob.fine].mask != 0
+    assert np.all(M[mask] == 0.0) and np.all(M[:, mask] == 0.0)
+    D = oracle.vector(n).set_value(7.0)
+    m.diagonal(D)
+    d = D.to_numpy()
+    assert np.all(d[~mask] > 0.0) and np.all(d[mask] == 0.0)
+    assert np.abs(d - np.diag(M)).max() <= 1e-14 * d.max()
+    w = np.linalg.eigvalsh(M[~mask][:, ~mask])
+    assert w.min() > 0.0
+    prob.destroy()
+
+
+def test_mask_semantics(oracle):
+    prob = SolidProblem(oracle, box_mesh(2, 2, 1), 2, "linElas", nu=NU, E=E, bc_sides=[1, 6])
+    n = prob.lsize()
+    mask = prob.levels[prob.fine].mask != 0
+    x = np.random.default_rng(5).uniform(-1, 1, n)
+    m3, m2 = MassOperator(prob, prob.fine, RHO), MassOperator(prob, prob.fine, RHO, mask_mode=2)
+    X, Y = oracle.vector(n).set_array(x), oracle.vector(n + 5).set_value(9.0)
+    m3.apply(X, Y)
+    y = Y.to_numpy()
+    assert np.all(y[:n][mask] == 0.0) and np.all(y[n:] == 0.0)                 # overwrite: masked rows and the tail are zero
+    assert np.array_equal(y[:n], np.where(mask, 0.0, m3.apply_host(np.where(mask, 0.0, x))))      # masked input reads as zero
+    Y.set_value(9.0)
+    m3.apply_add(X, Y)
+    ya = Y.to_numpy()
+    assert np.all(ya[:n][mask] == 9.0) and np.all(ya[n:] == 9.0)               # add: both left alone
+    assert np.array_equal(ya[:n][~mask], (9.0 + y[:n])[~mask])
+    y2 = m2.apply_host(x)                                                      # the residual's form reads the boundary values
+    assert np.abs(y2 - m3.apply_host(x))[~mask].max() > 1e-3
+    free = MassOperator(SolidProblem(oracle, box_mesh(2, 2, 1), 2, "linElas", nu=NU, E=E, multigrid="none"), 0, RHO)
+    assert np.array_equal(y2[~mask], free.apply_host(x)[~mask])
+    prob.destroy()
+
+
+def test_assembled_level_carries_the_mass_term(oracle):
+    prob = SolidProblem(oracle, box_mesh(2, 2, 1), 2, "linElas", nu=NU, E=E, bc_sides=[1])
+    coef = 2.5
+    asm = AssembledLevel(prob, 0, mass_coef=coef)
+    asm.assemble()
+    n = prob.lsize(0)
+    mask = prob.levels[0].mask != 0
+    x = np.random.default_rng(3).uniform(-1, 1, n) * ~mask
+    X, Y, Z = oracle.vector(n).set_array(x), oracle.vector(n), oracle.vector(n)
+    asm.apply(X, Y)
+    prob.apply_jacobian(0, X, Z)
+    m = MassOperator(prob, 0, coef)
+    m.apply_add(X, Z)
+    y, z = Y.to_numpy(), Z.to_numpy()
+    assert np.abs(y - z)[~mask].max() <= 1e-13 * np.abs(z).max()
+    plain = AssembledLevel(prob, 0)
+    assert plain.mass is None
+    asm.destroy(); plain.destroy(); prob.destroy()
+
+
+def test_newmark_reproduces_the_exact_discrete_solution(oracle):
+    worst_u, worst_e, bound, theta, theta_meas = eigenvector_run(oracle)
+    print(f"eigenvector run: worst |u_n - phi cos(n theta)| / |phi| = {worst_u:.3e}, worst energy drift {worst_e:.3e}, bound {bound:.3e}; "
+          f"theta exact {theta:.12f}, measured {theta_meas:.12f}")
+    assert worst_u <= bound
+    assert worst_e <= bound
+
+
+def test_hyperfs_dynamic_residual_identity(oracle):
+    sol, prob, out, stats = hyperfs_run(oracle, box_mesh(2, 1, 1), 3)
+    for k, (rec, last) in enumerate(out):
+        print(f"step {k + 1}: recomputed |F_int + rho M a - load f| = {rec:.3e}, last Newton |R| = {last:.3e}, "
+              f"{stats[k].newton_its} Newton / {stats[k].ksp_its} Krylov its")
+        assert rec <= 10 * last
+    assert np.abs(sol.U.to_numpy()).max() > 1e-3 and sol.kinetic_energy() > 0.0       # the body moves
+    sol.destroy_mass(); prob.destroy()
+
+
+def test_no_density_takes_no_new_path(oracle):
+    """NewtonPMG itself: its assembled level has no mass operator, and the diagonal hook gives the bits of the direct call."""
+    prob = SolidProblem(oracle, box_mesh(2, 1, 1), 2, "hyperFS", nu=NU, E=E, bc_sides=[1])
+    force = 0.01 * np.random.default_rng(2).uniform(-1, 1, prob.lsize())
+
+    class Direct(NewtonPMG):                 # setup_preconditioner's diagonal as it was before the hook existed
+        def _get_diag(self, lv, d):
+            self.p.get_diag(lv, d)
+
+    a = NewtonPMG(prob, forcing=force, coarse="assembled")
+    sa = a.solve(num_increments=1)
+    assert a._asm_kwargs == {} and a.asm.mass is None
+    b = Direct(prob, forcing=force, coarse="assembled")
+    sb = b.solve(num_increments=1)
+    assert (sa.newton_its, sa.ksp_its) == (sb.newton_its, sb.ksp_its)
+    assert np.array_equal(a.U.to_numpy(), b.U.to_numpy()) and np.abs(a.U.to_numpy()).max() > 0
+    prob.destroy()
+
+
+def test_refusals(oracle):
+    prob = SolidProblem(oracle, box_mesh(1, 1, 1), 2, "linElas", nu=NU, E=E, bc_sides=[1])
+    with pytest.raises(ValueError, match="pbjacobi"):
+        NewmarkPMG(prob, RHO, 0.1, smoother="pbjacobi")
+
+    class TwoRanks:
+        world = 2
+
+    with pytest.raises(ValueError, match="several ranks"):
+        NewmarkPMG(prob, RHO, 0.1, halo=[TwoRanks(), TwoRanks()])
+    with pytest.raises(ValueError):
+        NewmarkPMG(prob, 0.0, 0.1)
+    prob.destroy()
