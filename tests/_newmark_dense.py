@@ -1,0 +1,343 @@
+"""Dense references for the Newmark solve (dynamics.NewmarkPMG) and its tangent K + a0 rho M, and the checks that use them; shared by
+tests/test_dynamics_dense.py (the CPU oracle) and tests/test_dynamics_dense_gpu.py (the device).  Every function takes the Ceed under
+test and, where a reference has to come from somewhere else than the code under test, the oracle's Ceed: stiffness columns and the
+portable mass operator are then formed on a problem of the ORACLE and reach the comparison as host arrays only.
+
+References, all plain NumPy in float64 (dense solves refined on a long-double residual):
+  K_full      linElas: column j is form_residual(e_j), boundary columns as they are, constrained rows dropped
+  M_full      columns of the portable mass operator in the residual's form (mask mode 2: boundary columns as they are)
+  recursion   Newmark's rule on full-length x, v, a with a0, a2, a3 computed here from beta and dt
+  level       K_lv + a0 rho M_lv from unit-vector apply_jacobian(lv) and the level's portable mass operator (mask mode 3)
+
+The meshes are _numbering.distorted_box(2, 1, 1): two non-affine elements, one shared face, a partial last group in every packing of
+k_mass, side 1 clamped."""
+import numpy as np
+
+from _mass_common import E, NU, RHO, dense_from_applies
+from _numbering import distorted_box
+from ceedpetscsolid_amd.dynamics import NewmarkPMG
+from ceedpetscsolid_amd.mass import MassOperator
+from ceedpetscsolid_amd.solid import SolidProblem
+
+TOL = 1e-10                  # the project's operator parity bound (tests/test_mass_gpu.py)
+DT_FS = 0.4                  # the finite-strain runs' step
+
+
+def relmax(got, want):
+    """max |got - want| / max |want|."""
+    return float(np.abs(np.asarray(got) - np.asarray(want)).max() / np.abs(want).max())
+
+
+def teardown(sol, prob):
+    sol.destroy_mass()
+    sol.destroy_surface_loads()
+    prob.destroy()
+
+
+# ---- 1. dense references -----------------------------------------------------------------------------------------------------------
+def K_full(prob):
+    """linElas: the internal force is linear, so column j is form_residual(e_j) -- all columns, the boundary's as they are."""
+    assert prob.problem == "linElas"
+    n = prob.lsize()
+    return dense_from_applies(prob.ceed, n, prob.form_residual, range(n))
+
+
+def M_full(prob, level=None, mask_mode=2):
+    """Columns of the portable mass operator of ``level`` (default: the fine one) at coefficient 1; rows are NOT dropped (apply_host)."""
+    level = prob.fine if level is None else level
+    m = MassOperator(prob, level, 1.0, portable=True, mask_mode=mask_mode)
+    n = prob.lsize(level)
+    M = np.zeros((n, n))
+    e = np.zeros(n)
+    for j in range(n):
+        e[j] = 1.0
+        M[:, j] = m.apply_host(e)
+        e[j] = 0.0
+    return M
+
+
+def solve_refined(A, b):
+    """A^-1 b: LAPACK's solve, then two steps of iterative refinement on a residual formed in long double (where long double is no
+    wider than double this is plain float64 refinement: the condition numbers here are a few hundred)."""
+    x = np.linalg.solve(A, b)
+    Al, bl = A.astype(np.longdouble), b.astype(np.longdouble)
+    for _ in range(2):
+        r = (bl - Al @ x.astype(np.longdouble)).astype(np.float64)
+        x = x + np.linalg.solve(A, r)
+    return x
+
+
+def newmark_reference(K, M, free, f, xb, load, u0, v0, rho, dt, beta, gamma, nsteps):
+    """[(x_n, v_n, a_n) for n = 0 .. nsteps], full-length vectors with the boundary entries.  ``K``, ``M``: K_full, M_full; ``f``: the
+    load vector (zero on constrained rows); ``xb(l)``: the boundary values at load fraction l (zero on the free dofs)."""
+    a0, a2, a3 = 1.0 / (beta * dt * dt), 1.0 / (beta * dt), 1.0 / (2.0 * beta) - 1.0
+    fr = np.flatnonzero(free)
+    Mff = rho * M[np.ix_(fr, fr)]
+    Aff = K[np.ix_(fr, fr)] + a0 * Mff
+    l0 = load(0.0)
+    x = u0 * free + xb(l0)
+    v = v0 * free
+    a = np.zeros_like(x)
+    a[fr] = solve_refined(Mff, (l0 * f - K @ x)[fr])
+    out = [(x, v, a)]
+    for k in range(1, nsteps + 1):
+        l = load(k * dt)
+        xn = xb(l)
+        pred = -(a0 * x + a2 * v + a3 * a)
+        rhs = (l * f - K @ xn - rho * (M @ (a0 * xn + pred)))[fr]
+        xn[fr] = solve_refined(Aff, rhs)
+        an = a0 * xn + pred
+        v = v + dt * ((1.0 - gamma) * a + gamma * an)
+        x, a = xn, an
+        out.append((x, v, a))
+    return out
+
+
+def level_reference(prob, lv, coef, unit_diagonal):
+    """(K_lv + coef M_lv, coef M_lv) of ``prob`` in its current stored state: unit-vector apply_jacobian(lv) and the level's portable
+    mass operator, masked rows and columns zero; ``unit_diagonal``: ones on the constrained rows' diagonal (an assembled level)."""
+    n = prob.lsize(lv)
+    mask = prob.levels[lv].mask != 0
+    K = dense_from_applies(prob.ceed, n, lambda x, y: prob.apply_jacobian(lv, x, y), range(n))
+    M = coef * M_full(prob, lv, mask_mode=3)
+    M[mask] = 0.0
+    assert not K[mask].any() and not K[:, mask].any() and not M[:, mask].any()
+    ref = K + M
+    if unit_diagonal:
+        ref[mask, mask] = 1.0
+    return ref, M
+
+
+# ---- the finite-strain set-up of items 2, 3 and 5 -----------------------------------------------------------------------------------
+def hyperfs_solver(ceed, degree, nsteps, prob_kw=None, **solver_kw):
+    """hyperFS on distorted_box(2, 1, 1), side 1 clamped, the nodal force of _mass_common.hyperfs_run switched on at t = 0, ``nsteps``
+    Newmark steps of dt = 0.4 from rest.  Returns (problem, solver)."""
+    prob = SolidProblem(ceed, distorted_box(2, 1, 1), degree, "hyperFS", nu=NU, E=E, bc_sides=[1], **(prob_kw or {}))
+    force = np.tile([0.002, 0.0, 0.001], prob.lsize() // 3)
+    sol = NewmarkPMG(prob, RHO, DT_FS, forcing=force, snes_rtol=1e-10, **solver_kw)
+    sol.set_initial()
+    for _ in range(nsteps):
+        st = sol.step()
+        assert st.converged, st.history
+    return prob, sol
+
+
+# ---- 2. the effective operator, level by level ---------------------------------------------------------------------------------------
+LEVEL_VARIANTS = {       # name -> (SolidProblem keywords, solver keywords, (P, Q) per level)
+    "fine-amg": (dict(coarse_quadrature="fine"), dict(coarse="amg"), [(2, 4), (3, 4), (4, 4)]),
+    "own-cg": (dict(coarse_quadrature="own"), dict(coarse="cg"), [(2, 2), (3, 3), (4, 4)]),
+}
+
+
+def effective_operator_check(ceed, oracle, variant, tag):
+    """Item 2: the dense matrix of NewmarkPMG.A(lv) and the smoother's diagonal on every level of a deformed hyperFS state at p = 3
+    against K_lv + a0 rho M_lv of the oracle problem linearised at the same U.  Returns the figures per level."""
+    prob_kw, sol_kw, pq = LEVEL_VARIANTS[variant]
+    device = ceed is not oracle
+    prob, sol = hyperfs_solver(ceed, 3, 2, prob_kw, **sol_kw)
+    assert [(lv.degree + 1, lv.Q) for lv in prob.levels] == pq
+    sol.residual(sol.U, sol.R)
+    sol.setup_preconditioner()
+    U = sol.U.to_numpy()
+    if device:                       # the reference's state: the oracle's problem linearised at the device's U (host array)
+        rprob, rsol = hyperfs_solver(oracle, 3, 2, prob_kw, **sol_kw)
+        rsol._set(rsol.U, U)
+        rsol.residual(rsol.U, rsol.R)
+    else:
+        rprob, rsol = prob, sol
+    coef = 1.0 / (0.25 * DT_FS * DT_FS) * RHO                   # a0 rho, computed here
+    assert sol.a0 * sol.density == coef
+    figures = []
+    for lv in range(sol.nlev):
+        n = prob.lsize(lv)
+        mask = prob.levels[lv].mask != 0
+        assembled = lv == 0 and sol.asm is not None
+        ref, Mterm = level_reference(rprob, lv, coef, assembled)
+        A = dense_from_applies(ceed, n, lambda x, y: sol.A(lv, x, y), range(n))
+        P, Q = pq[lv]
+        if device:
+            if assembled:            # the matrix holds the mass term: its columns came from the element-discontinuous operator
+                assert sol.asm.mass.kernel_name == f"mass<{P},{Q}>"
+                X, Y = ceed.vector(n).set_value(0.0), ceed.vector(n).set_value(0.0)
+                sol.mass[lv].apply_add(X, Y)
+                X.destroy(); Y.destroy()
+            assert sol.mass[lv].kernel_name == f"mass<{P},{Q}>", (lv, sol.mass[lv].kernel_name)
+        e_op = relmax(A, ref)
+        if assembled:
+            off = A.copy()
+            off[mask, mask] -= 1.0
+            assert not off[mask].any() and not off[:, mask].any(), "assembled level: constrained rows / columns are not the unit diagonal"
+        else:
+            assert not A[mask].any() and not A[:, mask].any(), f"level {lv}: constrained rows / columns are not zero"
+        # the smoother's diagonal is the matrix-free operator's on every level: zero (not one) on the constrained rows
+        want_d = np.where(mask, 0.0, np.diag(ref))
+        D1, D2 = ceed.vector(n).set_value(3.0), ceed.vector(n).set_value(5.0)
+        sol._get_diag(lv, D1)
+        assert lv in sol._mdiag
+        sol._get_diag(lv, D2)
+        d1, d2 = D1.to_numpy(), D2.to_numpy()
+        D1.destroy(); D2.destroy()
+        e_diag = relmax(d1, want_d)
+        share = float(np.abs(Mterm).max() / np.abs(ref).max())
+        e_sym = float(np.abs(A - A.T).max() / np.abs(A).max())
+        figures.append(dict(level=lv, P=P, Q=Q, n=n, operator=e_op, diagonal=e_diag, mass_share=share, asymmetry=e_sym))
+        print(f"DENSE item 2 {tag} {variant} level {lv} (P, Q) = ({P}, {Q}), {n} dofs: |A - ref| / max|ref| = {e_op:.2e}, diagonal {e_diag:.2e}, "
+              f"max|a0 rho M| / max|ref| = {share:.2f}, |A - A^T| / max|A| = {e_sym:.2e}")
+        assert e_op <= TOL, (lv, e_op)
+        assert e_diag <= TOL, (lv, e_diag)
+        assert np.array_equal(d1, d2), f"level {lv}: the second diagonal differs from the first"
+        assert np.all(d1[mask] == 0.0)
+        assert share >= 0.1, (lv, share)
+        if not device:
+            assert e_sym <= 1e-14, (lv, e_sym)
+    umax = float(np.abs(U).max())
+    print(f"DENSE item 2 {tag} {variant}: max |u| = {umax:.3f}")
+    assert umax > 0.1                                           # a deformed state: the tangent is not the undeformed one
+    if device:
+        teardown(rsol, rprob)
+    teardown(sol, prob)
+    return figures
+
+
+# ---- 3. the tangent is the derivative of the residual --------------------------------------------------------------------------------
+def tangent_fd_check(ceed, tag):
+    """Item 3: central differences of NewmarkPMG.residual at U +- h v against A_outer(top) v on the free rows, hyperFS p = 2 with a
+    follower pressure, after three steps; and the two controls (no pressure tangent; no mass term), which must miss."""
+    prob, sol = hyperfs_solver(ceed, 2, 3, pressure={2: 0.02})
+    n, top = prob.lsize(), sol.nlev - 1
+    free = sol.free
+    v = np.random.default_rng(31).uniform(-1, 1, n) * free
+    U = sol.U.to_numpy()
+    Ut, Rt, V, Y = (ceed.vector(n).set_value(0.0) for _ in range(4))
+    fd = {}
+    for h in (1e-4, 1e-5):
+        r = []
+        for s in (1.0, -1.0):
+            Ut.set_array(U + s * h * v)
+            sol.residual(Ut, Rt)
+            r.append(Rt.to_numpy())
+        fd[h] = (r[0] - r[1]) / (2.0 * h)
+    sol.residual(sol.U, sol.R)                                  # the stored state and Xloc are those of U again
+    V.set_array(v)
+    outs = {}
+    for name, apply in (("A_outer", lambda: sol.A_outer(top, V, Y)), ("A", lambda: sol.A(top, V, Y)),
+                        ("jacobian", lambda: prob.apply_jacobian(top, V, Y))):
+        Y.set_value(0.0)
+        apply()
+        outs[name] = Y.to_numpy()
+    scale = np.abs(outs["A_outer"][free]).max()
+    err = lambda y, h: float(np.abs(y - fd[h])[free].max() / scale)
+    e4, e5 = err(outs["A_outer"], 1e-4), err(outs["A_outer"], 1e-5)
+    c_press, c_mass = err(outs["A"], 1e-5), err(outs["jacobian"], 1e-5)
+    print(f"DENSE item 3 {tag}: |A_outer v - FD| / max|A_outer v| = {e4:.3e} (h = 1e-4), {e5:.3e} (h = 1e-5), ratio {e4 / e5:.1f}; controls at "
+          f"h = 1e-5: without the pressure tangent {c_press:.3e}, without the mass term {c_mass:.3e}")
+    for a in (Ut, Rt, V, Y):
+        a.destroy()
+    teardown(sol, prob)
+    assert e5 <= 1e-7
+    assert 30.0 <= e4 / e5 <= 300.0
+    assert c_press > 1e-5 and c_mass > 1e-5
+    return e4, e5, c_press, c_mass
+
+
+# ---- 4. Newmark against the dense recursion ------------------------------------------------------------------------------------------
+TRANSLATE = (0.02, 0.0, 0.01)
+NEWMARK_VARIANTS = {"average-cg": (0.25, 0.5, "cg"), "damped-amg": (0.3025, 0.6, "amg")}
+
+
+def _load(t):
+    return 0.5 + 0.5 * np.sin(2.0 * t)
+
+
+def newmark_dense_check(ceed, oracle, variant, tag, nsteps=8):
+    """Item 4: eight steps of linElas p = 2 with a moving clamp, a body force, a traction, a load function, u0, v0 and a nonzero a_0
+    against the dense recursion; kinetic_energy(); run() against step()."""
+    beta, gamma, coarse = NEWMARK_VARIANTS[variant]
+    dt, rho = 0.5, 1.5
+    mesh = distorted_box(2, 1, 1)
+    mk = lambda c: SolidProblem(c, mesh, 2, "linElas", nu=NU, E=E, bc_sides=[1])
+    prob = mk(ceed)
+    rprob = mk(oracle) if ceed is not oracle else prob          # the reference matrices: the oracle's
+    n = prob.lsize()
+    rng = np.random.default_rng(53)
+    forcing, u0, v0 = (0.01 * rng.uniform(-1, 1, n) for _ in range(3))
+    sol = NewmarkPMG(prob, rho, dt, beta, gamma, clamp={1: dict(translate=TRANSLATE)}, forcing=forcing, traction={2: (0.0, 0.01, 0.0)},
+                     coarse=coarse, ksp_rtol=1e-12, snes_rtol=1e-11)
+    free = sol.free
+    bound = np.tile(TRANSLATE, n // 3) * ~free                  # every constrained node is on side 1 and carries the translation
+    xb = lambda l: bound * l
+    assert np.array_equal(sol.bc_values(0.7), xb(0.7)) and (~free).any()
+    K, M = K_full(rprob), M_full(rprob)
+    if rprob is not prob:
+        rprob.destroy()
+    f = sol.fv.to_numpy()
+    assert not f[~free].any() and np.abs(f - forcing * free).max() > 1e-4        # the traction is in it
+    ref = newmark_reference(K, M, free, f, xb, _load, u0, v0, rho, dt, beta, gamma, nsteps)
+    fr = np.flatnonzero(free)
+    kinetic = lambda v: 0.5 * float(v[fr] @ (rho * (M @ v))[fr])
+
+    sol.set_initial(u0=u0, v0=v0, load=_load)
+    x, v, a = ref[0]
+    e_a0 = relmax(sol.an.to_numpy(), a)
+    assert np.array_equal(sol.xn.to_numpy(), x) and np.array_equal(sol.vn.to_numpy(), v)
+    assert np.abs(a).max() > 1e-3 and not a[~free].any()        # a nonzero initial acceleration from the mass solve
+    worst = dict(x=0.0, v=0.0, a=0.0, kinetic=0.0)
+    for k in range(1, nsteps + 1):
+        st = sol.step()
+        assert st.converged, (k, st.history)
+        x, v, a = ref[k]
+        assert np.abs(x[~free]).max() > 0 and np.abs(a[~free]).max() > 0         # the boundary moves and accelerates
+        for name, got, want in (("x", sol.xn, x), ("v", sol.vn, v), ("a", sol.an, a)):
+            worst[name] = max(worst[name], relmax(got.to_numpy(), want))
+        ke = kinetic(v)
+        worst["kinetic"] = max(worst["kinetic"], abs(sol.kinetic_energy() - ke) / ke)
+        assert abs(sol.t - k * dt) < 1e-14
+    print(f"DENSE item 4 {tag} {variant} (beta {beta}, gamma {gamma}, coarse {coarse}): |a_0 - ref| / max|ref| = {e_a0:.2e}; worst over "
+          f"{nsteps} steps x {worst['x']:.2e}  v {worst['v']:.2e}  a {worst['a']:.2e}  kinetic energy {worst['kinetic']:.2e}")
+    assert e_a0 <= 1e-12
+    assert worst["x"] <= 1e-9 and worst["v"] <= 1e-9 and worst["a"] <= 1e-9
+    assert worst["kinetic"] <= 1e-9
+
+    # run(2) from the same start against two step() calls from the same start, on the same solver
+    sol.set_initial(u0=u0, v0=v0, load=_load)
+    h = sol.run(2)
+    sol.set_initial(u0=u0, v0=v0, load=_load)
+    t, ke, conv = [], [], []
+    for _ in range(2):
+        st = sol.step()
+        t.append(sol.t); ke.append(sol.kinetic_energy()); conv.append(st.converged)
+    assert h["t"] == t and h["converged"] == conv == [True, True]
+    assert h["kinetic"] == ke, (h["kinetic"], ke)
+    assert abs(ke[1] - kinetic(ref[2][1])) <= 1e-9 * kinetic(ref[2][1])
+    teardown(sol, prob)
+    return e_a0, worst
+
+
+# ---- 5. restart and the coefficient's round trip -------------------------------------------------------------------------------------
+def restart_check(ceed, tag, **solver_kw):
+    """Item 5: set_initial(v0 = 0.01) and three steps, twice on the same solver object: the same bits, and the tangent's coefficient is
+    a0 rho again after the mass solve."""
+    prob = SolidProblem(ceed, distorted_box(2, 1, 1), 2, "hyperFS", nu=NU, E=E, bc_sides=[1])
+    force = np.tile([0.002, 0.0, 0.001], prob.lsize() // 3)
+    sol = NewmarkPMG(prob, RHO, DT_FS, forcing=force, snes_rtol=1e-10, coarse="amg", **solver_kw)
+    top = sol.nlev - 1
+    coef = 1.0 / (0.25 * DT_FS * DT_FS) * RHO
+    triples, its = [], []
+    for _ in range(2):
+        sol.set_initial(v0=0.01)
+        assert sol.mass[top].coef == coef and all(m.coef == coef for m in sol.mass)
+        assert sol.t == 0.0 and np.abs(sol.vn.to_numpy()).max() == 0.01
+        k = []
+        for _ in range(3):
+            st = sol.step()
+            assert st.converged, st.history
+            k.append((st.newton_its, st.ksp_its))
+        its.append(k)
+        triples.append(tuple(w.to_numpy().copy() for w in (sol.U, sol.vn, sol.an)))
+    same = [bool(np.array_equal(p, q)) for p, q in zip(*triples)]
+    diff = [float(np.abs(p - q).max()) for p, q in zip(*triples)]
+    print(f"DENSE item 5 {tag}: second run bitwise the first (U, v, a): {same}, max abs differences {diff}; (Newton, Krylov) per step {its}")
+    teardown(sol, prob)
+    assert np.abs(triples[0][0]).max() > 1e-3
+    assert all(same), diff
+    return same
