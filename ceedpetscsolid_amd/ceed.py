@@ -78,7 +78,8 @@ class CeedLib:
     OPTIONAL = ["CeedXOperatorApplyState", "CeedOperatorLinearAssemblePointBlockDiagonal", "CeedXVectorPointBlockInvert",
                 "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock",
                 "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
-                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction"]
+                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction",
+                "CeedXVectorBlockGram", "CeedXVectorBlockCombine", "CeedXVectorBlockGetLimits"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -474,6 +475,10 @@ class Ceed:
         v.touched()                  # (a device tensor: handed over as a device pointer)
         return v
 
+    def block(self, n: int, k: int, ld: Optional[int] = None) -> "BlockVector":
+        """k columns of length n in one allocation of k * ld doubles (ld = n unless given) in the Ceed's own memory: a BlockVector."""
+        return BlockVector(self, n, k, ld)
+
     def elem_restriction(self, nelem, elemsize, ncomp, compstride, lsize, offsets) -> "ElemRestriction":
         return ElemRestriction(self, nelem, elemsize, ncomp, compstride, lsize, offsets=offsets)
 
@@ -594,6 +599,187 @@ class Vector:
     def destroy(self):
         if self.h:
             self.L.lib.CeedVectorDestroy(C.byref(self.h))
+
+
+# ---- block vectors: CeedXVectorBlockGram / CeedXVectorBlockCombine and their portable forms (NumPy on host arrays) ----------------
+BLOCK_MAX_COLS = 48
+BLOCK_HOST_CHUNK = 1024          # rows per np.add.reduce of the portable Gram matrix: a fixed chunking, so it is deterministic too
+
+
+def block_limits(lib: CeedLib):
+    """(largest column count, rows of a chunk of the library's Gram reduction, its largest number of partial matrices, rows of a chunk
+    of its combination, the combination's largest grid) as CeedXVectorBlockGetLimits reports them; (48, None, None, None, None) where
+    the library lacks the block entry points."""
+    if not lib.has("CeedXVectorBlockGetLimits"):
+        return BLOCK_MAX_COLS, None, None, None, None
+    v = [c_int() for _ in range(5)]
+    lib.chk(lib.lib.CeedXVectorBlockGetLimits(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def block_gram_host(A: np.ndarray, B: np.ndarray, w: Optional[np.ndarray] = None) -> np.ndarray:
+    """G[i][j] = sum_r w[r] (A[i][r] B[j][r]) of host arrays [ka][n], [kb][n]: the products of BLOCK_HOST_CHUNK rows summed by
+    np.add.reduce, the chunks added in row order."""
+    ka, n = A.shape
+    G = np.zeros((ka, B.shape[0]))
+    for c in range(0, n, BLOCK_HOST_CHUNK):
+        T = A[:, None, c:c + BLOCK_HOST_CHUNK] * B[None, :, c:c + BLOCK_HOST_CHUNK]
+        if w is not None:
+            T = w[c:c + BLOCK_HOST_CHUNK] * T
+        G += np.add.reduce(T, axis=2)
+    return G
+
+
+def block_combine_host(Y: np.ndarray, A: np.ndarray, Cm: np.ndarray, beta: float):
+    """Y[j] = sum_i A[i] Cm[i][j] + beta Y[j] in place on host arrays [ky][n], [ka][n]; i in order; beta == 0 does not read Y."""
+    acc = np.zeros(Y.shape)
+    for i in range(A.shape[0]):
+        acc += Cm[i][:, None] * A[i][None, :]
+    Y[...] = acc if beta == 0.0 else acc + beta * Y
+
+
+def _block_check(who: str, n: int, ld: int, ranges):
+    """The checks of csrc/block_args.hpp for the portable form: ranges = (name, first column, count, vector length)."""
+    if n < 1:
+        raise CeedError(f"{who}: the number of rows n must be at least 1 (n = {n}, ld = {ld})")
+    if ld < n:
+        raise CeedError(f"{who}: the leading dimension ld must be at least n (n = {n}, ld = {ld})")
+    for name, x0, kx, length in ranges:
+        if not 1 <= kx <= BLOCK_MAX_COLS:
+            raise CeedError(f"{who}: {name}: a column count must lie in 1 .. 48")
+        if x0 < 0:
+            raise CeedError(f"{who}: {name}: a first column must not be negative")
+        if (x0 + kx) * ld - (ld - n) > length:
+            raise CeedError(f"{who}: {name}: the column range reaches past the end of its vector")
+
+
+class BlockVector:
+    """k columns of length n in ONE allocation of k * ld doubles in the Ceed's own memory (device memory for the product library, host
+    memory for the CPU oracle), column j at element j * ld.  ``owner`` is the CeedVector over the whole allocation, which the block
+    operations (``gram``, ``combine``) take; ``cols[j]`` is an ordinary CeedVector that borrows column j, which operators, the mass apply
+    and the V-cycle take one at a time.
+
+    A column and the owner are two CeedVectors over the same memory, and each carries the validity flags of its mirrors.
+    The rule that keeps them coherent: the memory itself is the only copy that counts.  A block-level write (``combine``, ``fill``,
+    ``zero``) hands every column written over again, which drops a host mirror it may have; a column-level write is not seen here, so
+    every block-level call hands the owner over again first.  Neither ever keeps a host mirror across a write of the other; whoever
+    writes the tensor ``t`` directly calls ``touched()``.  (On the CPU oracle all of them are the same host array and there is nothing to
+    keep coherent.)"""
+
+    def __init__(self, ceed: Ceed, n: int, k: int, ld: Optional[int] = None):
+        import torch
+        self.ceed, self.L, self.n, self.k = ceed, ceed.L, int(n), int(k)
+        self.ld = self.n if ld is None else int(ld)
+        if self.n < 1 or self.k < 1 or self.ld < self.n:
+            raise ValueError(f"a block needs n >= 1, k >= 1 and ld >= n (n = {n}, k = {k}, ld = {ld})")
+        self.on_device = ceed.preferred_memtype == MEM_DEVICE
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.on_device else torch.device("cpu")
+        self.t = torch.zeros(self.k * self.ld, dtype=torch.float64, device=dev)
+        self.owner = self._view(self.t)
+        self.cols = [self._view(self.t[j * self.ld:j * self.ld + self.n]) for j in range(self.k)]
+        self._cvec = {}
+
+    def _view(self, t) -> "Vector":
+        v = self.ceed.vector(t.numel())
+        v.t = t
+        if not self.on_device:
+            v.set_array(t.numpy(), copy=False)
+        v.touched()
+        return v
+
+    def __getitem__(self, j: int) -> "Vector":
+        return self.cols[j]
+
+    def touched(self, first: int = 0, count: Optional[int] = None):
+        """The memory was written behind the vectors: the owner and the columns [first, first + count) are handed over again."""
+        self.owner.touched()
+        for v in self.cols[first:self.k if count is None else first + count]:
+            v.touched()
+
+    # ---- host access (tests, the solver's start vectors and results): through the tensor, never through a vector's mirror ------
+    def to_numpy(self) -> np.ndarray:
+        """A copy [k][n] of the columns (the padding left out)."""
+        if self.on_device:
+            self.ceed.synchronize()
+        return self.t.cpu().numpy().reshape(self.k, self.ld)[:, :self.n].copy()
+
+    def fill(self, arr, first: int = 0):
+        """Columns first .. := the rows of ``arr`` ([count][n], host); the padding is left as it is."""
+        import torch
+        a = _np_f64(arr).reshape(-1, self.n)
+        if self.on_device:
+            self.ceed.synchronize()
+        self.t.view(self.k, self.ld)[first:first + a.shape[0], :self.n].copy_(torch.from_numpy(a))
+        if self.on_device:
+            torch.cuda.current_stream().synchronize()
+        self.touched(first, a.shape[0])
+
+    # ---- the block operations ---------------------------------------------------------------------------------------------------
+    def _portable(self, who: str, symbol: str) -> bool:
+        if self.L.has(symbol):
+            return False
+        if self.on_device:
+            raise CeedError(f"{who}: {self.L.path} has no {symbol} and the block is in device memory: the portable form works on host arrays only")
+        return True
+
+    def _host(self, first: int, count: int) -> np.ndarray:
+        return self.t.numpy().reshape(self.k, self.ld)[first:first + count, :self.n]
+
+    def gram(self, other: "BlockVector", G: "Vector", a0: int = 0, ka: Optional[int] = None, b0: int = 0, kb: Optional[int] = None,
+             weight: Optional["Vector"] = None):
+        """G[i][j] = sum_r weight[r] self_{a0+i}[r] other_{b0+j}[r] (CeedXVectorBlockGram) into the first ka * kb entries of the vector G,
+        row-major; nothing is read on the host."""
+        ka = self.k - a0 if ka is None else ka
+        kb = other.k - b0 if kb is None else kb
+        if other.n != self.n or other.ld != self.ld:
+            raise CeedError("BlockVector.gram: the blocks differ in n or ld")
+        self.owner.touched(); other.owner.touched()
+        if not self._portable("BlockVector.gram", "CeedXVectorBlockGram"):
+            self.L.chk(self.L.lib.CeedXVectorBlockGram(self.owner.h, c_int(a0), c_int(ka), other.owner.h, c_int(b0), c_int(kb),
+                                                       c_int(self.n), c_int(self.ld), _h(weight), G.h))
+            return
+        _block_check("BlockVector.gram", self.n, self.ld, [("A", a0, ka, self.owner.n), ("B", b0, kb, other.owner.n)])
+        if G.n < ka * kb:
+            raise CeedError(f"BlockVector.gram: G holds {G.n} entries, {ka} x {kb} are written")
+        if weight is not None and weight.n < self.n:
+            raise CeedError(f"BlockVector.gram: the weight holds {weight.n} entries, n = {self.n} are read")
+        g = G.to_numpy()
+        g[:ka * kb] = block_gram_host(self._host(a0, ka), other._host(b0, kb), None if weight is None else weight.to_numpy()[:self.n]).reshape(-1)
+        G.set_array(g)
+
+    def combine(self, A: "BlockVector", Cm, y0: int = 0, ky: Optional[int] = None, a0: int = 0, ka: Optional[int] = None, beta: float = 0.0):
+        """self_{y0+j} = sum_i A_{a0+i} Cm[i][j] + beta self_{y0+j} (CeedXVectorBlockCombine); ``Cm`` is a host array [ka][ky] (written to
+        a device vector kept with the block) or a Vector that already holds it row-major."""
+        ka = A.k - a0 if ka is None else ka
+        ky = self.k - y0 if ky is None else ky
+        if A.n != self.n or A.ld != self.ld:
+            raise CeedError("BlockVector.combine: the blocks differ in n or ld")
+        if not isinstance(Cm, Vector):
+            cm = _np_f64(Cm)
+            if cm.shape != (ka, ky):
+                raise CeedError(f"BlockVector.combine: C is {cm.shape}, {ka} x {ky} expected")
+            if cm.size not in self._cvec:
+                self._cvec[cm.size] = self.ceed.vector(cm.size)
+            Cm = self._cvec[cm.size].set_array(cm.reshape(-1))
+        self.owner.touched(); A.owner.touched()
+        if not self._portable("BlockVector.combine", "CeedXVectorBlockCombine"):
+            self.L.chk(self.L.lib.CeedXVectorBlockCombine(self.owner.h, c_int(y0), c_int(ky), A.owner.h, c_int(a0), c_int(ka), Cm.h,
+                                                          C.c_double(beta), c_int(self.n), c_int(self.ld)))
+        else:
+            _block_check("BlockVector.combine", self.n, self.ld, [("Y", y0, ky, self.owner.n), ("A", a0, ka, A.owner.n)])
+            if Cm.n < ka * ky:
+                raise CeedError(f"BlockVector.combine: C holds {Cm.n} entries, {ka} x {ky} are read")
+            if A.t.data_ptr() == self.t.data_ptr() and y0 < a0 + ka and a0 < y0 + ky:
+                raise CeedError(f"BlockVector.combine: the columns {y0} .. {y0 + ky} of Y overlap the columns {a0} .. {a0 + ka} of A: "
+                                "the kernel does not work in place")
+            block_combine_host(self._host(y0, ky), A._host(a0, ka), Cm.to_numpy()[:ka * ky].reshape(ka, ky), beta)
+        for v in self.cols[y0:y0 + ky]:           # a block-level write: the columns written are handed over again
+            v.touched()
+
+    def destroy(self):
+        for v in self.cols + [self.owner] + list(self._cvec.values()):
+            v.destroy()
+        self.cols, self._cvec = [], {}
 
 
 class ElemRestriction:

@@ -87,6 +87,8 @@ extern "C" int CeedInit(const char *resource, Ceed *ceed) {
   o.fold_pack = env_int("CEED_MI355X_FOLD_PACK", o.fold_pack);
   o.row_code = !env_is("CEED_MI355X_ROWMAP", "plain");
   o.row_code_max = std::max(0, env_int("CEED_MI355X_ROWCODE_MAX", o.row_code_max));
+  // the one scratch of the block-vector Gram matrix, at its largest size: never built lazily, so the call can be recorded at once
+  if (c->d_block_part.alloc(nullptr, (size_t)cps::BLOCK_GRAM_MAX_PARTS * cps::BLOCK_MAX_COLS * cps::BLOCK_MAX_COLS)) { delete c; return 1; }
   *ceed = c;
   return 0;
 }
@@ -117,7 +119,7 @@ void ceed_unref(Ceed c) {
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   for (hipEvent_t ev : c->ev_seg) if (ev) (void)hipEventDestroy(ev);
   if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-  delete c;            // (d_scalar and d_pb_bad are bound to no Ceed: freed directly with it)
+  delete c;            // (d_scalar, d_pb_bad and d_block_part are bound to no Ceed: freed directly with it)
 }
 int ceed_need_side_stream(Ceed c) {
   if (c->side_stream) return 0;

@@ -1,6 +1,7 @@
 // ceed_impl.hpp -- private object layouts and helpers shared by the host-side sources of the MI355X backend
 // (ceed_core.cpp: Ceed, vectors, graphs; ceed_basis.cpp; ceed_restriction.cpp; ceed_qfunction.cpp; the operators: ceed_operator.cpp
-// with ceed_op_fused.cpp, ceed_op_other.cpp and ceed_op_mass.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp).
+// with ceed_op_fused.cpp, ceed_op_other.cpp and ceed_op_mass.cpp, which share ceed_operator.hpp on top of this; ceed_halo.cpp; ceed_csr.cpp;
+// ceed_block.cpp: block vectors).
 // Every device array one of these objects owns is a DevArray (dev_array.hpp): allocated under the object's Ceed, gone with the member,
 // through ceed_retire.  The one exception is a vector's host / device mirrors, which may be borrowed (ceed_core.cpp).
 // Every transpose map is a RowMap (CsrMap, PipeMap); an operator keeps its Dirichlet flags per RowMap in ONE cache (row_flags).
@@ -94,6 +95,8 @@ struct Ceed_private {
   DevArray<double> d_scalar;    // device scalar for reductions (1 + 2048 doubles)
   double *h_scalar = nullptr;   // pinned host landing slot for it (pageable targets make the runtime stage + pin per copy)
   DevArray<int> d_pb_bad;       // device counter of CeedXVectorPointBlockInvert (bad pivots), allocated when first asked for
+  DevArray<double> d_block_part;   // per-workgroup partial matrices of CeedXVectorBlockGram (BLOCK_GRAM_MAX_PARTS x 48 x 48), made by CeedInit:
+                                   // the call is recordable from its first use on
   // hipGraph capture (CeedXGraphBeginCapture): device work is recorded on `capture_stream`
   hipStream_t capture_stream = nullptr, saved_stream = nullptr;
   bool capturing = false;

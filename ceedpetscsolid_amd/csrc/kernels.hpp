@@ -377,4 +377,18 @@ hipError_t launch_dot(const double *x, const double *y, const double *w, size_t 
 hipError_t launch_scalar_div(double *sc, int dst, int num, int den, double scale, hipStream_t s);
 hipError_t launch_axpby_dev(double *y, const double *sc, int ia, double sa, const double *x, int ib, double sb, size_t n, hipStream_t s);
 
+// Block vectors (kernels_block.hip): k columns of length n in one array, column j at element j * ld (ld >= n).  A and B point at the first
+// column of their ranges.  G (ka x kb, row-major, device) = sum_r w[r] A_i[r] B_j[r] (w may be null) through per-workgroup partial
+// matrices in `part` (BLOCK_GRAM_MAX_PARTS x ka x kb doubles) summed in a fixed order; Y_j = sum_i A_i C[i][j] + beta Y_j with C (ka x ky,
+// row-major) on the device.  A row chunk of the Gram kernel is BLOCK_GRAM_ROWS rows; its grid is at most BLOCK_GRAM_MAX_PARTS workgroups.
+constexpr int BLOCK_MAX_COLS = 48;
+constexpr int BLOCK_GRAM_ROWS = 64;
+constexpr int BLOCK_GRAM_MAX_PARTS = 1024;
+constexpr int BLOCK_COMBINE_ROWS = 512;          // rows of a chunk of the combination: two per lane
+constexpr int BLOCK_COMBINE_MAX_GROUPS = 2048;   // its largest grid
+hipError_t launch_block_gram(const double *A, int ka, const double *B, int kb, const double *w, size_t n, size_t ld, double *part,
+                             double *G, hipStream_t s);
+hipError_t launch_block_combine(double *Y, int ky, const double *A, int ka, const double *C, double beta, size_t n, size_t ld,
+                                hipStream_t s);
+
 }  // namespace cps

@@ -297,6 +297,32 @@ CEED_EXTERN int CeedXVectorDotTo(CeedVector x, CeedVector y, CeedVector weight /
 CEED_EXTERN int CeedXScalarDivide(CeedVector scalars, CeedInt dst, CeedInt num, CeedInt den, double scale);
 CEED_EXTERN int CeedXVectorAXPBYScalars(CeedVector y, CeedVector scalars, CeedInt ia, double sa,
                                         CeedVector x, CeedInt ib, double sb);
+/* OPTIONAL entry points: BLOCK vectors.  A block is k columns of length n in  */
+/* one CeedVector, column j at element j * ld, ld >= n (column-major); the     */
+/* rows n <= r < ld of a column are padding: never read into a result, never   */
+/* written.  Column counts lie in 1 .. 48.  A column range [x0, x0 + kx) must  */
+/* fit its vector: (x0 + kx) * ld - (ld - n) <= length.                        */
+/*   BlockGram:    G[i][j] = sum_{r < n} weight[r] * A_{a0+i}[r] * B_{b0+j}[r], */
+/*     i < ka, j < kb; G row-major, at least ka * kb long, stays in backend    */
+/*     memory; weight NULL stands for ones and gives the same bits as a vector */
+/*     of ones.  A and B may be the same vector with overlapping ranges.       */
+/*     Every entry sums its rows in one fixed order: two calls give the same   */
+/*     bits, and G(A, A) is symmetric bit for bit.                             */
+/*   BlockCombine: Y_{y0+j}[r] = sum_{i < ka} A_{a0+i}[r] * C[i][j]             */
+/*     + beta * Y_{y0+j}[r], j < ky, r < n; C row-major, at least ka * ky long, */
+/*     in backend memory.  beta == 0 does not read Y.  The columns of Y must   */
+/*     not overlap the columns of A (refused: the call is not in place).       */
+/* Every argument is checked before anything is queued.  Both calls can be    */
+/* recorded in a CeedXGraph.  BlockGetLimits reports the largest column count, */
+/* the rows of one chunk of the Gram reduction, the largest number of partial  */
+/* matrices it sums, the rows of one chunk of the combination and its largest  */
+/* grid (any pointer may be NULL).                                             */
+CEED_EXTERN_OPTIONAL int CeedXVectorBlockGram(CeedVector A, CeedInt a0, CeedInt ka, CeedVector B, CeedInt b0, CeedInt kb,
+                                              CeedInt n, CeedInt ld, CeedVector weight /* or NULL */, CeedVector G);
+CEED_EXTERN_OPTIONAL int CeedXVectorBlockCombine(CeedVector Y, CeedInt y0, CeedInt ky, CeedVector A, CeedInt a0, CeedInt ka,
+                                                 CeedVector C, double beta, CeedInt n, CeedInt ld);
+CEED_EXTERN_OPTIONAL int CeedXVectorBlockGetLimits(CeedInt *max_cols, CeedInt *gram_rows, CeedInt *gram_max_parts,
+                                                   CeedInt *combine_rows, CeedInt *combine_max_groups);
 /* One Jacobi-Chebyshev smoother update in a single pass over the vectors     */
 /* (the KSPCHEBYSHEV + PCJACOBI smoother of elasticity.c:539-552):            */
 /*   r -= t (skipped if t is NULL);  d = c1 * dinv .* r + c2 * d;             */

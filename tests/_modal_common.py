@@ -1,0 +1,108 @@
+"""What the CPU and the device tests of the modal analysis (modal.Eigenmodes) share: the three problems, the dense generalised
+eigenproblem from unit-vector applies (``dense_K_M`` of _mass_common.py), and the checks of a result against it.  The same code runs on
+the CPU oracle and on the device.
+
+Bounds (u = 2^-53): an eigenvalue within eta_i + 1e3 u lambda_max of the dense one -- eta_i = sqrt(r' M^-1 r / x' M x), r = K x - lambda_i M x
+is the Krylov-Bogoliubov bound, the second term the dense eigh's own rounding at |M^-1/2 K M^-1/2| = lambda_max; eta_i <= 1e-6
+max(lambda_i, lambda_ref,nmodes); the angle to the dense mode within 2 eta_i / gap_i + 1e-9 (Davis-Kahan); |Phi' M Phi - I| <= 1e-10."""
+import numpy as np
+
+from _mass_common import E, NU, RHO, dense_K_M
+from ceedpetscsolid_amd.dynamics import NewmarkPMG
+from ceedpetscsolid_amd.mesh import box_mesh
+from ceedpetscsolid_amd.modal import Eigenmodes
+from ceedpetscsolid_amd.solid import SolidProblem
+from ceedpetscsolid_amd.solver import NewtonPMG
+
+U_ROUND = 2.0 ** -53
+TOL = 1e-8
+MAX_ITS = 60            # three times what the NumPy prototype of the algorithm needed (18, 21, 19): a condition, not a measurement
+SHIFT = 0.1             # a0 of the free-free case: dt = sqrt(4 / a0) at beta = 1/4
+CASES = ("clamped_p2_linelas", "clamped_p3_hyperfs_amg", "free_p2_newmark")
+
+
+def make_case(ceed, name, tip_fz=None, **solver_kw):
+    """(prob, sol, nmodes, guard, number of rigid-body modes); ``tip_fz``: a transverse nodal force on every node (the clamped cases)"""
+    forcing = (lambda prob: None if tip_fz is None else np.tile([0.0, 0.0, tip_fz], prob.lsize() // 3))
+    if name == "clamped_p2_linelas":
+        prob = SolidProblem(ceed, box_mesh(3, 1, 1, hi=(3.0, 1.0, 0.6)), 2, "linElas", nu=NU, E=E, bc_sides=[6])
+        return prob, NewtonPMG(prob, forcing=forcing(prob), **solver_kw), 4, 2, 0
+    if name == "clamped_p3_hyperfs_amg":
+        prob = SolidProblem(ceed, box_mesh(2, 1, 1, hi=(3.0, 1.0, 0.6)), 3, "hyperFS", nu=NU, E=E, bc_sides=[6])
+        assert len(prob.levels) == 3
+        return prob, NewtonPMG(prob, forcing=forcing(prob), coarse="amg", **solver_kw), 4, 2, 0
+    if name == "free_p2_newmark":
+        prob = SolidProblem(ceed, box_mesh(2, 1, 1, hi=(3.0, 1.0, 0.6)), 2, "linElas", nu=NU, E=E, bc_sides=[])
+        return prob, NewmarkPMG(prob, RHO, float(np.sqrt(4.0 / SHIFT)), coarse="assembled", **solver_kw), 8, 2, 6
+    raise KeyError(name)
+
+
+def dense_modes(K, M):
+    """(lambda ascending, Phi M-orthonormal) of K phi = lambda M phi: Cholesky of M, then eigh."""
+    L = np.linalg.cholesky(0.5 * (M + M.T))
+    A = np.linalg.solve(L, np.linalg.solve(L, 0.5 * (K + K.T)).T).T
+    lam, Y = np.linalg.eigh(0.5 * (A + A.T))
+    return lam, np.linalg.solve(L.T, Y)
+
+
+def dense_reference(ceed, prob):
+    """(K, M, free, lambda_ref, Phi_ref) at the state the problem's stored state holds."""
+    K, M, free = dense_K_M(ceed, prob, RHO)
+    K, M = 0.5 * (K + K.T), 0.5 * (M + M.T)
+    lam, Phi = dense_modes(K, M)
+    return K, M, free, lam, Phi
+
+
+def run(sol, nmodes, guard, seed=0, **kw):
+    em = Eigenmodes(sol, RHO, nmodes, guard=guard, tol=TOL, maxit=MAX_ITS, seed=seed, **kw)
+    res = em.solve()
+    calls = dict(em.block_calls)
+    em.destroy()
+    return res, calls
+
+
+def _sin_to_span(x, N, M):
+    """sin of the M-angle between x and the span of the M-orthonormal columns of N"""
+    d = x - N @ (N.T @ (M @ x))
+    return float(np.sqrt(max(d @ M @ d, 0.0) / (x @ M @ x)))
+
+
+def check_result(res, K, M, free, lam_ref, Phi_ref, nmodes, nrigid=0, label=""):
+    """Every assertion of a result against the dense pencil; returns (eigenvalue bounds, eigenvalue errors) for cross-device checks."""
+    assert res.converged and res.iterations <= MAX_ITS, (label, res.iterations, res.history)
+    assert np.all(res.residuals < TOL), (label, res.residuals)
+    X = res.modes.to_numpy()
+    n = X.shape[1]
+    constrained = np.setdiff1d(np.arange(n), free)
+    assert np.all(X[:, constrained] == 0.0), label
+    Xf = X[:, free]
+    lam = res.eigenvalues
+    lam_max = float(lam_ref[-1])
+    Minv = np.linalg.inv(M)
+    gram = Xf @ M @ Xf.T
+    print(f"{label}: {res.iterations} iterations, |Phi' M Phi - I| = {np.abs(gram - np.eye(nmodes)).max():.2e}")
+    assert np.abs(gram - np.eye(nmodes)).max() <= 1e-10, label
+    bounds, errs = np.zeros(nmodes), np.zeros(nmodes)
+    for i in range(nmodes):
+        x = Xf[i]
+        r = K @ x - lam[i] * (M @ x)
+        eta = float(np.sqrt((r @ Minv @ r) / (x @ M @ x)))
+        bounds[i] = eta + 1e3 * U_ROUND * lam_max
+        errs[i] = abs(lam[i] - lam_ref[i])
+        if i < nrigid:
+            gap = float(lam_ref[nrigid])
+            s = _sin_to_span(x, Phi_ref[:, :nrigid], M)
+        else:
+            gap = float(min(abs(lam_ref[i] - lam_ref[j]) for j in range(len(lam_ref)) if j != i and not (j < nrigid and i < nrigid)))
+            s = _sin_to_span(x, Phi_ref[:, i:i + 1], M)
+        print(f"  mode {i}: lambda {lam[i]: .12e}  dense {lam_ref[i]: .12e}  |diff| {errs[i]:.2e}  bound {bounds[i]:.2e}  eta {eta:.2e}  "
+              f"sin angle {s:.2e}  bound {2 * eta / gap + 1e-9:.2e}  rn {res.residuals[i]:.2e}")
+        assert errs[i] <= bounds[i], (label, i)
+        assert eta <= 1e-6 * max(lam[i], lam_ref[nmodes - 1]), (label, i, eta)
+        assert s <= 2.0 * eta / gap + 1e-9, (label, i, s)
+        if i < nrigid:
+            assert abs(lam[i]) <= 1e-9 * lam_ref[nrigid], (label, i, lam[i])
+    return bounds, errs
+
+
+TIP_FZ = -5e-6          # per node of the p = 3 bar (112 nodes): a cantilever estimate q L^4 / (8 E I) puts the tip at a few per cent of L = 3
