@@ -13,6 +13,7 @@ device addresses (e.g. ``torch.Tensor.data_ptr()``) on the device side.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Sequence
@@ -79,7 +80,8 @@ class CeedLib:
                 "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock",
                 "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
                 "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction",
-                "CeedXVectorBlockGram", "CeedXVectorBlockCombine", "CeedXVectorBlockGetLimits"]
+                "CeedXVectorBlockGram", "CeedXVectorBlockCombine", "CeedXVectorBlockGetLimits",
+                "CeedXVectorLeapfrogStep"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -234,6 +236,26 @@ def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b
         r.set_array(ri)
     d.set_array(dn)
     x.set_array(xn)
+
+
+# ---- explicit dynamics: the portable form of CeedXVectorLeapfrogStep (NumPy on host arrays) ----------------------------------------
+def leapfrog_step_host(x: np.ndarray, vh: np.ndarray, r: np.ndarray, f: Optional[np.ndarray], m: np.ndarray, load: float, c1: float,
+                       c2: float, dt: float, tally: bool = True) -> Optional[float]:
+    """One leapfrog step IN PLACE on the float64 host arrays x and vh (all arrays of one length), as CeedXVectorLeapfrogStep defines it
+    (include/ceed.h): the same operations in the same order, each rounded on its own, so x and vh carry the bits of the device kernel.
+    Rows with m <= 0 are neither read into a result nor written.  Returns 0.5 sum m vm^2 (``tally``), else None."""
+    act = m > 0.0
+    mi, ri, vo = m[act], r[act], vh[act]
+    g = load * f[act] - ri if f is not None else -ri
+    q = g / mi
+    vn = c1 * vo + c2 * q
+    ke = None
+    if tally:
+        vm = 0.5 * (vo + vn)
+        ke = 0.5 * float(np.sum(mi * (vm * vm)))
+    vh[act] = vn
+    x[act] = x[act] + dt * vn
+    return ke
 
 
 class Csr:
@@ -427,9 +449,9 @@ class Ceed:
 
     @property
     def scalars(self) -> "Vector":
-        """The Ceed's one register file of device scalars, made at first use: 8 working slots, two coefficients for each of 16 steps."""
+        """The Ceed's one register file of device scalars, made at first use: 8 working slots, two coefficients for each of 32 steps."""
         if self._scalars is None:
-            self._scalars = self.vector(8 + 2 * 16)
+            self._scalars = self.vector(8 + 2 * 32)
         return self._scalars
 
     def scalar_divide(self, scalars: "Vector", dst: int, num: int, den: int, scale: float = 1.0):
@@ -595,6 +617,53 @@ class Vector:
 
     def chebyshev_step(self, d, r, b, t, dinv, c1: float, c2: float, assign_x: bool):   # ri = b - t (stored if r);  d = c1 dinv .* ri + c2 d;  self (+)= d
         self.L.chk(self.L.lib.CeedXVectorChebyshevStep(self.h, d.h, _h(r), b.h, _h(t), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+
+    def leapfrog_step(self, vh: "Vector", r: "Vector", f: Optional["Vector"], m: "Vector", load: float, c1: float, c2: float, dt: float,
+                      n: Optional[int] = None, scalars: Optional["Vector"] = None, slot: int = 0):
+        """CeedXVectorLeapfrogStep on the first n rows (default: all of self), self the displacement x: on the rows with m > 0
+        vh = c1 vh + c2 (load f - r) / m, self += dt vh; scalars[slot] = the kinetic energy at the step r belongs to (None: no sum).
+        Where the library lacks the entry point (the CPU oracle) the portable form works in place on the vectors' host arrays."""
+        n = self.n if n is None else int(n)
+        if self.L.has("CeedXVectorLeapfrogStep"):
+            self.L.chk(self.L.lib.CeedXVectorLeapfrogStep(self.h, vh.h, r.h, _h(f), m.h, C.c_double(load), C.c_double(c1), C.c_double(c2),
+                                                          C.c_double(dt), c_int(n), _h(scalars), c_int(slot)))
+            return
+        who, ops = "leapfrog_step", [("x", self), ("vh", vh), ("r", r), ("m", m)] + ([("f", f)] if f is not None else [])
+        if any(v is None for _, v in ops):
+            raise CeedError(f"{who}: x, vh, r and m must be vectors")
+        if n < 1:
+            raise CeedError(f"{who}: the number of rows n must be at least 1 (n = {n})")
+        for i, (name, v) in enumerate(ops):
+            if v.n < n:
+                raise CeedError(f"{who}: {name} holds {v.n} entries, n = {n} are read")
+            for other, w in ops[:i]:
+                if w is v:
+                    raise CeedError(f"{who}: {other} and {name} are the same vector: the operands must be pairwise distinct")
+            if scalars is v:
+                raise CeedError(f"{who}: scalars must not be one of the operands ({name})")
+        if scalars is not None and not 0 <= slot < scalars.n:
+            raise CeedError(f"{who}: scalar {slot} of {scalars.n}")
+        with self.host_view(True) as xa, vh.host_view(True) as va, r.host_view(False) as ra, m.host_view(False) as ma:
+            if f is not None:
+                with f.host_view(False) as fa:
+                    ke = leapfrog_step_host(xa[:n], va[:n], ra[:n], fa[:n], ma[:n], load, c1, c2, dt, scalars is not None)
+            else:
+                ke = leapfrog_step_host(xa[:n], va[:n], ra[:n], None, ma[:n], load, c1, c2, dt, scalars is not None)
+        if scalars is not None:
+            with scalars.host_view(True) as sa:
+                sa[slot] = ke
+
+    @contextlib.contextmanager
+    def host_view(self, write: bool):
+        """The vector's host storage as a NumPy array WITHOUT a copy (CeedVectorGetArray / GetArrayRead ... Restore), valid inside the
+        ``with`` block only; ``write``: the array may be written."""
+        p = c_scalar_p()
+        lib = self.L.lib
+        self.L.chk((lib.CeedVectorGetArray if write else lib.CeedVectorGetArrayRead)(self.h, MEM_HOST, C.byref(p)))
+        try:
+            yield np.ctypeslib.as_array(p, shape=(self.n,)) if self.n else np.zeros(0)
+        finally:
+            self.L.chk((lib.CeedVectorRestoreArray if write else lib.CeedVectorRestoreArrayRead)(self.h, C.byref(p)))
 
     def destroy(self):
         if self.h:

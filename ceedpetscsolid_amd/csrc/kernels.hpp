@@ -391,4 +391,10 @@ hipError_t launch_block_gram(const double *A, int ka, const double *B, int kb, c
 hipError_t launch_block_combine(double *Y, int ky, const double *A, int ka, const double *C, double beta, size_t n, size_t ld,
                                 hipStream_t s);
 
+// The explicit time step (kernels_explicit.hip; formulas: include/ceed.h, CeedXVectorLeapfrogStep) on the first n rows: f may be null;
+// with out the kinetic-energy tally goes to *out (device) through `part`, one double per workgroup of the streaming grid (at most 2048:
+// stream_grid), summed in a fixed order; without out no reduction is launched.  n >= 1.
+hipError_t launch_leapfrog(double *x, double *vh, const double *r, const double *f, const double *m, double load, double c1, double c2,
+                           double dt, size_t n, double *part, double *out, hipStream_t s);
+
 }  // namespace cps

@@ -1,4 +1,5 @@
-"""Elastodynamics: implicit Newmark time stepping on top of the Newton - CG - p-multigrid solve (solver.py).
+"""Elastodynamics: implicit Newmark time stepping on top of the Newton - CG - p-multigrid solve (solver.py), and explicit
+central-difference stepping with a lumped mass (``ExplicitDynamics``, at the end of the file: its equations are in its docstring).
 
 The semi-discrete equations, with the sign and load conventions of ``solver.NewtonPMG`` (R = F_int - load (f + tractions) + load
 sum_s p_s g_s^pressure, a pressure p > 0 pushing on the body),
@@ -30,6 +31,7 @@ from typing import Callable, Optional, Union
 
 import numpy as np
 
+from .krylov import lanczos_device, lanczos_emax
 from .mass import MassOperator
 from .solid import SolidProblem
 from .solver import NewtonPMG, SolveStats
@@ -231,3 +233,236 @@ class NewmarkPMG(NewtonPMG):
     def destroy_mass(self):
         for m in self.mass + [self.mass_res]:
             m.destroy()
+
+
+class ExplicitDynamics(NewtonPMG):
+    """Explicit elastodynamics: the central-difference ("leapfrog") rule with a lumped mass m (mass.MassOperator.lumped: the row sums of
+    rho M) and a mass-proportional damping alpha,
+
+        m a_n + alpha m v_n + R(x_n, t_n) = 0,      R = F_int(x) - load(t) (f + tractions) + load(t) sum_s p_s g_s^pressure(x)
+        a_n = (vh_{n+1/2} - vh_{n-1/2}) / dt,       v_n = (vh_{n+1/2} + vh_{n-1/2}) / 2
+        vh_{n+1/2} = c1 vh_{n-1/2} + c2 (-R_n / m), c1 = (1 - alpha dt/2) / (1 + alpha dt/2),  c2 = dt / (1 + alpha dt/2)
+        x_{n+1} = x_n + dt vh_{n+1/2}
+
+    on the free rows; the constrained rows of x carry the boundary values of load(t) (``bc_values``), m is zero there and the step
+    leaves them alone.  A step is ONE vector kernel (CeedXVectorLeapfrogStep, csrc/kernels_explicit.hip; its NumPy form on the CPU
+    oracle) and one evaluation of the residual: no preconditioner, no Krylov loop, no coarse level -- the parent class is subclassed for
+    the boundary values, the load vector, the surface loads and ``A`` (the tangent of the stable-step estimate) only, and its
+    preconditioner is never set up.  With a constant load nothing between two steps touches the host.
+
+    State: ``x`` (the L-vector WITH the boundary values: what the residual reads; it is the parent's ``Xloc``), ``vh`` (the half-step
+    velocity), ``R`` (the residual at x), ``m``.  After ``step()``: x = x_{n+1}, vh = vh_{n+1/2}, R = R(x_{n+1}), t = t_{n+1}.
+
+    The step is conditionally stable: dt < 2 / sqrt(lambda_max(m^-1 K_T)).  ``stable_dt`` estimates the bound with the Lanczos
+    recurrence of krylov.py and the margin 1.1 the Chebyshev smoothers put on the same estimate; ``dt=None`` takes it at
+    ``set_initial``, a given dt beyond it is refused there.  dt is fixed per object.
+
+    Refused: a halo with several ranks (the mass operator's interface sums were never run there), density <= 0, dt <= 0, damping < 0,
+    and at ``set_initial`` a lumped mass with a non-positive free row."""
+
+    def __init__(self, prob: SolidProblem, density: float, dt: Optional[float] = None, damping: float = 0.0, safety: float = 0.9, **kw):
+        if not (density > 0.0 and (dt is None or dt > 0.0)):
+            raise ValueError("density and dt must be positive")
+        if not damping >= 0.0:
+            raise ValueError("damping (the mass-proportional coefficient alpha) must not be negative")
+        if not 0.0 < safety <= 1.0:
+            raise ValueError("safety must lie in (0, 1]")
+        halo = kw.get("halo")
+        if halo is not None:
+            hl = halo if isinstance(halo, (list, tuple)) else [halo]
+            if hl[-1].world > 1:
+                raise ValueError("ExplicitDynamics is not provided with a halo (several ranks): the mass operator's sums at the interface "
+                                 "nodes have not been run over several ranks")
+        super().__init__(prob, **kw)
+        self.density, self.damping, self.safety = float(density), float(damping), float(safety)
+        self.dt = None if dt is None else float(dt)
+        self.c1 = self.c2 = None
+        n, top = prob.lsize(), self.nlev - 1
+        self.x = self.Xloc                      # (the parent's name for "free part + boundary values": A_outer reads it)
+        self.vh, self.m, self.minv_m, self._freev = (self._vec(n, top) for _ in range(4))
+        self._tally = self._vec(2, top)         # slot 0: the kinetic energy of a sampled step
+        self.mass_lumped = MassOperator(prob, prob.fine, self.density, mask_mode=2)
+        self.mass_lumped.lumped(self.m)         # formed once per solver object
+        self._set(self._freev, self.free.astype(np.float64))
+        self.t, self.nsteps_done = 0.0, 0
+        self._load_fn: Callable[[float], float] = lambda t: 1.0
+        self._load_const = True
+        self._started = self._have_R = False
+        self._x_start = None
+        self.emax_K = None
+
+    # ---- pieces ---------------------------------------------------------------------------------------------------------------
+    def _force(self):
+        """R = F_int(x) + load sum_s p_s g_s^pressure(x), constrained rows dropped (the load vector enters in the step itself)."""
+        self.p.form_residual(self.x, self.R)
+        for sl, pval in self.pressure_loads:
+            sl.pressure_add(pval, self.load, self.x, self.R)
+        self.stats.residual_evals += 1
+        self._have_R = True
+
+    def _set_boundary(self, load: float):
+        """The constrained rows of x := the boundary values at ``load`` (one upload; the free rows keep their bits: x * 1 + 0)."""
+        self._set(self.bcv, self.bc_values(load))
+        self.x.pointwise_mult(self.x, self._freev)
+        self.axpby(self.x, 1.0, self.bcv, 1.0)
+
+    def _check_mass(self) -> np.ndarray:
+        m = self.m.to_numpy()
+        bad = self.free & ~(m > 0.0)
+        if bad.any():
+            rows = np.flatnonzero(bad)
+            worst = int(rows[np.argmin(np.where(np.isnan(m[rows]), -np.inf, m[rows]))])
+            raise ValueError(f"ExplicitDynamics: the lumped mass is not positive on {rows.size} free rows; the worst is row {worst} "
+                             f"(m = {m[worst]!r})")
+        return m
+
+    def _q_host(self, m: np.ndarray) -> np.ndarray:
+        """(load f - R) / m on the free rows (host), zero elsewhere: the undamped acceleration at the state of the last residual."""
+        g = -self.R.to_numpy()
+        if self.fv is not None:
+            g = self.load * self.fv.to_numpy() + g
+        q = np.zeros_like(g)
+        q[self.free] = g[self.free] / m[self.free]
+        return q
+
+    # ---- the stable step ------------------------------------------------------------------------------------------------------------
+    def stable_dt(self, steps: int = 20) -> float:
+        """safety * 2 / sqrt(1.1 emax), emax the Lanczos estimate (``steps`` steps; an estimate from below, hence the margin 1.1 of
+        ``krylov.chebyshev_coefficients``) of lambda_max(m^-1 K_T), K_T the tangent at the state of the last residual evaluation."""
+        if not self._have_R:
+            self._force()
+        self._set(self.minv_m, np.where(self.free, 1.0 / np.where(self.free, self._check_mass(), 1.0), 0.0))
+        top = self.nlev - 1
+        if top not in self._x0:
+            x = np.random.default_rng(1234 + top).uniform(-1, 1, self.free.size) * self.free
+            x0 = self._vec(self.free.size, top)
+            self._set(x0, x / np.sqrt(np.square(x).sum()))
+            self._x0[top] = x0
+        w = self.w[top]
+        al, be = lanczos_device(self.ceed, lambda x, y: self.A(top, x, y), lambda z, r: z.pointwise_mult(r, self.minv_m), self._x0[top],
+                                w["r"], w["z"], w["d"], w["t"], steps)
+        self.emax_K = lanczos_emax(al, be)
+        return self.safety * 2.0 / np.sqrt(1.1 * self.emax_K)
+
+    # ---- start ---------------------------------------------------------------------------------------------------------------------
+    def set_initial(self, u0=None, v0=None, load: Union[float, Callable[[float], float]] = 1.0):
+        """State at t = 0: u0, v0 (host L-vectors; None: zero) on the free rows, the boundary values of load(0) on the others;
+        a_0 = (load f - R(x_0)) / m - alpha v_0 (the damping term in the form the step takes it) and vh_{-1/2} = v_0 - dt/2 a_0, so
+        that (vh_{-1/2} + vh_{1/2}) / 2 = v_0.  dt is settled here: ``stable_dt()`` if none was given; a given one above
+        stable_dt() / safety is refused."""
+        self._load_const = not callable(load)
+        self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+        n, free = self.p.lsize(), self.free
+        m = self._check_mass()
+        self.t, self.nsteps_done = 0.0, 0
+        self.load = float(self._load_fn(0.0))
+        as_l = lambda a: np.zeros(n) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)[:n]
+        x0 = as_l(u0) * free + self.bc_values(self.load)
+        self._set(self.x, x0)
+        self._x_start = x0
+        self._force()
+        limit = self.stable_dt()
+        if self.dt is None:
+            self.dt = float(limit)
+        elif self.dt > limit / self.safety:
+            raise ValueError(f"ExplicitDynamics: dt = {self.dt:.6g} is above the stable step {limit / self.safety:.6g} "
+                             f"(2 / sqrt(1.1 x the estimate {self.emax_K:.6g} of lambda_max(m^-1 K_T)))")
+        h = 0.5 * self.damping * self.dt
+        self.c1, self.c2 = (1.0 - h) / (1.0 + h), self.dt / (1.0 + h)
+        v = as_l(v0) * free
+        self._set(self.vh, (v - 0.5 * self.dt * (self._q_host(m) - self.damping * v)) * free)
+        self._started = True
+
+    # ---- one step --------------------------------------------------------------------------------------------------------------------
+    def _kernel(self, tally: bool):
+        self.x.leapfrog_step(self.vh, self.R, self.fv, self.m, self.load, self.c1, self.c2, self.dt, self.p.lsize(),
+                             self._tally if tally else None, 0)
+
+    def _device_step(self, tally: bool):
+        """The kernel and the residual of one step at a load that does not change: everything here is queued, nothing read."""
+        self._kernel(tally)
+        self._force()
+
+    def step(self, tally: bool = False):
+        """(x_n, vh_{n-1/2}, R_n) -> (x_{n+1}, vh_{n+1/2}, R_{n+1}); ``tally``: the kinetic energy 1/2 sum m v_n^2 goes to the device
+        slot that ``run`` samples."""
+        if not self._started:
+            self.set_initial()
+        self._kernel(tally)
+        self.nsteps_done += 1
+        self.t = self.nsteps_done * self.dt
+        load = float(self._load_fn(self.t))
+        if load != self.load:                    # (a constant load: no upload, no host read between two steps)
+            self._set_boundary(load)
+            self.load = load
+        self._force()
+
+    def run(self, nsteps: int, sample_every: int = 0, graph: bool = False) -> dict:
+        """``nsteps`` steps from the current state.  Every ``sample_every`` steps (0: never; the kernel then sums nothing) the history
+        takes t (the time of x), the kinetic energy and its time t - dt (the step the tally belongs to) and max |x - x_0|; the run ends
+        with ``diverged`` at the first sample that is not finite.  ``graph``: after one eager step, one step (kernel + residual) is
+        recorded and replayed; load, c1, c2, dt are frozen in the recording, so a load FUNCTION is refused, and the tally is recorded
+        in or out according to sample_every > 0."""
+        if graph and not self._load_const:
+            raise ValueError("ExplicitDynamics.run: graph=True needs a constant load (the load is a launch argument frozen in the recording)")
+        if sample_every < 0:
+            raise ValueError("sample_every must not be negative")
+        if not self._started:
+            self.set_initial(load=self._load_fn if not self._load_const else self.load)
+        h = {"t": [], "t_kinetic": [], "kinetic": [], "max_disp": [], "steps": 0, "diverged": False, "seconds": 0.0}
+        rec = None
+        t0 = time.perf_counter()
+        try:
+            for k in range(nsteps):
+                sample = sample_every > 0 and (k + 1) % sample_every == 0
+                if graph and k == 1:
+                    rec = self.ceed.capture(lambda: self._device_step(sample_every > 0))
+                    self.stats.residual_evals -= 1
+                if rec is not None:
+                    rec.launch()
+                    self.nsteps_done += 1
+                    self.t = self.nsteps_done * self.dt
+                    self.stats.residual_evals += 1
+                else:
+                    self.step(sample or (graph and sample_every > 0))
+                h["steps"] += 1
+                if sample:
+                    ke = float(self._tally.to_numpy()[0])
+                    d = float(np.abs(self.x.to_numpy() - self._x_start).max())
+                    h["t"].append(self.t); h["t_kinetic"].append(self.t - self.dt); h["kinetic"].append(ke); h["max_disp"].append(d)
+                    if graph:                    # a replay writes the arrays behind the vectors: the host mirrors just made are dropped
+                        self._drop_host_mirrors()
+                    if not (np.isfinite(ke) and np.isfinite(d)):
+                        h["diverged"] = True
+                        break
+            self.ceed.synchronize()
+        finally:
+            if rec is not None:
+                rec.destroy()
+                self._drop_host_mirrors()
+        h["seconds"] = time.perf_counter() - t0
+        return h
+
+    def _drop_host_mirrors(self):
+        """A replayed recording writes x, vh, R and the tally by device address, which their validity flags do not see: asking for the
+        device array with write access (no copy, no synchronisation: the device side is the valid one) drops a host mirror."""
+        for v in (self.x, self.vh, self.R, self._tally):
+            v.device_pointer()
+
+    # ---- off the hot path ------------------------------------------------------------------------------------------------------------
+    def velocity(self) -> np.ndarray:
+        """The full-step velocity at the time of x (host): (vh_{n-1/2} + vh_{n+1/2}) / 2 with the half step ahead formed from the
+        current R as the kernel will form it; zero on the constrained rows."""
+        vh = self.vh.to_numpy()
+        vn = self.c1 * vh + self.c2 * self._q_host(self.m.to_numpy())
+        return 0.5 * (vh + vn) * self.free
+
+    def kinetic_energy(self) -> float:
+        """1/2 sum m v^2 over the free rows, v = ``velocity()``."""
+        v = self.velocity()
+        return 0.5 * float(np.sum(self.m.to_numpy() * (v * v)))
+
+    def destroy_mass(self):
+        self.mass_lumped.destroy()
+        for v in (self.vh, self.m, self.minv_m, self._freev, self._tally):
+            v.destroy()

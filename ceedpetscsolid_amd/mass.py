@@ -139,6 +139,39 @@ class MassOperator:
             v[:self.lsize] = self.diagonal_host()
             d.fill(v)
 
+    # ---- the lumped mass: row sums ---------------------------------------------------------------------------------------------
+    def lumped_host(self) -> np.ndarray:
+        """m_i = c sum_e sum_q N_i(q) w det J(q), the row sums of the consistent mass matrix (M 1 with the ones read unmasked, whatever
+        the mask mode); zero on masked rows.  Positive on Gauss-Lobatto nodes for the meshes of this project."""
+        mode, self.mask_mode = self.mask_mode, 2
+        try:
+            d = self.apply_host(np.ones(self.lsize))
+        finally:
+            self.mask_mode = mode
+        if self.mask is not None:
+            d[self.mask] = 0.0
+        return d
+
+    def lumped(self, d: cd.Vector):
+        """d = the lumped mass (``lumped_host``) on a vector of the Ceed: the mass apply on a vector of ones; entries of d beyond the
+        L-size are zero."""
+        if self.op is None:
+            v = np.zeros(d.n)
+            v[:self.lsize] = self.lumped_host()
+            d.fill(v)
+            return
+        ones = self.ceed.vector(self.lsize).set_value(1.0)
+        swap = self.mask is not None and self.mask_mode != 2
+        m8 = self.mask.astype(np.uint8) if swap else None
+        if swap:                          # the ones are read on the masked entries too: the residual's mask form for this one apply
+            self.op.set_dirichlet_mask_mode(m8, None, 2)
+        try:
+            self.op.apply(ones, d)
+        finally:
+            if swap:
+                self.op.set_dirichlet_mask_mode(m8, None, self.mask_mode)
+            ones.destroy()
+
     def destroy(self):
         for o in (self.op, self.qf):
             if o is not None:

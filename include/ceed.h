@@ -323,6 +323,29 @@ CEED_EXTERN_OPTIONAL int CeedXVectorBlockCombine(CeedVector Y, CeedInt y0, CeedI
                                                  CeedVector C, double beta, CeedInt n, CeedInt ld);
 CEED_EXTERN_OPTIONAL int CeedXVectorBlockGetLimits(CeedInt *max_cols, CeedInt *gram_rows, CeedInt *gram_max_parts,
                                                    CeedInt *combine_rows, CeedInt *combine_max_groups);
+/* OPTIONAL entry point: one leapfrog (central-difference) step of explicit    */
+/* elastodynamics with a lumped mass, on the rows i < n with m[i] > 0:         */
+/*     g  = load * f[i] - r[i]            (f NULL: g = -r[i])                  */
+/*     q  = g / m[i]                                                           */
+/*     vn = c1 * vh[i] + c2 * q                                                */
+/*     vm = 0.5 * (vh[i] + vn)   (the velocity AT the step r belongs to)       */
+/*     ke += m[i] * (vm * vm)                                                  */
+/*     vh[i] = vn;   x[i] = x[i] + dt * vn                                     */
+/* every operation rounded on its own, in the order written.  Rows with        */
+/* m[i] <= 0 (constrained rows, a longer vector's tail) are neither written    */
+/* nor summed, whatever r, f, vh hold there (NaN included).                    */
+/* scalars[slot] = 0.5 * ke when scalars is given (a fixed summation order:    */
+/* two calls give the same bits); with scalars NULL no reduction is launched.  */
+/* c1 = (1 - alpha dt/2) / (1 + alpha dt/2), c2 = dt / (1 + alpha dt/2) carry  */
+/* a mass-proportional damping alpha (the caller computes them).               */
+/* Checked before anything is queued: x, vh, r, m are vectors; n >= 1 and      */
+/* every vector holds at least n entries; x, vh, r, m, f are pairwise          */
+/* distinct; 0 <= slot < length of scalars; scalars is none of the operands.   */
+/* Only queues kernels on the Ceed's stream: it can be recorded in a           */
+/* CeedXGraph (after one eager call with a tally, if the tally is recorded).   */
+CEED_EXTERN_OPTIONAL int CeedXVectorLeapfrogStep(CeedVector x, CeedVector vh, CeedVector r, CeedVector f /* or NULL */,
+                                                 CeedVector m, double load, double c1, double c2, double dt,
+                                                 CeedInt n, CeedVector scalars /* or NULL */, CeedInt slot);
 /* One Jacobi-Chebyshev smoother update in a single pass over the vectors     */
 /* (the KSPCHEBYSHEV + PCJACOBI smoother of elasticity.c:539-552):            */
 /*   r -= t (skipped if t is NULL);  d = c1 * dinv .* r + c2 * d;             */

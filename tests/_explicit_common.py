@@ -1,0 +1,167 @@
+"""What the CPU and the device tests of explicit elastodynamics (dynamics.ExplicitDynamics, CeedXVectorLeapfrogStep) share: the meshes,
+the mass-scaled body load, the step's formulas typed out once, the dense references and the runs that both files make.  Every function
+takes the Ceed under test; a reference that must not come from the code under test is formed on the ORACLE's problem and reaches the
+comparison as host arrays only.
+
+Material and load: E = 1, nu = 0.3, rho = 1.5 (_mass_common); the load is f = m (.) g with g = (0.06, 0, 0.03) per node, so the same body
+load acts at every degree (50 steps from rest at the stable step move a unit-sized body by 0.17 - 0.53; a perturbation of the start
+grows by a factor of at most 8 over them)."""
+import os
+
+import numpy as np
+
+from _mass_common import E, NU, RHO
+from _newmark_dense import K_full, M_full
+from _numbering import distorted_box
+from conftest import GOLDEN
+from ceedpetscsolid_amd.dynamics import ExplicitDynamics
+from ceedpetscsolid_amd.mesh import load_mesh_npz
+from ceedpetscsolid_amd.solid import SolidProblem
+
+G = (0.06, 0.0, 0.03)
+CYL672 = os.path.join(GOLDEN, "mesh_cylinder8_672e_4ss_us.npz")
+
+
+def box_problem(ceed, degree, model):
+    """distorted_box(2, 1, 1): two non-affine elements, side 1 clamped; 36, 135, 336, 675 dofs at p = 1 .. 4."""
+    return SolidProblem(ceed, distorted_box(2, 1, 1), degree, model, nu=NU, E=E, bc_sides=[1], multigrid="none")
+
+
+def cylinder_problem(ceed, degree, model="linElas"):
+    return SolidProblem(ceed, load_mesh_npz(CYL672), degree, model, nu=NU, E=E, bc_sides=[998, 999], multigrid="none")
+
+
+def body_load(m):
+    """f = m (.) g on an L-vector of lumped masses."""
+    return m * np.tile(G, m.size // 3)
+
+
+def teardown(sol, prob):
+    sol.destroy_mass()
+    sol.destroy_surface_loads()
+    prob.destroy()
+
+
+class Unchecked(ExplicitDynamics):
+    """The solver without its refusal of an unstable step (the instability itself is what a test wants to see)."""
+
+    def stable_dt(self, steps=20):
+        return float("inf")
+
+
+def coefficients(alpha, dt):
+    """(c1, c2) of include/ceed.h."""
+    return (1.0 - 0.5 * alpha * dt) / (1.0 + 0.5 * alpha * dt), dt / (1.0 + 0.5 * alpha * dt)
+
+
+def step_typed_out(x, vh, r, f, m, load, c1, c2, dt):
+    """The formulas of CeedXVectorLeapfrogStep row by row in Python floats (IEEE doubles: every operation rounded on its own).  Returns
+    (x, vh, the terms m vm^2 of the tally); the inputs are left alone."""
+    x, vh = x.copy(), vh.copy()
+    terms = []
+    for i in range(x.size):
+        mi = float(m[i])
+        if not mi > 0.0:
+            continue
+        g = load * float(f[i]) - float(r[i]) if f is not None else -float(r[i])
+        q = g / mi
+        vo = float(vh[i])
+        vn = c1 * vo + c2 * q
+        vm = 0.5 * (vo + vn)
+        terms.append(mi * (vm * vm))
+        vh[i] = vn
+        x[i] = float(x[i]) + dt * vn
+    return x, vh, terms
+
+
+def step_inputs(n, pad, seed, with_f=True):
+    """Host arrays of length n + pad for one call on n rows: every seventh node's three rows have m = 0 and NaN in r, f, vh; the pad
+    holds canaries.  Returns dict(x, vh, r, f, m)."""
+    rng = np.random.default_rng(seed)
+    a = {k: rng.uniform(-1.0, 1.0, n + pad) for k in ("x", "vh", "r", "f")}
+    a["m"] = rng.uniform(0.05, 2.0, n + pad)
+    dead = np.zeros(n + pad, dtype=bool)
+    dead[:n] = (np.arange(n) // 3) % 7 == 0
+    a["m"][dead] = 0.0
+    for k in ("r", "f", "vh"):
+        a[k][dead] = np.nan
+    for j, k in enumerate(("x", "vh", "r", "f", "m")):
+        a[k][n:] = 1000.0 + 10.0 * j + np.arange(pad)
+    if not with_f:
+        a["f"] = None
+    return a
+
+
+# ---- dense references ---------------------------------------------------------------------------------------------------------------
+def lumped_reference(rprob, rho=RHO):
+    """Row sums of rho x the consistent mass matrix in the residual's form (columns of the portable operator; rows NOT dropped)."""
+    return rho * M_full(rprob).sum(axis=1)
+
+
+def lambda_max(K, m, free):
+    """(lambda_max, eigenvector y) of m^-1/2 K m^-1/2 on the free rows."""
+    fr = np.flatnonzero(free)
+    s = 1.0 / np.sqrt(m[fr])
+    A = s[:, None] * K[np.ix_(fr, fr)] * s[None, :]
+    w, Y = np.linalg.eigh(0.5 * (A + A.T))
+    return float(w[-1]), Y[:, -1]
+
+
+def dense_tangent(ceed, prob):
+    """The tangent at the problem's stored state: unit-vector apply_jacobian of the fine level."""
+    from _mass_common import dense_from_applies
+    n = prob.lsize()
+    return dense_from_applies(ceed, n, lambda x, y: prob.apply_jacobian(prob.fine, x, y), range(n))
+
+
+# ---- runs shared by the two files -----------------------------------------------------------------------------------------------------
+def invariant_run(ceed, rprob, degree, frac, nsteps=400):
+    """linElas, alpha = 0, no load, a random u_0 of size 0.01, ``nsteps`` steps at ``frac`` dt_crit (dense K of ``rprob``): the worst
+    relative drift of the leapfrog invariant 1/2 vh^T m vh + 1/2 x_n^T K x_{n+1}."""
+    prob = box_problem(ceed, degree, "linElas")
+    K = K_full(rprob)
+    sol = ExplicitDynamics(prob, RHO)
+    m, free = sol.m.to_numpy(), sol.free
+    lam, _ = lambda_max(K, m, free)
+    sol.dt = frac * 2.0 / np.sqrt(lam)
+    u0 = 0.01 * np.random.default_rng(17 + degree).uniform(-1, 1, prob.lsize())
+    sol.set_initial(u0=u0)
+    inv = []
+    xa = sol.x.to_numpy()
+    for _ in range(nsteps):
+        sol.step()
+        xb, vh = sol.x.to_numpy(), sol.vh.to_numpy()
+        inv.append(0.5 * float(vh @ (m * vh)) + 0.5 * float(xa @ (K @ xb)))
+        xa = xb
+    teardown(sol, prob)
+    inv = np.array(inv)
+    return float(np.abs(inv - inv[0]).max() / abs(inv[0]))
+
+
+def relaxation_run(ceed, degree, nsteps=4000):
+    """hyperFS, the load m (.) g switched on at t = 0, alpha = 0.5, ``nsteps`` steps at stable_dt().  Returns (x, free, f)."""
+    prob = box_problem(ceed, degree, "hyperFS")
+    probe = ExplicitDynamics(prob, RHO)
+    f = body_load(probe.m.to_numpy())
+    probe.destroy_mass()
+    sol = ExplicitDynamics(prob, RHO, damping=0.5, forcing=f)
+    sol.set_initial()
+    sol.run(nsteps)
+    x, free = sol.x.to_numpy(), sol.free.copy()
+    teardown(sol, prob)
+    return x, free, f
+
+
+def loaded_run(ceed, degree, nsteps=50, dt=None):
+    """hyperFS, ``nsteps`` steps from rest under m (.) g (``dt`` None: the solver's stable step).  Returns (x, max |x - x_0|, dt)."""
+    prob = box_problem(ceed, degree, "hyperFS")
+    probe = ExplicitDynamics(prob, RHO)
+    f = body_load(probe.m.to_numpy())
+    probe.destroy_mass()
+    sol = ExplicitDynamics(prob, RHO, dt=dt, forcing=f)
+    sol.set_initial()
+    sol.run(nsteps)
+    x = sol.x.to_numpy()
+    out = (x, float(np.abs(x - sol._x_start).max()), sol.dt)
+    teardown(sol, prob)
+    return out

@@ -1,0 +1,335 @@
+"""Explicit elastodynamics on the CPU oracle: the lumped mass, the portable form of the step (ceed.leapfrog_step_host) and
+dynamics.ExplicitDynamics against dense references.  The oracle lacks CeedXVectorLeapfrogStep, so every step here takes the portable
+form; tests/test_explicit_gpu.py holds the device kernel against it."""
+import itertools
+import math
+
+import numpy as np
+import pytest
+
+import _explicit_common as ec
+from _mass_common import RHO
+from _newmark_dense import K_full, TOL, TRANSLATE
+from ceedpetscsolid_amd import ceed as cd
+from ceedpetscsolid_amd.dynamics import ExplicitDynamics
+from ceedpetscsolid_amd.mass import MassOperator
+from ceedpetscsolid_amd.solver import NewtonPMG
+
+DEGREES = [1, 2, 3, 4]
+
+
+# ---- 1. lumped mass --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("degree", DEGREES)
+def test_lumped_mass_is_the_row_sum_of_the_consistent_mass(oracle, degree):
+    assert not oracle.L.has("CeedXVectorLeapfrogStep") and "CeedXVectorLeapfrogStep" in cd.CeedLib.OPTIONAL
+    prob = ec.box_problem(oracle, degree, "linElas")
+    n = prob.lsize()
+    assert n == {1: 36, 2: 135, 3: 336, 4: 675}[degree]
+    mask = prob.levels[prob.fine].mask != 0
+    want = ec.lumped_reference(prob)
+    for mode in (2, 3):                          # the ones are read unmasked whatever the operator's mask mode
+        mop = MassOperator(prob, prob.fine, RHO, mask_mode=mode)
+        m = mop.lumped_host()
+        D = oracle.vector(n + 4).set_value(7.0)
+        mop.lumped(D)
+        d = D.to_numpy()
+        assert np.array_equal(d[:n], m) and np.all(d[n:] == 0.0)
+        assert mop.mask_mode == mode
+        err = np.abs(m - want)[~mask].max() / np.abs(want).max()
+        print(f"lumped mass p = {degree}, mask mode {mode}: |m - row sums| / max = {err:.2e}, min over free rows {m[~mask].min():.3e}")
+        assert err <= 1e-13
+        assert np.all(m[mask] == 0.0) and mask.any()
+        assert np.all(m[~mask] > 0.0)
+        mop.destroy(); D.destroy()
+    prob.destroy()
+
+
+@pytest.mark.parametrize("degree", [2, 4])
+def test_lumped_mass_is_positive_on_the_cylinder(oracle, degree):
+    prob = ec.cylinder_problem(oracle, degree)
+    mask = prob.levels[prob.fine].mask != 0
+    m = MassOperator(prob, prob.fine, RHO, mask_mode=2).lumped_host()
+    vol = prob.qdata.to_numpy().reshape(prob.mesh.nelem, 10, -1)[:, 0].sum()
+    print(f"cylinder p = {degree}: min m over free rows {m[~mask].min():.3e}")
+    assert np.all(m[~mask] > 0.0) and np.all(m[mask] == 0.0) and mask.any()
+    # the ones are read on the masked entries too, so the row sums of ALL rows would add up to rho x volume per component: the free rows
+    # hold less than that, and most of it
+    assert 0.5 * 3 * RHO * vol < m.sum() < 3 * RHO * vol
+    prob.destroy()
+
+
+def test_non_positive_lumped_mass_is_refused(oracle):
+    prob = ec.box_problem(oracle, 2, "linElas")
+    sol = ExplicitDynamics(prob, RHO)
+    m = sol.m.to_numpy()
+    row = int(np.flatnonzero(sol.free)[5])
+    m[row] = -1e-3
+    sol.m.set_array(m)
+    with pytest.raises(ValueError, match=f"row {row}"):
+        sol.set_initial()
+    ec.teardown(sol, prob)
+
+
+# ---- 2. the portable step against the formulas typed out ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_f,alpha,tally", list(itertools.product([True, False], [0.0, 0.3], [True, False])))
+def test_leapfrog_step_host_is_the_formulas_bit_for_bit(oracle, with_f, alpha, tally):
+    n, pad, dt, load = 231, 5, 0.037, 0.8
+    c1, c2 = ec.coefficients(alpha, dt)
+    assert (c1, c2) == (1.0, dt) if alpha == 0.0 else c1 < 1.0
+    a = ec.step_inputs(n, pad, 5, with_f)
+    fa = None if a["f"] is None else a["f"][:n]
+    wx, wv, terms = ec.step_typed_out(a["x"][:n], a["vh"][:n], a["r"][:n], fa, a["m"][:n], load, c1, c2, dt)
+    x, vh = a["x"].copy(), a["vh"].copy()
+    ke = cd.leapfrog_step_host(x[:n], vh[:n], a["r"][:n], fa, a["m"][:n], load, c1, c2, dt, tally)
+    assert x[:n].tobytes() == wx.tobytes() and vh[:n].tobytes() == wv.tobytes()        # (bytes: the NaN rows compare too)
+    assert np.array_equal(x[n:], a["x"][n:]) and np.array_equal(vh[n:], a["vh"][n:])
+    dead = a["m"][:n] == 0.0
+    assert dead.sum() == 3 * 11 and np.all(np.isnan(vh[:n][dead])) and np.array_equal(x[:n][dead], a["x"][:n][dead])
+    if tally:
+        want = 0.5 * math.fsum(terms)
+        assert abs(ke - want) <= n * 2.0 ** -52 * 0.5 * math.fsum(abs(t) for t in terms) and want > 0.0
+    else:
+        assert ke is None
+    # the same through the vectors of a Ceed without the entry point: in place on their host arrays
+    V = {k: oracle.vector(n + pad).set_array(v) for k, v in a.items() if v is not None}
+    S = oracle.vector(3).set_array(np.array([11.0, 12.0, 13.0]))
+    V["x"].leapfrog_step(V["vh"], V["r"], V.get("f"), V["m"], load, c1, c2, dt, n, S if tally else None, 1)
+    assert V["x"].to_numpy().tobytes() == x.tobytes() and V["vh"].to_numpy().tobytes() == vh.tobytes()
+    s = S.to_numpy()
+    assert (s[0], s[2]) == (11.0, 13.0) and s[1] == (ke if tally else 12.0)
+    for v in list(V.values()) + [S]:
+        v.destroy()
+
+
+# ---- 3. linear exactness --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("degree", DEGREES)
+@pytest.mark.parametrize("frac", [0.9, 0.5])
+def test_leapfrog_invariant_of_a_linear_material(oracle, degree, frac):
+    """1/2 vh^T m vh + 1/2 x_n^T K x_{n+1} is conserved by the scheme exactly; measured 2e-15 over 400 steps."""
+    rprob = ec.box_problem(oracle, degree, "linElas")
+    drift = ec.invariant_run(oracle, rprob, degree, frac)
+    rprob.destroy()
+    print(f"leapfrog invariant p = {degree}, dt = {frac} dt_crit: worst relative drift over 400 steps {drift:.2e}")
+    assert drift <= 1e-12
+
+
+@pytest.mark.parametrize("degree", DEGREES)
+def test_stability_limit_on_the_top_eigenvector(oracle, degree):
+    """Started on the eigenvector of lambda_max: beyond dt_crit = 2 / sqrt(lambda_max) the amplitude grows without bound (> 1e6 in 400 steps
+    at 1.01 dt_crit); at 0.9 dt_crit the exact discrete solution is x_0 cos(n theta), far below 1 / sqrt(1 - 0.81) times the start."""
+    prob = ec.box_problem(oracle, degree, "linElas")
+    K = K_full(prob)
+    grow = {}
+    for frac in (1.01, 0.9):
+        sol = ec.Unchecked(prob, RHO)
+        m, free = sol.m.to_numpy(), sol.free
+        lam, y = ec.lambda_max(K, m, free)
+        u0 = np.zeros(prob.lsize())
+        u0[free] = y / np.sqrt(m[free])
+        u0 *= 0.01 / np.abs(u0).max()
+        sol.dt = frac * 2.0 / np.sqrt(lam)
+        sol.set_initial(u0=u0)
+        amp = 0.0
+        for _ in range(400):
+            sol.step()
+            amp = max(amp, float(np.abs(sol.x.to_numpy()).max()))
+        grow[frac] = amp / 0.01
+        sol.destroy_mass()
+    prob.destroy()
+    print(f"top eigenvector p = {degree}: amplitude / start over 400 steps {grow[1.01]:.2e} at 1.01 dt_crit, {grow[0.9]:.4f} at 0.9 dt_crit")
+    assert grow[1.01] > 1e6
+    assert grow[0.9] < 1.0 / math.sqrt(1.0 - 0.81)
+
+
+# ---- 4. the dense recursion --------------------------------------------------------------------------------------------------------------
+def _load(t):
+    return 0.5 + 0.5 * np.sin(2.0 * t)
+
+
+def test_solver_against_the_dense_recursion(oracle):
+    """linElas p = 2, a moving clamp, u0, v0, a load function of time, alpha = 0.3, 50 steps, against the recursion on K_full and the row
+    sums of M_full typed out here."""
+    alpha, nsteps = 0.3, 50
+    prob = ec.box_problem(oracle, 2, "linElas")
+    n = prob.lsize()
+    K, m = K_full(prob), ec.lumped_reference(prob)
+    f_all = ec.body_load(m)
+    sol = ExplicitDynamics(prob, RHO, damping=alpha, clamp={1: dict(translate=TRANSLATE)}, forcing=f_all)
+    free = sol.free
+    fr = np.flatnonzero(free)
+    bound = np.tile(TRANSLATE, n // 3) * ~free
+    f = f_all * free
+    rng = np.random.default_rng(71)
+    u0, v0 = 0.01 * rng.uniform(-1, 1, n), 0.01 * rng.uniform(-1, 1, n)
+    sol.set_initial(u0=u0, v0=v0, load=_load)
+    dt = sol.dt
+    c1, c2 = ec.coefficients(alpha, dt)
+    # the reference
+    x = u0 * free + bound * _load(0.0)
+    v = v0 * free
+    q = np.zeros(n)
+    q[fr] = (_load(0.0) * f - K @ x)[fr] / m[fr]
+    vh = v - 0.5 * dt * (q - alpha * v)
+    worst_x = worst_v = 0.0
+    for k in range(nsteps):
+        q[fr] = (_load(k * dt) * f - K @ x)[fr] / m[fr]
+        vh = (c1 * vh + c2 * q) * free
+        x = (x + dt * vh) * free + bound * _load((k + 1) * dt)
+        sol.step()
+        assert abs(sol.t - (k + 1) * dt) <= 1e-14
+        worst_x = max(worst_x, float(np.abs(sol.x.to_numpy() - x).max() / np.abs(x).max()))
+        worst_v = max(worst_v, float(np.abs(sol.vh.to_numpy() - vh).max() / np.abs(vh).max()))
+    # the full-step velocity of the helper: the mean of the half steps on either side of x
+    q[fr] = (_load(nsteps * dt) * f - K @ x)[fr] / m[fr]
+    vfull = 0.5 * (vh + (c1 * vh + c2 * q)) * free
+    e_vel = float(np.abs(sol.velocity() - vfull).max() / np.abs(vfull).max())
+    ke = 0.5 * float(np.sum(m[fr] * vfull[fr] ** 2))
+    e_ke = abs(sol.kinetic_energy() - ke) / ke
+    print(f"dense recursion (p = 2, alpha = {alpha}, dt = {dt:.4f}, {nsteps} steps): worst |x - ref| / max|ref| = {worst_x:.2e}, "
+          f"vh {worst_v:.2e}, velocity() {e_vel:.2e}, kinetic_energy() {e_ke:.2e}")
+    assert np.abs(x[~free]).max() > 0.0 and np.abs(x[free]).max() > 0.02
+    assert worst_x <= TOL and worst_v <= TOL and e_vel <= TOL and e_ke <= TOL
+    ec.teardown(sol, prob)
+
+
+# ---- 5. the stable step ------------------------------------------------------------------------------------------------------------------
+def _check_stable_dt(sol, K, tag):
+    m, free = sol.m.to_numpy(), sol.free
+    lam, _ = ec.lambda_max(K, m, free)
+    got = {steps: sol.stable_dt(steps) for steps in (10, 20)}
+    ratio = {}
+    for steps, dt in got.items():
+        ratio[steps] = (sol.safety * 2.0 / dt) ** 2 / 1.1 / lam
+        assert sol.safety * 2.0 / math.sqrt(1.1 * lam) <= dt * (1.0 + 1e-12) and dt <= 2.0 / math.sqrt(lam), (steps, dt, lam)
+    print(f"stable_dt {tag}: lambda_max {lam:.4f}, estimate / lambda_max {ratio[10]:.4f} (10 Lanczos steps), {ratio[20]:.6f} (20); "
+          f"stable_dt() = {got[20]:.5f}, dt_crit = {2.0 / math.sqrt(lam):.5f}")
+    assert sol.stable_dt() == got[20]
+    return got[20]
+
+
+@pytest.mark.parametrize("degree", DEGREES)
+def test_stable_dt_brackets_the_dense_limit_at_rest(oracle, degree):
+    prob = ec.box_problem(oracle, degree, "linElas")
+    sol = ExplicitDynamics(prob, RHO)
+    limit = _check_stable_dt(sol, K_full(prob), f"linElas p = {degree} at rest")
+    sol.dt = 1.001 * limit / sol.safety
+    with pytest.raises(ValueError, match="stable step"):
+        sol.set_initial()
+    sol.dt = None
+    sol.set_initial()
+    assert sol.dt == limit and (sol.c1, sol.c2) == (1.0, limit)
+    ec.teardown(sol, prob)
+
+
+def test_stable_dt_brackets_the_dense_limit_of_a_deformed_state(oracle):
+    prob = ec.box_problem(oracle, 2, "hyperFS")
+    probe = ExplicitDynamics(prob, RHO)
+    sol = ExplicitDynamics(prob, RHO, forcing=ec.body_load(probe.m.to_numpy()))
+    sol.set_initial()
+    sol.run(50)
+    assert np.abs(sol.x.to_numpy()).max() > 0.1
+    _check_stable_dt(sol, ec.dense_tangent(oracle, prob), "hyperFS p = 2 after 50 steps")
+    ec.teardown(sol, prob)
+
+
+# ---- 6. dynamic relaxation -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("degree", DEGREES)
+def test_damped_run_relaxes_to_the_static_solution(oracle, degree):
+    x, free, f = ec.relaxation_run(oracle, degree)
+    prob = ec.box_problem(oracle, degree, "hyperFS")
+    st = NewtonPMG(prob, forcing=f, snes_rtol=1e-12)
+    assert st.solve(4).converged
+    u = st.U.to_numpy()
+    err = float(np.abs(x - u)[free].max())
+    print(f"relaxation p = {degree}: max |u| = {np.abs(u).max():.4f}, |x - static| = {err:.2e} after 4000 steps")
+    assert np.abs(u).max() > 0.1
+    assert err <= 1e-10 * np.abs(u).max()
+    prob.destroy()
+
+
+# ---- 7. no host traffic between steps ------------------------------------------------------------------------------------------------------
+def test_constant_load_steps_touch_no_host_array(oracle, monkeypatch):
+    """Steps 2 .. 20 of run(20) with a constant load and no sampling: no Vector.to_numpy, no Vector.set_array, no solver._set."""
+    prob = ec.box_problem(oracle, 2, "hyperFS")
+    probe = ExplicitDynamics(prob, RHO)
+    sol = ExplicitDynamics(prob, RHO, forcing=ec.body_load(probe.m.to_numpy()))
+    sol.set_initial()
+    calls, steps = [], [0]
+
+    def counted(cls, name):
+        plain = getattr(cls, name)
+
+        def wrapper(self, *a, **kw):
+            if steps[0] >= 2:
+                calls.append(name)
+            return plain(self, *a, **kw)
+        monkeypatch.setattr(cls, name, wrapper)
+
+    counted(cd.Vector, "to_numpy"); counted(cd.Vector, "set_array"); counted(ExplicitDynamics, "_set")
+    plain_step = ExplicitDynamics.step
+
+    def step(self, *a, **kw):
+        steps[0] += 1
+        return plain_step(self, *a, **kw)
+    monkeypatch.setattr(ExplicitDynamics, "step", step)
+    h = sol.run(20)
+    assert steps[0] == 20 and h["steps"] == 20 and not h["kinetic"]
+    assert calls == []
+    sol.x.to_numpy()
+    assert calls == ["to_numpy"]                 # (the count is alive)
+    probe.destroy_mass(); ec.teardown(sol, prob)
+
+
+def test_run_samples_and_stops_at_a_non_finite_sample(oracle):
+    prob = ec.box_problem(oracle, 2, "hyperFS")
+    probe = ExplicitDynamics(prob, RHO)
+    f = ec.body_load(probe.m.to_numpy())
+    sol = ExplicitDynamics(prob, RHO, forcing=f)
+    sol.set_initial()
+    h = sol.run(12, sample_every=4)
+    assert h["steps"] == 12 and len(h["kinetic"]) == 3 and not h["diverged"]
+    assert np.allclose(h["t"], [4 * sol.dt, 8 * sol.dt, 12 * sol.dt], rtol=1e-14) and np.allclose(np.array(h["t"]) - h["t_kinetic"], sol.dt)
+    assert all(k > 0.0 for k in h["kinetic"]) and h["max_disp"][-1] > h["max_disp"][0] > 0.0
+    # the sampled tally is the kinetic energy of the state BEFORE the step: step once more by hand and compare with the helper
+    ke = sol.kinetic_energy()
+    sol.step(tally=True)
+    assert abs(float(sol._tally.to_numpy()[0]) - ke) <= 1e-13 * ke
+    bad = ec.Unchecked(prob, RHO, dt=40.0 * sol.dt, forcing=f)
+    bad.set_initial()
+    with np.errstate(all="ignore"):
+        hb = bad.run(400, sample_every=10)
+    assert hb["diverged"] and hb["steps"] < 400 and not np.isfinite(hb["kinetic"][-1] + hb["max_disp"][-1])
+    sol.destroy_mass(); ec.teardown(bad, prob)
+
+
+# ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------------
+def test_refusals(oracle):
+    prob = ec.box_problem(oracle, 1, "linElas")
+
+    class TwoRanks:
+        world = 2
+
+    with pytest.raises(ValueError, match="several ranks"):
+        ExplicitDynamics(prob, RHO, halo=[TwoRanks()])
+    for kw in (dict(density=0.0), dict(density=-1.0), dict(density=RHO, dt=0.0), dict(density=RHO, dt=-0.1), dict(density=RHO, damping=-0.1)):
+        with pytest.raises(ValueError):
+            ExplicitDynamics(prob, **kw)
+    sol = ExplicitDynamics(prob, RHO, mms=True)                     # fine
+    sol.set_initial(load=lambda t: 1.0 + t)
+    with pytest.raises(ValueError, match="constant load"):
+        sol.run(3, graph=True)
+    # the portable step makes the checks of the entry point
+    n = 12
+    V = {k: oracle.vector(n).set_value(1.0) for k in ("x", "vh", "r", "f", "m")}
+    S, short = oracle.vector(2).set_value(0.0), oracle.vector(n - 1).set_value(1.0)
+    call = lambda **kw: (lambda a: a["x"].leapfrog_step(a["vh"], a["r"], a["f"], a["m"], 1.0, 1.0, 0.1, 0.1, a.get("n", n), a.get("scalars"),
+                                                        a.get("slot", 0)))({**V, **kw})
+    for kw in (dict(n=0), dict(n=n + 1), dict(r=short), dict(vh=V["x"]), dict(f=V["m"]), dict(r=V["vh"]), dict(scalars=S, slot=2),
+               dict(scalars=S, slot=-1), dict(scalars=V["r"])):
+        with pytest.raises(cd.CeedError):
+            call(**kw)
+    assert np.all(V["x"].to_numpy() == 1.0) and np.all(V["vh"].to_numpy() == 1.0)
+    call(scalars=S, slot=1)
+    # load f - r = 0: vh stays 1, x moves by dt vh, and the tally is 1/2 sum m vh^2
+    assert np.all(V["x"].to_numpy() == 1.0 + 0.1 * 1.0) and np.all(V["vh"].to_numpy() == 1.0) and S.to_numpy()[1] == 0.5 * n
+    ec.teardown(sol, prob)
