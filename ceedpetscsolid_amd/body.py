@@ -1,0 +1,303 @@
+"""A body and its loads: what the quasi-static solve (solver.NewtonPMG) and the implicit and explicit time steppers (dynamics.py) share,
+and nothing of how a system is solved.  ``LoadedBody`` holds the problem, its element partition over several ranks (halo.py: interface
+sums, owner-weighted dots), the boundary values (src/boundary.c), the load vector, the follower pressures (surface.py), the static
+residual and the tangent apply ``A`` in its plain form.  It owns every vector made through ``_vec`` and its surface loads: ``destroy()``
+releases them, and what it was handed (the problem, the halos, a caller's RcclHalo list) stays the caller's."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, Dict, Optional
+
+import numpy as np
+
+from .solid import SolidProblem
+
+
+# ---- boundary functions (src/boundary.c) -------------------------------------------------------
+def bc_mms(X: np.ndarray, load: float) -> np.ndarray:
+    """BCMMS, boundary.c:31-50."""
+    x, y, z = X[:, 0], X[:, 1], X[:, 2]
+    return np.stack([np.exp(2 * x) * np.sin(3 * y) * np.cos(4 * z), np.exp(3 * y) * np.sin(4 * z) * np.cos(2 * x),
+                     np.exp(4 * z) * np.sin(2 * x) * np.cos(3 * y)], axis=1) / 1e8 * load
+
+
+def bc_clamp(X: np.ndarray, load: float, translate=(0., 0., 0.), axis=(0., 0., 1.), angle_over_pi: float = 0.0) -> np.ndarray:
+    """BCClamp, boundary.c:53-74: translation + rotation about `axis` by angle_over_pi*pi, scaled by the load
+    fraction.  The x-component's (1-c) term is reproduced AS WRITTEN at boundary.c:69
+    (`-ky*ky + kz*kz*x + ...`)."""
+    x, y, z = X[:, 0], X[:, 1], X[:, 2]
+    lx, ly, lz = (t * load for t in translate)
+    kx, ky, kz = axis
+    th = angle_over_pi * np.pi * load
+    c, s = np.cos(th), np.sin(th)
+    u0 = lx + s * (-kz * y + ky * z) + (1 - c) * (-ky * ky + kz * kz * x + kx * ky * y + kx * kz * z)
+    u1 = ly + s * (kz * x + -kx * z) + (1 - c) * (kx * ky * x - (kx * kx + kz * kz) * y + ky * kz * z)
+    u2 = lz + s * (-ky * x + kx * y) + (1 - c) * (kx * kz * x + ky * kz * y - (kx * kx + ky * ky) * z)
+    return np.stack([u0, u1, u2], axis=1)
+
+
+@dataclass
+class SolveStats:
+    newton_its: int = 0
+    ksp_its: int = 0
+    coarse_its: int = 0
+    jacobian_applies: int = 0
+    coarse_spmv: int = 0
+    residual_evals: int = 0
+    seconds: float = 0.0
+    increments: int = 0
+    converged: bool = True
+    history: list = field(default_factory=list)
+    initial_residuals: list = field(default_factory=list)   # |R| at the start of every load increment (what snes_rtol is relative to)
+
+
+class LoadedBody:
+    def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None, halo=None,
+                 rccl="auto", traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None,
+                 pressure_tangent: str = "full", verbose: bool = False):
+        """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
+        -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
+        set but absent here are held at zero.
+        Surface loads (surface.py; one rank, and never on a clamped side set):
+        ``traction``: {side_set_id: (tx, ty, tz)} -- a dead load per unit REFERENCE area acting on the body in the direction t, scaled by
+        the load fraction like the body force; evaluated once and folded into the load vector.
+        ``pressure``: {side_set_id: p} -- a pressure on the CURRENT surface, p > 0 pushing on the body, scaled by the load fraction;
+        evaluated in every residual, R = F_int(u) - load (f + sum_s g_s^traction) + load sum_s p_s g_s^pressure(u).
+        ``pressure_tangent``: "full" adds load sum_s p_s T_s(u) to ``A_outer`` (the Jacobian of an outer Krylov iteration; ``A``, and
+        with it a V-cycle, its smoothers, diagonals and eigenvalue estimates, do not see it); "none" omits it (modified Newton).
+        T(u) is symmetric only on the variations that vanish on the rim of the loaded surface: a closed surface, or
+        a patch whose rim is clamped (a tube with clamped ends).  A CG iteration assumes a symmetric operator; a follower pressure on a
+        patch with a free rim is the caller's responsibility, as with any non-conservative load."""
+        self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
+        self.verbose = verbose
+        self.nlev = len(prob.levels)
+        # Several ranks (one element partition per rank, halo.py): `halo` is one HaloExchange per multigrid level (a single one stands
+        # for a one-level list).  Every vector then aliases a torch tensor (host memory for the CPU oracle, device memory otherwise;
+        # the Ceed's stream must be torch's current stream, as in bench.py), so the interface sums of halo.add() act on the operators'
+        # outputs in place: the L -> G sum of matops.c:57 after each Jacobian / residual / transfer / diagonal.  Dots are owner-weighted.
+        single = halo is not None and not isinstance(halo, (list, tuple))
+        halo = [halo] if single else halo
+        many = self._several_ranks(halo)
+        if traction or pressure:
+            # partial face sums at the interface nodes would need the exchange between the add and its consumer
+            self._refuse_several_ranks(halo, "surface loads (traction=, pressure=) are",
+                                       "the face sums of the interface nodes are not summed over the ranks")
+        if many and single and self.nlev > 1:
+            raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
+        if many and len(halo) != self.nlev:
+            raise ValueError("one HaloExchange per multigrid level expected")
+        self.halos = list(halo) if many else None
+        self.halo = self.halos[-1] if self.halos else None
+        self.clamp, self.mms = clamp or {}, mms
+        # the library's exchange per level (halo.RcclHalo), or None: torch.distributed point-to-point + index ops
+        self.rhalos, self._own_rhalos = None, []
+        if self.halos:
+            if isinstance(rccl, (list, tuple)):
+                self.rhalos = list(rccl)
+            elif rccl == "auto":
+                import torch.distributed as dist
+                if dist.is_initialized() and dist.get_backend(self.halos[-1].group) == "nccl" and self.halos[-1].device.type == "cuda":
+                    from .halo import RcclHalo
+                    self.rhalos = self._own_rhalos = [RcclHalo(self.ceed, h) for h in self.halos]
+            if self.rhalos is not None and len(self.rhalos) != self.nlev:
+                raise ValueError("one RcclHalo per multigrid level expected")
+        self._vectors = []                           # every vector made by _vec: what destroy() releases
+        self._x0 = {}
+        n, top = prob.lsize(), self.nlev - 1
+        self.R, self.Xloc, self.bcv = (self._vec(n, top) for _ in range(3))
+        self.free = prob.levels[prob.fine].mask == 0
+        self.weights = [None] * self.nlev
+        if self.halos:
+            for lv in range(self.nlev):
+                wv = self._vec(prob.lsize(lv), lv)
+                self._set(wv, self.halos[lv].owner_weight * (prob.levels[lv].mask == 0))
+                self.weights[lv] = wv
+                self._refresh_multiplicity(lv)
+        # body force vector (opSetupForce output, setuplibceed.c:555-583): SNESSolve(snes, F, U) solves
+        # residual(U) = load * F on the unconstrained dofs (elasticity.c:645-654)
+        self.fv = None
+        if forcing is not None:
+            self.fv = self._vec(n, top)
+            self._set(self.fv, np.asarray(forcing, dtype=np.float64) * self.free)
+            self._halo_sum(top, self.fv)
+        self.load = 1.0
+        self.stats = SolveStats()
+        self._bc_nodes = self._collect_bc_nodes()
+        self._setup_surface_loads(traction, pressure, pressure_tangent)
+
+    # ---- several ranks ------------------------------------------------------------------------
+    @staticmethod
+    def _several_ranks(halo) -> bool:
+        hl = halo if halo is None or isinstance(halo, (list, tuple)) else [halo]
+        return bool(hl) and hl[-1].world > 1
+
+    @classmethod
+    def _refuse_several_ranks(cls, halo, who: str, why: str):
+        if cls._several_ranks(halo):
+            raise ValueError(f"{who} not provided with a halo (several ranks): {why}")
+
+    @staticmethod
+    def _load_function(load) -> Callable[[float], float]:
+        """The load fraction as a function of time: ``load`` itself, or the constant it states."""
+        return load if callable(load) else (lambda t, v=float(load): v)
+
+    # ---- surface loads (surface.py) -----------------------------------------------------------
+    def _setup_surface_loads(self, traction, pressure, pressure_tangent):
+        """With no surface load given nothing here runs beyond the argument checks, and no solve takes a new path."""
+        if pressure_tangent not in ("full", "none"):
+            raise ValueError(f"pressure_tangent must be 'full' or 'none', not {pressure_tangent!r}")
+        self.pressure_tangent = pressure_tangent
+        self.pressure_loads = []                     # (SurfaceLoad, p) per loaded side set
+        self.surface_loads = []                      # every SurfaceLoad made here (destroy_surface_loads)
+        if not traction and not pressure:
+            return
+        from .mesh import side_set_nodes
+        from .surface import SurfaceLoad
+        prob, lv = self.p, self.p.levels[self.p.fine]
+        for sid in list(traction or {}) + list(pressure or {}):
+            if sid not in prob.mesh.side_sets:
+                raise ValueError(f"surface load on side set {sid}: the mesh has no such side set")
+            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
+            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
+                raise ValueError(f"surface load on side set {sid}, which is one of the problem's Dirichlet side sets")
+        n, top = prob.lsize(), self.nlev - 1
+        make = lambda sid: SurfaceLoad(self.ceed, prob.mesh, lv.dofmap, [sid], Q=prob.Q, mask=lv.mask)
+        for sid, t in (traction or {}).items():
+            t = np.asarray(t, dtype=np.float64).reshape(-1)
+            if t.size != 3:
+                raise ValueError(f"traction on side set {sid}: three components expected")
+            if self.fv is None:
+                self.fv = self._vec(n, top)
+            sl = make(sid)
+            sl.traction_add(t, 1.0, self.fv)         # masked rows are never written: fv stays zero on the constrained dofs
+            self.surface_loads.append(sl)
+        for sid, pval in (pressure or {}).items():
+            sl = make(sid)
+            self.pressure_loads.append((sl, float(pval)))
+            self.surface_loads.append(sl)
+
+    def destroy_surface_loads(self):
+        for sl in self.surface_loads:
+            sl.destroy()
+        self.surface_loads, self.pressure_loads = [], []
+
+    def destroy(self):
+        """Release what this object made: its vectors, its surface loads and the RcclHalos of rccl="auto".  Idempotent; a subclass
+        releases its own first and ends with super().destroy()."""
+        self.destroy_surface_loads()
+        for o in self._vectors + self._own_rhalos:
+            o.destroy()
+        self._vectors, self._own_rhalos, self._x0 = [], [], {}
+
+    # ---- vector helpers ---------------------------------------------------------------------
+    def axpby(self, y, a, x, b):
+        y.axpby(a, x, b)
+
+    def copy(self, dst, src):
+        dst.axpby(1.0, src, 0.0)
+
+    def dot(self, x, y, fine_weight=False, lv=None) -> float:
+        """x . y; on several ranks each dof counts once (owner weights of level `lv`, default the fine level)."""
+        lv = self.nlev - 1 if lv is None else lv
+        if self.rhalos:      # the sum over the ranks on the device (ncclAllReduce on the Ceed's stream), ONE read at the end
+            sc = self.ceed.scalars
+            x.dot_to(y, sc, 7, self.weights[lv])
+            self.ceed.all_reduce(sc, 7, 1)
+            return float(sc.to_numpy()[7])
+        v = x.dot(y, self.weights[lv])
+        if self.halos:
+            import torch, torch.distributed as dist
+            t = torch.tensor([v], dtype=torch.float64, device="cpu" if self.halos[lv].device.type == "cpu" or self.halos[lv].stage_host else self.halos[lv].device)
+            dist.all_reduce(t, group=self.halos[lv].group)
+            v = float(t.item())
+        return v
+
+    def _vec(self, n, lv):
+        """A zeroed vector of this object's (several ranks: one that aliases a torch tensor)."""
+        v = self.ceed.tensor_vector(n, self.halos[lv].device) if self.halos else self.ceed.vector(n).set_value(0.0)
+        self._vectors.append(v)
+        return v
+
+    def _set(self, vec, arr):
+        """vec := arr (host array), keeping the torch alias intact."""
+        vec.fill(arr)
+
+    def _halo_sum(self, lv, vec):
+        """Interface sum of an operator output at level lv (the DMLocalToGlobal(ADD_VALUES) of matops.c:57)."""
+        if self.rhalos:               # the library's exchange, on the Ceed's stream: nothing to synchronise, nothing to re-wrap
+            self.rhalos[lv].add(vec)
+        elif self.halos:
+            if vec.t.device.type == "cuda":
+                self.ceed.synchronize()
+            self.halos[lv].add(vec.t)
+            vec.touched()
+
+    def _refresh_multiplicity(self, lv):
+        """multVec of misc.c:115-143 counted over ALL ranks: 1 / (halo-summed element multiplicity)."""
+        level = self.p.levels[lv]
+        m = self._vec(self.p.lsize(lv), lv)
+        level.Erestrictu.multiplicity(m)
+        self._halo_sum(lv, m)
+        self._set(level.multinv, 1.0 / m.to_numpy())
+
+    def _start_vector(self, lv):
+        """The start vector of an eigenvalue estimate on level lv (free dofs only, norm 1), drawn once per level; no BLAS on the host
+        (a threaded BLAS call leaves its worker pool spinning, which starves a CPU-quota'd process for ~0.1 s a call)."""
+        if lv not in self._x0:
+            free = self.p.levels[lv].mask == 0
+            if self.halos:   # shared nodes must get the same value on every rank: a hash of the coordinates
+                X = self.p.levels[lv].dofmap.node_coords
+                k = np.array([[12.9898, 78.233, 37.719], [93.989, 67.345, 24.113], [45.164, 11.135, 83.951]])
+                v = np.sin(X @ k.T) * 437.5453
+                x = (2.0 * (v - np.floor(v)) - 1.0).reshape(-1) * free
+            else:
+                x = np.random.default_rng(1234 + lv).uniform(-1, 1, free.size) * free
+            x0 = self._vec(free.size, lv)
+            self._set(x0, x / np.sqrt(np.square(x).sum()))     # (any positive scale: the iteration renormalises)
+            self._x0[lv] = x0
+        return self._x0[lv]
+
+    # ---- operators ---------------------------------------------------------------------------
+    def A(self, lv, x, y):
+        """y = the tangent of level lv at the stored state applied to x, summed over the interfaces."""
+        self.p.apply_jacobian(lv, x, y)
+        self.stats.jacobian_applies += 1
+        self._halo_sum(lv, y)
+
+    def A_outer(self, lv, x, y):
+        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x, u the state of the last
+        residual evaluation (Xloc: free part + boundary values).  Masked entries of x read as zero and masked rows are not written,
+        as in the volume operator."""
+        self.A(lv, x, y)
+        if self.pressure_tangent == "full":
+            for sl, pval in self.pressure_loads:
+                sl.tangent_add(pval, self.load, self.Xloc, x, y)
+
+    def _collect_bc_nodes(self):
+        from .mesh import side_set_nodes
+        lv = self.p.levels[self.p.fine]
+        return {sid: side_set_nodes(self.p.mesh, lv.dofmap, [sid]) for sid in self.clamp}
+
+    def bc_values(self, load: float) -> np.ndarray:
+        """DMPlexInsertBoundaryValues at `time = loadIncrement` (matops.c:70-72)."""
+        lv = self.p.levels[self.p.fine]
+        v = np.zeros((lv.dofmap.nnodes, 3))
+        if self.mms:
+            nodes = np.nonzero(lv.mask.reshape(-1, 3)[:, 0])[0]
+            v[nodes] = bc_mms(lv.dofmap.node_coords[nodes], load)
+        for sid, par in self.clamp.items():
+            nodes = self._bc_nodes[sid]
+            v[nodes] = bc_clamp(lv.dofmap.node_coords[nodes], load, **par)
+        return (v.reshape(-1) * (lv.mask != 0))
+
+    def residual(self, U, R):
+        """FormResidual_Ceed: Xloc = free part of U + boundary values; R = F(Xloc), constrained rows dropped."""
+        self.copy(self.Xloc, U)
+        self.axpby(self.Xloc, 1.0, self.bcv, 1.0)
+        self.p.form_residual(self.Xloc, R)
+        self._halo_sum(self.nlev - 1, R)
+        if self.fv is not None:
+            self.axpby(R, -self.load, self.fv, 1.0)
+        for sl, pval in self.pressure_loads:           # follower pressure on the current surface (constrained rows are not written)
+            sl.pressure_add(pval, self.load, self.Xloc, R)
+        self.stats.residual_evals += 1

@@ -1,5 +1,5 @@
-"""Elastodynamics: implicit Newmark time stepping on top of the Newton - CG - p-multigrid solve (solver.py), and explicit
-central-difference stepping with a lumped mass (``ExplicitDynamics``, at the end of the file: its equations are in its docstring).
+"""Elastodynamics: implicit Newmark time stepping (``NewmarkPMG``: the Newton iteration of its parent solver.NewtonPMG on a residual with
+the inertia term), and explicit central-difference stepping with a lumped mass (``ExplicitDynamics``, a body.LoadedBody, at the end).
 
 The semi-discrete equations, with the sign and load conventions of ``solver.NewtonPMG`` (R = F_int - load (f + tractions) + load
 sum_s p_s g_s^pressure, a pressure p > 0 pushing on the body),
@@ -31,7 +31,8 @@ from typing import Callable, Optional, Union
 
 import numpy as np
 
-from .krylov import lanczos_device, lanczos_emax
+from .body import LoadedBody
+from .krylov import lanczos_device, lanczos_emax, pcg
 from .mass import MassOperator
 from .solid import SolidProblem
 from .solver import NewtonPMG, SolveStats
@@ -43,12 +44,8 @@ class NewmarkPMG(NewtonPMG):
             raise ValueError("density, dt and beta must be positive")
         if kw.get("smoother", "jacobi") == "pbjacobi":
             raise ValueError("NewmarkPMG: smoother='pbjacobi' is not provided: the 3 x 3 nodal blocks of the mass operator are not built")
-        halo = kw.get("halo")
-        if halo is not None:
-            hl = halo if isinstance(halo, (list, tuple)) else [halo]
-            if hl[-1].world > 1:
-                raise ValueError("NewmarkPMG is not provided with a halo (several ranks): the mass operator's sums at the interface nodes "
-                                 "have not been run over several ranks")
+        self._refuse_several_ranks(kw.get("halo"), "NewmarkPMG is", "the mass operator's sums at the interface nodes have not been run "
+                                   "over several ranks")
         if kw.get("line_search", "cp") == "cp-petsc":
             raise ValueError("NewmarkPMG: line_search must be 'cp' or 'full'")
         self.density, self.dt, self.beta, self.gamma = float(density), float(dt), float(beta), float(gamma)
@@ -100,7 +97,7 @@ class NewmarkPMG(NewtonPMG):
         """State at t = 0: displacement u0 and velocity v0 (host L-vectors; None: zero) on the free dofs, the boundary values of
         load(0) on the others, and a_0 = (rho M)^-1 (load f - F_int(u_0) - pressure terms) on the free dofs by Jacobi-preconditioned CG
         on the mass operator (its condition number is O(1))."""
-        self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+        self._load_fn = self._load_function(load)
         n = self.p.lsize()
         free = self.free
         self.t = 0.0
@@ -116,29 +113,12 @@ class NewmarkPMG(NewtonPMG):
 
     def _mass_solve(self, b, x, rtol: float = 1e-13, maxit: int = 200):
         """x = (rho M)^-1 b on the free dofs: Jacobi-preconditioned CG with the fine level's tangent mass operator at coefficient rho."""
-        top = self.nlev - 1
-        M = self.mass[top]
+        M, w = self.mass[self.nlev - 1], self.w[self.nlev - 1]
         M.set_coef(self.density)
-        w = self.w[top]
-        r, z, d, t, dinv = w["r"], w["z"], w["d"], w["t"], w["x"]
+        dinv = w["x"]
         M.diagonal(dinv)
         dinv.reciprocal()
-        x.set_value(0.0)
-        self.copy(r, b)
-        z.pointwise_mult(r, dinv); self.copy(d, z)
-        rz = rz0 = self.dot(r, z, True)
-        for _ in range(maxit):
-            if rz0 <= 0.0:
-                break
-            M.apply(d, t)
-            alpha = rz / self.dot(d, t, True)
-            self.axpby(x, alpha, d, 1.0); self.axpby(r, -alpha, t, 1.0)
-            z.pointwise_mult(r, dinv)
-            rz_new = self.dot(r, z, True)
-            if rz_new <= rtol ** 2 * rz0:
-                break
-            self.axpby(d, 1.0, z, rz_new / rz)
-            rz = rz_new
+        pcg(M.apply, lambda z, r: z.pointwise_mult(r, dinv), lambda u, v: self.dot(u, v, True), b, x, w["r"], w["z"], w["d"], w["t"], rtol, maxit)
         M.set_coef(self.a0 * self.density)
 
     # ---- one step ------------------------------------------------------------------------------------------------------------
@@ -156,26 +136,7 @@ class NewmarkPMG(NewtonPMG):
         self._pred.waxpby(-self.a0, self.xn, -self.a2, self.vn)
         self.axpby(self._pred, -self.a3, self.an, 1.0)
         self.residual(self.U, self.R)                    # the start of the iteration: u_n on the free dofs
-        rnorm0 = rnorm = np.sqrt(self.dot(self.R, self.R, True))
-        st.initial_residuals.append(rnorm0)
-        if self.verbose:
-            print(f"t = {self.t:.6g}: |R| = {rnorm0:.6e}")
-        for it in range(self.snes_maxit):
-            if rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50:
-                break
-            self.setup_preconditioner()
-            self.record_preconditioner(self.w[self.nlev - 1]["b"], self.kz)
-            self.axpby(self.Rtry, -1.0, self.R, 0.0)
-            k = self.fcg(self.Rtry, self.dU, self.ksp_rtol)
-            st.ksp_its += k
-            lam = self._line_search()
-            self.axpby(self.U, lam, self.dU, 1.0)
-            self.residual(self.U, self.R)                # also refreshes the stored state and Xloc
-            rnorm = np.sqrt(self.dot(self.R, self.R, True))
-            st.newton_its += 1
-            st.history.append((1, it + 1, k, lam, rnorm))
-            if self.verbose:
-                print(f"   newton {it + 1:2d}: ksp its {k:3d}  lambda {lam:.4f}  |R| = {rnorm:.6e}")
+        rnorm0, rnorm = self._newton(1, f"t = {self.t:.6g}")
         st.converged = bool(np.isfinite(rnorm) and (rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50))
         st.increments = 1
         self.last_rnorm = float(rnorm)
@@ -187,35 +148,15 @@ class NewmarkPMG(NewtonPMG):
         self.copy(self.xn, self.Xloc)
         self.ceed.synchronize()
         st.seconds = time.perf_counter() - t0
-        if self._pc_graph is not None:
-            self._pc_graph.destroy()
-            self._pc_graph = None
+        self._drop_pc_graph()
         return st
-
-    def _line_search(self) -> float:
-        """The parent's critical-point secant search on phi(l) = dU . R(U + l dU) ("cp"), or l = 1 ("full")."""
-        lam, lam_old = 1.0, 0.0
-        if self.line_search == "full":
-            return lam
-        phi_old = self.dot(self.dU, self.R, True)
-        for _ in range(3):
-            self.copy(self.Utry, self.U); self.axpby(self.Utry, lam, self.dU, 1.0)
-            self.residual(self.Utry, self.Rtry)
-            phi = self.dot(self.dU, self.Rtry, True)
-            if abs(phi) <= 1e-8 * abs(phi_old) or abs(phi - phi_old) < 1e-300:
-                break
-            lam_new = lam - phi * (lam - lam_old) / (phi - phi_old)
-            if not np.isfinite(lam_new) or abs(lam_new - lam) < 1e-8 or lam_new <= 0.0 or lam_new > 10.0:
-                break
-            lam_old, phi_old, lam = lam, phi, lam_new
-        return lam
 
     def run(self, nsteps: int, load: Union[float, Callable[[float], float], None] = None) -> dict:
         """``nsteps`` steps from the current state (``set_initial`` first; ``load`` given here replaces its load function).  Returns the
         history: per step t, |u| and max |u| over the free dofs, the kinetic energy 1/2 v . rho M v, Newton and Krylov counts, the last
         Newton residual norm and whether the step converged."""
         if load is not None:
-            self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+            self._load_fn = self._load_function(load)
         if not self._started:
             self.set_initial(load=self._load_fn)
         h = {k: [] for k in ("t", "norm_u", "max_u", "kinetic", "newton_its", "ksp_its", "rnorm", "converged")}
@@ -234,8 +175,12 @@ class NewmarkPMG(NewtonPMG):
         for m in self.mass + [self.mass_res]:
             m.destroy()
 
+    def destroy(self):
+        self.destroy_mass()
+        super().destroy()
 
-class ExplicitDynamics(NewtonPMG):
+
+class ExplicitDynamics(LoadedBody):
     """Explicit elastodynamics: the central-difference ("leapfrog") rule with a lumped mass m (mass.MassOperator.lumped: the row sums of
     rho M) and a mass-proportional damping alpha,
 
@@ -246,9 +191,9 @@ class ExplicitDynamics(NewtonPMG):
 
     on the free rows; the constrained rows of x carry the boundary values of load(t) (``bc_values``), m is zero there and the step
     leaves them alone.  A step is ONE vector kernel (CeedXVectorLeapfrogStep, csrc/kernels_explicit.hip; its NumPy form on the CPU
-    oracle) and one evaluation of the residual: no preconditioner, no Krylov loop, no coarse level -- the parent class is subclassed for
-    the boundary values, the load vector, the surface loads and ``A`` (the tangent of the stable-step estimate) only, and its
-    preconditioner is never set up.  With a constant load nothing between two steps touches the host.
+    oracle) and one evaluation of the residual: no preconditioner, no Krylov loop, no coarse level -- the class is a body.LoadedBody
+    (the boundary values, the load vector, the surface loads and ``A``, the tangent of the stable-step estimate) and takes its
+    keywords only; a preconditioner keyword is a TypeError.  With a constant load nothing between two steps touches the host.
 
     State: ``x`` (the L-vector WITH the boundary values: what the residual reads; it is the parent's ``Xloc``), ``vh`` (the half-step
     velocity), ``R`` (the residual at x), ``m``.  After ``step()``: x = x_{n+1}, vh = vh_{n+1/2}, R = R(x_{n+1}), t = t_{n+1}.
@@ -267,20 +212,17 @@ class ExplicitDynamics(NewtonPMG):
             raise ValueError("damping (the mass-proportional coefficient alpha) must not be negative")
         if not 0.0 < safety <= 1.0:
             raise ValueError("safety must lie in (0, 1]")
-        halo = kw.get("halo")
-        if halo is not None:
-            hl = halo if isinstance(halo, (list, tuple)) else [halo]
-            if hl[-1].world > 1:
-                raise ValueError("ExplicitDynamics is not provided with a halo (several ranks): the mass operator's sums at the interface "
-                                 "nodes have not been run over several ranks")
+        self._refuse_several_ranks(kw.get("halo"), "ExplicitDynamics is", "the mass operator's sums at the interface nodes have not been "
+                                   "run over several ranks")
         super().__init__(prob, **kw)
         self.density, self.damping, self.safety = float(density), float(damping), float(safety)
         self.dt = None if dt is None else float(dt)
         self.c1 = self.c2 = None
         n, top = prob.lsize(), self.nlev - 1
-        self.x = self.Xloc                      # (the parent's name for "free part + boundary values": A_outer reads it)
+        self.x = self.Xloc                      # (the body's name for "free part + boundary values": A_outer reads it)
         self.vh, self.m, self.minv_m, self._freev = (self._vec(n, top) for _ in range(4))
         self._tally = self._vec(2, top)         # slot 0: the kinetic energy of a sampled step
+        self._lanczos_work = None               # the four work vectors of stable_dt, made at its first call
         self.mass_lumped = MassOperator(prob, prob.fine, self.density, mask_mode=2)
         self.mass_lumped.lumped(self.m)         # formed once per solver object
         self._set(self._freev, self.free.astype(np.float64))
@@ -333,14 +275,10 @@ class ExplicitDynamics(NewtonPMG):
             self._force()
         self._set(self.minv_m, np.where(self.free, 1.0 / np.where(self.free, self._check_mass(), 1.0), 0.0))
         top = self.nlev - 1
-        if top not in self._x0:
-            x = np.random.default_rng(1234 + top).uniform(-1, 1, self.free.size) * self.free
-            x0 = self._vec(self.free.size, top)
-            self._set(x0, x / np.sqrt(np.square(x).sum()))
-            self._x0[top] = x0
-        w = self.w[top]
-        al, be = lanczos_device(self.ceed, lambda x, y: self.A(top, x, y), lambda z, r: z.pointwise_mult(r, self.minv_m), self._x0[top],
-                                w["r"], w["z"], w["d"], w["t"], steps)
+        if self._lanczos_work is None:
+            self._lanczos_work = [self._vec(self.free.size, top) for _ in range(4)]
+        al, be = lanczos_device(self.ceed, lambda x, y: self.A(top, x, y), lambda z, r: z.pointwise_mult(r, self.minv_m),
+                                self._start_vector(top), *self._lanczos_work, steps)
         self.emax_K = lanczos_emax(al, be)
         return self.safety * 2.0 / np.sqrt(1.1 * self.emax_K)
 
@@ -351,7 +289,7 @@ class ExplicitDynamics(NewtonPMG):
         that (vh_{-1/2} + vh_{1/2}) / 2 = v_0.  dt is settled here: ``stable_dt()`` if none was given; a given one above
         stable_dt() / safety is refused."""
         self._load_const = not callable(load)
-        self._load_fn = load if callable(load) else (lambda t, v=float(load): v)
+        self._load_fn = self._load_function(load)
         n, free = self.p.lsize(), self.free
         m = self._check_mass()
         self.t, self.nsteps_done = 0.0, 0
@@ -466,3 +404,7 @@ class ExplicitDynamics(NewtonPMG):
         self.mass_lumped.destroy()
         for v in (self.vh, self.m, self.minv_m, self._freev, self._tally):
             v.destroy()
+
+    def destroy(self):
+        self.destroy_mass()
+        super().destroy()

@@ -1,6 +1,8 @@
 """What the p-multigrid levels (solver.py) and the aggregation levels under them (amg.py) share: the eigenvalue estimate of the
-Chebyshev smoother -- KSPChebyshevEstEig's preconditioned CG and its Lanczos tridiagonal (elasticity.c:546-549) -- and the
-coefficients of the Chebyshev iteration itself.  Only `ceed.py` methods are called: no mesh, no operator, any backend of the ABI."""
+Chebyshev smoother -- KSPChebyshevEstEig's preconditioned CG and its Lanczos tridiagonal (elasticity.c:546-549) --, the
+coefficients of the Chebyshev iteration itself, and the one CG whose scalars are read on the host (``pcg``: the coarse solve, the mass
+solve of dynamics.py, the eigenvalue estimate over torch.distributed).  Only `ceed.py` methods are called: no mesh, no operator, any
+backend of the ABI."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,6 +40,40 @@ def lanczos_device(ceed, apply_A, apply_Minv, x0, r, z, p, Ap, steps, weight=Non
     good = (alphas > 0.0) & np.isfinite(betas)
     k = steps if good.all() else int(np.argmin(good))
     return alphas[:k].tolist(), betas[:k].tolist()
+
+
+def pcg(apply_A, apply_Minv, dot, b, x, r, z, d, t, rtol, maxit):
+    """Preconditioned CG with its scalars on the host: x = A^-1 b from x = 0 until r . z <= rtol^2 (r . z)_0 or ``maxit`` steps.
+    ``apply_A(d, t)``, ``apply_Minv(z, r)``, ``dot(u, v) -> float``; r, z, d, t: work vectors.  Returns (steps made, alphas, betas).
+    ``x=None``: no iterate is formed -- with rtol = 0 the coefficients of ``maxit`` steps from the right-hand side b, which
+    ``lanczos_emax`` takes (``lanczos_device`` is the same recurrence with the scalars left on the device).  A step whose r . z or
+    d . A d is not positive (breakdown, an indefinite operator, a NaN) ends the iteration before anything is divided by it."""
+    if x is not None:
+        x.set_value(0.0)
+    r.axpby(1.0, b, 0.0)
+    apply_Minv(z, r)
+    d.axpby(1.0, z, 0.0)
+    rz = rz0 = dot(r, z)
+    alphas, betas = [], []
+    for _ in range(maxit):
+        if not rz > 0.0:
+            break
+        apply_A(d, t)
+        pAp = dot(d, t)
+        if not pAp > 0.0:
+            break
+        alpha = rz / pAp
+        if x is not None:
+            x.axpby(alpha, d, 1.0)
+        r.axpby(-alpha, t, 1.0)
+        apply_Minv(z, r)
+        rz_new = dot(r, z)
+        alphas.append(alpha); betas.append(rz_new / rz)
+        if rz_new <= rtol ** 2 * rz0:
+            break
+        d.axpby(1.0, z, rz_new / rz)
+        rz = rz_new
+    return len(alphas), alphas, betas
 
 
 def lanczos_emax(alphas, betas) -> float:

@@ -15,6 +15,9 @@ hierarchy on the assembled matrix ("amg", amg.py: what the reference asks of PCG
 preconditioner mildly non-linear the outer Krylov method is the flexible (Polak-Ribiere) CG, which coincides with CG for a
 fixed preconditioner.
 
+The body, its loads and the ownership of every vector are body.LoadedBody's; the class here adds the preconditioner, the Krylov method
+and ONE Newton iteration (``_newton``, ``_line_search``: dynamics.NewmarkPMG runs it too); the coarse level's CG is krylov.pcg.
+
 Iteration counts are therefore this build's own, not PETSc's; the throughput figure reported is the
 reference's "DoFs/Sec in SNES" = 1e-6 * Ugsz * (total KSP iterations) / (solve time)
 (elasticity.c:755-764).
@@ -22,55 +25,17 @@ reference's "DoFs/Sec in SNES" = 1e-6 * Ugsz * (total KSP iterations) / (solve t
 from __future__ import annotations
 
 import time
-from dataclasses import dataclass, field
 from typing import Dict, Optional
 
 import numpy as np
 
 from . import ceed as cd
-from .krylov import chebyshev_coefficients, lanczos_device, lanczos_emax
+from .body import LoadedBody, SolveStats, bc_clamp, bc_mms  # noqa: F401 -- (the boundary functions stay importable from here)
+from .krylov import chebyshev_coefficients, lanczos_device, lanczos_emax, pcg
 from .solid import SolidProblem
 
 
-# ---- boundary functions (src/boundary.c) -------------------------------------------------------
-def bc_mms(X: np.ndarray, load: float) -> np.ndarray:
-    """BCMMS, boundary.c:31-50."""
-    x, y, z = X[:, 0], X[:, 1], X[:, 2]
-    return np.stack([np.exp(2 * x) * np.sin(3 * y) * np.cos(4 * z), np.exp(3 * y) * np.sin(4 * z) * np.cos(2 * x),
-                     np.exp(4 * z) * np.sin(2 * x) * np.cos(3 * y)], axis=1) / 1e8 * load
-
-
-def bc_clamp(X: np.ndarray, load: float, translate=(0., 0., 0.), axis=(0., 0., 1.), angle_over_pi: float = 0.0) -> np.ndarray:
-    """BCClamp, boundary.c:53-74: translation + rotation about `axis` by angle_over_pi*pi, scaled by the load
-    fraction.  The x-component's (1-c) term is reproduced AS WRITTEN at boundary.c:69
-    (`-ky*ky + kz*kz*x + ...`)."""
-    x, y, z = X[:, 0], X[:, 1], X[:, 2]
-    lx, ly, lz = (t * load for t in translate)
-    kx, ky, kz = axis
-    th = angle_over_pi * np.pi * load
-    c, s = np.cos(th), np.sin(th)
-    u0 = lx + s * (-kz * y + ky * z) + (1 - c) * (-ky * ky + kz * kz * x + kx * ky * y + kx * kz * z)
-    u1 = ly + s * (kz * x + -kx * z) + (1 - c) * (kx * ky * x - (kx * kx + kz * kz) * y + ky * kz * z)
-    u2 = lz + s * (-ky * x + kx * y) + (1 - c) * (kx * kz * x + ky * kz * y - (kx * kx + ky * ky) * z)
-    return np.stack([u0, u1, u2], axis=1)
-
-
-@dataclass
-class SolveStats:
-    newton_its: int = 0
-    ksp_its: int = 0
-    coarse_its: int = 0
-    jacobian_applies: int = 0
-    coarse_spmv: int = 0
-    residual_evals: int = 0
-    seconds: float = 0.0
-    increments: int = 0
-    converged: bool = True
-    history: list = field(default_factory=list)
-    initial_residuals: list = field(default_factory=list)   # |R| at the start of every load increment (what snes_rtol is relative to)
-
-
-class NewtonPMG:
+class NewtonPMG(LoadedBody):
     _asm_kwargs: dict = {}          # keywords of the assembled coarse level (dynamics.NewmarkPMG: its mass term); none here
 
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None,
@@ -80,20 +45,9 @@ class NewtonPMG:
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
                  line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi",
                  traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full"):
-        """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
-        -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
-        set but absent here are held at zero.
-        Surface loads (surface.py; one rank, and never on a clamped side set):
-        ``traction``: {side_set_id: (tx, ty, tz)} -- a dead load per unit REFERENCE area acting on the body in the direction t, scaled by
-        the load fraction like the body force; evaluated once and folded into the load vector.
-        ``pressure``: {side_set_id: p} -- a pressure on the CURRENT surface, p > 0 pushing on the body, scaled by the load fraction;
-        evaluated in every residual, R = F_int(u) - load (f + sum_s g_s^traction) + load sum_s p_s g_s^pressure(u).
-        ``pressure_tangent``: "full" adds load sum_s p_s T_s(u) to the Jacobian of the OUTER Krylov iteration (the V-cycle, its
-        smoothers, diagonals and eigenvalue estimates do not see it: the preconditioner is the volume operator's); "none" omits it
-        (modified Newton).  T(u) is symmetric only on the variations that vanish on the rim of the loaded surface: a closed surface, or
-        a patch whose rim is clamped (a tube with clamped ends).  The outer CG assumes a symmetric operator; a follower pressure on a
-        patch with a free rim is the caller's responsibility, as with any non-conservative load."""
-        self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
+        """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent``): body.LoadedBody.  Of a
+        follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner is
+        the volume operator's."""
         # smoother: what the Chebyshev iteration of every p-multigrid level, its eigenvalue estimate and the Jacobi-preconditioned
         # coarse CG are preconditioned with -- "jacobi" (default, the reference: PCJACOBI on GetDiag_Ceed) or "pbjacobi": the inverted
         # 3 x 3 nodal blocks (PCPBJACOBI on CeedOperatorLinearAssemblePointBlockDiagonal), which keep the coupling between the
@@ -102,35 +56,16 @@ class NewtonPMG:
         # values per node.
         if smoother not in ("jacobi", "pbjacobi"):
             raise ValueError(f"smoother must be 'jacobi' or 'pbjacobi', not {smoother!r}")
-        # Several ranks (one element partition per rank, halo.py): `halo` is one HaloExchange per multigrid level (a single one stands
-        # for a one-level list).  Every vector then aliases a torch tensor (host memory for the CPU oracle, device memory otherwise;
-        # the Ceed's stream must be torch's current stream, as in bench.py), so the interface sums of halo.add() act on the operators'
-        # outputs in place: the L -> G sum of matops.c:57 after each Jacobian / residual / transfer / diagonal.  Dots are owner-weighted.
-        single = halo is not None and not isinstance(halo, (list, tuple))
-        halo = [halo] if single else halo
-        many = halo is not None and halo[-1].world > 1
-        if smoother == "pbjacobi" and many:
-            raise ValueError("smoother='pbjacobi' is not provided with a halo (several ranks): the nodal blocks of the interface nodes "
-                             "are not summed over the ranks")
-        if many and (traction or pressure):
-            # partial face sums at the interface nodes would need the exchange between the add and its consumer
-            raise ValueError("surface loads (traction=, pressure=) are not provided with a halo (several ranks): the face sums of the "
-                             "interface nodes are not summed over the ranks")
-        if many and single and len(prob.levels) > 1:
-            raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
-        if many and len(halo) != len(prob.levels):
-            raise ValueError("one HaloExchange per multigrid level expected")
-        self.halos = list(halo) if many else None
-        self.halo = self.halos[-1] if self.halos else None
-        self.smoother, self._pb = smoother, smoother == "pbjacobi"
-        self.clamp, self.mms = clamp or {}, mms
-        # "cp": critical-point secant search, up to three secant steps, a step outside (0, 10] ends the search (this build's default);
-        # "cp-petsc": SNESLINESEARCHCP with PETSc's defaults (elasticity.c:596-601 sets the type and nothing else) as recalled from its
-        # source, which is NOT in this image (unverified): ONE secant step from (0, 1), downhill slope enforced, direction switched below
-        # steptol, lambda kept above maxstep, never a rejection; "full": lambda = 1 (SNESLINESEARCHBASIC)
-        if line_search not in ("cp", "cp-petsc", "full"):
+        if smoother == "pbjacobi":
+            self._refuse_several_ranks(halo, "smoother='pbjacobi' is", "the nodal blocks of the interface nodes are not summed over the ranks")
+        if line_search not in ("cp", "cp-petsc", "full"):           # (_line_search)
             raise ValueError(f"line_search {line_search!r}")
-        self.line_search = line_search
+        recordable = coarse in ("chebyshev", "assembled", "amg")
+        if graph != "auto" and graph and not recordable:
+            raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
+        super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
+                         pressure_tangent=pressure_tangent, verbose=verbose)
+        self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
         # "auto" (either switch): the forms give the same bits, so the first call of record_preconditioner TIMES the V-cycle in each
@@ -146,13 +81,17 @@ class NewtonPMG:
         self.coarse, self.coarse_cheb_its, self.coarse_cheb_ratio = coarse, coarse_cheb_its, coarse_cheb_ratio
         # graph=True: record the V-cycle (a fixed sequence of ~150 small launches once the eigenvalue
         # estimates are known) into a hipGraph per Newton step and replay it per Krylov iteration;
-        # needs the reduction-free Chebyshev coarse solver
-        self._auto_graph = graph == "auto"
-        self.graph = False if self._auto_graph else bool(graph)
-        if self._auto_graph and coarse not in ("chebyshev", "assembled", "amg"):
-            self._auto_graph = False               # (the CG coarse solve cannot be recorded: eager)
-        if self.graph and coarse not in ("chebyshev", "assembled", "amg"):
-            raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
+        # needs the reduction-free Chebyshev coarse solver (the CG coarse solve cannot be recorded: eager)
+        self._auto_graph = graph == "auto" and recordable
+        self.graph = graph != "auto" and bool(graph)
+        if self.halos and self.rhalos is None:
+            if self.graph:
+                raise ValueError("graph=True on several ranks needs the library's exchange (torch.distributed calls cannot be recorded)")
+            self._auto_graph = False
+        if self.rhalos is not None and lead_elements > 0:      # split-phase Jacobians: exchange under the interior elements
+            for lv, level in enumerate(prob.levels):
+                level.opJacob.set_overlap_split(int(lead_elements), self.halos[lv].interface_dof_mask())
+        self._split = bool(self.rhalos) and lead_elements > 0
         # coarse="assembled": the same Chebyshev polynomial, but on the ASSEMBLED p=1 matrix (assembly.py): a
         # coarse iteration is one SpMV on 81 entries per row instead of a matrix-free apply on the fine quadrature
         # coarse="amg": ONE cycle of a two-level smoothed-aggregation hierarchy on the assembled matrix (amg.py) -- what
@@ -161,7 +100,7 @@ class NewtonPMG:
         # Galerkin matrix, Chebyshev again.  8 matrix products per cycle instead of 40, and 2.3x fewer outer iterations.
         self.asm = self.amg = None
         self.amg_smooth_its, self.amg_smooth_ratio = amg_smooth_its, amg_smooth_ratio
-        if coarse in ("assembled", "amg") and len(prob.levels) > 1:
+        if coarse in ("assembled", "amg") and self.nlev > 1:
             from .assembly import AssembledLevel
             # several ranks: every rank assembles ITS OWN p = 1 matrix (its elements' sum; the operator is A = sum_r R_r^T A_r R_r, applied as
             # "local product, then the interface sum" like the matrix-free levels); with "amg" the first transfer of the aggregation
@@ -174,57 +113,14 @@ class NewtonPMG:
                                           smooth_its=amg_smooth_its, smooth_ratio=amg_smooth_ratio, coarse_cycles=amg_coarse_cycles,
                                           dist_halo=self.halos[0] if self.halos else None)
         self._pc_graph, self._pc_graph_io, self._pc_graph_counts, self._pc_warm = None, None, (0, 0), False
-        self.ksp_rtol, self.snes_rtol, self.snes_maxit, self.verbose = ksp_rtol, snes_rtol, snes_maxit, verbose
-        self.nlev = len(prob.levels)
-        # the library's exchange per level (halo.RcclHalo), or None: torch.distributed point-to-point + index ops
-        self.rhalos = None
-        if self.halos:
-            if isinstance(rccl, (list, tuple)):
-                self.rhalos = list(rccl)
-            elif rccl == "auto":
-                import torch.distributed as dist
-                if dist.is_initialized() and dist.get_backend(self.halos[-1].group) == "nccl" and self.halos[-1].device.type == "cuda":
-                    from .halo import RcclHalo
-                    self.rhalos = [RcclHalo(self.ceed, h) for h in self.halos]
-            if self.rhalos is not None and len(self.rhalos) != len(prob.levels):
-                raise ValueError("one RcclHalo per multigrid level expected")
-            if self.graph and self.rhalos is None:
-                raise ValueError("graph=True on several ranks needs the library's exchange (torch.distributed calls cannot be recorded)")
-            if self.rhalos is None:
-                self._auto_graph = False
-            if self.rhalos is not None and lead_elements > 0:      # split-phase Jacobians: exchange under the interior elements
-                for lv, level in enumerate(prob.levels):
-                    level.opJacob.set_overlap_split(int(lead_elements), self.halos[lv].interface_dof_mask())
-        self._split = bool(self.rhalos) and lead_elements > 0
+        self.ksp_rtol, self.snes_rtol, self.snes_maxit = ksp_rtol, snes_rtol, snes_maxit
         self.w = [{k: self._vec(prob.lsize(lv), lv) for k in ("x", "b", "r", "d", "t", "dinv", "z")} for lv in range(self.nlev)]
         if self._pb:
             for lv in range(self.nlev):
                 self.w[lv]["pb"] = self._vec(3 * prob.lsize(lv), lv)      # the inverted 3 x 3 blocks, [node][c out][c in]
         self.emax = [1.0] * self.nlev
-        self._x0 = {}
-        n = prob.lsize()
-        top = self.nlev - 1
-        self.U, self.R, self.dU, self.Xloc, self.bcv, self.Rtry, self.Utry = (self._vec(n, top) for _ in range(7))
-        self.kp, self.kz, self.kAp = (self._vec(n, top) for _ in range(3))
-        self.free = prob.levels[prob.fine].mask == 0
-        self.weights = [None] * self.nlev
-        if self.halos:
-            for lv in range(self.nlev):
-                wv = self._vec(prob.lsize(lv), lv)
-                self._set(wv, self.halos[lv].owner_weight * (prob.levels[lv].mask == 0))
-                self.weights[lv] = wv
-                self._refresh_multiplicity(lv)
-        # body force vector (opSetupForce output, setuplibceed.c:555-583): SNESSolve(snes, F, U) solves
-        # residual(U) = load * F on the unconstrained dofs (elasticity.c:645-654)
-        self.fv = None
-        if forcing is not None:
-            self.fv = self._vec(n, top)
-            self._set(self.fv, np.asarray(forcing, dtype=np.float64) * self.free)
-            self._halo_sum(top, self.fv)
-        self.load = 1.0
-        self.stats = SolveStats()
-        self._bc_nodes = self._collect_bc_nodes()
-        self._setup_surface_loads(traction, pressure, pressure_tangent)
+        n, top = prob.lsize(), self.nlev - 1
+        self.U, self.dU, self.Rtry, self.Utry, self.kp, self.kz, self.kAp = (self._vec(n, top) for _ in range(7))
         if self.amg is not None:
             # setup, not solve: aggregates, prolongation and the product patterns from the Jacobian of the undeformed state
             self.U.set_value(0.0)
@@ -232,62 +128,15 @@ class NewtonPMG:
             self.asm.assemble()
             self.amg.build()
 
-    # ---- surface loads (surface.py) -----------------------------------------------------------
-    def _setup_surface_loads(self, traction, pressure, pressure_tangent):
-        """With no surface load given nothing here runs beyond the argument checks, and no solve takes a new path."""
-        if pressure_tangent not in ("full", "none"):
-            raise ValueError(f"pressure_tangent must be 'full' or 'none', not {pressure_tangent!r}")
-        self.pressure_tangent = pressure_tangent
-        self.pressure_loads = []                     # (SurfaceLoad, p) per loaded side set
-        self.surface_loads = []                      # every SurfaceLoad made here (destroy_surface_loads)
-        if not traction and not pressure:
-            return
-        from .mesh import side_set_nodes
-        from .surface import SurfaceLoad
-        prob, lv = self.p, self.p.levels[self.p.fine]
-        for sid in list(traction or {}) + list(pressure or {}):
-            if sid not in prob.mesh.side_sets:
-                raise ValueError(f"surface load on side set {sid}: the mesh has no such side set")
-            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
-            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
-                raise ValueError(f"surface load on side set {sid}, which is one of the problem's Dirichlet side sets")
-        n, top = prob.lsize(), self.nlev - 1
-        make = lambda sid: SurfaceLoad(self.ceed, prob.mesh, lv.dofmap, [sid], Q=prob.Q, mask=lv.mask)
-        for sid, t in (traction or {}).items():
-            t = np.asarray(t, dtype=np.float64).reshape(-1)
-            if t.size != 3:
-                raise ValueError(f"traction on side set {sid}: three components expected")
-            if self.fv is None:
-                self.fv = self._vec(n, top)
-            sl = make(sid)
-            sl.traction_add(t, 1.0, self.fv)         # masked rows are never written: fv stays zero on the constrained dofs
-            self.surface_loads.append(sl)
-        for sid, pval in (pressure or {}).items():
-            sl = make(sid)
-            self.pressure_loads.append((sl, float(pval)))
-            self.surface_loads.append(sl)
-
-    def destroy_surface_loads(self):
-        for sl in self.surface_loads:
-            sl.destroy()
-        self.surface_loads, self.pressure_loads = [], []
-
-    def A_outer(self, lv, x, y):
-        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x, u the state of the last
-        residual evaluation (Xloc: free part + boundary values).  Masked entries of x read as zero and masked rows are not written,
-        as in the volume operator."""
-        self.A(lv, x, y)
-        if self.pressure_tangent == "full":
-            for sl, pval in self.pressure_loads:
-                sl.tangent_add(pval, self.load, self.Xloc, x, y)
+    def destroy(self):
+        """The recorded V-cycle, the aggregation hierarchy and the assembled level, then what the body made (idempotent)."""
+        self._drop_pc_graph()
+        for o in (self.amg, self.asm):
+            if o is not None:
+                o.destroy()
+        super().destroy()
 
     # ---- vector helpers ---------------------------------------------------------------------
-    def axpby(self, y, a, x, b):
-        y.axpby(a, x, b)
-
-    def copy(self, dst, src):
-        dst.axpby(1.0, src, 0.0)
-
     def minv(self, lv, z, r):
         """z = M^-1 r with the smoother's preconditioner of level lv: the inverted diagonal, or the inverted nodal blocks."""
         if self._pb:
@@ -295,61 +144,17 @@ class NewtonPMG:
         else:
             z.pointwise_mult(r, self.w[lv]["dinv"])
 
-    def dot(self, x, y, fine_weight=False, lv=None) -> float:
-        """x . y; on several ranks each dof counts once (owner weights of level `lv`, default the fine level)."""
-        lv = self.nlev - 1 if lv is None else lv
-        if self.rhalos:      # the sum over the ranks on the device (ncclAllReduce on the Ceed's stream), ONE read at the end
-            sc = self.ceed.scalars
-            x.dot_to(y, sc, 7, self.weights[lv])
-            self.ceed.all_reduce(sc, 7, 1)
-            return float(sc.to_numpy()[7])
-        v = x.dot(y, self.weights[lv])
-        if self.halos:
-            import torch, torch.distributed as dist
-            t = torch.tensor([v], dtype=torch.float64, device="cpu" if self.halos[lv].device.type == "cpu" or self.halos[lv].stage_host else self.halos[lv].device)
-            dist.all_reduce(t, group=self.halos[lv].group)
-            v = float(t.item())
-        return v
-
-    # ---- vectors that alias torch tensors (several ranks only) ----------------------------------------
-    def _vec(self, n, lv):
-        return self.ceed.tensor_vector(n, self.halos[lv].device) if self.halos else self.ceed.vector(n).set_value(0.0)
-
-    def _set(self, vec, arr):
-        """vec := arr (host array), keeping the torch alias intact."""
-        vec.fill(arr)
-
-    def _halo_sum(self, lv, vec):
-        """Interface sum of an operator output at level lv (the DMLocalToGlobal(ADD_VALUES) of matops.c:57)."""
-        if self.rhalos:               # the library's exchange, on the Ceed's stream: nothing to synchronise, nothing to re-wrap
-            self.rhalos[lv].add(vec)
-        elif self.halos:
-            if vec.t.device.type == "cuda":
-                self.ceed.synchronize()
-            self.halos[lv].add(vec.t)
-            vec.touched()
-
-    def _refresh_multiplicity(self, lv):
-        """multVec of misc.c:115-143 counted over ALL ranks: 1 / (halo-summed element multiplicity)."""
-        level = self.p.levels[lv]
-        m = self._vec(self.p.lsize(lv), lv)
-        level.Erestrictu.multiplicity(m)
-        self._halo_sum(lv, m)
-        self._set(level.multinv, 1.0 / m.to_numpy())
-
     # ---- operators ---------------------------------------------------------------------------
     def A(self, lv, x, y):
         if lv == 0 and self.asm is not None:
             self.asm.apply(x, y)
             self.stats.coarse_spmv += 1
+            self._halo_sum(lv, y)
         elif self._split:             # ApplyLocalCeedOp + DMLocalToGlobal(ADD_VALUES) in one library call, exchange overlapped
             self.p.levels[lv].opJacob.apply_with_halo(x, y, self.rhalos[lv])
             self.stats.jacobian_applies += 1
-            return
         else:
-            self.p.apply_jacobian(lv, x, y)
-            self.stats.jacobian_applies += 1
-        self._halo_sum(lv, y)
+            super().A(lv, x, y)
 
     def _fused_op(self, lv):
         """The level's Jacobian operator if its consumers may be fused behind it: matrix-free level, no interface sum."""
@@ -366,35 +171,6 @@ class NewtonPMG:
         else:
             self.A(lv, x, w["t"])
             z.waxpby(1.0, b, -1.0, w["t"])
-
-    def _collect_bc_nodes(self):
-        from .mesh import side_set_nodes
-        lv = self.p.levels[self.p.fine]
-        return {sid: side_set_nodes(self.p.mesh, lv.dofmap, [sid]) for sid in self.clamp}
-
-    def bc_values(self, load: float) -> np.ndarray:
-        """DMPlexInsertBoundaryValues at `time = loadIncrement` (matops.c:70-72)."""
-        lv = self.p.levels[self.p.fine]
-        v = np.zeros((lv.dofmap.nnodes, 3))
-        if self.mms:
-            nodes = np.nonzero(lv.mask.reshape(-1, 3)[:, 0])[0]
-            v[nodes] = bc_mms(lv.dofmap.node_coords[nodes], load)
-        for sid, par in self.clamp.items():
-            nodes = self._bc_nodes[sid]
-            v[nodes] = bc_clamp(lv.dofmap.node_coords[nodes], load, **par)
-        return (v.reshape(-1) * (lv.mask != 0))
-
-    def residual(self, U, R):
-        """FormResidual_Ceed: Xloc = free part of U + boundary values; R = F(Xloc), constrained rows dropped."""
-        self.copy(self.Xloc, U)
-        self.axpby(self.Xloc, 1.0, self.bcv, 1.0)
-        self.p.form_residual(self.Xloc, R)
-        self._halo_sum(self.nlev - 1, R)
-        if self.fv is not None:
-            self.axpby(R, -self.load, self.fv, 1.0)
-        for sl, pval in self.pressure_loads:           # follower pressure on the current surface (constrained rows are not written)
-            sl.pressure_add(pval, self.load, self.Xloc, R)
-        self.stats.residual_evals += 1
 
     # ---- multigrid preconditioner ---------------------------------------------------------------
     def setup_preconditioner(self):
@@ -420,20 +196,7 @@ class NewtonPMG:
                 # leaves zeros alone): residuals and corrections are zero there anyway.  No trip through the host.
                 w["dinv"].reciprocal()
                 w["dinv"].touched()
-            mask = self.p.levels[lv].mask != 0
-            # The start vector of the eigenvalue estimate is drawn once per level; no BLAS on the host (a threaded BLAS
-            # call leaves its worker pool spinning, which starves a CPU-quota'd process for ~0.1 s a call).
-            if lv not in self._x0:
-                if self.halos:   # shared nodes must get the same value on every rank: a hash of the coordinates
-                    X = self.p.levels[lv].dofmap.node_coords
-                    k = np.array([[12.9898, 78.233, 37.719], [93.989, 67.345, 24.113], [45.164, 11.135, 83.951]])
-                    v = np.sin(X @ k.T) * 437.5453
-                    x = (2.0 * (v - np.floor(v)) - 1.0).reshape(-1) * (~mask)
-                else:
-                    x = np.random.default_rng(1234 + lv).uniform(-1, 1, mask.size) * (~mask)
-                x0 = self._vec(mask.size, lv)
-                self._set(x0, x / np.sqrt(np.square(x).sum()))     # (any positive scale: the iteration renormalises)
-                self._x0[lv] = x0
+            self._start_vector(lv)
             # largest eigenvalue of D^-1 A: 10 steps of Jacobi-preconditioned CG on the noisy right-hand side and
             # the largest eigenvalue of its Lanczos tridiagonal -- what KSPChebyshevEstEig does (elasticity.c:546-549).
             # (A plain power iteration from the same vector was 2x low after 12 steps on the config-3 mesh.)
@@ -446,24 +209,8 @@ class NewtonPMG:
     def _lanczos_host(self, lv, steps):
         """CG coefficients with every dot product read on the host (several ranks: the dots are all-reduced)."""
         w = self.w[lv]
-        r, z, pv, Ap = w["r"], w["z"], w["d"], w["t"]
-        self.copy(r, self._x0[lv])
-        self.minv(lv, z, r); self.copy(pv, z)
-        rz = self.dot(r, z, lv=lv)
-        alphas, betas = [], []
-        for _ in range(steps):
-            self.A(lv, pv, Ap)
-            pAp = self.dot(pv, Ap, lv=lv)
-            if not (pAp > 0.0 and rz > 0.0):
-                break
-            alpha = rz / pAp
-            self.axpby(r, -alpha, Ap, 1.0)
-            self.minv(lv, z, r)
-            rz_new = self.dot(r, z, lv=lv)
-            alphas.append(alpha); betas.append(rz_new / rz)
-            self.axpby(pv, 1.0, z, rz_new / rz)
-            rz = rz_new
-        return alphas, betas
+        return pcg(lambda x, y: self.A(lv, x, y), lambda z, r: self.minv(lv, z, r), lambda x, y: self.dot(x, y, lv=lv), self._x0[lv],
+                   None, w["r"], w["z"], w["d"], w["t"], 0.0, steps)[1:]
 
     def _lanczos_device(self, lv, steps):
         """The same recurrence, scalars kept on the device; several ranks: every dof counts once, the library sums the dots."""
@@ -500,25 +247,9 @@ class NewtonPMG:
     def coarse_solve(self, b, x):
         """Jacobi-preconditioned CG on the coarsest operator (stands in for GAMG on the FD-coloured matrix)."""
         w = self.w[0]
-        r, d, t, z = w["r"], w["d"], w["t"], w["z"]
-        x.set_value(0.0)
-        self.copy(r, b)
-        self.minv(0, z, r); self.copy(d, z)
-        rz = self.dot(r, z, lv=0)
-        rz0 = rz
-        if rz0 <= 0.0:
-            return
-        for it in range(self.coarse_maxit):
-            self.A(0, d, t)
-            alpha = rz / self.dot(d, t, lv=0)
-            self.axpby(x, alpha, d, 1.0); self.axpby(r, -alpha, t, 1.0)
-            self.minv(0, z, r)
-            rz_new = self.dot(r, z, lv=0)
-            self.stats.coarse_its += 1
-            if rz_new <= self.coarse_rtol ** 2 * rz0:
-                break
-            self.axpby(d, 1.0, z, rz_new / rz)
-            rz = rz_new
+        its, _, _ = pcg(lambda x, y: self.A(0, x, y), lambda z, r: self.minv(0, z, r), lambda x, y: self.dot(x, y, lv=0), b, x,
+                        w["r"], w["z"], w["d"], w["t"], self.coarse_rtol, self.coarse_maxit)
+        self.stats.coarse_its += its
 
     def amg_cycle(self, b, x):
         """One V-cycle of the aggregation hierarchy under the assembled level (amg.py): the coarse solve."""
@@ -596,11 +327,15 @@ class NewtonPMG:
         if self.verbose:
             print("V-cycle forms (ms):", self.tuning["vcycle_ms"], "->", "fused" if self.fuse_epilogue else "two passes", "+", "graph" if self.graph else "eager")
 
-    def record_preconditioner(self, r, z):
-        """Capture vcycle(r -> z) for the current diagonals / eigenvalue bounds (call after setup_preconditioner)."""
+    def _drop_pc_graph(self):
+        """Destroy and forget the recorded V-cycle, if there is one."""
         if self._pc_graph is not None:
             self._pc_graph.destroy()
             self._pc_graph = None
+
+    def record_preconditioner(self, r, z):
+        """Capture vcycle(r -> z) for the current diagonals / eigenvalue bounds (call after setup_preconditioner)."""
+        self._drop_pc_graph()
         if (self._auto_fuse or self._auto_graph) and self.nlev > 1:
             self._autotune_vcycle(r, z)
         if not self.graph or self.nlev == 1:
@@ -620,8 +355,7 @@ class NewtonPMG:
             # a vector the recording depends on was overwritten behind it (CeedXGraphIsStale; the check is LOCAL to this rank): the
             # recording is dropped and this rank runs the V-cycle eagerly -- the same launches and, on several ranks, the same RCCL
             # exchanges in the same order as its peers' replays, so nobody waits for a message that never comes
-            self._pc_graph.destroy()
-            self._pc_graph = None
+            self._drop_pc_graph()
         if self._pc_graph is not None and self._pc_graph_io[0] is r and self._pc_graph_io[1] is z:
             self._pc_graph.launch()
             self.stats.jacobian_applies += self._pc_graph_counts[0]
@@ -634,7 +368,8 @@ class NewtonPMG:
 
     # ---- Krylov ---------------------------------------------------------------------------------
     def fcg(self, b, x, rtol):
-        """Flexible preconditioned CG, natural-norm convergence test (KSP_NORM_NATURAL: sqrt(r'z))."""
+        """Flexible preconditioned CG, natural-norm convergence test (KSP_NORM_NATURAL: sqrt(r'z)).  Not krylov.pcg: the Polak-Ribiere
+        beta takes a third dot per step (r_new . z_old), and r, z are the fixed pair a recorded V-cycle reads and writes."""
         fine = self.nlev - 1
         r, z, p, Ap = self.w[fine]["b"], self.kz, self.kp, self.kAp
         x.set_value(0.0)
@@ -664,6 +399,72 @@ class NewtonPMG:
         return its
 
     # ---- Newton with load increments ---------------------------------------------------------------
+    def _line_search(self) -> float:
+        """The step length along dU from U.  "cp": the critical-point search (SNESLINESEARCHCP), a secant iteration on
+        phi(l) = dU . R(U + l dU): up to three secant steps, a step outside (0, 10] ends the search (this build's default);
+        "cp-petsc": SNESLINESEARCHCP with PETSc's defaults (elasticity.c:596-601 sets the type and nothing else), see below;
+        "full": l = 1 (SNESLINESEARCHBASIC)."""
+        lam, lam_old = 1.0, 0.0
+        if self.line_search == "full":
+            return lam
+        phi_old = self.dot(self.dU, self.R, True)
+        for _ in range(1 if self.line_search == "cp-petsc" else 3):
+            self.copy(self.Utry, self.U); self.axpby(self.Utry, lam, self.dU, 1.0)
+            self.residual(self.Utry, self.Rtry)
+            phi = self.dot(self.dU, self.Rtry, True)
+            if abs(phi) <= 1e-8 * abs(phi_old) or abs(phi - phi_old) < 1e-300:
+                break
+            if self.line_search == "cp-petsc":
+                # ONE secant step in the form of PETSc's SNESLineSearchApply_CP (max_its 1, linear order) AS RECALLED -- PETSc's
+                # source is not in this image, so this is unverified against it (ADVICE r4): with fty = Y . F(X - lambda Y)
+                # (Y = -dU, so fty = -phi) the slope s = d fty / d lambda is made negative ("always go downhill"), the update is
+                # lambda - fty / s, a result below steptol (1e-12) switches direction (lambda + fty / s), one above maxstep (1e8)
+                # or a NaN leaves lambda as it was; the step is never rejected.  (Round 4 clamped the plain secant result to
+                # [1e-12, 1e8] instead: a negative secant step then took lambda = 1e-12, i.e. no step.)
+                fty, fty_old = -phi, -phi_old
+                sl = (fty - fty_old) / (lam - lam_old)
+                if sl > 0.0:
+                    sl = -sl
+                if sl != 0.0:
+                    lam_up = lam - fty / sl
+                    if lam_up < 1e-12:
+                        lam_up = lam + fty / sl
+                    if np.isfinite(lam_up) and lam_up <= 1e8:
+                        lam = lam_up
+                break
+            lam_new = lam - phi * (lam - lam_old) / (phi - phi_old)
+            if not np.isfinite(lam_new) or abs(lam_new - lam) < 1e-8 or lam_new <= 0.0 or lam_new > 10.0:
+                break
+            lam_old, phi_old, lam = lam, phi, lam_new
+        return lam
+
+    def _newton(self, label, head: str):
+        """Newton's iteration on U from the residual already in R, until |R| <= snes_rtol |R|_0 or snes_maxit steps; ``label``: the
+        first entry of this call's history tuples (label, iteration, Krylov iterations, step length, |R|); ``head``: what the verbose
+        line of |R|_0 begins with.  Returns (|R|_0, |R|); the caller decides what they mean."""
+        st = self.stats
+        rnorm0 = rnorm = np.sqrt(self.dot(self.R, self.R, True))
+        st.initial_residuals.append(rnorm0)
+        if self.verbose:
+            print(f"{head}: |R| = {rnorm0:.6e}")
+        for it in range(self.snes_maxit):
+            if rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50:
+                break
+            self.setup_preconditioner()
+            self.record_preconditioner(self.w[self.nlev - 1]["b"], self.kz)
+            self.axpby(self.Rtry, -1.0, self.R, 0.0)                 # rhs = -R
+            k = self.fcg(self.Rtry, self.dU, self.ksp_rtol)
+            st.ksp_its += k
+            lam = self._line_search()
+            self.axpby(self.U, lam, self.dU, 1.0)
+            self.residual(self.U, self.R)                              # also refreshes the stored state and Xloc
+            rnorm = np.sqrt(self.dot(self.R, self.R, True))
+            st.newton_its += 1
+            st.history.append((label, it + 1, k, lam, rnorm))
+            if self.verbose:
+                print(f"   newton {it + 1:2d}: ksp its {k:3d}  lambda {lam:.4f}  |R| = {rnorm:.6e}")
+        return rnorm0, rnorm
+
     def solve(self, num_increments: int = 10, stop_after: Optional[int] = None) -> SolveStats:
         """``stop_after``: run only the first so many of the ``num_increments`` load increments (load studies)."""
         st = self.stats
@@ -674,57 +475,7 @@ class NewtonPMG:
             self.load = load
             self._set(self.bcv, self.bc_values(load))
             self.residual(self.U, self.R)
-            rnorm0 = np.sqrt(self.dot(self.R, self.R, True))
-            rnorm = rnorm0
-            st.initial_residuals.append(rnorm0)
-            if self.verbose:
-                print(f"increment {inc}/{num_increments}: |R| = {rnorm0:.6e}")
-            for it in range(self.snes_maxit):
-                if rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50:
-                    break
-                self.setup_preconditioner()
-                self.record_preconditioner(self.w[self.nlev - 1]["b"], self.kz)
-                self.axpby(self.Rtry, -1.0, self.R, 0.0)                 # rhs = -R
-                k = self.fcg(self.Rtry, self.dU, self.ksp_rtol)
-                st.ksp_its += k
-                # critical-point line search (SNESLINESEARCHCP): secant on phi(l) = dU . R(U + l dU)
-                lam, lam_old = 1.0, 0.0
-                phi_old = self.dot(self.dU, self.R, True)
-                for _ in range(0 if self.line_search == "full" else (1 if self.line_search == "cp-petsc" else 3)):
-                    self.copy(self.Utry, self.U); self.axpby(self.Utry, lam, self.dU, 1.0)
-                    self.residual(self.Utry, self.Rtry)
-                    phi = self.dot(self.dU, self.Rtry, True)
-                    if abs(phi) <= 1e-8 * abs(phi_old) or abs(phi - phi_old) < 1e-300:
-                        break
-                    if self.line_search == "cp-petsc":
-                        # ONE secant step in the form of PETSc's SNESLineSearchApply_CP (max_its 1, linear order) AS RECALLED -- PETSc's
-                        # source is not in this image, so this is unverified against it: with fty = Y . F(X - lambda Y)
-                        # (Y = -dU, so fty = -phi) the slope s = d fty / d lambda is made negative ("always go downhill"), the update is
-                        # lambda - fty / s, a result below steptol (1e-12) switches direction (lambda + fty / s), one above maxstep (1e8)
-                        # or a NaN leaves lambda as it was; the step is never rejected.  (Round 4 clamped the plain secant result to
-                        # [1e-12, 1e8] instead: a negative secant step then took lambda = 1e-12, i.e. no step.)
-                        fty, fty_old = -phi, -phi_old
-                        sl = (fty - fty_old) / (lam - lam_old)
-                        if sl > 0.0:
-                            sl = -sl
-                        if sl != 0.0:
-                            lam_up = lam - fty / sl
-                            if lam_up < 1e-12:
-                                lam_up = lam + fty / sl
-                            if np.isfinite(lam_up) and lam_up <= 1e8:
-                                lam = lam_up
-                        break
-                    lam_new = lam - phi * (lam - lam_old) / (phi - phi_old)
-                    if not np.isfinite(lam_new) or abs(lam_new - lam) < 1e-8 or lam_new <= 0.0 or lam_new > 10.0:
-                        break
-                    lam_old, phi_old, lam = lam, phi, lam_new
-                self.axpby(self.U, lam, self.dU, 1.0)
-                self.residual(self.U, self.R)                              # also refreshes the stored state
-                rnorm = np.sqrt(self.dot(self.R, self.R, True))
-                st.newton_its += 1
-                st.history.append((inc, it + 1, k, lam, rnorm))
-                if self.verbose:
-                    print(f"   newton {it + 1:2d}: ksp its {k:3d}  lambda {lam:.4f}  |R| = {rnorm:.6e}")
+            rnorm0, rnorm = self._newton(inc, f"increment {inc}/{num_increments}")
             # decided on the residual itself: a step that meets the tolerance in the LAST allowed iteration has converged
             if not (rnorm <= self.snes_rtol * rnorm0 or rnorm < 1e-50):
                 st.converged = False
@@ -734,7 +485,5 @@ class NewtonPMG:
                 break
         self.ceed.synchronize()
         st.seconds = time.perf_counter() - t0
-        if self._pc_graph is not None:
-            self._pc_graph.destroy()
-            self._pc_graph = None
+        self._drop_pc_graph()
         return st

@@ -50,6 +50,7 @@ omega, phi = float(np.sqrt(w2[0])), np.linalg.solve(L.T, Yv[:, 0])
 bend = NewtonPMG(prob, forcing=np.tile([0.0, 0.0, -2e-6], n // 3), ksp_rtol=1e-10, snes_rtol=1e-10)
 bend.solve(num_increments=1)
 u0 = bend.U.to_numpy().copy()
+bend.destroy()                                  # (the static solver's vectors go before the time stepper makes its own)
 dt = 2.0 * np.pi / omega / a.steps_per_period
 theta = 2.0 * np.arctan(0.5 * omega * dt)
 sol = NewmarkPMG(prob, a.density, dt, ksp_rtol=1e-10, snes_rtol=1e-10)

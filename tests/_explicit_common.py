@@ -37,8 +37,7 @@ def body_load(m):
 
 
 def teardown(sol, prob):
-    sol.destroy_mass()
-    sol.destroy_surface_loads()
+    sol.destroy()
     prob.destroy()
 
 
@@ -143,7 +142,7 @@ def relaxation_run(ceed, degree, nsteps=4000):
     prob = box_problem(ceed, degree, "hyperFS")
     probe = ExplicitDynamics(prob, RHO)
     f = body_load(probe.m.to_numpy())
-    probe.destroy_mass()
+    probe.destroy()
     sol = ExplicitDynamics(prob, RHO, damping=0.5, forcing=f)
     sol.set_initial()
     sol.run(nsteps)
@@ -157,7 +156,7 @@ def loaded_run(ceed, degree, nsteps=50, dt=None):
     prob = box_problem(ceed, degree, "hyperFS")
     probe = ExplicitDynamics(prob, RHO)
     f = body_load(probe.m.to_numpy())
-    probe.destroy_mass()
+    probe.destroy()
     sol = ExplicitDynamics(prob, RHO, dt=dt, forcing=f)
     sol.set_initial()
     sol.run(nsteps)

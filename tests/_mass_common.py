@@ -72,7 +72,7 @@ def eigenvector_run(ceed, nsteps=40, steps_per_period=20, **solver_kw):
             theta_meas = float(np.arccos(np.clip((u @ M @ phi) / (phi @ M @ phi), -1.0, 1.0)))
         worst_u = max(worst_u, np.linalg.norm(u - phi * np.cos(n * theta)) / np.linalg.norm(phi))
         worst_e = max(worst_e, abs(energy() - e0) / e0)
-    sol.destroy_mass()
+    sol.destroy()
     prob.destroy()
     return worst_u, worst_e, bound, theta, theta_meas
 

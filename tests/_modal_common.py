@@ -61,6 +61,11 @@ def run(sol, nmodes, guard, seed=0, **kw):
     return res, calls
 
 
+def teardown(prob, sol):
+    sol.destroy()
+    prob.destroy()
+
+
 def _sin_to_span(x, N, M):
     """sin of the M-angle between x and the span of the M-orthonormal columns of N"""
     d = x - N @ (N.T @ (M @ x))

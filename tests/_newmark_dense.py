@@ -29,8 +29,7 @@ def relmax(got, want):
 
 
 def teardown(sol, prob):
-    sol.destroy_mass()
-    sol.destroy_surface_loads()
+    sol.destroy()
     prob.destroy()
 
 

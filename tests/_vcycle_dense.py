@@ -257,12 +257,7 @@ def build(ceed, name, U=None):
 
 
 def teardown(prob, sol):
-    if sol._pc_graph is not None:
-        sol._pc_graph.destroy()
-        sol._pc_graph = None
-    if hasattr(sol, "destroy_mass"):
-        sol.destroy_mass()
-    sol.destroy_surface_loads()
+    sol.destroy()
     prob.destroy()
 
 
@@ -625,8 +620,8 @@ def forms_check(gpu, name, tag="device", ncols=32):
                 assert sol._pc_graph is not None
             B = columns(sol, cols, level0, run)
             if graph and not level0:
-                sol._pc_graph.destroy()
-                sol._pc_graph, sol.graph = None, False
+                sol._drop_pc_graph()
+                sol.graph = False
             form = ("fused" if fuse else "two-pass") + "+" + ("replayed" if graph else "eager")
             results[form] = B
             n_fused = sum(calls.values())

@@ -134,7 +134,7 @@ def test_stability_limit_on_the_top_eigenvector(oracle, degree):
             sol.step()
             amp = max(amp, float(np.abs(sol.x.to_numpy()).max()))
         grow[frac] = amp / 0.01
-        sol.destroy_mass()
+        sol.destroy()
     prob.destroy()
     print(f"top eigenvector p = {degree}: amplitude / start over 400 steps {grow[1.01]:.2e} at 1.01 dt_crit, {grow[0.9]:.4f} at 0.9 dt_crit")
     assert grow[1.01] > 1e6
@@ -277,7 +277,7 @@ def test_constant_load_steps_touch_no_host_array(oracle, monkeypatch):
     assert calls == []
     sol.x.to_numpy()
     assert calls == ["to_numpy"]                 # (the count is alive)
-    probe.destroy_mass(); ec.teardown(sol, prob)
+    probe.destroy(); ec.teardown(sol, prob)
 
 
 def test_run_samples_and_stops_at_a_non_finite_sample(oracle):
@@ -299,7 +299,7 @@ def test_run_samples_and_stops_at_a_non_finite_sample(oracle):
     with np.errstate(all="ignore"):
         hb = bad.run(400, sample_every=10)
     assert hb["diverged"] and hb["steps"] < 400 and not np.isfinite(hb["kinetic"][-1] + hb["max_disp"][-1])
-    sol.destroy_mass(); ec.teardown(bad, prob)
+    sol.destroy(); ec.teardown(bad, prob)
 
 
 # ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------------

@@ -165,7 +165,7 @@ def test_relaxation_on_the_device_reaches_the_oracles_static_solution(gpu, oracl
     err = float(np.abs(x - u)[free].max())
     print(f"relaxation on the device p = 2: max |u| = {np.abs(u).max():.4f}, |x - static (oracle)| = {err:.2e}")
     assert err <= TOL * np.abs(u).max()
-    probe.destroy_mass(); prob.destroy()
+    probe.destroy(); prob.destroy()
 
 
 @pytest.mark.parametrize("sample_every", [0, 5])
@@ -180,7 +180,7 @@ def test_replayed_steps_give_the_bits_of_eager_steps(gpu, sample_every):
         h = sol.run(11, sample_every=sample_every, graph=graph)              # graph: one eager step, ten replayed
         assert h["steps"] == 11 and sol.nsteps_done == 11 and abs(sol.t - 11 * sol.dt) < 1e-14
         out.append((sol.x.to_numpy(), sol.vh.to_numpy(), h["kinetic"], h["max_disp"]))
-        sol.destroy_mass()
+        sol.destroy()
     assert np.abs(out[0][0]).max() > 1e-3
     assert out[0][0].tobytes() == out[1][0].tobytes() and out[0][1].tobytes() == out[1][1].tobytes()
     assert out[0][2] == out[1][2] and out[0][3] == out[1][3] and len(out[0][2]) == (2 if sample_every else 0)
@@ -188,4 +188,4 @@ def test_replayed_steps_give_the_bits_of_eager_steps(gpu, sample_every):
     sol.set_initial(load=lambda t: min(1.0, t))
     with pytest.raises(ValueError, match="constant load"):
         sol.run(3, graph=True)
-    sol.destroy_mass(); probe.destroy_mass(); prob.destroy()
+    sol.destroy(); probe.destroy(); prob.destroy()

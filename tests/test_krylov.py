@@ -1,13 +1,14 @@
 """krylov.py on both backends through ceed.Csr: no mesh, no operator.  The device-scalar Lanczos recurrence against its restatement
 in NumPy float64 (same order of operations, sums taken front to back as the oracle takes them), its breakdown and its empty case,
-the weighted dots, and the Chebyshev coefficients against their closed forms."""
+the weighted dots, the Chebyshev coefficients against their closed forms, and the host-scalar CG (krylov.pcg) on a dense matrix of
+order 9: its solution, its coefficients against lanczos_device's, an indefinite matrix, and the run without an iterate."""
 import functools
 
 import numpy as np
 import pytest
 
 from ceedpetscsolid_amd import ceed as cd
-from ceedpetscsolid_amd.krylov import chebyshev_coefficients, lanczos_device, lanczos_emax
+from ceedpetscsolid_amd.krylov import chebyshev_coefficients, lanczos_device, lanczos_emax, pcg
 from conftest import rel_err
 
 # host against device coefficients, as tests/test_solver.py::lanczos_paths_agree has them
@@ -151,3 +152,90 @@ def test_chebyshev_coefficients_closed_forms():
         assert c1 == pytest.approx(w1, rel=1e-14) and c2 == pytest.approx(w2, rel=1e-14, abs=0.0)
     one = list(chebyshev_coefficients(2.0, 0.1, 1))
     assert len(one) == 1 and one[0][1] == 0.0 and one[0][0] == pytest.approx(5.0 / 6.0, rel=1e-14)
+
+
+# ---- krylov.pcg: a dense matrix of order 9 with its Jacobi preconditioner -------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def dense9(kind):
+    """(A, b): A = Q diag(lambda) Q^T with a random orthogonal Q; "spd": lambda = 1 .. 10, "indefinite": three of them negative (the
+    diagonal, which the preconditioner inverts, stays positive: checked)."""
+    rng = np.random.default_rng(9)
+    Q, _ = np.linalg.qr(rng.standard_normal((9, 9)))
+    lam = np.linspace(1.0, 10.0, 9)
+    if kind == "indefinite":
+        lam[[1, 4, 7]] *= -0.2
+    A = (Q * lam) @ Q.T
+    A = 0.5 * (A + A.T)
+    assert np.all(np.diag(A) > 0.1)
+    b = rng.uniform(-1.0, 1.0, 9)
+    A.setflags(write=False); b.setflags(write=False)
+    return A, b
+
+
+def run_pcg(ceed, kind, rtol, maxit, iterate=True):
+    """krylov.pcg on Ceed vectors; returns (its, alphas, betas, x or None, b after the call, the four work vectors after the call)"""
+    A, b = dense9(kind)
+    M = cd.Csr.rect(ceed, 9, 9, np.arange(0, 82, 9), np.tile(np.arange(9), 9), A.reshape(-1))
+    v = {k: ceed.vector(9).set_value(0.0) for k in ("x", "r", "z", "d", "t")}
+    v["b"], v["dinv"] = ceed.vector(9).set_array(b), ceed.vector(9).set_array(1.0 / np.diag(A))
+    its, alphas, betas = pcg(M.apply, lambda z, r: z.pointwise_mult(r, v["dinv"]), lambda p, q: p.dot(q), v["b"],
+                             v["x"] if iterate else None, v["r"], v["z"], v["d"], v["t"], rtol, maxit)
+    out = (its, alphas, betas, v["x"].to_numpy(), v["b"].to_numpy(), [v[k].to_numpy() for k in ("r", "z", "d", "t")])
+    for o in list(v.values()) + [M]:
+        o.destroy()
+    return out
+
+
+def test_pcg_solves_to_the_bound_of_its_stop_rule(backend):
+    """The stop rule r . D^-1 r <= rtol^2 b . D^-1 b gives |r| <= sqrt(dmax / dmin) rtol |b|, and |x - x*| <= |A^-1| |r|,
+    |b| <= |A| |x*|: |x - x*| / |x*| <= cond(A) sqrt(dmax / dmin) rtol.  The recurrence's r drifts from b - A x by rounding, a few
+    u |A| |x| per step (Greenbaum); 20 steps' worth at 10 u each is allowed for: + 200 u cond(A)."""
+    ceed, _ = backend
+    A, b = dense9("spd")
+    d = np.diag(A)
+    bound = np.linalg.cond(A) * np.sqrt(d.max() / d.min()) * 1e-13 + 200 * 2.0 ** -53 * np.linalg.cond(A)
+    assert bound <= 1e-10
+    its, alphas, betas, x, _, _ = run_pcg(ceed, "spd", 1e-13, 50)
+    want = np.linalg.solve(A, b)
+    err = np.linalg.norm(x - want) / np.linalg.norm(want)
+    print(f"order 9, cond {np.linalg.cond(A):.1f}: {its} steps, |x - x*| / |x*| = {err:.2e} (bound {bound:.2e})")
+    assert its == len(alphas) == len(betas) and 0 < its < 50           # the stop rule ended it, not the step limit
+    assert err <= bound
+
+
+def test_pcg_coefficients_are_those_of_lanczos_device(backend):
+    ceed, tol = backend
+    A, b = dense9("spd")
+    steps = 6
+    its, alphas, betas, x, _, _ = run_pcg(ceed, "spd", 0.0, steps, iterate=False)
+    assert its == steps
+    M = cd.Csr.rect(ceed, 9, 9, np.arange(0, 82, 9), np.tile(np.arange(9), 9), A.reshape(-1))
+    v = {k: ceed.vector(9).set_value(0.0) for k in ("r", "z", "p", "Ap")}
+    v["b"], v["dinv"] = ceed.vector(9).set_array(b), ceed.vector(9).set_array(1.0 / np.diag(A))
+    want_a, want_b = lanczos_device(ceed, M.apply, lambda z, r: z.pointwise_mult(r, v["dinv"]), v["b"], v["r"], v["z"], v["p"], v["Ap"], steps)
+    for o in list(v.values()) + [M]:
+        o.destroy()
+    ea, eb = rel_err(np.array(alphas), np.array(want_a)), rel_err(np.array(betas), np.array(want_b))
+    print(f"order 9, {steps} steps: alphas {ea:.2e}, betas {eb:.2e} from lanczos_device (allowed {tol:.0e})")
+    assert len(want_a) == steps and ea < tol and eb < tol
+
+
+def test_pcg_on_an_indefinite_matrix_ends_with_finite_output(backend):
+    ceed, _ = backend
+    A, _ = dense9("indefinite")
+    assert np.linalg.eigvalsh(A).min() < -0.1
+    its, alphas, betas, x, _, work = run_pcg(ceed, "indefinite", 1e-13, 50)
+    print(f"indefinite, order 9: ended after {its} steps")
+    assert its < 50 and all(a > 0.0 for a in alphas)                   # a direction of non-positive curvature ended it
+    assert np.all(np.isfinite(alphas)) and np.all(np.isfinite(betas)) and np.all(np.isfinite(x))
+    assert all(np.all(np.isfinite(w)) for w in work)
+
+
+def test_pcg_without_an_iterate_writes_the_work_vectors_only(backend):
+    ceed, _ = backend
+    _, b = dense9("spd")
+    its, alphas, betas, x, b_after, work = run_pcg(ceed, "spd", 0.0, 6, iterate=False)
+    with_x = run_pcg(ceed, "spd", 0.0, 6, iterate=True)
+    assert np.array_equal(b_after, b) and not x.any()                  # the vector not handed over stayed as it was made
+    assert (its, alphas, betas) == with_x[:3] and with_x[3].any()      # the iterate does not enter the coefficients
+    assert all(np.array_equal(p, q) for p, q in zip(work, with_x[5]))

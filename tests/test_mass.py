@@ -135,7 +135,7 @@ def test_hyperfs_dynamic_residual_identity(oracle):
               f"{stats[k].newton_its} Newton / {stats[k].ksp_its} Krylov its")
         assert rec <= 10 * last
     assert np.abs(sol.U.to_numpy()).max() > 1e-3 and sol.kinetic_energy() > 0.0       # the body moves
-    sol.destroy_mass(); prob.destroy()
+    sol.destroy(); prob.destroy()
 
 
 def test_no_density_takes_no_new_path(oracle):

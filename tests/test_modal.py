@@ -24,12 +24,14 @@ def test_modes_match_the_dense_pencil(oracle, name):
     assert np.allclose(res.frequencies, np.sqrt(np.maximum(res.eigenvalues, 0.0)))
     res2, _ = mc.run(sol, nmodes, guard, seed=7)          # a second seed: the same eigenvalues within the same bounds
     mc.check_result(res2, K, M, free, lam, Phi, nmodes, nrigid, name + " seed 7")
+    mc.teardown(prob, sol)
 
 
 def test_prestressed_modes(oracle):
     name = "clamped_p3_hyperfs_amg"
     prob, sol, nmodes, guard, _ = mc.make_case(oracle, name)
     lam0 = mc.run(sol, nmodes, guard)[0].eigenvalues
+    mc.teardown(prob, sol)
     prob, sol, nmodes, guard, _ = mc.make_case(oracle, name, tip_fz=mc.TIP_FZ)
     st = sol.solve(num_increments=2)
     assert st.converged
@@ -41,6 +43,7 @@ def test_prestressed_modes(oracle):
     mc.check_result(res, K, M, free, lam, Phi, nmodes, 0, name + " prestressed")
     print(f"lambda_1 unstressed {lam0[0]:.12e}, prestressed {res.eigenvalues[0]:.12e}")
     assert abs(res.eigenvalues[0] - lam0[0]) > 1e-6 * lam0[0]        # the control: the solver linearises about the current state
+    mc.teardown(prob, sol)
 
 
 def test_refusals(oracle):

@@ -32,12 +32,14 @@ def test_modes_match_the_dense_pencil_and_the_oracle(gpu, oracle, name, monkeypa
     diff = np.abs(res.eigenvalues - res_o.eigenvalues)
     print(f"{name}: |lambda device - lambda oracle| = {diff}, bounds {bounds + bounds_o}")
     assert np.all(diff <= bounds + bounds_o)
+    mc.teardown(prob, sol); mc.teardown(prob_o, sol_o)
 
 
 def test_prestressed_modes_with_the_recorded_vcycle(gpu):
     name = "clamped_p3_hyperfs_amg"
     prob, sol, nmodes, guard, _ = mc.make_case(gpu, name)
     lam0 = mc.run(sol, nmodes, guard)[0].eigenvalues
+    mc.teardown(prob, sol)
     prob, sol, nmodes, guard, _ = mc.make_case(gpu, name, tip_fz=mc.TIP_FZ, graph=True)
     assert sol.solve(num_increments=2).converged
     tip = np.abs(sol.U.to_numpy()).max()
@@ -48,3 +50,4 @@ def test_prestressed_modes_with_the_recorded_vcycle(gpu):
     mc.check_result(res, K, M, free, lam, Phi, nmodes, 0, name + " prestressed (device, recorded V-cycle)")
     print(f"lambda_1 unstressed {lam0[0]:.12e}, prestressed {res.eigenvalues[0]:.12e}")
     assert abs(res.eigenvalues[0] - lam0[0]) > 1e-6 * lam0[0]
+    mc.teardown(prob, sol)                                # (the recording still alive goes with the solver)

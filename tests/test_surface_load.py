@@ -208,6 +208,6 @@ def test_solver_argument_checks(oracle):
     s = NewtonPMG(prob, traction={2: (0, 0, 0.01)}, pressure={2: 0.02}, pressure_tangent="none")
     assert len(s.surface_loads) == 2 and len(s.pressure_loads) == 1 and s.fv is not None
     assert np.all(s.fv.to_numpy()[prob.levels[prob.fine].mask != 0] == 0.0)
-    s.destroy_surface_loads()
+    s.destroy()
     assert NewtonPMG(prob).pressure_loads == []
     prob.destroy()

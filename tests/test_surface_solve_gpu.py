@@ -100,7 +100,7 @@ def test_clamped_plate_under_follower_pressure(gpu):
     u0 = total_displacement(none)
     print(f"pressure plate, no tangent: {st0.newton_its} Newton / {st0.ksp_its} Krylov its, |U - U_full| / |U_full| = {np.linalg.norm(u0 - u) / np.linalg.norm(u):.2e}")
     assert np.linalg.norm(u0 - u) <= 1e-6 * np.linalg.norm(u)
-    full.destroy_surface_loads(); none.destroy_surface_loads()
+    full.destroy(); none.destroy()
     prob.destroy()
 
 
@@ -120,5 +120,5 @@ def test_inflation_of_a_clamped_tube(gpu):
     ur = np.einsum("nc,nc->n", total_displacement(s).reshape(-1, 3)[mid, :2], rhat)
     print(f"inflation: {st.newton_its} Newton / {st.ksp_its} Krylov its, radial displacement at mid-height {ur.min():.4e} .. {ur.max():.4e}")
     assert np.all(ur > 0)
-    s.destroy_surface_loads()
+    s.destroy()
     prob.destroy()

@@ -30,7 +30,7 @@ p = SolidProblem(c, mesh, a.degree, "hyperFS", nu=0.3, E=1.0, bc_sides=[998, 999
 n = p.lsize()
 probe = ExplicitDynamics(p, a.density)
 m_host = probe.m.to_numpy()
-probe.destroy_mass()
+probe.destroy()
 sol = ExplicitDynamics(p, a.density, forcing=m_host * np.tile([0.0, 0.0, -a.gravity], n // 3))
 sol.set_initial()
 out = {"resource": c.resource, "mesh": a.mesh, "elements": mesh.nelem, "degree": a.degree, "dofs": n, "dt": sol.dt, "emax": sol.emax_K,
