@@ -81,7 +81,7 @@ class CeedLib:
                 "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
                 "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction",
                 "CeedXVectorBlockGram", "CeedXVectorBlockCombine", "CeedXVectorBlockGetLimits",
-                "CeedXVectorLeapfrogStep"]
+                "CeedXVectorLeapfrogStep", "CeedXOperatorSetMassTerm", "CeedXOperatorMassTermAvailable"]
     DATA = [
         "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
         "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
@@ -1050,6 +1050,23 @@ class Operator:
     def apply_state(self, u: "Vector"):
         """CeedXOperatorApplyState: write only the stored state (passive gradu output) of a residual-shaped operator."""
         self.L.chk(self.L.lib.CeedXOperatorApplyState(self.h, u.h))
+
+    def mass_term_available(self) -> bool:
+        """CeedXOperatorMassTermAvailable: is a fused kernel with the mass term (K + c M in the launches of K) instantiated for this
+        Jacobian operator's (P, Q, QFunction)?  False where the library lacks the entry point (CEED_EXTERN_OPTIONAL: the CPU oracle); an
+        operator that is no Jacobian is refused by the library."""
+        if not self.L.has("CeedXOperatorMassTermAvailable"):
+            return False
+        has = C.c_int(0)
+        self.L.chk(self.L.lib.CeedXOperatorMassTermAvailable(self.h, C.byref(has)))
+        return bool(has.value)
+
+    def set_mass_term(self, c: float):
+        """CeedXOperatorSetMassTerm: every apply form of this Jacobian operator then gives (K + c M) x; 0 clears the term.  A recorded
+        graph keeps the coefficient it was recorded with.  The diagonals ignore the term."""
+        if not self.L.has("CeedXOperatorSetMassTerm"):
+            raise CeedError("this library has no CeedXOperatorSetMassTerm (CEED_EXTERN_OPTIONAL): apply the mass operator on its own")
+        self.L.chk(self.L.lib.CeedXOperatorSetMassTerm(self.h, C.c_double(c)))
 
     def apply_phase(self, vin: "Vector", vout: "Vector", phase: int):
         self.L.chk(self.L.lib.CeedXOperatorApplyPhase(self.h, vin.h, vout.h, C.c_int(phase)))

@@ -234,6 +234,7 @@ struct CeedOperator_private {
   bool kernel_fused = false;          // CeedXOperatorGetKernelName then adds how the geometric factors were obtained (kernel_name_full)
   std::string kernel_name_full;
   int geo_mode = 0;                   // last fused launch: 0 qdata read, 1 recomputed per point, 2 affine elements, 3 swept elements
+  double mass_term = 0.;              // Jacobian operators: c of K + c M (CeedXOperatorSetMassTerm); 0: no term, the kernels without it
   // Dirichlet flags (op_free_flags drops them all)
   DevArray<uint32_t> d_off_flagged;             // the offsets with the flag bits of their nodes: the active restriction's; of a transfer, the
                                                 // COARSE side's (input of a prolongation, output of a restriction) -- one array either way

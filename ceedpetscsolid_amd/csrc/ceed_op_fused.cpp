@@ -92,6 +92,7 @@ static int fused_prepare(CeedOperator op, CeedVector in, CeedVector out, bool ad
     }
   }
   a.mask_in = (op->mask_mode & 1) ? 1 : 0; a.mask_out = (op->mask_mode & 2) ? 1 : 0;
+  a.mass_c = op->mass_term;     // (non-zero on a Jacobian operator only: CeedXOperatorSetMassTerm)
   if (pencil_even_odd(ai.basis->Q1d)) memcpy(a.eo, op->eo, sizeof a.eo);
   {  // geometric factors recomputed in the kernel if the qdata vector still is what SetupGeo wrote on these elements
     CeedVector qv = op->in[op->i_qdata].vec;
@@ -142,9 +143,11 @@ static int fused_launch(CeedOperator op, const FusedApply &F, int e0, int ne, in
   FusedGradArgs ak = F.a;
   ak.elem_begin = e0; ak.nelem = ne;
   const char *kname = "";
-  hipError_t e = launch_fused_grad(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, ak, FusedLaunch{wave_groups, op->ceed->opt.pencil_waves}, s, &kname);
+  // with a mass term the other entry of the same body, K + c M in this one launch; without, the kernels there always were
+  const bool mass = F.a.mass_c != 0.;
+  hipError_t e = (mass ? launch_fused_mass : launch_fused_grad)(F.b->P1d, F.b->Q1d, F.qfkind, op->tables, ak, FusedLaunch{wave_groups, op->ceed->opt.pencil_waves}, s, &kname);
   if (no_kernel(e, kname))
-    return ceed_error("no fused kernel instantiated for P=%d Q=%d QFunction %s", F.b->P1d, F.b->Q1d, op->qf->name.c_str());
+    return ceed_error("no fused kernel %sinstantiated for P=%d Q=%d QFunction %s", mass ? "with the mass term " : "", F.b->P1d, F.b->Q1d, op->qf->name.c_str());
   HIPCHK(e);
   set_kernel_name(op, kname, true);
   op->geo_mode = fused_geo_mode(F.a);
@@ -398,6 +401,10 @@ extern "C" int CeedXOperatorApplyPhase(CeedOperator op, CeedVector in, CeedVecto
 // the arrivals added (apply_fused_with_halo).  `halo` with no neighbours: a plain apply.
 extern "C" int CeedXOperatorApplyWithHalo(CeedOperator op, CeedVector in, CeedVector out, CeedXHalo halo) {
   CHK(need_fused(op, "split-phase apply", Kind::any));
+  // refused whatever the halo holds (none, no neighbours, several): the call is the several-rank form of the apply
+  if (op->mass_term != 0.)
+    return ceed_error("CeedXOperatorApplyWithHalo: the operator carries a mass term (CeedXOperatorSetMassTerm); the interface sums of the "
+                      "mass operator were never run over several ranks -- clear the term and apply the mass operator on its own");
   if (!halo || halo->nb.empty()) return CeedOperatorApply(op, in, out, CEED_REQUEST_IMMEDIATE);
   if (op->plan != PLAN_FUSED_GRAD) {
     CHK(CeedOperatorApply(op, in, out, CEED_REQUEST_IMMEDIATE));
@@ -413,6 +420,34 @@ extern "C" int CeedXOperatorApplyWithHalo(CeedOperator op, CeedVector in, CeedVe
   // (while a graph is recorded always this form: RCCL's calls record correctly only in order on the capturing stream)
   if (op->ceed->opt.ovl_mode == 0 || op->ceed->capturing || op->ovl_lead <= 0 || !op->ovl_csr.built) return apply_fused(op, in, out, false, halo);
   return apply_fused_with_halo(op, in, out, halo);
+}
+
+// The mass term of a Jacobian operator (include/ceed.h): K + c M in the launches of K.  The coefficient lives on the operator and goes into
+// the launch arguments of every apply form (fused_prepare, fused_launch); the two diagonals never read it.
+static int mass_term_shape(CeedOperator op, const char *who, int *P, int *Q) {
+  if (op->composite) return ceed_error("%s: not provided for composite operators (call it on the sub-operators)", who);
+  CHK(op_plan(op));
+  if (op->plan != PLAN_FUSED_GRAD || op->o_state >= 0)
+    return ceed_error("%s: a mass term belongs to a Jacobian operator (K + c M, the tangent of a dynamic solve); QFunction '%s' is %s", who,
+                      op->qf ? op->qf->name.c_str() : "?", op->plan == PLAN_FUSED_GRAD ? "a residual" : "not of the residual / Jacobian family");
+  *P = op->in[op->i_active].basis->P1d; *Q = op->in[op->i_active].basis->Q1d;
+  return 0;
+}
+extern "C" int CeedXOperatorMassTermAvailable(CeedOperator op, int *has) {
+  int P, Q;
+  CHK(mass_term_shape(op, "CeedXOperatorMassTermAvailable", &P, &Q));
+  *has = fused_mass_instantiated(P, Q, op->qf->kind) ? 1 : 0;
+  return 0;
+}
+extern "C" int CeedXOperatorSetMassTerm(CeedOperator op, double c) {
+  int P, Q;
+  CHK(mass_term_shape(op, "CeedXOperatorSetMassTerm", &P, &Q));
+  if (!(c == c) || c - c != 0.) return ceed_error("CeedXOperatorSetMassTerm: the coefficient must be finite");
+  if (c != 0. && !fused_mass_instantiated(P, Q, op->qf->kind))
+    return ceed_error("CeedXOperatorSetMassTerm: no fused kernel with the mass term is instantiated for P=%d Q=%d QFunction %s "
+                      "(CeedXOperatorMassTermAvailable); apply the mass operator on its own", P, Q, op->qf->name.c_str());
+  op->mass_term = c;
+  return 0;
 }
 
 // The apply fused with its consumer (include/ceed.h; elasticity.c:539-552, 588-590)

@@ -92,6 +92,8 @@ struct FusedGradArgs {
                                // host) are stored straight into y and skip the E-vector round trip; the E-vector then is
                                // [elem][shell node][3] and the transpose map handed to launch_assemble() holds the shell
                                // nodes only, its columns being positions e * element_shell_size(P) + rank
+  double mass_c;              // k_fused_pencil_mass only: the coefficient c of K + c M (CeedXOperatorSetMassTerm), read at every launch
+                               // like MassArgs::coef -- a recorded graph keeps the value it was recorded with
 #ifdef CPS_PHASE_TIMING       // (diagnostic build only) the time-stamp buffer, filled in by the launcher from CEED_MI355X_PHASE_BUF
   long long *phase_buf;
 #endif
@@ -218,6 +220,14 @@ struct MassArgs {
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
 hipError_t launch_fused_grad(int P, int Q, int qf, const BasisTables &t, const FusedGradArgs &a, FusedLaunch l, hipStream_t s, const char **name);
+// The Jacobian operators with the mass term, K + a.mass_c M, in the same launch (k_fused_pencil_mass; name "fused_grad<P=..,Q=..,<QF>+mass>/pencil").
+// Instantiated for the Jacobian functors of every (P, Q) of the fused kernel up to Q = FUSED_MASS_QMAX; elsewhere hipErrorInvalidValue, the name empty.
+constexpr int FUSED_MASS_QMAX = 7;
+constexpr bool fused_mass_instantiated(int P, int Q, int qf) {
+  return Q >= 2 && Q <= FUSED_MASS_QMAX && P >= 2 && P <= Q &&
+         (qf == QF_LINELAS || qf == QF_HYPERSS_DF || qf == QF_HYPERFS_DF || (qf == QF_HYPERFS_DF_DS && pencil_derived_state(Q)));
+}
+hipError_t launch_fused_mass(int P, int Q, int qf, const BasisTables &t, const FusedGradArgs &a, FusedLaunch l, hipStream_t s, const char **name);
 hipError_t launch_transfer(int Pc, int Pf, bool prolong, const BasisTables &t, const TransferArgs &a,
                            hipStream_t s, const char **name);
 hipError_t launch_setup_geo(int Q, const BasisTables &t, const SetupGeoArgs &a, hipStream_t s,

@@ -35,4 +35,22 @@ hipError_t launch_fused_grad(int P, int Q, int qf, const BasisTables &t, const F
   return hipErrorInvalidValue;
 }
 
+// The same dispatch over the objects of the entry with the mass term (kernels_fused_inst.hip with -DCPS_MASS; csrc/Makefile FUSEDM_QP).
+#define CPS_DECL_MQP(Qv, Pt) hipError_t launch_fused_mass_q##Qv##p##Pt(int, int, const BasisTables &, const FusedGradArgs &, FusedLaunch, hipStream_t, const char **);
+CPS_DECL_MQP(2, 0) CPS_DECL_MQP(3, 0) CPS_DECL_MQP(4, 0) CPS_DECL_MQP(5, 0) CPS_DECL_MQP(6, 0) CPS_DECL_MQP(7, 0) CPS_DECL_MQP(7, 1)
+hipError_t launch_fused_mass(int P, int Q, int qf, const BasisTables &t, const FusedGradArgs &a, FusedLaunch l,
+                             hipStream_t s, const char **name) {
+  static_assert(FUSED_MASS_QMAX == 7, "the objects declared above");
+  if (!fused_mass_instantiated(P, Q, qf)) return hipErrorInvalidValue;
+  switch (Q) {
+    case 2: return launch_fused_mass_q2p0(P, qf, t, a, l, s, name);
+    case 3: return launch_fused_mass_q3p0(P, qf, t, a, l, s, name);
+    case 4: return launch_fused_mass_q4p0(P, qf, t, a, l, s, name);
+    case 5: return launch_fused_mass_q5p0(P, qf, t, a, l, s, name);
+    case 6: return launch_fused_mass_q6p0(P, qf, t, a, l, s, name);
+    case 7: return (Q - P) % pencil_inst_parts(7) == 0 ? launch_fused_mass_q7p0(P, qf, t, a, l, s, name) : launch_fused_mass_q7p1(P, qf, t, a, l, s, name);
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace cps

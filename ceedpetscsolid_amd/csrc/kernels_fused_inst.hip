@@ -7,6 +7,9 @@
 // (cloptions.c:195-225): the fine level has P = Q (qextra = 0), coarse levels
 // use degrees 1, 2, 4 (logarithmic) or every degree below the fine one (uniform) with the FINE quadrature (setuplibceed.c:757).
 // Residual kernels (which write the stored state) only exist on the fine level (P = Q, and P = Q - 1, Q - 2 for -qextra 1, 2).
+//
+// With -DCPS_MASS the object holds the OTHER entry of the same body instead: k_fused_pencil_mass, K + c M (kernel_fused_pencil.hpp), for the
+// Jacobian functors of the same (P, Q) set, behind launch_fused_mass_q<Q>p<k> (build/fusedm_q<Q>p<k>.o).
 #include "kernel_fused_pencil.hpp"
 
 #ifndef CPS_Q
@@ -14,6 +17,15 @@
 #endif
 #ifndef CPS_PART
 #define CPS_PART 0
+#endif
+#ifdef CPS_MASS
+#define CPS_WITH_MASS true
+#define CPS_NAME_TAIL "+mass>/pencil"
+#define CPS_LAUNCH_STEM launch_fused_mass_q
+#else
+#define CPS_WITH_MASS false
+#define CPS_NAME_TAIL ">/pencil"
+#define CPS_LAUNCH_STEM launch_fused_grad_q
 #endif
 
 namespace cps {
@@ -28,8 +40,8 @@ namespace cps {
 #define CPS_CASE(Pv, QFv, QFname)                                                   \
   if constexpr ((CPS_Q - (Pv)) % pencil_inst_parts(CPS_Q) == PART) {                \
     if (P == Pv && qf == QFv) {                                                     \
-      *name = "fused_grad<P=" #Pv ",Q=" CPS_STR(CPS_Q) "," QFname ">/pencil";       \
-      return launch_fused_pencil_t<Pv, CPS_Q, QFv>(t, a, l, s);                     \
+      *name = "fused_grad<P=" #Pv ",Q=" CPS_STR(CPS_Q) "," QFname CPS_NAME_TAIL;    \
+      return launch_fused_pencil_t<Pv, CPS_Q, QFv, CPS_WITH_MASS>(t, a, l, s);      \
     }                                                                               \
   }
 // The derived-state tangent is instantiated where it measured a gain: Q >= 6 (one element per wave; -2.6 ... -3.1 % on config 5's
@@ -44,7 +56,11 @@ namespace cps {
 
 // Residual kernels (they write the stored state) run on the FINE level only: P = Q, and P = Q - 1, Q - 2 for -qextra 1, 2
 // (src/cloptions.c:53-55: Q = degree + 1 + qextra, setuplibceed.c:252).  A larger qextra is a loud "no fused kernel instantiated".
+#ifdef CPS_MASS
+#define CPS_RESIDUALS(Pv)     // the mass term belongs to the tangents
+#else
 #define CPS_RESIDUALS(Pv) CPS_CASE(Pv, QF_HYPERSS_F, "HyperSSF") CPS_CASE(Pv, QF_HYPERFS_F, "HyperFSF")
+#endif
 #define CPS_FINE_WITH_QEXTRA(Pv) ((CPS_Q) > (Pv) && (CPS_Q) - (Pv) <= 2)
 // a coarse degree (or the fine one under -qextra): its Jacobians, and the residuals where it can be the fine level
 #define CPS_LEVEL(Pv)                                                                  \
@@ -62,7 +78,7 @@ static hipError_t dispatch_part(int P, int qf, const BasisTables &t, const Fused
   return hipErrorInvalidValue;
 }
 
-hipError_t CPS_CAT(CPS_CAT(CPS_CAT(launch_fused_grad_q, CPS_Q), p), CPS_PART)(int P, int qf, const BasisTables &t, const FusedGradArgs &a,
+hipError_t CPS_CAT(CPS_CAT(CPS_CAT(CPS_LAUNCH_STEM, CPS_Q), p), CPS_PART)(int P, int qf, const BasisTables &t, const FusedGradArgs &a,
                                                                               FusedLaunch l, hipStream_t s, const char **name) {
   static_assert(CPS_PART >= 0 && CPS_PART < pencil_inst_parts(CPS_Q), "part of this quadrature size");
   return dispatch_part<CPS_PART>(P, qf, t, a, l, s, name);

@@ -17,9 +17,20 @@ the formulas above then give the clamped nodes the velocity and acceleration of 
 u_{n+1} with the residual above and the effective tangent K + a0 rho M on every multigrid level: ``A`` is the parent's apply followed by
 the level's mass operator (mass.py) in add mode; the smoother's diagonal is diag K + a0 rho diag M; an assembled coarse level
 (``coarse="assembled"`` / ``"amg"``) carries a0 rho M in its element matrices, so the p = 1 matrix and the aggregation hierarchy under
-it are those of the effective operator.  The consumers fused into the Jacobian apply's epilogue have no mass term, so the two-pass
-forms are used throughout (``_fused_op`` is None; same bits).  dt is fixed per solver object: a recorded V-cycle keeps the
-coefficient a0 rho it was recorded with.
+it are those of the effective operator.  By default (``fused_mass=False``) the consumers fused into the Jacobian apply's epilogue
+are not used (they have no mass term: ``_fused_op`` is None) and every form is two passes.  dt is fixed per solver object: a recorded
+V-cycle keeps the coefficient a0 rho it was recorded with.
+
+``fused_mass=True`` / ``"auto"``: the level's Jacobian operator carries the term itself (``ceed.Operator.set_mass_term(a0 rho)``,
+CeedXOperatorSetMassTerm: K + a0 rho M in the launches of K), ``A`` is ONE apply of it on every matrix-free level, and ``_fused_op``
+hands it to the smoother step and the V-cycle's residual again, so ``fuse_epilogue=`` and ``graph=`` act as in the parent.  ``True``
+raises a ValueError where the library or a level has no such kernel; ``"auto"`` keeps two passes on that level.  The term is never
+set on a level whose matrix is assembled (its matrix already holds a0 rho M); the diagonal, the residual's inertia term, the start-up
+mass solve and the kinetic energy keep the mass operator of mass.py; ``destroy()`` clears every term it set.
+The term is state of the PROBLEM's operator (``prob.levels[lv].opJacob``), not of this object: while a solver with fused_mass lives,
+``prob.apply_jacobian(lv)`` -- and any other user of that operator, a second solver on the same problem among them -- gets
+K + a0 rho M on the levels of ``_mass_in_op``; a second NewmarkPMG with fused_mass on the same problem overwrites the coefficient
+(another dt), and destroying either clears the term under the other.  One solver with fused_mass per problem at a time.
 
 Refused: ``smoother="pbjacobi"`` (the nodal blocks of M are not built) and a halo with several ranks (the mass operator's interface sums
 were never run there).
@@ -39,9 +50,11 @@ from .solver import NewtonPMG, SolveStats
 
 
 class NewmarkPMG(NewtonPMG):
-    def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, **kw):
+    def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, fused_mass=False, **kw):
         if not (density > 0.0 and dt > 0.0 and beta > 0.0):
             raise ValueError("density, dt and beta must be positive")
+        if not (fused_mass is True or fused_mass is False or fused_mass == "auto"):
+            raise ValueError(f"fused_mass must be False, True or 'auto', not {fused_mass!r}")
         if kw.get("smoother", "jacobi") == "pbjacobi":
             raise ValueError("NewmarkPMG: smoother='pbjacobi' is not provided: the 3 x 3 nodal blocks of the mass operator are not built")
         self._refuse_several_ranks(kw.get("halo"), "NewmarkPMG is", "the mass operator's sums at the interface nodes have not been run "
@@ -54,7 +67,18 @@ class NewmarkPMG(NewtonPMG):
         # the tangent's mass term per level (read by A and _get_diag, which the parent's constructor may already call)
         self.mass = [MassOperator(prob, lv, self.a0 * self.density) for lv in range(len(prob.levels))]
         self._mdiag = {}
+        self.fused_mass = fused_mass
+        self._mass_in_op = []            # the levels whose Jacobian operator carries a0 rho M (fused_mass): cleared by destroy()
         super().__init__(prob, **kw)
+        if fused_mass is not False:
+            try:
+                self._set_mass_terms()
+            except Exception:            # (fused_mass=True without the kernel): nothing of this object is left behind, no term stays set
+                self._clear_mass_terms()
+                for m in self.mass:
+                    m.destroy()
+                NewtonPMG.destroy(self)
+                raise
         n, top = prob.lsize(), self.nlev - 1
         self.mass_res = MassOperator(prob, prob.fine, self.density, mask_mode=2)      # the residual's: reads the boundary values
         self.xn, self.vn, self.an, self._pred, self._acc, self._mt = (self._vec(n, top) for _ in range(6))
@@ -64,13 +88,34 @@ class NewmarkPMG(NewtonPMG):
         self._started = False
 
     # ---- the effective operator K + a0 rho M --------------------------------------------------------------------------------
+    def _set_mass_terms(self):
+        """fused_mass: a0 rho M into the Jacobian operator of every matrix-free level that has the kernel.  Never on a level whose matrix
+        is assembled: AssembledLevel(mass_coef=) already adds M there, and its probes apply this operator."""
+        for lv, level in enumerate(self.p.levels):
+            if lv == 0 and self.asm is not None:
+                continue
+            op = level.opJacob
+            if not (op.L.has("CeedXOperatorSetMassTerm") and op.mass_term_available()):
+                if self.fused_mass is True:
+                    raise ValueError(f"NewmarkPMG(fused_mass=True): no fused Jacobian kernel with the mass term for level {lv} "
+                                     f"(P={level.degree + 1}, Q={level.Q}) in this library; fused_mass='auto' keeps two passes there")
+                continue
+            op.set_mass_term(self.a0 * self.density)
+            self._mass_in_op.append(lv)
+
+    def _clear_mass_terms(self):
+        for lv in self._mass_in_op:
+            self.p.levels[lv].opJacob.set_mass_term(0.0)
+        self._mass_in_op = []
+
     def A(self, lv, x, y):
-        super().A(lv, x, y)
-        if not (lv == 0 and self.asm is not None):     # (the assembled level holds its mass term in the matrix)
+        super().A(lv, x, y)           # (a level in _mass_in_op: K + a0 rho M in this one apply)
+        if lv not in self._mass_in_op and not (lv == 0 and self.asm is not None):     # (the assembled level holds its mass term in the matrix)
             self.mass[lv].apply_add(x, y)
 
     def _fused_op(self, lv):
-        return None
+        """The level's Jacobian operator where it carries the mass term itself (the parent's conditions besides); None: two passes."""
+        return super()._fused_op(lv) if lv in self._mass_in_op else None
 
     def _get_diag(self, lv, d):
         super()._get_diag(lv, d)
@@ -176,6 +221,8 @@ class NewmarkPMG(NewtonPMG):
             m.destroy()
 
     def destroy(self):
+        self._drop_pc_graph()            # (a recording holds the coefficient: gone before the term is)
+        self._clear_mass_terms()         # the problem's operators are left as they were found
         self.destroy_mass()
         super().destroy()
 

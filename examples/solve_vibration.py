@@ -9,6 +9,7 @@ the zero crossings of q_n and the continuous 2 pi / omega_1, and the total energ
 
     python examples/solve_vibration.py            # on the device
     python examples/solve_vibration.py --oracle   # on the CPU oracle (portable mass operator)
+    python examples/solve_vibration.py --fused-mass auto   # K + a0 rho M in ONE fused apply per level where the library has the kernel
 """
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +25,7 @@ from ceedpetscsolid_amd.solver import NewtonPMG
 ap = argparse.ArgumentParser()
 ap.add_argument("--oracle", action="store_true"); ap.add_argument("--steps-per-period", type=int, default=40)
 ap.add_argument("--periods", type=float, default=2.0); ap.add_argument("--density", type=float, default=1.0)
+ap.add_argument("--fused-mass", choices=["off", "on", "auto"], default="off", help="NewmarkPMG(fused_mass=False / True / 'auto')")
 a = ap.parse_args()
 c = cd.Ceed(cd.CeedLib(os.path.join(ROOT, "oracle", "liboracle_ceed.so")), "/cpu/self/oracle") if a.oracle else cd.Ceed(cd.CeedLib(cd.PRODUCT_LIB), "/gpu/hip/mi355x")
 prob = SolidProblem(c, box_mesh(4, 1, 1, hi=(4.0, 1.0, 0.5)), 2, "linElas", nu=0.3, E=1.0, bc_sides=[6])
@@ -53,7 +55,7 @@ u0 = bend.U.to_numpy().copy()
 bend.destroy()                                  # (the static solver's vectors go before the time stepper makes its own)
 dt = 2.0 * np.pi / omega / a.steps_per_period
 theta = 2.0 * np.arctan(0.5 * omega * dt)
-sol = NewmarkPMG(prob, a.density, dt, ksp_rtol=1e-10, snes_rtol=1e-10)
+sol = NewmarkPMG(prob, a.density, dt, ksp_rtol=1e-10, snes_rtol=1e-10, fused_mass={"off": False, "on": True, "auto": "auto"}[a.fused_mass])
 sol.set_initial(u0=u0)
 q = lambda u: float(phi @ M @ u[free]) / float(phi @ M @ phi)
 energy = lambda: 0.5 * sol.vn.to_numpy()[free] @ M @ sol.vn.to_numpy()[free] + 0.5 * sol.xn.to_numpy()[free] @ K @ sol.xn.to_numpy()[free]
@@ -74,3 +76,4 @@ print(f"period continuous 2 pi / omega = {2 * np.pi / omega:.6f}   discrete 2 pi
 print(f"worst |q_n - q_0 cos(n theta)| / |q_0| over {nsteps} steps = {np.abs(qs - qs[0] * np.cos(theta * np.arange(nsteps + 1))).max() / abs(qs[0]):.3e}")
 print(f"energy at the start {e0:.12e}   at the end {energy():.12e}   kinetic energy peak {max(kin):.6e}")
 print(f"Newton / Krylov iterations per step: {its[-1][0]} / {its[-1][1]}")
+print(f"tangent of the fine level: {prob.levels[prob.fine].opJacob.kernel_name}" + ("" if sol._mass_in_op else " + the mass operator (two passes)"))

@@ -395,6 +395,32 @@ CEED_EXTERN int CeedXOperatorApplyResidual(CeedOperator op, CeedVector in, CeedV
 /* refreshed from the fine displacement.  The active output does not exist for */
 /* this call; kernel name "state<Pf=..,Qc=..>".                                */
 CEED_EXTERN_OPTIONAL int CeedXOperatorApplyState(CeedOperator op, CeedVector u);
+/* OPTIONAL entry points: the mass term of a Jacobian operator.  With c != 0    */
+/* the operator applies K + c M -- M the consistent mass matrix of its basis    */
+/* and qdata, B^T (w det J) B on the three components, the "Mass" QFunction     */
+/* with context c -- in the launches of K alone: the effective tangent          */
+/* K + a0 rho M of an implicit Newmark step (c = a0 rho) without a second pass. */
+/* The Dirichlet mask applies to the sum as it does to K: masked inputs read as */
+/* zero, masked rows dropped (mask mode 3 of a mass operator).                  */
+/*   SetMassTerm: Jacobian operators only (an operator that stores grad u, and  */
+/*     every other kind, is refused).  c = 0 clears the term: the operator then */
+/*     launches the kernels and gives the bits it gave before.  Every apply     */
+/*     form carries the term -- CeedOperatorApply / ApplyAdd (serial and        */
+/*     pipelined), CeedXOperatorApplyPhase, CeedXOperatorApplyChebyshev,        */
+/*     CeedXOperatorApplyResidual (both with the bits of apply-then-step) and a */
+/*     recorded CeedXGraph, which FREEZES the coefficient it was recorded with: */
+/*     record again after changing the term.  CeedXOperatorApplyWithHalo        */
+/*     refuses an operator with a term, whatever the halo (the interface sums   */
+/*     of the mass operator were never run over ranks).                         */
+/*     CeedOperatorLinearAssembleDiagonal and ...PointBlockDiagonal IGNORE the  */
+/*     term: they return the diagonal of K, bit for bit; add c diag(M) from the */
+/*     mass operator's own diagonal.                                            */
+/*     Kernel name after an apply: "fused_grad<P=..,Q=..,<QF>+mass>/pencil".    */
+/*   MassTermAvailable: *has = 1 where a kernel with the term is instantiated   */
+/*     for this operator's (P, Q, QFunction), else 0 -- SetMassTerm with c != 0 */
+/*     is then an error, and the caller keeps the two-pass form.                */
+CEED_EXTERN_OPTIONAL int CeedXOperatorSetMassTerm(CeedOperator op, double c);
+CEED_EXTERN_OPTIONAL int CeedXOperatorMassTermAvailable(CeedOperator op, int *has);
 /* OPTIONAL entry point: does the QFunction `name` ("Mass", or a source string  */
 /* "file:Mass") have a device functor in this library?  *has = 1 or 0.  A      */
 /* caller looks the entry point up and, where it is absent or answers 0, takes */

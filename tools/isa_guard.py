@@ -14,7 +14,8 @@ workgroup barrier.  None of this is promised by the language, so the build check
   * at most 256 VGPRs (two waves per SIMD) for the kernels of the metric configurations
 
 usage: isa_guard.py build/fused_q5p0.o [build/fused_q7p0.o ...] [--summary out.txt]
-Exit status 1 on a violation in a guarded kernel (k_fused_pencil<P,Q,...>; Q = 8 -- degree 7, one wave per SIMD by design -- is held to
+Exit status 1 on a violation in a guarded kernel (k_fused_pencil<P,Q,...> and k_fused_pencil_mass<P,Q,...>, the entry of the same body with
+the mass term, whose rows are named so in the summary; Q = 8 -- degree 7, one wave per SIMD by design -- is held to
 the same LDS / barrier / scratch rules with a 512-register limit).
 """
 import argparse
@@ -78,6 +79,11 @@ def other_name(mangled):
 
 def short_name(mangled):
     m = re.search(r"k_fused_pencilILi(\d+)ELi(\d+)ELi(\d+)ELi(\d)E", mangled)
+    mm = re.search(r"k_fused_pencil_massILi(\d+)ELi(\d+)ELi(\d+)ELi(\d)E", mangled)
+    if mm:                           # the entry with the mass term (K + c M): the same body, the same contract
+        P, Q, qf, geo = (int(x) for x in mm.groups())
+        eo = 1 if 4 <= Q <= 7 else 0
+        return f"k_fused_pencil_mass<P={P},Q={Q},{QF_NAMES.get(qf, qf)},geo={geo},eo={eo}>", Q, eo
     if not m:
         o = other_name(mangled)
         if o:
