@@ -10,12 +10,20 @@ of the reference's ``src/setuplibceed.c`` / ``src/matops.c``.
 
 Raw pointers only cross the boundary: numpy arrays on the host side, integer
 device addresses (e.g. ``torch.Tensor.data_ptr()``) on the device side.
+
+The prototypes are read out of ``include/ceed.h`` at import (``header_prototypes``) and declared on every library loaded, so a call
+with an argument missing or of the wrong kind is a Python exception before anything reaches C.  ``L.lib.CeedName(...)`` is the raw call:
+it returns the library's code and raises nothing (a code that is inspected, the destroy paths).  ``L.CeedName(...)`` is its checked
+twin: same prototype, ``CeedError`` with the library's message on a non-zero code; an optional entry point the library lacks has no
+twin (ask ``L.has`` first).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import os
+import re
 from typing import Optional, Sequence
 
 import numpy as np
@@ -33,66 +41,103 @@ GAUSS, GAUSS_LOBATTO = 0, 1
 QFUNCTION_USER = C.CFUNCTYPE(C.c_int, C.c_void_p, c_int, C.POINTER(c_scalar_p), C.POINTER(c_scalar_p))
 
 PRODUCT_LIB = os.environ.get(  # override only for A/B-ing kernel builds (tools/); must still be a *mi355x* build
-    "CEEDPETSCSOLID_MI355X_LIB",
-    os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libceed_mi355x.so"))
+    "CEEDPETSCSOLID_MI355X_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libceed_mi355x.so"))
 
 
 class CeedError(RuntimeError):
     pass
 
 
-class CeedLib:
-    """One loaded shared object exporting the ``include/ceed.h`` ABI."""
+# ---- the prototypes of a header of the ABI as ctypes types -----------------------------------------------------------------------
+class _Handle:
+    """Parameter type of an opaque handle (``typedef struct X_private *X``) and of a pointer to one: whatever ``c_void_p`` takes (a
+    ``c_void_p``, ``byref`` of one, an address held as an integer such as the CEED_* sentinels, None for NULL) except text, which
+    ``c_void_p`` would pass on as the address of the string."""
 
-    # every symbol include/ceed.h declares (functions); checked by tests
-    FUNCTIONS = [
-        "CeedInit", "CeedDestroy", "CeedGetResource", "CeedGetPreferredMemType",
-        "CeedVectorCreate", "CeedVectorSetArray", "CeedVectorTakeArray", "CeedVectorSetValue",
-        "CeedVectorSyncArray", "CeedVectorGetArray", "CeedVectorGetArrayRead",
-        "CeedVectorRestoreArray", "CeedVectorRestoreArrayRead", "CeedVectorGetLength",
-        "CeedVectorReciprocal", "CeedVectorDestroy",
-        "CeedElemRestrictionCreate", "CeedElemRestrictionCreateStrided",
-        "CeedElemRestrictionCreateVector", "CeedElemRestrictionApply",
-        "CeedElemRestrictionGetMultiplicity", "CeedElemRestrictionDestroy",
-        "CeedBasisCreateTensorH1Lagrange", "CeedBasisGetNumQuadraturePoints", "CeedBasisGetNumNodes",
-        "CeedBasisApply", "CeedBasisDestroy", "CeedGaussQuadrature", "CeedLobattoQuadrature",
-        "CeedBasisGetInterp1D", "CeedBasisGetGrad1D", "CeedBasisGetQWeights1D",
-        "CeedQFunctionCreateInterior", "CeedQFunctionCreateIdentity", "CeedQFunctionAddInput",
-        "CeedQFunctionAddOutput", "CeedQFunctionSetContext", "CeedQFunctionDestroy",
-        "CeedOperatorCreate", "CeedCompositeOperatorCreate", "CeedCompositeOperatorAddSub",
-        "CeedOperatorSetField", "CeedOperatorApply", "CeedOperatorApplyAdd",
-        "CeedOperatorLinearAssembleDiagonal", "CeedOperatorDestroy",
-        "CeedXSetErrorReturn", "CeedXLastError", "CeedXSetStream", "CeedXSynchronize",
-        "CeedXOperatorGetKernelName", "CeedXOperatorSetDirichletMask",
-        "CeedXOperatorSetTiming", "CeedXOperatorGetTiming", "CeedXOperatorSetDirichletMaskMode", "CeedXOperatorGetLaunchInfo", "CeedXOperatorApplyWithHalo", "CeedXCommAllReduce",
-        "CeedXCommGetUniqueId", "CeedXCommInit", "CeedXCommDestroy", "CeedXCommGetSize", "CeedXHaloCreate", "CeedXHaloStart", "CeedXHaloFinish", "CeedXHaloDestroy",
-        "CeedXOperatorSetFineScale", "CeedXOperatorSetOverlapSplit", "CeedXOperatorApplyPhase",
-        "CeedXVectorPointwiseMult", "CeedXVectorAXPBY", "CeedXVectorDot", "CeedXVectorChebyshevUpdate",
-        "CeedXGraphBeginCapture", "CeedXGraphEndCapture", "CeedXGraphLaunch", "CeedXGraphDestroy", "CeedXGraphIsStale",
-        "CeedXOperatorApplyChebyshev", "CeedXOperatorApplyResidual", "CeedXClockProbe",
-        "CeedXVectorChebyshevStart", "CeedXVectorChebyshevStep", "CeedXVectorWAXPBY", "CeedXVectorDotTo", "CeedXScalarDivide", "CeedXVectorAXPBYScalars",
-        "CeedXCsrCreate", "CeedXCsrAssemble", "CeedXCsrApply", "CeedXCsrGetDiagonal", "CeedXCsrDestroy",
-        "CeedXCsrCreateRect", "CeedXCsrCreateProduct", "CeedXCsrGetPattern", "CeedXCsrUpdate", "CeedXCsrGetValues", "CeedXCsrInvertDenseSPD",
-    ]
-    # declared CEED_EXTERN_OPTIONAL in include/ceed.h: the product library exports them, another backend of the ABI (the CPU oracle) may
-    # not -- the callers look them up (``has``) and otherwise take the portable form built from the entry points above
-    OPTIONAL = ["CeedXOperatorApplyState", "CeedOperatorLinearAssemblePointBlockDiagonal", "CeedXVectorPointBlockInvert",
-                "CeedXVectorPointBlockMult", "CeedXVectorChebyshevStepPointBlock",
-                "CeedXSurfaceLoadCreate", "CeedXSurfaceLoadSetDirichletMask", "CeedXSurfaceLoadApplyAdd",
-                "CeedXSurfaceLoadApplyTangentAdd", "CeedXSurfaceLoadGetKernelName", "CeedXSurfaceLoadDestroy", "CeedXHasQFunction",
-                "CeedXVectorBlockGram", "CeedXVectorBlockCombine", "CeedXVectorBlockGetLimits",
-                "CeedXVectorLeapfrogStep", "CeedXOperatorSetMassTerm", "CeedXOperatorMassTermAvailable"]
-    DATA = [
-        "CeedMemTypes", "CEED_VECTOR_ACTIVE", "CEED_VECTOR_NONE", "CEED_ELEMRESTRICTION_NONE",
-        "CEED_BASIS_COLLOCATED", "CEED_QFUNCTION_NONE", "CEED_REQUEST_IMMEDIATE",
-        "CEED_REQUEST_ORDERED", "CEED_STRIDES_BACKEND",
-    ]
+    @staticmethod
+    def from_param(v, _vp=C.c_void_p):
+        if type(v) is _vp or v is None:
+            return v
+        if isinstance(v, (str, bytes, bytearray)):
+            raise TypeError("a handle is expected, not text")
+        return _vp.from_param(v)
+
+
+_BASE_TYPES = {"int": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "int32_t": C.c_int32, "int64_t": C.c_int64,
+               "unsigned char": C.c_ubyte, "CeedQFunctionUser": C.c_void_p}      # (a callback is passed as the address it was cast to)
+Prototype = collections.namedtuple("Prototype", "restype argtypes optional")
+Prototypes = collections.namedtuple("Prototypes", "types functions data")
+
+
+def _ctype(types: dict, decl: str, named: bool, where: str):
+    """The ctypes type of a C parameter declaration (``named``: it may end in the parameter's name) or return type.  The pointer depth
+    is the number of ``*`` and ``[]``; a base type outside ``types`` is an error, never a ``void *``."""
+    depth = decl.count("*") + decl.count("[")
+    words = re.sub(r"\[[^\]]*\]|\*|\bconst\b", " ", decl).split()
+    if named and len(words) > 1 and " ".join(words) not in types:
+        words.pop()
+    base = " ".join(words)
+    if base in ("char", "void") and depth:
+        t, depth = (C.c_char_p if base == "char" else C.c_void_p), depth - 1
+    elif base in types:
+        t = types[base]
+    else:
+        raise CeedError(f"{where}: unknown type '{base}' in '{decl.strip()}'")
+    for _ in range(0 if t is _Handle else depth):
+        t = C.POINTER(t)
+    return t
+
+
+def header_prototypes(path: str, types: Optional[dict] = None) -> Prototypes:
+    """Of a header written like include/ceed.h: its typedefs as ctypes types (on top of ``types``, those of a header it includes),
+    ``{name: Prototype}`` of every ``CEED_EXTERN[_OPTIONAL] <ret> Name(args);`` in the order of declaration, its data symbols."""
+    if not os.path.exists(path):
+        raise CeedError(f"header not found: {path} -- the binding takes its prototypes from it")
+    with open(path) as f:
+        txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    txt = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", " ", txt, flags=re.M)          # preprocessor lines and their continuations
+    types = dict(_BASE_TYPES if types is None else types)
+    types.update({n: _Handle for n in re.findall(r"\btypedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;", txt)})
+    types.update({n: C.c_int for n in re.findall(r"\btypedef\s+enum\s*\{[^}]*\}\s*(\w+)\s*;", txt)})
+    types.update({n: types[b] for b, n in re.findall(r"\btypedef\s+(\w+)\s+(\w+)\s*;", txt) if b in types})
+    functions = {}
+    for optional, ret, name, args in re.findall(r"\bCEED_EXTERN(_OPTIONAL)?\s+([^;()]+?)\b(\w+)\s*\(([^()]*)\)\s*;", txt):
+        where, args = f"{path}: {name}", [] if args.strip() in ("", "void") else args.split(",")
+        functions[name] = Prototype(_ctype(types, ret, False, where), tuple(_ctype(types, a, True, where) for a in args), bool(optional))
+    return Prototypes(types, functions, re.findall(r"\bCEED_EXTERN\s+[^;()]+?\b(\w+)\s*(?:\[\d*\])?\s*;", txt))
+
+
+def declare(cdll, functions: dict, chk) -> dict:
+    """Put ``argtypes`` and ``restype`` on every function of ``functions`` that ``cdll`` exports and return ``{name: checked twin}``:
+    ``cdll[name]`` is a function object of its own, given the same prototype and ``chk(code, function, arguments)`` as its ``errcheck``."""
+    twins = {}
+    for name, p in functions.items():
+        if hasattr(cdll, name):
+            for f in (getattr(cdll, name), cdll[name]):
+                f.restype, f.argtypes = p.restype, p.argtypes
+            if p.restype is C.c_int:
+                f.errcheck = chk
+            twins[name] = f
+    return twins
+
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ceed.h")
+PROTOTYPES = header_prototypes(HEADER)
+
+
+class CeedLib:
+    """One loaded shared object exporting the ``include/ceed.h`` ABI: ``lib`` the raw functions, ``CeedName`` their checked twins."""
+
+    # what include/ceed.h declares: CEED_EXTERN functions, CEED_EXTERN_OPTIONAL functions (the product library exports them, another
+    # backend of the ABI -- the CPU oracle -- may not: the callers ask ``has`` and otherwise take the portable form), data symbols
+    FUNCTIONS = [n for n, p in PROTOTYPES.functions.items() if not p.optional]
+    OPTIONAL = [n for n, p in PROTOTYPES.functions.items() if p.optional]
+    DATA = list(PROTOTYPES.data)
 
     def __init__(self, path: str = PRODUCT_LIB):
         if not os.path.exists(path):
-            raise CeedError(
-                f"Ceed backend library not found: {path} -- build it first "
-                "(python -c 'import __graft_entry__ as g; g.build()'); there is no fallback path")
+            raise CeedError(f"Ceed backend library not found: {path} -- build it first "
+                            "(python -c 'import __graft_entry__ as g; g.build()'); there is no fallback path")
         self.path = path
         if "mi355x" in os.path.basename(path):
             # One HIP runtime per process.  PyTorch-ROCm bundles its own libamdhip64 /
@@ -105,15 +150,14 @@ class CeedLib:
         # RTLD_LOCAL: the oracle and the product export the same Ceed* names
         self.lib = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
         L = self.lib
-        L.CeedXLastError.restype = C.c_char_p
+        def errcheck(rc, _func, _args, chk=self.chk):          # a plain function: a checked call that succeeds pays for no more than this
+            if rc:
+                chk(rc)
+        self.errcheck = errcheck
+        vars(self).update(declare(L, PROTOTYPES.functions, errcheck))      # instance attributes: nothing between a call and its function
         L.CeedXSetErrorReturn(1)
-        vp = C.c_void_p
-        self.VECTOR_ACTIVE = vp.in_dll(L, "CEED_VECTOR_ACTIVE").value
-        self.VECTOR_NONE = vp.in_dll(L, "CEED_VECTOR_NONE").value
-        self.ELEMRESTRICTION_NONE = vp.in_dll(L, "CEED_ELEMRESTRICTION_NONE").value
-        self.BASIS_COLLOCATED = vp.in_dll(L, "CEED_BASIS_COLLOCATED").value
-        self.QFUNCTION_NONE = vp.in_dll(L, "CEED_QFUNCTION_NONE").value
-        self.REQUEST_IMMEDIATE = vp.in_dll(L, "CEED_REQUEST_IMMEDIATE").value
+        for s in ("VECTOR_ACTIVE", "VECTOR_NONE", "ELEMRESTRICTION_NONE", "BASIS_COLLOCATED", "QFUNCTION_NONE", "REQUEST_IMMEDIATE"):
+            setattr(self, s, C.c_void_p.in_dll(L, "CEED_" + s).value)          # the sentinels: addresses, as integers
         self.STRIDES_BACKEND = (c_int * 3).in_dll(L, "CEED_STRIDES_BACKEND")
 
     def chk(self, rc: int):
@@ -129,6 +173,13 @@ class CeedLib:
         the ABI must export; the product library exports all of them (build() checks with the default)."""
         want = self.FUNCTIONS + self.DATA + (self.OPTIONAL if optional else [])
         return [s for s in want if not hasattr(self.lib, s)]
+
+
+def out_value(fn, ctype, *args):
+    """The value ``fn(*args, &value)`` writes into its last parameter, a ``ctype``."""
+    v = ctype()
+    fn(*args, C.byref(v))
+    return v.value
 
 
 def _np_f64(a) -> np.ndarray:
@@ -198,9 +249,7 @@ def pointblock_invert(blocks: "Vector", want_n_bad: bool = True) -> Optional[int
     ``want_n_bad=False``, None without involving the host.  The portable NumPy form where the library lacks the entry point."""
     L = blocks.L
     if L.has("CeedXVectorPointBlockInvert"):
-        nb = C.c_int(0)
-        L.chk(L.lib.CeedXVectorPointBlockInvert(blocks.h, C.byref(nb) if want_n_bad else None))
-        return nb.value if want_n_bad else None
+        return out_value(L.CeedXVectorPointBlockInvert, C.c_int, blocks.h) if want_n_bad else L.CeedXVectorPointBlockInvert(blocks.h, None)
     if blocks.n % 9:
         raise CeedError(f"pointblock_invert: vector length {blocks.n} is not a multiple of 9")
     inv, nb = pointblock_invert_host(blocks.to_numpy())
@@ -212,7 +261,7 @@ def pointblock_mult(w: "Vector", blocks: "Vector", x: "Vector"):
     """CeedXVectorPointBlockMult: w_n = B_n x_n."""
     L = w.L
     if L.has("CeedXVectorPointBlockMult"):
-        L.chk(L.lib.CeedXVectorPointBlockMult(w.h, blocks.h, x.h))
+        L.CeedXVectorPointBlockMult(w.h, blocks.h, x.h)
         return
     if w.n != x.n:
         raise CeedError("pointblock_mult: vector lengths differ")
@@ -225,7 +274,7 @@ def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b
     """CeedXVectorChebyshevStepPointBlock: ri = b - t; d = c1 B ri + c2 d; x = d or x + d (ri stored if r is given)."""
     L = x.L
     if L.has("CeedXVectorChebyshevStepPointBlock"):
-        L.chk(L.lib.CeedXVectorChebyshevStepPointBlock(x.h, d.h, _h(r), b.h, _h(t), blocks.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        L.CeedXVectorChebyshevStepPointBlock(x.h, d.h, _h(r), b.h, _h(t), blocks.h, c1, c2, int(bool(assign_x)))
         return
     if any(v is not None and v.n != x.n for v in (d, r, b, t)):
         raise CeedError("chebyshev_step_pointblock: vector lengths differ")
@@ -267,18 +316,17 @@ class Csr:
         rp = np.ascontiguousarray(rowptr, dtype=np.int32); cl = np.ascontiguousarray(cols, dtype=np.int32)
         sl = np.ascontiguousarray(coo_slot, dtype=np.int32); ur = np.ascontiguousarray(unit_rows, dtype=np.int32)
         self.nrows, self.nnz, self.ncoo = rp.size - 1, int(rp[-1]), sl.size
-        self.L.chk(self.L.lib.CeedXCsrCreate(ceed.h, c_int(self.nrows), rp.ctypes.data_as(c_int_p), cl.ctypes.data_as(c_int_p),
-                                             c_int(sl.size), sl.ctypes.data_as(c_int_p), c_int(ur.size),
-                                             ur.ctypes.data_as(c_int_p), C.byref(self.h)))
+        self.L.CeedXCsrCreate(ceed.h, self.nrows, rp.ctypes.data_as(c_int_p), cl.ctypes.data_as(c_int_p), sl.size,
+                              sl.ctypes.data_as(c_int_p), ur.size, ur.ctypes.data_as(c_int_p), C.byref(self.h))
 
     def assemble(self, coo_values: "Vector"):
-        self.L.chk(self.L.lib.CeedXCsrAssemble(self.h, coo_values.h))
+        self.L.CeedXCsrAssemble(self.h, coo_values.h)
 
     def apply(self, x: "Vector", y: "Vector"):
-        self.L.chk(self.L.lib.CeedXCsrApply(self.h, x.h, y.h))
+        self.L.CeedXCsrApply(self.h, x.h, y.h)
 
     def diagonal(self, d: "Vector"):
-        self.L.chk(self.L.lib.CeedXCsrGetDiagonal(self.h, d.h))
+        self.L.CeedXCsrGetDiagonal(self.h, d.h)
 
     # ---- pieces of the aggregation hierarchy (amg.py) ------------------------------------------------------
     @classmethod
@@ -296,8 +344,7 @@ class Csr:
             if va.size != self.nnz:
                 raise ValueError("one value per pattern entry expected")
             vp = va.ctypes.data_as(C.POINTER(C.c_double))
-        self.L.chk(self.L.lib.CeedXCsrCreateRect(ceed.h, c_int(nrows), c_int(ncols), rp.ctypes.data_as(c_int_p),
-                                                 cl.ctypes.data_as(c_int_p), vp, C.byref(self.h)))
+        self.L.CeedXCsrCreateRect(ceed.h, nrows, ncols, rp.ctypes.data_as(c_int_p), cl.ctypes.data_as(c_int_p), vp, C.byref(self.h))
         return self
 
     @classmethod
@@ -306,7 +353,7 @@ class Csr:
         ``update()``; pattern and term lists are worked out by the library (CeedXCsrCreateProduct)."""
         self = cls.__new__(cls)
         self.L, self.h, self._ceed = left.L, C.c_void_p(), left._ceed
-        self.L.chk(self.L.lib.CeedXCsrCreateProduct(left.h, right.h, c_int(variable), c_int(1 if dense else 0), C.byref(self.h)))
+        self.L.CeedXCsrCreateProduct(left.h, right.h, variable, 1 if dense else 0, C.byref(self.h))
         self.nrows, self.ncols, self.nnz = self.pattern()[:3]
         self.ncoo = 0
         return self
@@ -315,16 +362,16 @@ class Csr:
         """(nrows, ncols, nnz, rowptr, cols): copies of the library's host pattern."""
         nr, nc, nz = c_int(), c_int(), c_int()
         rp, cl = c_int_p(), c_int_p()
-        self.L.chk(self.L.lib.CeedXCsrGetPattern(self.h, C.byref(nr), C.byref(nc), C.byref(nz), C.byref(rp), C.byref(cl)))
+        self.L.CeedXCsrGetPattern(self.h, C.byref(nr), C.byref(nc), C.byref(nz), C.byref(rp), C.byref(cl))
         rowptr = np.ctypeslib.as_array(rp, shape=(nr.value + 1,)).copy()
         cols = np.ctypeslib.as_array(cl, shape=(max(nz.value, 1),))[:nz.value].copy() if nz.value else np.zeros(0, np.int32)
         return nr.value, nc.value, nz.value, rowptr, cols
 
     def update(self):
-        self.L.chk(self.L.lib.CeedXCsrUpdate(self.h))
+        self.L.CeedXCsrUpdate(self.h)
 
     def get_values(self, v: "Vector"):
-        self.L.chk(self.L.lib.CeedXCsrGetValues(self.h, v.h))
+        self.L.CeedXCsrGetValues(self.h, v.h)
 
     def values(self, ceed: "Ceed" = None) -> np.ndarray:
         v = (ceed or self._ceed).vector(max(self.nnz, 1))
@@ -334,7 +381,7 @@ class Csr:
         return out
 
     def invert_dense_spd(self):
-        self.L.chk(self.L.lib.CeedXCsrInvertDenseSPD(self.h))
+        self.L.CeedXCsrInvertDenseSPD(self.h)
 
     def destroy(self):
         if self.h:
@@ -356,26 +403,22 @@ class SurfaceLoadHandle:
         self.h = C.c_void_p()
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, P * P)
         self.nface = off.shape[0]
-        self.L.chk(self.L.lib.CeedXSurfaceLoadCreate(ceed.h, c_int(self.nface), c_int(P), c_int(Q), off.ctypes.data_as(c_int_p),
-                                                     c_int(lsize), C.byref(self.h)))
+        self.L.CeedXSurfaceLoadCreate(ceed.h, self.nface, P, Q, off.ctypes.data_as(c_int_p), lsize, C.byref(self.h))
 
     def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        self.L.chk(self.L.lib.CeedXSurfaceLoadSetDirichletMask(self.h, MEM_HOST, None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                                               c_int(0 if m is None else m.size)))
+        _, p, n = Operator._bytes(mask)
+        self.L.CeedXSurfaceLoadSetDirichletMask(self.h, MEM_HOST, p, n)
 
     def apply_add(self, kind: int, coef, scale: float, X: "Vector", u: Optional["Vector"], y: "Vector"):   # y += scale g
         cf = (C.c_double * 3)(*[float(v) for v in coef])
-        self.L.chk(self.L.lib.CeedXSurfaceLoadApplyAdd(self.h, int(kind), cf, C.c_double(scale), X.h, _h(u), y.h))
+        self.L.CeedXSurfaceLoadApplyAdd(self.h, int(kind), cf, scale, X.h, _h(u), y.h)
 
     def apply_tangent_add(self, p: float, scale: float, X: "Vector", u: Optional["Vector"], du: "Vector", y: "Vector"):   # y += scale p T(u) du
-        self.L.chk(self.L.lib.CeedXSurfaceLoadApplyTangentAdd(self.h, C.c_double(p), C.c_double(scale), X.h, _h(u), du.h, y.h))
+        self.L.CeedXSurfaceLoadApplyTangentAdd(self.h, p, scale, X.h, _h(u), du.h, y.h)
 
     @property
     def kernel_name(self) -> str:
-        s = C.c_char_p()
-        self.L.chk(self.L.lib.CeedXSurfaceLoadGetKernelName(self.h, C.byref(s)))
-        return s.value.decode() if s.value else ""
+        return (out_value(self.L.CeedXSurfaceLoadGetKernelName, C.c_char_p, self.h) or b"").decode()
 
     def destroy(self):
         if self.h:
@@ -388,13 +431,11 @@ class Graph:
         self.L, self.h = L, h
 
     def launch(self):
-        self.L.chk(self.L.lib.CeedXGraphLaunch(self.h))
+        self.L.CeedXGraphLaunch(self.h)
 
     def stale(self) -> int:
         """What CeedXGraphLaunch would refuse for (0: nothing) -- local to this rank."""
-        st = c_int()
-        self.L.chk(self.L.lib.CeedXGraphIsStale(self.h, C.byref(st)))
-        return st.value
+        return out_value(self.L.CeedXGraphIsStale, C.c_int, self.h)
 
     def destroy(self):
         if self.h:
@@ -407,44 +448,34 @@ class Ceed:
         self.L = lib
         self.h = C.c_void_p()
         self._scalars = None
-        lib.chk(lib.lib.CeedInit(resource.encode(), C.byref(self.h)))
+        lib.CeedInit(resource.encode(), C.byref(self.h))
 
     @property
     def resource(self) -> str:
-        s = C.c_char_p()
-        self.L.chk(self.L.lib.CeedGetResource(self.h, C.byref(s)))
-        return s.value.decode()
+        return out_value(self.L.CeedGetResource, C.c_char_p, self.h).decode()
 
     @property
     def preferred_memtype(self) -> int:
-        m = C.c_int()
-        self.L.chk(self.L.lib.CeedGetPreferredMemType(self.h, C.byref(m)))
-        return m.value
+        return out_value(self.L.CeedGetPreferredMemType, C.c_int, self.h)
 
     def has_qfunction(self, name: str) -> bool:
         """Does the library have a device functor for the QFunction ``name`` (CeedXHasQFunction)?  False where it lacks the entry point."""
-        if not self.L.has("CeedXHasQFunction"):
-            return False
-        r = C.c_int(0)
-        self.L.chk(self.L.lib.CeedXHasQFunction(self.h, name.encode(), C.byref(r)))
-        return bool(r.value)
+        return self.L.has("CeedXHasQFunction") and bool(out_value(self.L.CeedXHasQFunction, C.c_int, self.h, name.encode()))
 
     def set_stream(self, hip_stream: int):
-        self.L.chk(self.L.lib.CeedXSetStream(self.h, C.c_void_p(hip_stream)))
+        self.L.CeedXSetStream(self.h, hip_stream)
 
     def synchronize(self):
-        self.L.chk(self.L.lib.CeedXSynchronize(self.h))
+        self.L.CeedXSynchronize(self.h)
 
     def clock_probe(self, spin_us: int = 2000) -> float:
         """Shader clock (GHz) while the work queued on this Ceed's stream runs (CeedXClockProbe)."""
-        g = C.c_double()
-        self.L.chk(self.L.lib.CeedXClockProbe(self.h, C.c_int(spin_us), C.byref(g)))
-        return g.value
+        return out_value(self.L.CeedXClockProbe, C.c_double, self.h, spin_us)
 
     def comm_size(self):
         """(ranks, this rank) of the Ceed's RCCL communicator as RCCL reports them (CeedXCommGetSize); (0, -1) without one."""
         n, r = C.c_int(), C.c_int()
-        self.L.chk(self.L.lib.CeedXCommGetSize(self.h, C.byref(n), C.byref(r)))
+        self.L.CeedXCommGetSize(self.h, C.byref(n), C.byref(r))
         return n.value, r.value
 
     @property
@@ -456,15 +487,15 @@ class Ceed:
 
     def scalar_divide(self, scalars: "Vector", dst: int, num: int, den: int, scale: float = 1.0):
         """scalars[dst] = scale * scalars[num] / scalars[den] (den < 0: no division; a non-positive denominator gives 0)"""
-        self.L.chk(self.L.lib.CeedXScalarDivide(scalars.h, dst, num, den, C.c_double(scale)))
+        self.L.CeedXScalarDivide(scalars.h, dst, num, den, scale)
 
     def all_reduce(self, v: "Vector", first: int = 0, n: Optional[int] = None):
         """Entries [first, first + n) of v (default: all) summed over the ranks of the Ceed's communicator, in place, on its stream."""
-        self.L.chk(self.L.lib.CeedXCommAllReduce(self.h, v.h, first, v.n if n is None else n))
+        self.L.CeedXCommAllReduce(self.h, v.h, first, v.n if n is None else n)
 
     def capture(self, fn) -> "Graph":
         """Record the device work `fn()` queues on this Ceed into a hipGraph (CeedXGraph*)."""
-        self.L.chk(self.L.lib.CeedXGraphBeginCapture(self.h))
+        self.L.CeedXGraphBeginCapture(self.h)
         g, ok = C.c_void_p(), False
         try:
             fn()
@@ -532,47 +563,46 @@ class Vector:
         self.ceed, self.L, self.n = ceed, ceed.L, int(n)
         self.h = C.c_void_p()
         self._keep = None
-        self.L.chk(self.L.lib.CeedVectorCreate(ceed.h, c_int(n), C.byref(self.h)))
+        self.L.CeedVectorCreate(ceed.h, n, C.byref(self.h))
 
     def set_array(self, arr: np.ndarray, copy=True):
         a = _np_f64(arr)
         assert a.size == self.n, (a.size, self.n)
         if not copy:
             self._keep = a
-        self.L.chk(self.L.lib.CeedVectorSetArray(
-            self.h, MEM_HOST, COPY_VALUES if copy else USE_POINTER, a.ctypes.data_as(c_scalar_p)))
+        self.L.CeedVectorSetArray(self.h, MEM_HOST, COPY_VALUES if copy else USE_POINTER, a.ctypes.data_as(c_scalar_p))
         return self
 
     def set_device_pointer(self, ptr: int):
         """Borrow a device buffer (CEED_MEM_DEVICE, CEED_USE_POINTER), matops.c:40-41."""
-        self.L.chk(self.L.lib.CeedVectorSetArray(self.h, MEM_DEVICE, USE_POINTER, C.cast(C.c_void_p(ptr), c_scalar_p)))
+        self.L.CeedVectorSetArray(self.h, MEM_DEVICE, USE_POINTER, C.cast(C.c_void_p(ptr), c_scalar_p))
         return self
 
     def take_array(self, mtype=MEM_HOST):
-        self.L.chk(self.L.lib.CeedVectorTakeArray(self.h, mtype, None))
+        self.L.CeedVectorTakeArray(self.h, mtype, None)
         self._keep = None
 
     def set_value(self, v: float):
-        self.L.chk(self.L.lib.CeedVectorSetValue(self.h, C.c_double(v)))
+        self.L.CeedVectorSetValue(self.h, v)
         return self
 
     def to_numpy(self) -> np.ndarray:
         p = c_scalar_p()
-        self.L.chk(self.L.lib.CeedVectorGetArrayRead(self.h, MEM_HOST, C.byref(p)))
+        self.L.CeedVectorGetArrayRead(self.h, MEM_HOST, C.byref(p))
         out = np.ctypeslib.as_array(p, shape=(self.n,)).copy() if self.n else np.zeros(0)
-        self.L.chk(self.L.lib.CeedVectorRestoreArrayRead(self.h, C.byref(p)))
+        self.L.CeedVectorRestoreArrayRead(self.h, C.byref(p))
         return out
 
     def device_pointer(self) -> int:
         """Device address of the vector's storage (valid until the next Set/Take)."""
         p = c_scalar_p()
-        self.L.chk(self.L.lib.CeedVectorGetArray(self.h, MEM_DEVICE, C.byref(p)))
+        self.L.CeedVectorGetArray(self.h, MEM_DEVICE, C.byref(p))
         addr = C.cast(p, C.c_void_p).value
-        self.L.chk(self.L.lib.CeedVectorRestoreArray(self.h, C.byref(p)))
+        self.L.CeedVectorRestoreArray(self.h, C.byref(p))
         return addr
 
     def reciprocal(self):
-        self.L.chk(self.L.lib.CeedVectorReciprocal(self.h))
+        self.L.CeedVectorReciprocal(self.h)
 
     # ---- vectors over a torch tensor (Ceed.tensor_vector) -----------------------------------------------------------------
     def fill(self, arr):
@@ -590,33 +620,31 @@ class Vector:
 
     # ---- CeedXVector* (formulas: include/ceed.h): self is the vector written (the left operand of a dot), None an absent operand ----
     def axpby(self, a: float, x: "Vector", b: float):                      # self = a x + b self
-        self.L.chk(self.L.lib.CeedXVectorAXPBY(self.h, C.c_double(a), x.h, C.c_double(b)))
+        self.L.CeedXVectorAXPBY(self.h, a, x.h, b)
 
     def waxpby(self, a: float, x: "Vector", b: float, y: "Vector"):        # self = a x + b y
-        self.L.chk(self.L.lib.CeedXVectorWAXPBY(self.h, C.c_double(a), x.h, C.c_double(b), y.h))
+        self.L.CeedXVectorWAXPBY(self.h, a, x.h, b, y.h)
 
     def pointwise_mult(self, x: "Vector", y: "Vector"):                    # self = x .* y
-        self.L.chk(self.L.lib.CeedXVectorPointwiseMult(self.h, x.h, y.h))
+        self.L.CeedXVectorPointwiseMult(self.h, x.h, y.h)
 
     def dot(self, y: "Vector", weight: Optional["Vector"] = None) -> float:   # sum weight .* self .* y, read on the host
-        r = C.c_double()
-        self.L.chk(self.L.lib.CeedXVectorDot(self.h, y.h, _h(weight), C.byref(r)))
-        return r.value
+        return out_value(self.L.CeedXVectorDot, C.c_double, self.h, y.h, _h(weight))
 
     def dot_to(self, y: "Vector", scalars: "Vector", slot: int, weight: Optional["Vector"] = None):   # the same into scalars[slot]
-        self.L.chk(self.L.lib.CeedXVectorDotTo(self.h, y.h, _h(weight), scalars.h, slot))
+        self.L.CeedXVectorDotTo(self.h, y.h, _h(weight), scalars.h, slot)
 
     def axpby_scalars(self, scalars, ia: int, sa: float, x, ib: int, sb: float):   # axpby, a = sa scalars[ia], b = sb scalars[ib]; index < 0: 1
-        self.L.chk(self.L.lib.CeedXVectorAXPBYScalars(self.h, scalars.h, ia, C.c_double(sa), x.h, ib, C.c_double(sb)))
+        self.L.CeedXVectorAXPBYScalars(self.h, scalars.h, ia, sa, x.h, ib, sb)
 
     def chebyshev_start(self, d, r, b, t, dinv, c1: float, assign_x: bool):   # r = b - t;  d = c1 dinv .* r;  self = d or self + d
-        self.L.chk(self.L.lib.CeedXVectorChebyshevStart(self.h, d.h, r.h, b.h, _h(t), dinv.h, C.c_double(c1), int(bool(assign_x))))
+        self.L.CeedXVectorChebyshevStart(self.h, d.h, r.h, b.h, _h(t), dinv.h, c1, int(bool(assign_x)))
 
     def chebyshev_update(self, d, r, t, dinv, c1: float, c2: float, assign_x: bool = False):   # r -= t;  d = c1 dinv .* r + c2 d;  self (+)= d
-        self.L.chk(self.L.lib.CeedXVectorChebyshevUpdate(self.h, d.h, r.h, _h(t), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        self.L.CeedXVectorChebyshevUpdate(self.h, d.h, r.h, _h(t), dinv.h, c1, c2, int(bool(assign_x)))
 
     def chebyshev_step(self, d, r, b, t, dinv, c1: float, c2: float, assign_x: bool):   # ri = b - t (stored if r);  d = c1 dinv .* ri + c2 d;  self (+)= d
-        self.L.chk(self.L.lib.CeedXVectorChebyshevStep(self.h, d.h, _h(r), b.h, _h(t), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        self.L.CeedXVectorChebyshevStep(self.h, d.h, _h(r), b.h, _h(t), dinv.h, c1, c2, int(bool(assign_x)))
 
     def leapfrog_step(self, vh: "Vector", r: "Vector", f: Optional["Vector"], m: "Vector", load: float, c1: float, c2: float, dt: float,
                       n: Optional[int] = None, scalars: Optional["Vector"] = None, slot: int = 0):
@@ -625,8 +653,7 @@ class Vector:
         Where the library lacks the entry point (the CPU oracle) the portable form works in place on the vectors' host arrays."""
         n = self.n if n is None else int(n)
         if self.L.has("CeedXVectorLeapfrogStep"):
-            self.L.chk(self.L.lib.CeedXVectorLeapfrogStep(self.h, vh.h, r.h, _h(f), m.h, C.c_double(load), C.c_double(c1), C.c_double(c2),
-                                                          C.c_double(dt), c_int(n), _h(scalars), c_int(slot)))
+            self.L.CeedXVectorLeapfrogStep(self.h, vh.h, r.h, _h(f), m.h, load, c1, c2, dt, n, _h(scalars), slot)
             return
         who, ops = "leapfrog_step", [("x", self), ("vh", vh), ("r", r), ("m", m)] + ([("f", f)] if f is not None else [])
         if any(v is None for _, v in ops):
@@ -658,12 +685,11 @@ class Vector:
         """The vector's host storage as a NumPy array WITHOUT a copy (CeedVectorGetArray / GetArrayRead ... Restore), valid inside the
         ``with`` block only; ``write``: the array may be written."""
         p = c_scalar_p()
-        lib = self.L.lib
-        self.L.chk((lib.CeedVectorGetArray if write else lib.CeedVectorGetArrayRead)(self.h, MEM_HOST, C.byref(p)))
+        (self.L.CeedVectorGetArray if write else self.L.CeedVectorGetArrayRead)(self.h, MEM_HOST, C.byref(p))
         try:
             yield np.ctypeslib.as_array(p, shape=(self.n,)) if self.n else np.zeros(0)
         finally:
-            self.L.chk((lib.CeedVectorRestoreArray if write else lib.CeedVectorRestoreArrayRead)(self.h, C.byref(p)))
+            (self.L.CeedVectorRestoreArray if write else self.L.CeedVectorRestoreArrayRead)(self.h, C.byref(p))
 
     def destroy(self):
         if self.h:
@@ -682,7 +708,7 @@ def block_limits(lib: CeedLib):
     if not lib.has("CeedXVectorBlockGetLimits"):
         return BLOCK_MAX_COLS, None, None, None, None
     v = [c_int() for _ in range(5)]
-    lib.chk(lib.lib.CeedXVectorBlockGetLimits(*[C.byref(x) for x in v]))
+    lib.CeedXVectorBlockGetLimits(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 
@@ -804,8 +830,7 @@ class BlockVector:
             raise CeedError("BlockVector.gram: the blocks differ in n or ld")
         self.owner.touched(); other.owner.touched()
         if not self._portable("BlockVector.gram", "CeedXVectorBlockGram"):
-            self.L.chk(self.L.lib.CeedXVectorBlockGram(self.owner.h, c_int(a0), c_int(ka), other.owner.h, c_int(b0), c_int(kb),
-                                                       c_int(self.n), c_int(self.ld), _h(weight), G.h))
+            self.L.CeedXVectorBlockGram(self.owner.h, a0, ka, other.owner.h, b0, kb, self.n, self.ld, _h(weight), G.h)
             return
         _block_check("BlockVector.gram", self.n, self.ld, [("A", a0, ka, self.owner.n), ("B", b0, kb, other.owner.n)])
         if G.n < ka * kb:
@@ -832,8 +857,7 @@ class BlockVector:
             Cm = self._cvec[cm.size].set_array(cm.reshape(-1))
         self.owner.touched(); A.owner.touched()
         if not self._portable("BlockVector.combine", "CeedXVectorBlockCombine"):
-            self.L.chk(self.L.lib.CeedXVectorBlockCombine(self.owner.h, c_int(y0), c_int(ky), A.owner.h, c_int(a0), c_int(ka), Cm.h,
-                                                          C.c_double(beta), c_int(self.n), c_int(self.ld)))
+            self.L.CeedXVectorBlockCombine(self.owner.h, y0, ky, A.owner.h, a0, ka, Cm.h, beta, self.n, self.ld)
         else:
             _block_check("BlockVector.combine", self.n, self.ld, [("Y", y0, ky, self.owner.n), ("A", a0, ka, A.owner.n)])
             if Cm.n < ka * ky:
@@ -858,19 +882,17 @@ class ElemRestriction:
         self.h = C.c_void_p()
         if strided:
             st = self.L.STRIDES_BACKEND if strides is None else (c_int * 3)(*strides)
-            self.L.chk(self.L.lib.CeedElemRestrictionCreateStrided(
-                ceed.h, c_int(nelem), c_int(elemsize), c_int(ncomp), c_int(lsize), st, C.byref(self.h)))
+            self.L.CeedElemRestrictionCreateStrided(ceed.h, nelem, elemsize, ncomp, lsize, st, C.byref(self.h))
         else:
             off = np.ascontiguousarray(offsets, dtype=np.int32)
             assert off.size == nelem * elemsize
-            self.L.chk(self.L.lib.CeedElemRestrictionCreate(
-                ceed.h, c_int(nelem), c_int(elemsize), c_int(ncomp), c_int(compstride), c_int(lsize),
-                MEM_HOST, COPY_VALUES, off.ctypes.data_as(c_int_p), C.byref(self.h)))
+            self.L.CeedElemRestrictionCreate(ceed.h, nelem, elemsize, ncomp, compstride, lsize, MEM_HOST, COPY_VALUES,
+                                             off.ctypes.data_as(c_int_p), C.byref(self.h))
 
     def _create_vector(self, n: int, evector: bool) -> Vector:
         v = Vector.__new__(Vector)
         v.ceed, v.L, v.n, v._keep, v.h = self.ceed, self.L, n, None, C.c_void_p()
-        self.L.chk(self.L.lib.CeedElemRestrictionCreateVector(self.h, *((None, C.byref(v.h)) if evector else (C.byref(v.h), None))))
+        self.L.CeedElemRestrictionCreateVector(self.h, None if evector else C.byref(v.h), C.byref(v.h) if evector else None)
         return v
 
     def create_lvector(self) -> Vector:
@@ -880,10 +902,10 @@ class ElemRestriction:
         return self._create_vector(self.nelem * self.elemsize * self.ncomp, True)
 
     def apply(self, tmode, u: Vector, v: Vector):
-        self.L.chk(self.L.lib.CeedElemRestrictionApply(self.h, tmode, u.h, v.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+        self.L.CeedElemRestrictionApply(self.h, tmode, u.h, v.h, self.L.REQUEST_IMMEDIATE)
 
     def multiplicity(self, mult: Vector):
-        self.L.chk(self.L.lib.CeedElemRestrictionGetMultiplicity(self.h, mult.h))
+        self.L.CeedElemRestrictionGetMultiplicity(self.h, mult.h)
 
     def destroy(self):
         if self.h:
@@ -895,34 +917,31 @@ class Basis:
         self.ceed, self.L = ceed, ceed.L
         self.dim, self.ncomp, self.P, self.Q, self.qmode = dim, ncomp, P, Q, qmode
         self.h = C.c_void_p()
-        self.L.chk(self.L.lib.CeedBasisCreateTensorH1Lagrange(
-            ceed.h, c_int(dim), c_int(ncomp), c_int(P), c_int(Q), qmode, C.byref(self.h)))
+        self.L.CeedBasisCreateTensorH1Lagrange(ceed.h, dim, ncomp, P, Q, qmode, C.byref(self.h))
 
     @property
     def num_qpts(self) -> int:
-        q = c_int()
-        self.L.chk(self.L.lib.CeedBasisGetNumQuadraturePoints(self.h, C.byref(q)))
-        return q.value
+        return out_value(self.L.CeedBasisGetNumQuadraturePoints, c_int, self.h)
 
     def _table(self, fn, shape):
         p = c_scalar_p()
-        self.L.chk(fn(self.h, C.byref(p)))
+        fn(self.h, C.byref(p))
         return np.ctypeslib.as_array(p, shape=shape).copy()
 
     @property
     def interp1d(self):
-        return self._table(self.L.lib.CeedBasisGetInterp1D, (self.Q, self.P))
+        return self._table(self.L.CeedBasisGetInterp1D, (self.Q, self.P))
 
     @property
     def grad1d(self):
-        return self._table(self.L.lib.CeedBasisGetGrad1D, (self.Q, self.P))
+        return self._table(self.L.CeedBasisGetGrad1D, (self.Q, self.P))
 
     @property
     def qweight1d(self):
-        return self._table(self.L.lib.CeedBasisGetQWeights1D, (self.Q,))
+        return self._table(self.L.CeedBasisGetQWeights1D, (self.Q,))
 
     def apply(self, nelem, tmode, emode, u: Vector, v: Vector):
-        self.L.chk(self.L.lib.CeedBasisApply(self.h, c_int(nelem), tmode, emode, u.h, v.h))
+        self.L.CeedBasisApply(self.h, nelem, tmode, emode, u.h, v.h)
 
     def destroy(self):
         if self.h:
@@ -939,18 +958,17 @@ class QFunction:
         self._ctx = None
         if identity is not None:
             size, inmode, outmode = identity
-            self.L.chk(self.L.lib.CeedQFunctionCreateIdentity(ceed.h, c_int(size), inmode, outmode, C.byref(self.h)))
+            self.L.CeedQFunctionCreateIdentity(ceed.h, size, inmode, outmode, C.byref(self.h))
         else:
             src = (source or f"qfunctions/{name}.h:{name}").encode()
-            fptr = C.cast(f, C.c_void_p) if f is not None else C.c_void_p(0)
-            self.L.chk(self.L.lib.CeedQFunctionCreateInterior(ceed.h, c_int(1), fptr, src, C.byref(self.h)))
+            self.L.CeedQFunctionCreateInterior(ceed.h, 1, None if f is None else C.cast(f, C.c_void_p), src, C.byref(self.h))
 
     def add_input(self, name, size, emode):
-        self.L.chk(self.L.lib.CeedQFunctionAddInput(self.h, name.encode(), c_int(size), emode))
+        self.L.CeedQFunctionAddInput(self.h, name.encode(), size, emode)
         return self
 
     def add_output(self, name, size, emode):
-        self.L.chk(self.L.lib.CeedQFunctionAddOutput(self.h, name.encode(), c_int(size), emode))
+        self.L.CeedQFunctionAddOutput(self.h, name.encode(), size, emode)
         return self
 
     def set_context(self, values: Sequence[float], reported_size: Optional[int] = None):
@@ -958,7 +976,7 @@ class QFunction:
         ``reported_size`` lets tests reproduce the reference's sizeof(pointer) quirk."""
         self._ctx = _np_f64(values).copy()
         size = self._ctx.nbytes if reported_size is None else reported_size
-        self.L.chk(self.L.lib.CeedQFunctionSetContext(self.h, self._ctx.ctypes.data_as(C.c_void_p), C.c_size_t(size)))
+        self.L.CeedQFunctionSetContext(self.h, self._ctx.ctypes.data_as(C.c_void_p), size)
         return self
 
     def destroy(self):
@@ -970,125 +988,111 @@ class Operator:
     def __init__(self, ceed, qf: QFunction):
         self.ceed, self.L, self.qf = ceed, ceed.L, qf
         self.h = C.c_void_p()
-        none = C.c_void_p(self.L.QFUNCTION_NONE)
-        self.L.chk(self.L.lib.CeedOperatorCreate(ceed.h, qf.h, none, none, C.byref(self.h)))
+        self.L.CeedOperatorCreate(ceed.h, qf.h, self.L.QFUNCTION_NONE, self.L.QFUNCTION_NONE, C.byref(self.h))
         self._keep = []
 
     def set_field(self, name, rstr, basis, vec):
         """rstr/basis/vec: wrapper objects, or None for the NONE/COLLOCATED sentinels,
         or the string "active" for CEED_VECTOR_ACTIVE."""
         L = self.L
-        r = C.c_void_p(L.ELEMRESTRICTION_NONE) if rstr is None else rstr.h
-        b = C.c_void_p(L.BASIS_COLLOCATED) if basis is None else basis.h
-        if isinstance(vec, str):
-            assert vec == "active"
-            v = C.c_void_p(L.VECTOR_ACTIVE)
-        elif vec is None:
-            v = C.c_void_p(L.VECTOR_NONE)
-        else:
-            v = vec.h
-        L.chk(L.lib.CeedOperatorSetField(self.h, name.encode(), r, b, v))
+        r = L.ELEMRESTRICTION_NONE if rstr is None else rstr.h
+        b = L.BASIS_COLLOCATED if basis is None else basis.h
+        assert not isinstance(vec, str) or vec == "active"
+        v = L.VECTOR_ACTIVE if isinstance(vec, str) else L.VECTOR_NONE if vec is None else vec.h
+        L.CeedOperatorSetField(self.h, name.encode(), r, b, v)
         self._keep.append((rstr, basis, vec))
         return self
 
     def apply(self, vin: Optional[Vector], vout: Optional[Vector]):
         L = self.L
-        i = vin.h if vin is not None else C.c_void_p(L.VECTOR_NONE)
-        o = vout.h if vout is not None else C.c_void_p(L.VECTOR_NONE)
-        L.chk(L.lib.CeedOperatorApply(self.h, i, o, C.c_void_p(L.REQUEST_IMMEDIATE)))
+        L.CeedOperatorApply(self.h, L.VECTOR_NONE if vin is None else vin.h, L.VECTOR_NONE if vout is None else vout.h, L.REQUEST_IMMEDIATE)
 
     def apply_add(self, vin: Vector, vout: Vector):                         # vout += A vin
-        self.L.chk(self.L.lib.CeedOperatorApplyAdd(self.h, vin.h, vout.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+        self.L.CeedOperatorApplyAdd(self.h, vin.h, vout.h, self.L.REQUEST_IMMEDIATE)
 
     def apply_residual(self, vin: Vector, t: Vector, b: Vector, w: Vector):   # w = b - A vin in the apply's epilogue (t: scratch)
-        self.L.chk(self.L.lib.CeedXOperatorApplyResidual(self.h, vin.h, t.h, b.h, w.h))
+        self.L.CeedXOperatorApplyResidual(self.h, vin.h, t.h, b.h, w.h)
 
     def apply_chebyshev(self, vin, t, x, d, r, b, dinv, c1: float, c2: float, assign_x: bool = False):
         """t = A vin consumed where it is formed by the smoother's step on x (with b: Vector.chebyshev_step, without: chebyshev_update)"""
-        self.L.chk(self.L.lib.CeedXOperatorApplyChebyshev(self.h, vin.h, t.h, x.h, d.h, _h(r), _h(b), dinv.h, C.c_double(c1), C.c_double(c2), int(bool(assign_x))))
+        self.L.CeedXOperatorApplyChebyshev(self.h, vin.h, t.h, x.h, d.h, _h(r), _h(b), dinv.h, c1, c2, int(bool(assign_x)))
 
     def assemble_diagonal(self, vec: Vector):
-        self.L.chk(self.L.lib.CeedOperatorLinearAssembleDiagonal(self.h, vec.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+        self.L.CeedOperatorLinearAssembleDiagonal(self.h, vec.h, self.L.REQUEST_IMMEDIATE)
 
     def assemble_pointblock_diagonal(self, vec: Vector):
         """CeedOperatorLinearAssemblePointBlockDiagonal (CEED_EXTERN_OPTIONAL: check ``CeedLib.has`` first): the 3 x 3 nodal blocks,
         [node][comp out][comp in], the block of the node at component-0 L-offset o at 3 * o."""
-        self.L.chk(self.L.lib.CeedOperatorLinearAssemblePointBlockDiagonal(self.h, vec.h, C.c_void_p(self.L.REQUEST_IMMEDIATE)))
+        self.L.CeedOperatorLinearAssemblePointBlockDiagonal(self.h, vec.h, self.L.REQUEST_IMMEDIATE)
 
     @property
     def kernel_name(self) -> str:
-        s = C.c_char_p()
-        self.L.chk(self.L.lib.CeedXOperatorGetKernelName(self.h, C.byref(s)))
-        return s.value.decode() if s.value else ""
+        return (out_value(self.L.CeedXOperatorGetKernelName, C.c_char_p, self.h) or b"").decode()
 
     @staticmethod
     def _bytes(mask):
         """(the byte array to keep alive over the call, its pointer, its length) of a mask; (None, None, 0) of an absent one"""
         if mask is None:
-            return None, None, c_int(0)
+            return None, None, 0
         m = np.ascontiguousarray(mask, dtype=np.uint8)
-        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte)), c_int(m.size)
+        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte)), m.size
 
     def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
         _, p, n = self._bytes(mask)
-        self.L.chk(self.L.lib.CeedXOperatorSetDirichletMask(self.h, MEM_HOST, p, n))
+        self.L.CeedXOperatorSetDirichletMask(self.h, MEM_HOST, p, n)
 
     def set_dirichlet_mask_mode(self, mask_in, mask_out=None, mode: int = 3):
         """1 = masked entries read as zero on input, 2 = masked rows dropped on output, 3 = both; transfer operators have different
         L-vectors on their two sides and take both masks."""
         mi, mo = self._bytes(mask_in), self._bytes(mask_out)
-        self.L.chk(self.L.lib.CeedXOperatorSetDirichletMaskMode(self.h, MEM_HOST, mi[1], mi[2], mo[1], mo[2], mode))
+        self.L.CeedXOperatorSetDirichletMaskMode(self.h, MEM_HOST, mi[1], mi[2], mo[1], mo[2], mode)
 
     def set_fine_scale(self, scale: Optional[Vector]):      # the fine-side 1 / multiplicity of a transfer operator (None clears)
-        self.L.chk(self.L.lib.CeedXOperatorSetFineScale(self.h, _h(scale)))
+        self.L.CeedXOperatorSetFineScale(self.h, _h(scale))
 
     def set_overlap_split(self, n_leading_elems: int, priority: Optional[np.ndarray]):
         """CeedXOperatorSetOverlapSplit: leading elements / priority L-vector entries of the split-phase apply."""
         _, p, n = self._bytes(priority)
-        self.L.chk(self.L.lib.CeedXOperatorSetOverlapSplit(self.h, c_int(n_leading_elems if priority is not None else 0), p, n))
+        self.L.CeedXOperatorSetOverlapSplit(self.h, n_leading_elems if priority is not None else 0, p, n)
 
     def apply_state(self, u: "Vector"):
         """CeedXOperatorApplyState: write only the stored state (passive gradu output) of a residual-shaped operator."""
-        self.L.chk(self.L.lib.CeedXOperatorApplyState(self.h, u.h))
+        self.L.CeedXOperatorApplyState(self.h, u.h)
 
     def mass_term_available(self) -> bool:
         """CeedXOperatorMassTermAvailable: is a fused kernel with the mass term (K + c M in the launches of K) instantiated for this
         Jacobian operator's (P, Q, QFunction)?  False where the library lacks the entry point (CEED_EXTERN_OPTIONAL: the CPU oracle); an
         operator that is no Jacobian is refused by the library."""
-        if not self.L.has("CeedXOperatorMassTermAvailable"):
-            return False
-        has = C.c_int(0)
-        self.L.chk(self.L.lib.CeedXOperatorMassTermAvailable(self.h, C.byref(has)))
-        return bool(has.value)
+        return self.L.has("CeedXOperatorMassTermAvailable") and bool(out_value(self.L.CeedXOperatorMassTermAvailable, C.c_int, self.h))
 
     def set_mass_term(self, c: float):
         """CeedXOperatorSetMassTerm: every apply form of this Jacobian operator then gives (K + c M) x; 0 clears the term.  A recorded
         graph keeps the coefficient it was recorded with.  The diagonals ignore the term."""
         if not self.L.has("CeedXOperatorSetMassTerm"):
             raise CeedError("this library has no CeedXOperatorSetMassTerm (CEED_EXTERN_OPTIONAL): apply the mass operator on its own")
-        self.L.chk(self.L.lib.CeedXOperatorSetMassTerm(self.h, C.c_double(c)))
+        self.L.CeedXOperatorSetMassTerm(self.h, c)
 
     def apply_phase(self, vin: "Vector", vout: "Vector", phase: int):
-        self.L.chk(self.L.lib.CeedXOperatorApplyPhase(self.h, vin.h, vout.h, C.c_int(phase)))
+        self.L.CeedXOperatorApplyPhase(self.h, vin.h, vout.h, phase)
 
     def set_timing(self, enable: bool):
-        self.L.chk(self.L.lib.CeedXOperatorSetTiming(self.h, int(enable)))
+        self.L.CeedXOperatorSetTiming(self.h, int(enable))
 
     def get_timing(self):
         ms, n = C.c_double(), C.c_int64()
-        self.L.chk(self.L.lib.CeedXOperatorGetTiming(self.h, C.byref(ms), C.byref(n)))
+        self.L.CeedXOperatorGetTiming(self.h, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def launch_info(self) -> dict:
         """CeedXOperatorGetLaunchInfo: how the last apply was launched (segments of the pipelined restriction transpose)."""
         out = (C.c_int * 4)()
-        self.L.chk(self.L.lib.CeedXOperatorGetLaunchInfo(self.h, out))
+        self.L.CeedXOperatorGetLaunchInfo(self.h, out)
         return dict(segments=out[0], streams=out[1], assemble_launches=out[2], last_segment_elements=out[3])
 
     def apply_with_halo(self, vin: "Vector", vout: "Vector", halo):
         """CeedXOperatorApplyWithHalo: the (split-phase) apply and the interface sum of its output in one call; `halo` is a
         halo.RcclHalo or a raw CeedXHalo handle."""
-        self.L.chk(self.L.lib.CeedXOperatorApplyWithHalo(self.h, vin.h, vout.h, getattr(halo, "h", halo)))
+        self.L.CeedXOperatorApplyWithHalo(self.h, vin.h, vout.h, getattr(halo, "h", halo))
 
     def destroy(self):
         if self.h:

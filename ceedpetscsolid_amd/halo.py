@@ -14,6 +14,7 @@ Shared nodes are discovered from partition-independent topological keys
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -163,12 +164,11 @@ class RcclHalo:
     def unique_id(ceed, halo: "HaloExchange"):
         """Rank 0's communicator id on every rank (collective over the torch group; MPI_Bcast in the reference's world).
         Call it from the thread that owns the process group: the worker thread of checked_rccl_halo must not."""
-        import ctypes as C
         ident = [None]
         if halo.rank == 0:
             try:
                 buf = C.create_string_buffer(128)
-                ceed.L.chk(ceed.L.lib.CeedXCommGetUniqueId(ceed.h, buf))
+                ceed.L.CeedXCommGetUniqueId(ceed.h, buf)
                 ident = [buf.raw]
             except Exception as e:   # noqa: BLE001 -- the other ranks are waiting in the broadcast: tell them
                 ident = [RuntimeError(f"CeedXCommGetUniqueId failed on rank 0: {e!r}")]
@@ -182,41 +182,39 @@ class RcclHalo:
         from this rank itself -- the launches, buffer sizes and stream hand-overs of the real exchange on a single GPU (the
         sums it produces are those of a vector folded onto itself, not of the partitioned problem).
         ident: the communicator id from unique_id() (taken here, collectively, if not given)."""
-        import ctypes as C
         self.ceed, self.L = ceed, ceed.L
         self.h = C.c_void_p()
         self.world = halo.world
-        lib = self.L.lib
         if emulate_self:
             if not getattr(ceed, "_comm_ready", False):
                 buf = C.create_string_buffer(128)
-                self.L.chk(lib.CeedXCommGetUniqueId(ceed.h, buf))
-                self.L.chk(lib.CeedXCommInit(ceed.h, C.c_int(1), C.c_int(0), C.c_char_p(buf.raw)))
+                self.L.CeedXCommGetUniqueId(ceed.h, buf)
+                self.L.CeedXCommInit(ceed.h, 1, 0, buf.raw)
                 ceed._comm_ready = True
         elif halo.world > 1 and not getattr(ceed, "_comm_ready", False):
             if ident is None:
                 ident = RcclHalo.unique_id(ceed, halo)
-            self.L.chk(lib.CeedXCommInit(ceed.h, C.c_int(halo.world), C.c_int(halo.rank), C.c_char_p(ident)))
+            self.L.CeedXCommInit(ceed.h, halo.world, halo.rank, ident)
             ceed._comm_ready = True
         nn = len(halo.neigh)
         ranks = (C.c_int * max(nn, 1))(*[0 if emulate_self else n.rank for n in halo.neigh])
         counts = (C.c_int * max(nn, 1))(*[int(n.dof_idx.numel()) for n in halo.neigh])
         self._idx = [np.ascontiguousarray(n.dof_idx.cpu().numpy().astype(np.int32)) for n in halo.neigh]
         ptrs = (C.POINTER(C.c_int) * max(nn, 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in self._idx])
-        self.L.chk(lib.CeedXHaloCreate(ceed.h, C.c_int(nn), ranks, counts, ptrs, C.byref(self.h)))
+        self.L.CeedXHaloCreate(ceed.h, nn, ranks, counts, ptrs, C.byref(self.h))
 
     def start(self, y):
-        self.L.chk(self.L.lib.CeedXHaloStart(self.h, y.h))
+        self.L.CeedXHaloStart(self.h, y.h)
 
     def finish(self, y):
-        self.L.chk(self.L.lib.CeedXHaloFinish(self.h, y.h))
+        self.L.CeedXHaloFinish(self.h, y.h)
 
     def add(self, y):
         self.start(y); self.finish(y)
 
     def destroy(self):
         if self.h:
-            self.L.lib.CeedXHaloDestroy(__import__("ctypes").byref(self.h))
+            self.L.lib.CeedXHaloDestroy(C.byref(self.h))
             self.h = None
 
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -19,19 +20,19 @@ from .solid import level_degrees
 
 PROBLEM_TYPES = {"linElas": 0, "hyperSS": 1, "hyperFS": 2}
 PRODUCT_HARNESS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsolid_harness_mi355x.so")
+# include/solid_harness.h on top of the typedefs of include/ceed.h, which it includes
+PROTOTYPES = cd.header_prototypes(os.path.join(os.path.dirname(cd.HEADER), "solid_harness.h"), cd.PROTOTYPES.types)
 
 
 def _wrap_vector(ceed: cd.Ceed, handle: int, n: int) -> cd.Vector:
     v = cd.Vector.__new__(cd.Vector)
-    v.ceed, v.L, v.n, v._keep = ceed, ceed.L, n, None
-    v.h = C.c_void_p(handle)
+    v.ceed, v.L, v.n, v._keep, v.h = ceed, ceed.L, n, None, C.c_void_p(handle)
     return v
 
 
 def _wrap_operator(ceed: cd.Ceed, handle: int) -> cd.Operator:
     o = cd.Operator.__new__(cd.Operator)
-    o.ceed, o.L, o.qf, o._keep = ceed, ceed.L, None, []
-    o.h = C.c_void_p(handle)
+    o.ceed, o.L, o.qf, o._keep, o.h = ceed, ceed.L, None, [], C.c_void_p(handle)
     return o
 
 
@@ -47,7 +48,8 @@ class SolidApp:
         # the harness library NEEDs its Ceed backend; load the backend first through CeedLib so the
         # one-HIP-runtime rule of ceed.py applies
         self.ceed, self.mesh, self.problem = ceed, mesh, problem
-        self.H = C.CDLL(harness_lib, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
+        self.H = C.CDLL(harness_lib, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))     # raw, as CeedLib.lib
+        self.Hc = types.SimpleNamespace(**cd.declare(self.H, PROTOTYPES.functions, ceed.L.errcheck))      # checked twins
         self.degrees = level_degrees(degree, multigrid)
         self.fine = len(self.degrees) - 1
         self.Q = degree + 1 + qextra
@@ -71,12 +73,10 @@ class SolidApp:
         coords = np.ascontiguousarray(mesh.coords, dtype=np.float64)
         cells = np.ascontiguousarray(mesh.cells, dtype=np.int32)
         self.h = C.c_void_p()
-        rc = self.H.SolidAppCreate(ceed.h, C.c_int(PROBLEM_TYPES[problem]), C.c_double(nu), C.c_double(E),
-                                   C.c_int32(nl), degs, C.c_int32(qextra), C.c_int32(mesh.nelem), C.c_int32(mesh.nvert),
-                                   coords.ctypes.data_as(C.POINTER(C.c_double)), cells.ctypes.data_as(C.POINTER(C.c_int32)),
-                                   offs, lsz, msk, C.byref(self.h))
-        ceed.L.chk(rc)
-        # handles
+        self.Hc.SolidAppCreate(ceed.h, PROBLEM_TYPES[problem], nu, E, nl, degs, qextra, mesh.nelem, mesh.nvert,
+                               coords.ctypes.data_as(C.POINTER(C.c_double)), cells.ctypes.data_as(C.POINTER(C.c_int32)),
+                               offs, lsz, msk, C.byref(self.h))
+        # handles (the accessors report nothing: raw)
         q, g = C.c_void_p(), C.c_void_p()
         self.H.SolidAppGetVectors(self.h, C.byref(q), C.byref(g))
         nq = self.Q ** 3
@@ -85,11 +85,9 @@ class SolidApp:
         self.opJacob: List[cd.Operator] = []
         for l in range(nl):
             oj = C.c_void_p()
-            self.H.SolidAppGetLevelOperators(self.h, C.c_int32(l), C.byref(oj), None, None)
+            self.H.SolidAppGetLevelOperators(self.h, l, C.byref(oj), None, None)
             self.opJacob.append(_wrap_operator(ceed, oj.value))
-        oa = C.c_void_p()
-        self.H.SolidAppGetResidualOperator(self.h, C.byref(oa))
-        self.opApply = _wrap_operator(ceed, oa.value)
+        self.opApply = _wrap_operator(ceed, cd.out_value(self.H.SolidAppGetResidualOperator, C.c_void_p, self.h))
 
     def lsize(self, level=None) -> int:
         return self.dofmaps[self.fine if level is None else level].lsize
@@ -99,34 +97,32 @@ class SolidApp:
         return int(m.size - m.sum())
 
     def multinv(self, level) -> cd.Vector:
-        v = C.c_void_p()
-        self.H.SolidAppGetMultiplicityInverse(self.h, C.c_int32(level), C.byref(v))
-        return _wrap_vector(self.ceed, v.value, self.lsize(level))
+        return _wrap_vector(self.ceed, cd.out_value(self.H.SolidAppGetMultiplicityInverse, C.c_void_p, self.h, level), self.lsize(level))
 
     # src/matops.c
     def apply_jacobian(self, level: int, x: cd.Vector, y: cd.Vector):
-        self.ceed.L.chk(self.H.ApplyJacobian_Ceed(self.h, C.c_int32(level), x.h, y.h))
+        self.Hc.ApplyJacobian_Ceed(self.h, level, x.h, y.h)
 
     def form_residual(self, x: cd.Vector, y: cd.Vector):
-        self.ceed.L.chk(self.H.FormResidual_Ceed(self.h, x.h, y.h))
+        self.Hc.FormResidual_Ceed(self.h, x.h, y.h)
 
     def prolong(self, level: int, xc: cd.Vector, yf: cd.Vector):
-        self.ceed.L.chk(self.H.Prolong_Ceed(self.h, C.c_int32(level), xc.h, yf.h))
+        self.Hc.Prolong_Ceed(self.h, level, xc.h, yf.h)
 
     def restrict(self, level: int, xf: cd.Vector, yc: cd.Vector):
-        self.ceed.L.chk(self.H.Restrict_Ceed(self.h, C.c_int32(level), xf.h, yc.h))
+        self.Hc.Restrict_Ceed(self.h, level, xf.h, yc.h)
 
     def get_diag(self, level: int, d: cd.Vector):
-        self.ceed.L.chk(self.H.GetDiag_Ceed(self.h, C.c_int32(level), d.h))
+        self.Hc.GetDiag_Ceed(self.h, level, d.h)
 
     def set_halo(self, level: int, halo):
         """Attach the interface sum of one level (a halo.RcclHalo or a raw CeedXHalo handle; None clears): every matops
         function then ends with it, as the reference's end with DMLocalToGlobal(ADD_VALUES)."""
         h = None if halo is None else getattr(halo, "h", halo)
-        self.ceed.L.chk(self.H.SolidAppSetHalo(self.h, C.c_int32(level), h))
+        self.Hc.SolidAppSetHalo(self.h, level, h)
 
     def set_smoother_nu(self, nu: float):
-        self.ceed.L.chk(self.H.SolidAppSetSmootherNu(self.h, C.c_double(nu)))
+        self.Hc.SolidAppSetSmootherNu(self.h, nu)
 
     def destroy(self):
         if self.h:
