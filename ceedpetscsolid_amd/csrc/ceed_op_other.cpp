@@ -1,5 +1,5 @@
 // ceed_op_other.cpp -- the operator families beside the residual / Jacobian one (op_plan, ceed_operator.cpp): the transfer operators in
-// owner form, SetupGeo with the provenance it leaves on the qdata vector, and the coordinate-driven and energy operators.
+// owner form, SetupGeo with the provenance it leaves on the qdata vector, the coordinate-driven and energy operators, and stress recovery.
 #include "ceed_operator.hpp"
 
 using namespace cps;
@@ -221,6 +221,44 @@ int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   HIPCHK(launch_coord_op(op->tables, a, op->ceed->stream));
   return cold_sum_finish(op, o.rstr, a.evec, py, add,
                          a.mode == 2 ? "coord_op<MMSTrueSoln>" : (a.mode == 1 ? "coord_op<SetupMMSForce>" : "coord_op<SetupConstantForce>"));
+}
+// Stress recovery (kernels_stress.hip, k_stress; op_plan's PLAN_STRESS).  The displacement is read as it is, boundary values included: the
+// restriction's plain offsets, never an operator's flagged ones.  Points: the kernel stores every entry of [nelem][6][Q^3] and nothing else
+// (a longer vector keeps its tail; ApplyAdd is refused: nothing is summed).  Nodal: the element results of B^T (w det J {sigma, 1}) go to the
+// Ceed's scratch in the E-layout of the 7-component output restriction, whose ordered transpose sums them (cold_sum_prepare / _finish).
+int apply_stress(CeedOperator op, CeedVector in, CeedVector out, bool add) {
+  CeedQFunction qf = op->qf;
+  OpField &u = op->in[0], &o = op->out[0];
+  const bool nodal = qf->out[0].emode == CEED_EVAL_INTERP;
+  const int P = u.basis->P1d, Q = u.basis->Q1d;
+  const size_t npts = (size_t)u.rstr->nelem * Q * Q * Q;
+  if (!in || in == CEED_VECTOR_NONE || !out || out == CEED_VECTOR_NONE) return ceed_error("active vectors required");
+  if (in == out) return ceed_error("in-place operator apply is not supported");
+  if (in->length < u.rstr->lsize) return ceed_error("displacement vector too short");
+  if (nodal ? out->length < o.rstr->lsize : (size_t)out->length < 6 * npts)
+    return ceed_error("stress vector too short: %lld entries, %lld are written", (long long)out->length, (long long)(nodal ? (size_t)o.rstr->lsize : 6 * npts));
+  if (!nodal && add) return ceed_error("the stress at the points is stored, not summed: CeedOperatorApplyAdd is not provided for it");
+  CeedVector qd = op->in[op->i_qdata].vec;
+  if (!is_passive(qd)) return ceed_error("qdata needs a passive vector");
+  if ((size_t)qd->length < 10 * npts) return ceed_error("qdata vector too short");
+  StressArgs a{};
+  double *pu, *py, *pq;
+  CHK(read_phys(qf, &a.nu, &a.E));
+  lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
+  a.model = qf->kind == QF_STRESS_LINELAS ? 0 : (qf->kind == QF_STRESS_HYPERSS ? 1 : 2);
+  CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(qd, false, &pq));
+  a.offsets = u.rstr->d_offsets.get(); a.x = pu; a.qdata = pq; a.nelem = u.rstr->nelem;
+  a.out = py;
+  if (nodal) CHK(cold_sum_prepare(op, o.rstr, out, py, add, &a.out));
+  TimerScope ts(op, op->ceed->stream);
+  const char *kname = "";
+  hipError_t e = launch_stress(P, Q, nodal, op->tables, a, op->ceed->stream, &kname);
+  if (no_kernel(e, kname)) return ceed_error("no stress kernel instantiated for P=%d Q=%d", P, Q);
+  HIPCHK(e);
+  if (nodal) return cold_sum_finish(op, o.rstr, a.out, py, add, kname);
+  set_kernel_name(op, kname, false);
+  op->launches++;
+  return 0;
 }
 // Fine-side multiplicity scale of the transfer operators (matops.c:149,176); NULL clears.
 extern "C" int CeedXOperatorSetFineScale(CeedOperator op, CeedVector scale) {

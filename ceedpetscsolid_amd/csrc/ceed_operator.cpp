@@ -12,6 +12,7 @@
 //   restrict   : Identity, NONE in  -> INTERP out               (:849-854)
 //   coord / energy : forcing, MMS, strain energy, diagnostics   (:555-737)
 //   mass       : INTERP active in, NONE qdata, INTERP active out (no call site in the reference: the elastodynamic solve, dynamics.py)
+//   stress     : GRAD active in, NONE qdata -> NONE (6, at the points) or INTERP (7, summed at the nodes) (none either: postprocess.py)
 //
 // There is NO host fallback: a graph outside these families or a QFunction without a device functor (ceed_qfunction.cpp) is a loud
 // error.  The families' applies: ceed_op_fused.cpp (fused_grad, with its diagonals and the state kernel), ceed_op_other.cpp (the rest but the mass operator: ceed_op_mass.cpp).
@@ -281,6 +282,39 @@ int op_plan(CeedOperator op) {
     op->plan = PLAN_MASS;
     return 0;
   }
+  if (k == QF_STRESS_LINELAS || k == QF_STRESS_HYPERSS || k == QF_STRESS_HYPERFS) {
+    // (du GRAD(9) active, qdata NONE(10)) -> stress NONE(6) at the points (strided 6 x Q^3, collocated)
+    //                                      | stress INTERP(7) at the nodes (7 interlaced components: w det J {sigma, 1} summed per node)
+    if (qf->in.size() != 2 || qf->out.size() != 1) return unsupported("stress takes (du, qdata) -> stress");
+    const QFField &fdu = qf->in[0], &fqd = qf->in[1], &fo = qf->out[0];
+    const bool points = fo.emode == CEED_EVAL_NONE && fo.size == 6, nodal = fo.emode == CEED_EVAL_INTERP && fo.size == 7;
+    if (fdu.emode != CEED_EVAL_GRAD || fdu.size != 9 || fqd.emode != CEED_EVAL_NONE || fqd.size != 10 || !(points || nodal))
+      return unsupported("stress eval modes must be GRAD(9), NONE(10) -> NONE(6) at the points or INTERP(7) at the nodes");
+    OpField &u = op->in[0], &qd = op->in[1], &o = op->out[0];
+    if (u.vec != CEED_VECTOR_ACTIVE) return unsupported("du must be the active input of a stress operator");
+    if (o.vec != CEED_VECTOR_ACTIVE) return unsupported("stress must be the active output");
+    if (!is_disp(u)) return unsupported("displacement field");
+    const int P = u.basis->P1d, Q = u.basis->Q1d;
+    if (!nodes_fit(u)) return unsupported("restriction element size is not P^3");
+    if (!is_qdata(qd, Q) || qd.rstr->nelem != u.rstr->nelem) return unsupported("qdata must be strided 10 x Q^3");
+    if (P > Q) return unsupported("the stress kernel needs P <= Q");
+    if (points) {
+      // (a strided restriction of this backend has one layout, [elem][comp][point]: CeedElemRestrictionCreateStrided takes no other)
+      if (!is_strided(o.rstr) || o.rstr->ncomp != 6 || o.rstr->elemsize != cube(Q) || o.rstr->nelem != u.rstr->nelem)
+        return unsupported("stress at the points must be a strided 6 x Q^3 field on the displacement's elements");
+      if (o.basis != CEED_BASIS_COLLOCATED) return unsupported("stress at the points is collocated: it takes no basis");
+    } else {
+      if (!is_offsets(o.rstr) || o.rstr->ncomp != 7 || o.rstr->compstride != 1 || o.rstr->nelem != u.rstr->nelem || o.rstr->elemsize != cube(P))
+        return unsupported("nodal stress must be an offsets restriction with 7 interlaced components on the displacement's elements and nodes");
+      // (the same points: the kernel takes INTERP^T of the stress basis from the displacement basis's table, compared entry by entry)
+      if (o.basis == CEED_BASIS_COLLOCATED || o.basis->P1d != P || o.basis->Q1d != Q || o.basis->interp1d != u.basis->interp1d)
+        return unsupported("nodal stress basis must have the displacement basis's P, Q and interp table");
+    }
+    op->i_active = 0; op->i_qdata = 1; op->o_active = 0;
+    fill_tables(op->tables, u.basis);
+    op->plan = PLAN_STRESS;
+    return 0;
+  }
   return unsupported("no kernel family");
 }
 
@@ -305,6 +339,7 @@ static int op_apply_single(CeedOperator op, CeedVector in, CeedVector out, bool 
   case PLAN_ENERGY: return apply_energy(op, in, out, add);
   case PLAN_COORD: return apply_coord(op, in, out, add);
   case PLAN_MASS: return apply_mass(op, in, out, add);
+  case PLAN_STRESS: return apply_stress(op, in, out, add);
   default: return ceed_error("operator has no plan");
   }
 }

@@ -30,6 +30,7 @@ int apply_setup_geo(CeedOperator op, CeedVector in, CeedVector out);
 int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add);
+int apply_stress(CeedOperator op, CeedVector in, CeedVector out, bool add);
 // CeedOperatorLinearAssembleDiagonal of a PLAN_MASS operator (overwrites `assembled`; masked rows are zero)
 int mass_diagonal(CeedOperator op, CeedVector assembled);
 // The Dirichlet flags of the operator's mask in the row order of a transpose map, as an apply hands them to launch_assemble (*flags

@@ -12,6 +12,7 @@ static int resolve_qf(const std::string &name) {
       {"MMSTrueSoln", QF_MMS_TRUE},  {"LinElasEnergy", QF_ENERGY_LINELAS}, {"HyperSSEnergy", QF_ENERGY_HYPERSS},
       {"HyperFSEnergy", QF_ENERGY_HYPERFS}, {"LinElasDiagnostic", QF_DIAG_LINELAS}, {"HyperSSDiagnostic", QF_DIAG_HYPERSS},
       {"HyperFSDiagnostic", QF_DIAG_HYPERFS}, {"Mass", QF_MASS},
+      {"LinElasStress", QF_STRESS_LINELAS}, {"HyperSSStress", QF_STRESS_HYPERSS}, {"HyperFSStress", QF_STRESS_HYPERFS},
   };
   for (auto &t : tab) if (name == t.n) return t.k;
   return QF_NONE;

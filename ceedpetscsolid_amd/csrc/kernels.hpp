@@ -25,6 +25,9 @@ enum QFKind : int {
   QF_DIAG_HYPERFS,
   QF_HYPERFS_DF_DS,   // HyperFSdF reading the DERIVED state (F^-1, lambda ln J - mu) the residual kernel wrote beside grad u
   QF_MASS,            // v = c qdata[0] u: the mass operator of the elastodynamic solve (kernels_mass.hip)
+  QF_STRESS_LINELAS,  // the Cauchy stress the residual integrates, at the points or projected to the nodes (kernels_stress.hip)
+  QF_STRESS_HYPERSS,
+  QF_STRESS_HYPERFS,
 };
 
 constexpr int MAXN1D = 8;  // largest P or Q supported by the kernel tables
@@ -216,6 +219,19 @@ struct MassArgs {
   double coef;              // the QFunction context c, read by the host at every apply
 };
 
+// Stress recovery (kernels_stress.hip, k_stress): the Cauchy stress the residual integrates (qfunctions_device.hpp, qf_stress), six
+// components in the order xx, yy, zz, yz, xz, xy, from the displacement L-vector read AS IT IS (boundary values included, no mask).
+struct StressArgs {
+  const uint32_t *offsets;  // [nelem][P^3]; Dirichlet flags in the top bits, if any, are stripped and never honoured
+  const double *x;          // the displacement L-vector, interlaced [node][3]
+  const double *qdata;      // [nelem][10][Q^3]
+  double *out;              // points: [nelem][6][Q^3], plain coalesced stores.  nodal: the element results [nelem][7][P^3] of
+                            // B^T (w det J {sigma, 1}), the E-layout of the output restriction; launch_rstr_transpose() sums them per node
+  int nelem;
+  int model;                // 0 linElas, 1 hyperSS, 2 hyperFS: wave-uniform, read at run time
+  double nu, E, lambda, TwoMu;
+};
+
 // Each returns hipSuccess or the launch error; `name` receives a static string
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
@@ -238,6 +254,8 @@ hipError_t launch_state_at_points(int Pf, int Qc, const BasisTables &t, const St
                                   const char **name);
 // diag: `t.interp` holds the entry-wise SQUARED table; names "mass<P,Q>" / "mass_diag<P,Q>"; the pairs of CPS_DIAG_PQ (kernel_diag_sf.hpp)
 hipError_t launch_mass(int P, int Q, bool diag, const BasisTables &t, const MassArgs &a, hipStream_t s, const char **name);
+// names "stress<P=..,Q=..,points>" / "stress<P=..,Q=..,nodal>"; the pairs of CPS_DIAG_PQ
+hipError_t launch_stress(int P, int Q, bool nodal, const BasisTables &t, const StressArgs &a, hipStream_t s, const char **name);
 
 // The instantiations of one quadrature size are compiled as pencil_inst_parts(Q) objects (kernels_fused_inst.hip, -DCPS_PART=<k>): the kernels
 // with (Q - P) % parts == k -- the Q = 8 object alone took 72 s of a 90 s build.  csrc/Makefile lists the same parts.

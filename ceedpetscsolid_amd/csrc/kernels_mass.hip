@@ -18,34 +18,11 @@
 // 256 lanes EPB = 256 / TPE elements (16, 8, 4, 2, 2, 1, 1), so that no wave idles on a handful of lines; LDS per workgroup 5.1, 5.7,
 // 8.2, 6.5, 12.6, 8.7, 14.3 KB with the table.  The 1-D table (BasisTables kernarg) is staged into LDS once per workgroup.
 #include "kernel_diag_sf.hpp"      // CPS_DIAG_PQ: the one list of (P, Q) pairs
+#include "kernel_line_pass.hpp"    // MassGeom, mass_line: the packing and the in-place line pass, shared with k_stress
 
 namespace cps {
 
 enum MassMode : int { MASS_APPLY = 0, MASS_DIAG = 1 };
-
-template <int Q> struct MassGeom {
-  static constexpr int QP = Q | 1, LINES = 3 * Q * Q;
-  static constexpr int TPE = next_pow2(LINES) > 256 ? 256 : next_pow2(LINES), EPB = 256 / TPE;
-  static constexpr int NE = 3 * Q * Q * QP;      // doubles per element
-  static_assert(TPE >= LINES, "a lane per line in the fullest stage");
-  static_assert(sizeof(double) * ((size_t)EPB * NE + MAXN1D * MAXN1D) <= 64 * 1024, "static LDS");
-};
-
-// One line, in place: in[i] = s[i * stride], i < NIN;  s[o * stride] = sum_i M(o, i) in[i], o < NOUT.
-// sB is B[q][p] (Q x P row-major).  Forward (P -> Q): M(o, i) = B[o][i];  transposed (Q -> P): M(o, i) = B[i][o].
-template <int P, int Q, bool TR> CPS_DEV void mass_line(double *s, int stride, const double *sB) {
-  constexpr int NIN = TR ? Q : P, NOUT = TR ? P : Q;
-  double in[NIN];
-#pragma unroll
-  for (int i = 0; i < NIN; i++) in[i] = s[i * stride];
-#pragma unroll
-  for (int o = 0; o < NOUT; o++) {
-    double v = 0.;
-#pragma unroll
-    for (int i = 0; i < NIN; i++) v += (TR ? sB[i * P + o] : sB[o * P + i]) * in[i];
-    s[o * stride] = v;
-  }
-}
 
 template <int P, int Q, int MODE>
 __global__ __launch_bounds__(256) void k_mass(const BasisTables tab, const MassArgs a) {

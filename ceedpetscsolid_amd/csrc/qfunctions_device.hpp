@@ -363,6 +363,74 @@ CPS_DEV void qf_hyperfs_df_ds(const Phys ph, const double *dug, const double *qd
 }
 // (The reference's own evaluation order, dP = grad(du) S + F dS, is restated in oracle/oracle_qfunctions.c: Oracle_HyperFSdF.)
 
+// ---- Cauchy stress at a point (kernels_stress.hip) ------------
+// THE STRESS THE RESIDUAL INTEGRATES, from the physical gradient g[c][k] = d u_c / d x_k, as six scalars in CPS_SYM's order
+// (xx, yy, zz, yz, xz, xy).  The three functions restate what qf_linelas / qf_hyperss_f / qf_hyperfs_f form before pull_back, from
+// the same pieces; the residual functors above are not touched.
+// linElas: sigma of linElas.h:133-139 AS WRITTEN -- the shear entries are ss (1 - 2 nu) e_ij / 2 = mu e_ij with the TENSOR strain
+// e_ij, not 2 mu e_ij (the reference's quirk: that model is anisotropic, and the stress reported is the one it integrates).
+CPS_DEV void stress_linelas(const Phys ph, const double g[3][3], double sg[6]) {
+  const double nu = ph.nu;
+  const double ss = ph.E / ((1 + nu) * (1 - 2 * nu));
+  const double e00 = g[0][0], e11 = g[1][1], e22 = g[2][2];
+  const double e12 = (g[1][2] + g[2][1]) / 2., e02 = (g[0][2] + g[2][0]) / 2., e01 = (g[0][1] + g[1][0]) / 2.;
+  sg[0] = ss * ((1 - nu) * e00 + nu * e11 + nu * e22);
+  sg[1] = ss * (nu * e00 + (1 - nu) * e11 + nu * e22);
+  sg[2] = ss * (nu * e00 + nu * e11 + (1 - nu) * e22);
+  sg[3] = ss * (1 - 2 * nu) * e12 * 0.5;
+  sg[4] = ss * (1 - 2 * nu) * e02 * 0.5;
+  sg[5] = ss * (1 - 2 * nu) * e01 * 0.5;
+}
+// hyperSS: sigma = lambda log1p(tr e) I + 2 mu e, the reference's series (hyperSS.h:43-55)
+CPS_DEV void stress_hyperss(const Phys ph, const double g[3][3], double sg[6]) {
+  constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
+  double lambda, TwoMu;
+  lame(ph, lambda, TwoMu);
+  const double llv = log1p_series4(g[0][0] + g[1][1] + g[2][2]);
+#pragma unroll
+  for (int m = 0; m < 6; m++) sg[m] = TwoMu * ((g[J[m]][K[m]] + g[K[m]][J[m]]) / 2.) + (m < 3 ? lambda * llv : 0.);
+}
+// hyperFS: Cauchy stress sigma = F S F^T / det F, F = I + grad u, S the second Piola-Kirchhoff stress of fs_state (the residual's,
+// with the reference's series for ln J); det F by cofactors of F itself
+CPS_DEV void stress_hyperfs(const Phys ph, const double g[3][3], double sg[6]) {
+  constexpr int J[6] = {0, 1, 2, 1, 0, 0}, K[6] = {0, 1, 2, 2, 2, 1};
+  double lambda, mu, F[3][3], FS[3][3];
+  fs_lame(ph, lambda, mu);
+  FSState s;
+  fs_state(lambda, mu, g, s);
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) F[a][b] = g[a][b] + (a == b ? 1. : 0.);
+#pragma unroll
+  for (int a = 0; a < 3; a++)      // F S: the first Piola-Kirchhoff stress of qf_hyperfs_f
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+      double t = 0.;
+#pragma unroll
+      for (int m = 0; m < 3; m++) t += F[a][m] * CPS_SYM(s.S, m, b);
+      FS[a][b] = t;
+    }
+  const double detF = F[0][0] * (F[1][1] * F[2][2] - F[1][2] * F[2][1]) + F[0][1] * (F[1][2] * F[2][0] - F[1][0] * F[2][2]) +
+                      F[0][2] * (F[1][0] * F[2][1] - F[1][1] * F[2][0]);
+  const double rJ = 1. / detF;
+#pragma unroll
+  for (int m = 0; m < 6; m++) {
+    double t = 0.;
+#pragma unroll
+    for (int n = 0; n < 3; n++) t += FS[J[m]][n] * F[K[m]][n];
+    sg[m] = t * rJ;
+  }
+}
+// model (wave-uniform, a run-time value): 0 linElas, 1 hyperSS, 2 hyperFS.  ug, qd as in the fused kernels (the top of this file).
+CPS_DEV void qf_stress(int model, const Phys ph, const double *ug, const double *qd, double sg[6]) {
+  double g[3][3];
+  physical_grad<false>(ug, qd, g);
+  if (model == 2) stress_hyperfs(ph, g, sg);
+  else if (model == 1) stress_hyperss(ph, g, sg);
+  else stress_linelas(ph, g, sg);
+}
+
 // ---- geometry (common.h:47-101).  Jg[d*3+c] = d x_c / d xi_d ---------------
 CPS_DEV void qf_setup_geo(const double *Jg, double w, double *qd) {
   double adj[3][3];

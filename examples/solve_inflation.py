@@ -3,8 +3,10 @@
 deforming surface (NewtonPMG(pressure={996: p}); surface.py, csrc/kernels_surface.hip).
 
 Prints the Newton and Krylov iteration counts and the inner radius at mid-height.  ``--tangent none`` leaves the pressure's tangent out
-of the outer Jacobian (modified Newton): the same solution in more Newton steps.
-    python examples/solve_inflation.py [--nr 2 --nth 16 --nz 8] [--degree 2] [--pressure 0.02] [--increments 5] [--tangent full|none] [--oracle]
+of the outer Jacobian (modified Newton): the same solution in more Newton steps.  ``--stress`` adds a second line: the largest nodal
+von Mises stress with its node's coordinates, and the hoop stress at the inner and the outer wall at mid-height (postprocess.Stress)
+beside Lame's values for the applied pressure -- for orientation only: the ends are clamped and the model is finite-strain.
+    python examples/solve_inflation.py [--nr 2 --nth 16 --nz 8] [--degree 2] [--pressure 0.02] [--increments 5] [--tangent full|none] [--stress] [--oracle]
 """
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +28,7 @@ ap.add_argument("--nu", type=float, default=0.3)
 ap.add_argument("--pressure", type=float, default=0.02, help="in units of E")
 ap.add_argument("--increments", type=int, default=5)
 ap.add_argument("--tangent", choices=("full", "none"), default="full")
+ap.add_argument("--stress", action="store_true", help="report the von Mises and hoop stresses of the solution")
 ap.add_argument("--oracle", action="store_true", help="TESTS ONLY: the same solve on the CPU oracle (portable surface load)")
 args = ap.parse_args()
 if args.oracle:
@@ -47,4 +50,26 @@ print(json.dumps({"resource": c.resource, "elements": mesh.nelem, "degree": args
                   "increments": st.increments, "snes_its": st.newton_its, "ksp_its": st.ksp_its, "snes_solve_s": st.seconds,
                   "inner_radius_reference": float(np.linalg.norm(dm.node_coords[mid, :2], axis=1).mean()),
                   "inner_radius_mid_height": float(radius.mean()), "inner_radius_spread": float(radius.max() - radius.min())}))
+if args.stress:
+    from ceedpetscsolid_amd.postprocess import Stress
+    xloc = c.vector(p.lsize()).set_array(s.U.to_numpy() + s.bcv.to_numpy())      # the displacement with the boundary values inserted
+    sr = Stress(p, "hyperFS")
+    vm, node = sr.max_von_mises(xloc)
+    sig = sr.nodal(xloc)
+    pos = dm.node_coords + xloc.to_numpy().reshape(-1, 3)
+
+    def hoop(side):
+        nodes = side_set_nodes(mesh, dm, [side])
+        nodes = nodes[np.abs(dm.node_coords[nodes, 2]) < 1e-12]
+        t = np.stack([-pos[nodes, 1], pos[nodes, 0]], axis=1) / np.linalg.norm(pos[nodes, :2], axis=1)[:, None]     # e_theta at the deformed position
+        xx, yy, xy = sig[nodes, 0], sig[nodes, 1], sig[nodes, 5]
+        return float((t[:, 0] ** 2 * xx + t[:, 1] ** 2 * yy + 2 * t[:, 0] * t[:, 1] * xy).mean())
+
+    pr, a2, b2 = args.pressure * args.E, r_in ** 2, 1.0
+    lame = lambda r2: pr * a2 / (b2 - a2) * (1 + b2 / r2)
+    print(json.dumps({"stress_kernels": sr.kernel_names, "max_von_mises": vm, "max_von_mises_node": node,
+                      "max_von_mises_at": [float(v) for v in dm.node_coords[node]],
+                      "hoop_inner_wall_mid_height": hoop(996), "hoop_inner_lame": lame(a2),
+                      "hoop_outer_wall_mid_height": hoop(997), "hoop_outer_lame": lame(b2)}))
+    sr.destroy()
 sys.exit(0 if st.converged else 1)
