@@ -566,10 +566,21 @@ class Vector:
         self.L.CeedVectorCreate(ceed.h, n, C.byref(self.h))
 
     def set_array(self, arr: np.ndarray, copy=True):
-        a = _np_f64(arr)
-        assert a.size == self.n, (a.size, self.n)
+        """self := arr.  ``copy=False`` borrows ``arr`` itself (CEED_USE_POINTER: the vector's results appear in it), so it must be
+        the memory the library can use as it is -- a C-contiguous, writable float64 ndarray of the vector's size; anything else
+        would be converted into a private copy that the caller never sees, and is refused."""
         if not copy:
+            if not (isinstance(arr, np.ndarray) and arr.dtype == np.float64 and arr.flags.c_contiguous and arr.flags.writeable
+                    and arr.size == self.n):
+                raise ValueError(f"set_array(copy=False) borrows the array itself: a C-contiguous, writable float64 ndarray of {self.n} "
+                                 f"entries is needed, not {type(arr).__name__}"
+                                 + (f" {arr.dtype}{list(arr.shape)}, contiguous={arr.flags.c_contiguous}, writeable={arr.flags.writeable}"
+                                    if isinstance(arr, np.ndarray) else ""))
+            a = arr
             self._keep = a
+        else:
+            a = _np_f64(arr)
+        assert a.size == self.n, (a.size, self.n)
         self.L.CeedVectorSetArray(self.h, MEM_HOST, COPY_VALUES if copy else USE_POINTER, a.ctypes.data_as(c_scalar_p))
         return self
 

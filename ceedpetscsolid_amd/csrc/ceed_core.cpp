@@ -344,11 +344,13 @@ extern "C" int CeedVectorTakeArray(CeedVector v, CeedMemType mtype, CeedScalar *
   if (mtype == CEED_MEM_HOST) {
     if (v->h || v->d_valid) CHK(vec_sync_to(v, CEED_MEM_HOST));
     if (array) *array = v->h;
+    else if (v->h_owned) free(v->h);     // (the library's own buffer and nobody to hand it to)
     v->h = nullptr; v->h_owned = false; v->h_valid = false;
     if (!v->d_valid) vec_drop_geo(v);
   } else {
     if (v->d || v->h_valid) CHK(vec_sync_to(v, CEED_MEM_DEVICE));
     if (array) *array = v->d;
+    else if (v->d_owned && v->d) (void)hipFree(v->d);
     v->d = nullptr; v->d_owned = false; v->d_valid = false;
     vec_drop_geo(v);
   }
@@ -356,7 +358,7 @@ extern "C" int CeedVectorTakeArray(CeedVector v, CeedMemType mtype, CeedScalar *
 }
 extern "C" int CeedVectorSetValue(CeedVector v, CeedScalar value) {
   CHK(vec_need_dev(v));
-  if (value == 0.) CHK(dev_zero(v->ceed, v->d, (size_t)v->length));
+  if (value == 0. && !std::signbit(value)) CHK(dev_zero(v->ceed, v->d, (size_t)v->length));   // (-0.0 has bits of its own: the fill kernel)
   else HIPCHK(launch_set_value(v->d, (size_t)v->length, value, v->ceed->stream));
   v->d_valid = true; v->h_valid = false; vec_drop_geo(v);
   return 0;
@@ -414,12 +416,25 @@ extern "C" int CeedXVectorAXPBY(CeedVector y, double a, CeedVector x, double b) 
   HIPCHK(launch_axpby(py, a, px, b, (size_t)y->length, y->ceed->stream));
   return 0;
 }
+// The alias rule of the Chebyshev entries (include/ceed.h): the outputs x, d, r are pairwise distinct and none of them is t, dinv
+// or b (an absent vector -- NULL -- aliases nothing).
+static bool cheb_aliased(CeedVector x, CeedVector d, CeedVector r, CeedVector b, CeedVector t, CeedVector dinv) {
+  const CeedVector out[3] = {x, d, r}, in[3] = {b, t, dinv};
+  for (int i = 0; i < 3; i++) {
+    if (!out[i]) continue;
+    for (int j = 0; j < i; j++) if (out[j] == out[i]) return true;
+    for (int k = 0; k < 3; k++) if (in[k] == out[i]) return true;
+  }
+  return false;
+}
 extern "C" int CeedXVectorChebyshevUpdate(CeedVector x, CeedVector d, CeedVector r, CeedVector t, CeedVector dinv,
                                           double c1, double c2, int assign_x) {
   double *px, *pd, *pr, *pt = nullptr, *pi;
   const CeedInt n = x->length;
   if (d->length != n || r->length != n || dinv->length != n || (t && t != CEED_VECTOR_NONE && t->length != n))
     return ceed_error("CeedXVectorChebyshevUpdate: vector lengths differ");
+  if (cheb_aliased(x, d, r, nullptr, t && t != CEED_VECTOR_NONE ? t : nullptr, dinv))
+    return ceed_error("CeedXVectorChebyshevUpdate: x, d, r alias each other or an input");
   CHK(vec_dev(dinv, false, &pi));
   if (t && t != CEED_VECTOR_NONE) CHK(vec_dev(t, false, &pt));
   CHK(vec_dev(r, pt != nullptr, &pr)); CHK(vec_dev(d, true, &pd)); CHK(vec_dev(x, true, &px));
@@ -434,6 +449,8 @@ extern "C" int CeedXVectorChebyshevStart(CeedVector x, CeedVector d, CeedVector 
   if (d->length != n || r->length != n || b->length != n || dinv->length != n || (t && t != CEED_VECTOR_NONE && t->length != n))
     return ceed_error("CeedXVectorChebyshevStart: vector lengths differ");
   if (b == r || b == x || b == d) return ceed_error("CeedXVectorChebyshevStart: the right-hand side must be a vector of its own");
+  if (cheb_aliased(x, d, r, b, t && t != CEED_VECTOR_NONE ? t : nullptr, dinv))
+    return ceed_error("CeedXVectorChebyshevStart: x, d, r alias each other or an input");
   CHK(vec_dev(dinv, false, &pi)); CHK(vec_dev(b, false, &pb));
   if (t && t != CEED_VECTOR_NONE) CHK(vec_dev(t, false, &pt));
   CHK(vec_dev(r, true, &pr)); CHK(vec_dev(d, true, &pd)); CHK(vec_dev(x, true, &px));
@@ -450,6 +467,8 @@ extern "C" int CeedXVectorChebyshevStep(CeedVector x, CeedVector d, CeedVector r
   if (d->length != n || b->length != n || dinv->length != n || (has_r && r->length != n) || (has_t && t->length != n))
     return ceed_error("CeedXVectorChebyshevStep: vector lengths differ");
   if (b == x || b == d || (has_r && b == r)) return ceed_error("CeedXVectorChebyshevStep: the right-hand side must be a vector of its own");
+  if (cheb_aliased(x, d, has_r ? r : nullptr, b, has_t ? t : nullptr, dinv))
+    return ceed_error("CeedXVectorChebyshevStep: x, d, r alias each other or an input");
   CHK(vec_dev(dinv, false, &pi)); CHK(vec_dev(b, false, &pb));
   if (has_t) CHK(vec_dev(t, false, &pt));
   if (has_r) CHK(vec_dev(r, true, &pr));

@@ -120,7 +120,7 @@ CEED_EXTERN int CeedVectorCreate(Ceed ceed, CeedInt length, CeedVector *vec);
 CEED_EXTERN int CeedVectorSetArray(CeedVector vec, CeedMemType mtype,
                                    CeedCopyMode cmode, CeedScalar *array);
 CEED_EXTERN int CeedVectorTakeArray(CeedVector vec, CeedMemType mtype,
-                                    CeedScalar **array /* may be NULL */);
+                                    CeedScalar **array /* may be NULL: a buffer of the library's own is then freed */);
 CEED_EXTERN int CeedVectorSetValue(CeedVector vec, CeedScalar value);
 CEED_EXTERN int CeedVectorSyncArray(CeedVector vec, CeedMemType mtype);
 CEED_EXTERN int CeedVectorGetArray(CeedVector vec, CeedMemType mtype,
@@ -350,6 +350,11 @@ CEED_EXTERN_OPTIONAL int CeedXVectorLeapfrogStep(CeedVector x, CeedVector vh, Ce
 /* (the KSPCHEBYSHEV + PCJACOBI smoother of elasticity.c:539-552):            */
 /*   r -= t (skipped if t is NULL);  d = c1 * dinv .* r + c2 * d;             */
 /*   x = d if assign_x else x + d.                                            */
+/* ALIAS RULE of Update, Start and Step alike: the outputs x, d and r are      */
+/* pairwise distinct vectors, and none of them is t, dinv or b (an absent     */
+/* vector aliases nothing).  Anything else is refused before a vector is       */
+/* touched -- the entries work entry by entry in one pass, so an alias would   */
+/* return success with a meaningless result.                                   */
 CEED_EXTERN int CeedXVectorChebyshevUpdate(CeedVector x, CeedVector d, CeedVector r,
                                            CeedVector t /* or NULL */, CeedVector dinv,
                                            double c1, double c2, int assign_x);

@@ -241,6 +241,7 @@ int CeedVectorSetArray(CeedVector v, CeedMemType mtype, CeedCopyMode cmode,
 int CeedVectorTakeArray(CeedVector v, CeedMemType mtype, CeedScalar **array) {
   CHK(vec_host_only(mtype));
   if (array) *array = v->array;
+  else if (v->owned) free(v->array);   /* (the library's own buffer and nobody to hand it to) */
   v->array = NULL; v->owned = 0;
   return 0;
 }
@@ -1109,12 +1110,24 @@ int CeedXVectorWAXPBY(CeedVector w, double a, CeedVector x, double b, CeedVector
   for (CeedInt i = 0; i < w->length; i++) w->array[i] = a * x->array[i] + b * y->array[i];
   return 0;
 }
+/* The alias rule of the Chebyshev entries (include/ceed.h): the outputs x, d, r are pairwise distinct and none of them is t,
+   dinv or b (an absent vector -- NULL -- aliases nothing). */
+static int cheb_aliased(CeedVector x, CeedVector d, CeedVector r, CeedVector b, CeedVector t, CeedVector dinv) {
+  const CeedVector out[3] = {x, d, r}, in[3] = {b, t, dinv};
+  for (int i = 0; i < 3; i++) {
+    if (!out[i]) continue;
+    for (int j = 0; j < i; j++) if (out[j] == out[i]) return 1;
+    for (int k = 0; k < 3; k++) if (in[k] == out[i]) return 1;
+  }
+  return 0;
+}
 int CeedXVectorChebyshevStart(CeedVector x, CeedVector d, CeedVector r, CeedVector b, CeedVector t, CeedVector dinv,
                               double c1, int assign_x) {
   vec_ensure(x); vec_ensure(d); vec_ensure(r); vec_ensure(b); vec_ensure(dinv);
   const int have_t = t && t != CEED_VECTOR_NONE;
   if (have_t) vec_ensure(t);
   if (b == r || b == x || b == d) return oracle_error("CeedXVectorChebyshevStart: the right-hand side must be a vector of its own");
+  if (cheb_aliased(x, d, r, b, have_t ? t : NULL, dinv)) return oracle_error("CeedXVectorChebyshevStart: x, d, r alias each other or an input");
   for (CeedInt i = 0; i < x->length; i++) {
     double ri = b->array[i];
     if (have_t) ri -= t->array[i];
@@ -1132,6 +1145,7 @@ int CeedXVectorChebyshevStep(CeedVector x, CeedVector d, CeedVector r, CeedVecto
   if (have_t) vec_ensure(t);
   if (have_r) vec_ensure(r);
   if (b == x || b == d || (have_r && b == r)) return oracle_error("CeedXVectorChebyshevStep: the right-hand side must be a vector of its own");
+  if (cheb_aliased(x, d, have_r ? r : NULL, b, have_t ? t : NULL, dinv)) return oracle_error("CeedXVectorChebyshevStep: x, d, r alias each other or an input");
   for (CeedInt i = 0; i < x->length; i++) {
     double ri = b->array[i];
     if (have_t) ri -= t->array[i];
@@ -1148,6 +1162,7 @@ int CeedXVectorChebyshevUpdate(CeedVector x, CeedVector d, CeedVector r, CeedVec
   vec_ensure(x); vec_ensure(d); vec_ensure(r); vec_ensure(dinv);
   const int have_t = t && t != CEED_VECTOR_NONE;
   if (have_t) vec_ensure(t);
+  if (cheb_aliased(x, d, r, NULL, have_t ? t : NULL, dinv)) return oracle_error("CeedXVectorChebyshevUpdate: x, d, r alias each other or an input");
   for (CeedInt i = 0; i < x->length; i++) {
     if (have_t) r->array[i] -= t->array[i];
     const double di = c1 * dinv->array[i] * r->array[i] + (c2 == 0. ? 0. : c2 * d->array[i]);

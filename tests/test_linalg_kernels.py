@@ -1,6 +1,7 @@
 """The assembled coarse level and the Krylov vector helpers at their edge shapes: CSR-stream SpMV (CeedXCsrApply), the COO sum
 (CeedXCsrAssemble / GetDiagonal), the three Galerkin-product kernels (CeedXCsrUpdate: dense, row and generic form), the dot
-products and the elementwise helpers.  Each case is a function of the Ceed; a thin test runs it on the CPU oracle and a thin
+products, the elementwise helpers, and the rest of kernels_vector.hip -- SetValue, Reciprocal, the Chebyshev entries, ScalarDivide and
+AXPBYScalars -- bit for bit on vectors that are windows between sentinels.  Each case is a function of the Ceed; a thin test runs it on the CPU oracle and a thin
 `gpu` test on the device.  References are numpy / scipy / math.fsum in f64, and every bound is PER ENTRY, scaled by the absolute
 product and the summation depth of the kernel, so that one dropped or doubled term fails it."""
 import ctypes as C
@@ -10,16 +11,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from _vector_model import PAD, DeviceBuffer, HostBuffer, intact, same_bits   # noqa: F401  (same_bits: -0.0 is not 0.0, a NaN equals itself)
 from ceedpetscsolid_amd import ceed as cd
 
 u = 2.0 ** -53
 GRID_CAP = 2048 * 256                 # threads of the vector kernels' grid (2048-block cap): beyond it they stride
-
-
-def same_bits(a, b):
-    """Bitwise equality of two f64 arrays (-0.0 differs from 0.0, a NaN equals the same NaN)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 def csr_rows(lens, ncols, rng):
@@ -462,7 +458,297 @@ def refusal_case(ceed):
     assert abs(S.to_numpy()[1] - math.fsum(terms)) <= (n + 2) * u * math.fsum(np.abs(terms))
 
 
+# ---- the remaining vector kernels: k_set_value, k_reciprocal, k_cheb_update, k_scalar_div, k_axpby_dev ---------------------------
+# (k_masked_copy is launched by no entry point of the ABI, so there is nothing to call it through.)
+# Sizes: the wave and workgroup edges of a 256-thread block, one grid-stride pass plus one element, two passes plus a tail.
+EDGE_SIZES = [1, 63, 64, 65, 257, GRID_CAP + 1, 2 * GRID_CAP + 3]
+
+
+def on_device(ceed):
+    return "mi355x" in ceed.L.path.rsplit("/", 1)[-1]
+
+
+class Window:
+    """A vector of `ceed` that is a window into a longer allocation (a device tensor behind set_device_pointer; on the oracle a host
+    array behind set_array(copy=False)), PAD sentinel entries either side.  read() is the window as the BUFFER holds it -- the
+    library's results must be there without a further call -- and asserts that the sentinels are intact."""
+
+    def __init__(self, ceed, data):
+        data = np.asarray(data, dtype=np.float64)
+        self.ceed, self.n, self.dev = ceed, data.size, on_device(ceed)
+        self.buf = DeviceBuffer(data, "cuda") if self.dev else HostBuffer(data)
+        self.v = ceed.vector(self.n)
+        ceed.L.CeedVectorSetArray(self.v.h, cd.MEM_DEVICE if self.dev else cd.MEM_HOST, cd.USE_POINTER, self.buf.pointer())
+        self.h = self.v.h
+
+    def read(self):
+        if self.dev:
+            self.ceed.synchronize()
+        full = self.buf.read()
+        intact(full, "a window")
+        return full[PAD:PAD + self.n].copy()
+
+    def destroy(self):
+        self.v.take_array(cd.MEM_DEVICE if self.dev else cd.MEM_HOST)
+        self.v.destroy()
+
+
+def set_value_case(ceed, n):
+    """Every entry has the value's bits -- +0.0 (the memset path of the device) and -0.0 are different values."""
+    w = Window(ceed, np.full(n, 7.0))
+    for val in (0.0, -0.0, 1.5, np.nan, np.inf, 5e-324):
+        w.v.set_value(val)
+        assert same_bits(w.read(), np.full(n, val)), (n, val, w.read()[:4])
+        w.v.set_value(7.0)
+        assert same_bits(w.read(), np.full(n, 7.0))
+    w.destroy()
+
+
+PLANTED = [0.0, -0.0, 1e-300, -1e-300, np.nextafter(1e-300, 1.0), 5e-324, -5e-324, np.inf, -np.inf, np.nan, 3.0, 1e308, 1.7e308,
+           -np.nextafter(1e-300, 1.0), -1.7e308]
+
+
+def reciprocal_case(ceed, n):
+    """CeedVectorReciprocal: 1 / v where |v| > 1e-300 (the correctly rounded quotient, denormal results included), v left as it is
+    elsewhere (zeros of either sign, +-1e-300 itself, denormals, NaN).  Planted at fixed positions, the first and the last entry
+    among them; a vector too short for all of them takes them in turns."""
+    rng = np.random.default_rng(n)
+    rounds = 1 if n >= len(PLANTED) else -(-len(PLANTED) // n)
+    for k in range(rounds):
+        v = rng.uniform(-4, 4, n)
+        if n >= len(PLANTED):
+            pos = [(j * (n - 1)) // (len(PLANTED) - 1) for j in range(len(PLANTED))]       # pos[0] = 0, pos[-1] = n - 1
+            v[pos] = PLANTED
+        else:
+            part = PLANTED[k * n:(k + 1) * n]
+            v[:len(part)] = part
+            v[-1] = PLANTED[(k * n + len(part) - 1) % len(PLANTED)]
+        with np.errstate(all="ignore"):
+            exp = np.where(np.abs(v) > 1e-300, 1.0 / v, v)
+        w = Window(ceed, v)
+        w.v.reciprocal()
+        got = w.read()
+        bad = np.flatnonzero(got.view(np.int64) != exp.view(np.int64))
+        assert bad.size == 0, (n, bad[:5], v[bad[:5]], got[bad[:5]], exp[bad[:5]])
+        w.destroy()
+
+
+# -- the Chebyshev entries.  What cheb_dof_regs (kernel_node_sum.hpp) does per entry, one rounding per line:
+#      ri = rbase - t          (rbase: b in Start and Step, r in Update; without t, ri = rbase and nothing is rounded)
+#      m  = c1 * dinv
+#      di = m * ri
+#      di = fma(c2, d, di)     (only if c2 != 0: ONE rounding of c2 d + di)
+#      x  = di  or  x + di
+#    r = ri is stored by Start, by Step if r is given, by Update if t is given.
+def fma(a, b, c):
+    """The correctly rounded a b + c (CPython rounds int / int correctly, and so Fraction.__float__)."""
+    from fractions import Fraction
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def cheb_data(n):
+    """Operands for which the one-ulp bound between the fused and the unfused c2 d + di is a theorem: per entry c2 d and di have
+    the same sign (sigma), so nothing cancels.  [With p = fl(c2 d), |p - c2 d| <= ulp(c2 d) / 2 <= ulp(s) / 2 for s = c2 d + di,
+    because |c2 d| <= |s|; two reals no further apart than half the spacing of the grid round to the same or to neighbouring
+    grid points, also across a power of two.]  x is of either sign."""
+    rng = np.random.default_rng(100 + n)
+    sigma = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    return {"x": rng.uniform(-2, 2, n), "d": sigma * rng.uniform(0.1, 2, n), "r": sigma * rng.uniform(1, 2, n),
+            "b": sigma * rng.uniform(1, 2, n), "t": sigma * rng.uniform(0.01, 0.9, n), "dinv": rng.uniform(0.1, 3, n)}
+
+
+def cheb_subsample(n):
+    if n <= 4096:
+        return np.arange(n)
+    return np.unique(np.concatenate([np.arange(300), np.arange(n - 300, n), np.linspace(300, n - 301, 3496).astype(np.int64)]))
+
+
+def cheb_case(ceed, n, entry):
+    """Every combination CeedXVectorChebyshevStart / Update / Step accepts: t given or absent, r given or absent (Step), assign_x 0 or
+    1, c2 zero or not.  The vectors the formula must not read hold NaN, the vectors it must not write keep their bits."""
+    L = ceed.L
+    base, sub, dev = cheb_data(n), cheb_subsample(n), on_device(ceed)
+    c1 = 0.7
+    for has_t in (True, False):
+        for has_r in ((True, False) if entry == "Step" else (True,)):
+            for assign_x in (0, 1):
+                for c2 in ((0.0,) if entry == "Start" else (0.0, 0.45)):
+                    a = {k: v.copy() for k, v in base.items()}
+                    if assign_x:
+                        a["x"][:] = np.nan
+                    if c2 == 0.0:
+                        a["d"][:] = np.nan
+                    if entry != "Update":
+                        a["r"][:] = np.nan
+                    w = {k: Window(ceed, v) for k, v in a.items()}
+                    th, rh = (w["t"].h if has_t else None), (w["r"].h if has_r else None)
+                    if entry == "Start":
+                        L.CeedXVectorChebyshevStart(w["x"].h, w["d"].h, rh, w["b"].h, th, w["dinv"].h, c1, assign_x)
+                    elif entry == "Step":
+                        L.CeedXVectorChebyshevStep(w["x"].h, w["d"].h, rh, w["b"].h, th, w["dinv"].h, c1, c2, assign_x)
+                    else:
+                        L.CeedXVectorChebyshevUpdate(w["x"].h, w["d"].h, rh, th, w["dinv"].h, c1, c2, assign_x)
+                    got = {k: w[k].read() for k in w}
+                    what = (entry, n, has_t, has_r, assign_x, c2)
+                    rbase = a["r"] if entry == "Update" else a["b"]
+                    ri = rbase - a["t"] if has_t else rbase
+                    di = (c1 * a["dinv"]) * ri
+                    if c2 != 0.0:
+                        unfused = c2 * a["d"] + di                         # numpy rounds the product, then the sum
+                        exact = np.array([fma(c2, a["d"][i], di[i]) for i in sub])
+                        assert np.all(np.abs(got["d"] - unfused) <= np.spacing(np.abs(unfused))), what
+                        if dev:                                            # (the oracle's compiler is free to contract: not the yardstick for bits)
+                            assert same_bits(got["d"][sub], exact), what
+                    elif dev:
+                        assert same_bits(got["d"], di), what
+                    else:
+                        assert np.all(np.abs(got["d"] - di) <= np.spacing(np.abs(di))), what
+                    assert same_bits(got["x"], got["d"] if assign_x else a["x"] + got["d"]), what
+                    stored = has_r and (entry != "Update" or has_t)
+                    assert same_bits(got["r"], ri if stored else a["r"]), what
+                    for k in ("b", "t", "dinv"):
+                        assert same_bits(got[k], a[k]), (what, k)
+                    assert np.all(np.isfinite(got["d"])) and np.all(np.isfinite(got["x"])), what
+                    for o in w.values():
+                        o.destroy()
+
+
+def cheb_alias_case(ceed):
+    """The rule of include/ceed.h: the outputs x, d, r pairwise distinct and none of them t, dinv or b.  Each alias is refused and
+    the vectors are left as they were."""
+    L = ceed.L
+    n = 300
+    base = cheb_data(n)
+    w = {k: Window(ceed, v) for k, v in base.items()}
+    outs, ins = ("x", "d", "r"), ("t", "dinv", "b")
+    pairs = [(p, q) for i, p in enumerate(outs) for q in outs[:i]] + [(i, o) for i in ins for o in outs]
+    for entry in ("Start", "Update", "Step"):
+        for role, other in pairs:                                         # the vector `other` stands in `role`'s place as well
+            if entry == "Update" and role == "b":
+                continue
+            h = {k: w[k].h for k in w}
+            h[role] = w[other].h
+            with pytest.raises(cd.CeedError, match="alias|of its own"):
+                if entry == "Start":
+                    L.CeedXVectorChebyshevStart(h["x"], h["d"], h["r"], h["b"], h["t"], h["dinv"], 0.7, 0)
+                elif entry == "Step":
+                    L.CeedXVectorChebyshevStep(h["x"], h["d"], h["r"], h["b"], h["t"], h["dinv"], 0.7, 0.45, 0)
+                else:
+                    L.CeedXVectorChebyshevUpdate(h["x"], h["d"], h["r"], h["t"], h["dinv"], 0.7, 0.45, 0)
+            for k in w:
+                assert same_bits(w[k].read(), base[k]), (entry, role, other, k)
+    # absent vectors alias nothing
+    L.CeedXVectorChebyshevStep(w["x"].h, w["d"].h, None, w["b"].h, None, w["dinv"].h, 0.7, 0.45, 0)
+    L.CeedXVectorChebyshevUpdate(w["x"].h, w["d"].h, w["r"].h, None, w["dinv"].h, 0.7, 0.45, 0)
+    for o in w.values():
+        o.destroy()
+
+
+def scalar_divide_case(ceed):
+    """k_scalar_div: s[dst] = (scale * s[num]) / s[den] -- the product rounded, then the quotient rounded; den < 0: scale * s[num],
+    one rounding; a denominator that is not > 0 (0.0, negative, NaN) gives +0.0.  dst may be num or den.  No other slot is written."""
+    L = ceed.L
+    scale, num = -2.3, 0.7310585786300049
+    for den, dst in [(None, 5), (3.3, 5), (0.0, 5), (-0.0, 5), (-2.0, 5), (np.nan, 5), (5e-324, 5), (np.inf, 5),
+                     (None, 1), (3.3, 1), (3.3, 2), (0.0, 2), (np.nan, 1)]:            # slot 1 holds num, slot 2 den
+        s = np.full(8, np.nan)
+        s[1] = num
+        if den is not None:
+            s[2] = den
+        w = Window(ceed, s)
+        L.CeedXScalarDivide(w.h, dst, 1, 2 if den is not None else -1, scale)
+        with np.errstate(all="ignore"):
+            exp = np.float64(scale * num) if den is None else (np.float64(scale * num) / np.float64(den) if den > 0.0 else 0.0)
+        got = w.read()
+        assert same_bits(got[dst], exp), (den, dst, got[dst], exp)
+        s[dst] = exp
+        assert same_bits(got, s), (den, dst, got)
+        w.destroy()
+    w = Window(ceed, np.arange(8.0))
+    for dst, nm, dn in ((-1, 1, 2), (8, 1, 2), (3, -1, 2), (3, 8, 2), (3, 1, 8)):
+        with pytest.raises(cd.CeedError, match="out of range"):
+            L.CeedXScalarDivide(w.h, dst, nm, dn, 1.0)
+        assert same_bits(w.read(), np.arange(8.0))
+    w.destroy()
+
+
+def fma_everywhere(got, a, x, c):
+    """got_i == fma(a, x_i, c_i) bit for bit on EVERY entry.  Vectorised: a x_i = p + e exactly (two_prod), p + c_i = s + t exactly
+    (two-sum), and s + fl(t + e) is the fused value unless the two roundings of the tail meet a tie; an entry where it differs from
+    `got` is decided by the exact `fma` -- up to 64 of them, more than that is a kernel that does not compute this."""
+    p, e = two_prod(np.full_like(x, a), x)
+    s = p + c
+    bb = s - p
+    t = (p - (s - bb)) + (c - bb)
+    differ = np.flatnonzero((s + (t + e)).view(np.int64) != got.view(np.int64))
+    return differ.size <= 64 and all(same_bits(got[i], fma(a, x[i], c[i])) for i in differ)
+
+
+def axpby_scalars_case(ceed, n):
+    """k_axpby_dev: a = sa * s[ia] and b = sb * s[ib], each rounded once (a negative index: the factor 1, so a = sa, b = sb), then
+    y = a x + b y per entry, compared on EVERY entry, bit for bit.  The compiler may contract that sum; the correct evaluations are
+    the unfused fl(fl(a x) + fl(b y)), fma(a, x, fl(b y)) and fma(b, y, fl(a x)).  The device build is pinned to the one it is
+    compiled to -- v_mul_f64 of b y, then v_fmac_f64 with a and x in the kernel's loop, and the form the MI355X matched: fma(a, x,
+    fl(b y)) -- so that a change of contraction is noticed; the oracle's compiler is free to choose, and one form gives all of its
+    entries.  Besides, every entry lies within 2 u (|a x| + |b y|) of the exact a x + b y."""
+    L = ceed.L
+    rng = np.random.default_rng(n + 11)
+    x, y0 = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n)
+    s = np.full(6, np.nan)
+    s[1], s[4] = 1.7320508075688772, -0.5772156649015329
+    X, S = Window(ceed, x), Window(ceed, s)
+    for ia, ib in ((1, 4), (-1, 4), (1, -1), (-1, -3), (4, 4)):
+        sa, sb = 0.7, -1.3
+        a, b = sa * (1.0 if ia < 0 else s[ia]), sb * (1.0 if ib < 0 else s[ib])
+        Y = Window(ceed, y0)
+        L.CeedXVectorAXPBYScalars(Y.h, S.h, ia, sa, X.h, ib, sb)
+        got = Y.read()
+        assert np.all(np.abs(axpby_error(got, a, x, b, y0)) <= 2 * u * (np.abs(a * x) + np.abs(b * y0))), (n, ia, ib)
+        if on_device(ceed):
+            assert fma_everywhere(got, a, x, b * y0), (n, ia, ib)
+        else:
+            assert same_bits(got, a * x + b * y0) or fma_everywhere(got, a, x, b * y0) or fma_everywhere(got, b, y0, a * x), (n, ia, ib)
+        assert same_bits(X.read(), x) and same_bits(S.read(), s)
+        Y.destroy()
+    Y = Window(ceed, y0)
+    for args in ((Y.h, S.h, 6, 1.0, X.h, 1, 1.0), (Y.h, S.h, 1, 1.0, X.h, 6, 1.0), (Y.h, S.h, 1, 1.0, Y.h, 4, 1.0)):
+        with pytest.raises(cd.CeedError):
+            L.CeedXVectorAXPBYScalars(*args)
+        assert same_bits(Y.read(), y0)
+    for o in (X, Y, S):
+        o.destroy()
+
+
 # ---- on the oracle --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_set_value_on_oracle(oracle, n):
+    set_value_case(oracle, n)
+
+
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_reciprocal_on_oracle(oracle, n):
+    reciprocal_case(oracle, n)
+
+
+@pytest.mark.parametrize("entry", ["Start", "Update", "Step"])
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_chebyshev_entries_on_oracle(oracle, n, entry):
+    cheb_case(oracle, n, entry)
+
+
+def test_chebyshev_aliases_refused_on_oracle(oracle):
+    cheb_alias_case(oracle)
+
+
+def test_scalar_divide_on_oracle(oracle):
+    scalar_divide_case(oracle)
+
+
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_axpby_scalars_on_oracle(oracle, n):
+    axpby_scalars_case(oracle, n)
+
+
 @pytest.mark.parametrize("name", list(SPMV))
 def test_spmv_shapes_on_oracle(oracle, name):
     spmv_case(oracle, name)
@@ -562,3 +848,38 @@ def test_elementwise_helpers_on_device(gpu, n):
 @pytest.mark.gpu
 def test_short_operands_refused_on_device(gpu):
     refusal_case(gpu)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_set_value_on_device(gpu, n):
+    set_value_case(gpu, n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_reciprocal_on_device(gpu, n):
+    reciprocal_case(gpu, n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["Start", "Update", "Step"])
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_chebyshev_entries_on_device(gpu, n, entry):
+    cheb_case(gpu, n, entry)
+
+
+@pytest.mark.gpu
+def test_chebyshev_aliases_refused_on_device(gpu):
+    cheb_alias_case(gpu)
+
+
+@pytest.mark.gpu
+def test_scalar_divide_on_device(gpu):
+    scalar_divide_case(gpu)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_axpby_scalars_on_device(gpu, n):
+    axpby_scalars_case(gpu, n)
