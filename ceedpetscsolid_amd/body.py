@@ -1,7 +1,8 @@
 """A body and its loads: what the quasi-static solve (solver.NewtonPMG) and the implicit and explicit time steppers (dynamics.py) share,
 and nothing of how a system is solved.  ``LoadedBody`` holds the problem, its element partition over several ranks (halo.py: interface
-sums, owner-weighted dots), the boundary values (src/boundary.c), the load vector, the follower pressures (surface.py), the static
-residual and the tangent apply ``A`` in its plain form.  It owns every vector made through ``_vec`` and its surface loads: ``destroy()``
+sums, owner-weighted dots), the boundary values (src/boundary.c), the load vector, the follower pressures (surface.py), the contact
+surfaces with their stored state (contact.py), the static
+residual and the tangent apply ``A`` in its plain form.  It owns every vector made through ``_vec``, its surface loads and its contact surfaces: ``destroy()``
 releases them, and what it was handed (the problem, the halos, a caller's RcclHalo list) stays the caller's."""
 from __future__ import annotations
 
@@ -54,7 +55,8 @@ class SolveStats:
 class LoadedBody:
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None, halo=None,
                  rccl="auto", traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None,
-                 pressure_tangent: str = "full", verbose: bool = False):
+                 pressure_tangent: str = "full", verbose: bool = False, contact: Optional[Dict[int, dict]] = None,
+                 contact_tangent: str = "levels"):
         """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
         set but absent here are held at zero.
@@ -67,7 +69,13 @@ class LoadedBody:
         with it a V-cycle, its smoothers, diagonals and eigenvalue estimates, do not see it); "none" omits it (modified Newton).
         T(u) is symmetric only on the variations that vanish on the rim of the loaded surface: a closed surface, or
         a patch whose rim is clamped (a tube with clamped ends).  A CG iteration assumes a symmetric operator; a follower pressure on a
-        patch with a free rim is the caller's responsibility, as with any non-conservative load."""
+        patch with a free rim is the caller's responsibility, as with any non-conservative load.
+        ``contact``: {side_set_id: dict(plane=(x0, n) | sphere=(c, R, s), penalty=eps, travel=(0, 0, 0))} -- frictionless penalty
+        contact of the side set with a rigid obstacle (contact.py: g > 0 separated, n the unit normal from the obstacle to the body,
+        s = +1 a ball, -1 a cavity, eps per unit reference area).  The contact term is NOT scaled by the load fraction; only the
+        obstacle moves with it: x0 or c at load l is x0 + l travel.  Every residual adds r(u) and refreshes the contact state, which the
+        tangent reads: ``contact_tangent`` "levels" (solver.NewtonPMG: C in every matrix-free level's operator and diagonal) or "outer"
+        (C in ``A_outer`` only, the follower pressure's form).  One rank, and never on a clamped side set."""
         self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
         self.verbose = verbose
         self.nlev = len(prob.levels)
@@ -82,6 +90,8 @@ class LoadedBody:
             # partial face sums at the interface nodes would need the exchange between the add and its consumer
             self._refuse_several_ranks(halo, "surface loads (traction=, pressure=) are",
                                        "the face sums of the interface nodes are not summed over the ranks")
+        if contact:
+            self._refuse_several_ranks(halo, "contact surfaces (contact=) are", "the face sums of the interface nodes are not summed over the ranks")
         if many and single and self.nlev > 1:
             raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
         if many and len(halo) != self.nlev:
@@ -124,6 +134,7 @@ class LoadedBody:
         self.stats = SolveStats()
         self._bc_nodes = self._collect_bc_nodes()
         self._setup_surface_loads(traction, pressure, pressure_tangent)
+        self._setup_contact(contact, contact_tangent)
 
     # ---- several ranks ------------------------------------------------------------------------
     @staticmethod
@@ -176,6 +187,72 @@ class LoadedBody:
             self.pressure_loads.append((sl, float(pval)))
             self.surface_loads.append(sl)
 
+    # ---- contact with a rigid obstacle (contact.py) -------------------------------------------
+    def _setup_contact(self, contact, contact_tangent):
+        """With no contact given nothing here runs beyond the argument check, and no solve takes a new path."""
+        if contact_tangent not in ("levels", "outer"):
+            raise ValueError(f"contact_tangent must be 'levels' or 'outer', not {contact_tangent!r}")
+        self.contact_tangent = contact_tangent
+        self.contacts = []          # per side set: dict(sid, kind, at, rest, travel, penalty, state, levels={level: ContactSurface})
+        if not contact:
+            return
+        from .contact import ContactSurface, obstacle_parameters
+        from .mesh import side_set_nodes
+        prob, top = self.p, self.nlev - 1
+        lv = prob.levels[prob.fine]
+        for sid, spec in contact.items():
+            if sid not in prob.mesh.side_sets:
+                raise ValueError(f"contact on side set {sid}: the mesh has no such side set")
+            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
+            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
+                raise ValueError(f"contact on side set {sid}, which is one of the problem's Dirichlet side sets")
+            unknown = set(spec) - {"plane", "sphere", "penalty", "travel"}
+            if unknown or "penalty" not in spec:
+                raise ValueError(f"contact on side set {sid}: dict(plane=(x0, n) | sphere=(c, R, s), penalty=eps, travel=(0, 0, 0)) expected")
+            obstacle_parameters(spec.get("plane"), spec.get("sphere"))          # (refuses what the library would)
+            if not float(spec["penalty"]) > 0.0:
+                raise ValueError(f"contact on side set {sid}: the penalty {float(spec['penalty']):g} is not positive")
+            travel = np.asarray(spec.get("travel", (0.0, 0.0, 0.0)), dtype=np.float64).reshape(-1)
+            if travel.size != 3:
+                raise ValueError(f"contact on side set {sid}: travel has three components")
+            kind = "plane" if spec.get("plane") is not None else "sphere"
+            at, rest = np.asarray(spec[kind][0], dtype=np.float64).reshape(3), tuple(spec[kind][1:])
+            fine = ContactSurface(self.ceed, prob.mesh, lv.dofmap, [sid], prob.Q, mask=lv.mask)
+            self.contacts.append(dict(sid=sid, kind=kind, at=at, rest=rest, travel=travel, penalty=float(spec["penalty"]),
+                                      state=fine.new_state(), levels={top: fine}, placed=None))
+
+    def _place_obstacles(self):
+        """The obstacles at the current load fraction: x0 + load travel."""
+        for c in self.contacts:
+            if c["placed"] != self.load:
+                c["levels"][self.nlev - 1].set_obstacle(penalty=c["penalty"], **{c["kind"]: (c["at"] + self.load * c["travel"],) + c["rest"]})
+                c["placed"] = self.load
+
+    def contact_tangent_add(self, lv, x, y):
+        """y += sum_s C_s x with level lv's tables on the state of the last residual evaluation."""
+        for c in self.contacts:
+            c["levels"][lv].tangent_add(1.0, c["state"], x, y)
+
+    def _contact_gaps(self) -> np.ndarray:
+        return np.concatenate([c["levels"][self.nlev - 1]._gaps(c["state"]).reshape(-1) for c in self.contacts]) if self.contacts else np.zeros(0)
+
+    def min_gap(self) -> float:
+        """The smallest gap over all contact points at the last residual evaluation (negative: the largest penetration)."""
+        g = self._contact_gaps()
+        return float(g.min()) if g.size else float("inf")
+
+    def active_fraction(self) -> float:
+        """The share of the contact points in contact (g < 0) at the last residual evaluation."""
+        g = self._contact_gaps()
+        return float((g < 0.0).mean()) if g.size else 0.0
+
+    def destroy_contacts(self):
+        for c in self.contacts:
+            for cs in c["levels"].values():
+                cs.destroy()
+            c["state"].destroy()
+        self.contacts = []
+
     def destroy_surface_loads(self):
         for sl in self.surface_loads:
             sl.destroy()
@@ -185,6 +262,7 @@ class LoadedBody:
         """Release what this object made: its vectors, its surface loads and the RcclHalos of rccl="auto".  Idempotent; a subclass
         releases its own first and ends with super().destroy()."""
         self.destroy_surface_loads()
+        self.destroy_contacts()
         for o in self._vectors + self._own_rhalos:
             o.destroy()
         self._vectors, self._own_rhalos, self._x0 = [], [], {}
@@ -265,13 +343,16 @@ class LoadedBody:
         self._halo_sum(lv, y)
 
     def A_outer(self, lv, x, y):
-        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x, u the state of the last
+        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x (and, with
+        contact_tangent="outer", the contact tangent sum_s C_s x), u the state of the last
         residual evaluation (Xloc: free part + boundary values).  Masked entries of x read as zero and masked rows are not written,
         as in the volume operator."""
         self.A(lv, x, y)
         if self.pressure_tangent == "full":
             for sl, pval in self.pressure_loads:
                 sl.tangent_add(pval, self.load, self.Xloc, x, y)
+        if self.contacts and self.contact_tangent == "outer":
+            self.contact_tangent_add(lv, x, y)
 
     def _collect_bc_nodes(self):
         from .mesh import side_set_nodes
@@ -300,4 +381,8 @@ class LoadedBody:
             self.axpby(R, -self.load, self.fv, 1.0)
         for sl, pval in self.pressure_loads:           # follower pressure on the current surface (constrained rows are not written)
             sl.pressure_add(pval, self.load, self.Xloc, R)
+        if self.contacts:                              # contact is not scaled by the load: only the obstacle travels with it
+            self._place_obstacles()
+            for c in self.contacts:
+                c["levels"][self.nlev - 1].residual_add(1.0, self.Xloc, R, c["state"])
         self.stats.residual_evals += 1

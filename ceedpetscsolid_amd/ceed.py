@@ -11,7 +11,7 @@ of the reference's ``src/setuplibceed.c`` / ``src/matops.c``.
 Raw pointers only cross the boundary: numpy arrays on the host side, integer
 device addresses (e.g. ``torch.Tensor.data_ptr()``) on the device side.
 
-The prototypes are read out of ``include/ceed.h`` at import (``header_prototypes``) and declared on every library loaded, so a call
+The prototypes are read out of ``include/ceed.h`` (and ``include/ceed_contact.h``, the contact entry points) at import (``header_prototypes``) and declared on every library loaded, so a call
 with an argument missing or of the wrong kind is a Python exception before anything reaches C.  ``L.lib.CeedName(...)`` is the raw call:
 it returns the library's code and raises nothing (a code that is inspected, the destroy paths).  ``L.CeedName(...)`` is its checked
 twin: same prototype, ``CeedError`` with the library's message on a non-zero code; an optional entry point the library lacks has no
@@ -123,6 +123,9 @@ def declare(cdll, functions: dict, chk) -> dict:
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ceed.h")
 PROTOTYPES = header_prototypes(HEADER)
+# include/ceed_contact.h (CeedXContact*, all optional) on top of the typedefs of include/ceed.h, which it includes
+CONTACT_HEADER = os.path.join(os.path.dirname(HEADER), "ceed_contact.h")
+CONTACT_PROTOTYPES = header_prototypes(CONTACT_HEADER, PROTOTYPES.types)
 
 
 class CeedLib:
@@ -133,6 +136,7 @@ class CeedLib:
     FUNCTIONS = [n for n, p in PROTOTYPES.functions.items() if not p.optional]
     OPTIONAL = [n for n, p in PROTOTYPES.functions.items() if p.optional]
     DATA = list(PROTOTYPES.data)
+    CONTACT = list(CONTACT_PROTOTYPES.functions)       # include/ceed_contact.h: optional like OPTIONAL, declared and checked the same way
 
     def __init__(self, path: str = PRODUCT_LIB):
         if not os.path.exists(path):
@@ -155,6 +159,7 @@ class CeedLib:
                 chk(rc)
         self.errcheck = errcheck
         vars(self).update(declare(L, PROTOTYPES.functions, errcheck))      # instance attributes: nothing between a call and its function
+        vars(self).update(declare(L, CONTACT_PROTOTYPES.functions, errcheck))
         L.CeedXSetErrorReturn(1)
         for s in ("VECTOR_ACTIVE", "VECTOR_NONE", "ELEMRESTRICTION_NONE", "BASIS_COLLOCATED", "QFUNCTION_NONE", "REQUEST_IMMEDIATE"):
             setattr(self, s, C.c_void_p.in_dll(L, "CEED_" + s).value)          # the sentinels: addresses, as integers
@@ -171,7 +176,7 @@ class CeedLib:
     def missing_symbols(self, optional: bool = True):
         """Declared symbols this library lacks.  ``optional=False`` leaves the CEED_EXTERN_OPTIONAL ones out: what another backend of
         the ABI must export; the product library exports all of them (build() checks with the default)."""
-        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL if optional else [])
+        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL + self.CONTACT if optional else [])
         return [s for s in want if not hasattr(self.lib, s)]
 
 
@@ -423,6 +428,50 @@ class SurfaceLoadHandle:
     def destroy(self):
         if self.h:
             self.L.lib.CeedXSurfaceLoadDestroy(C.byref(self.h))
+            self.h = None
+
+
+CONTACT_PLANE, CONTACT_SPHERE = 0, 1
+CONTACT_NSTATE = 7                  # per point: K (xx, yy, zz, yz, xz, xy), then the gap
+
+
+class ContactHandle:
+    """CeedXContact* (include/ceed_contact.h): penalty contact of a list of element faces with a rigid plane or sphere, on the device.
+    Optional: only where the library has ``CeedXContactCreate``; contact.py's ContactSurface takes its portable NumPy form otherwise."""
+
+    def __init__(self, ceed: "Ceed", P: int, Q: int, offsets, lsize: int):
+        self.L, self._ceed = ceed.L, ceed
+        if not self.L.has("CeedXContactCreate"):
+            raise CeedError(f"{self.L.path} has no CeedXContactCreate: use the portable form (contact.ContactSurface)")
+        self.h = C.c_void_p()
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, P * P)
+        self.nface = off.shape[0]
+        self.L.CeedXContactCreate(ceed.h, self.nface, P, Q, off.ctypes.data_as(c_int_p), lsize, C.byref(self.h))
+
+    def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
+        _, p, n = Operator._bytes(mask)
+        self.L.CeedXContactSetDirichletMask(self.h, MEM_HOST, p, n)
+
+    def set_obstacle(self, kind: int, params, penalty: float):
+        par = [float(v) for v in params]
+        self.L.CeedXContactSetObstacle(self.h, int(kind), (C.c_double * 8)(*(par + [0.0] * (8 - len(par)))), penalty)
+
+    def apply_residual_add(self, scale: float, X: "Vector", u: "Vector", y: "Vector", state: "Vector"):   # y += scale r(u); state := state(u)
+        self.L.CeedXContactApplyResidualAdd(self.h, scale, X.h, u.h, y.h, state.h)
+
+    def apply_tangent_add(self, scale: float, state: "Vector", du: "Vector", y: "Vector"):                 # y += scale C du
+        self.L.CeedXContactApplyTangentAdd(self.h, scale, state.h, du.h, y.h)
+
+    def diagonal_add(self, scale: float, state: "Vector", d: "Vector"):                                    # d += scale diag C
+        self.L.CeedXContactDiagonalAdd(self.h, scale, state.h, d.h)
+
+    @property
+    def kernel_name(self) -> str:
+        return (out_value(self.L.CeedXContactGetKernelName, C.c_char_p, self.h) or b"").decode()
+
+    def destroy(self):
+        if self.h:
+            self.L.lib.CeedXContactDestroy(C.byref(self.h))
             self.h = None
 
 

@@ -335,6 +335,31 @@ bool surface_instantiated(int P, int Q);
 // transpose map; components flagged in `flags` (a byte per row, may be null) are skipped, rows off the faces are never touched
 hipError_t launch_surface_sum(const NodeMap &m, const unsigned char *flags, const double *evec, double *y, hipStream_t s);
 
+// Frictionless penalty contact of element faces with a rigid obstacle (kernels_contact.hip, k_contact): g(x) the signed distance to the
+// obstacle (g > 0: separated), n = grad g, x = X + u, J = |X_xi x X_eta|, eps the penalty per unit REFERENCE area.  Per face
+//   residual  r_a      = -sum_q N_a(q) w_q J_q eps <-g> n                             and the state K_q, g per point (below)
+//   tangent   C du |_a =  sum_q N_a(q) K_q du(q),   K_q = w_q J_q eps [H(-g) n (x) n - <-g> grad grad g]
+//   diagonal  d_{a,c}  =  sum_q N_a(q)^2 K_q[c][c]                                    (the tables come entry-wise squared)
+// in a face E-vector [face][P^2][3] that launch_surface_sum() adds into y.  The tangent and the diagonal read the state alone.
+enum ContactMode : int { CONTACT_RESIDUAL = 0, CONTACT_TANGENT = 1, CONTACT_DIAGONAL = 2 };
+enum ContactObstacle : int { CONTACT_PLANE = 0, CONTACT_SPHERE = 1 };
+constexpr int CONTACT_NSTATE = 7;   // K_q as (xx, yy, zz, yz, xz, xy), then the gap g
+struct ContactArgs {
+  const uint32_t *offsets;  // [nface][P^2] component-0 L-offsets, the Dirichlet flags of their nodes in the top bits
+  const double *X;          // residual: node coordinates, an L-vector interlaced [node][3]
+  const double *u;          // residual: displacement, read as it is (boundary values)
+  const double *du;         // tangent: the variation; flagged components read as zero
+  double *state;            // [nface][7][Q^2]: written by the residual, read by the tangent and the diagonal
+  double *evec;             // face results [face][P^2][3], plain coalesced stores
+  int nface, kind;          // kind: ContactObstacle, uniform over the launch (residual)
+  double par[8];            // plane: x0[3], n[3] (unit, from the obstacle to the body); sphere: c[3], R, s = +1 (ball) / -1 (cavity)
+  double penalty, scale;    // eps (residual: it is inside the stored K_q); the caller's factor on the face results (never on the state)
+};
+// hipErrorInvalidValue with *name left empty when (P, Q) is not instantiated: the pairs of CPS_DIAG_PQ (P = 2 .. 8, Q = P .. 8);
+// names "contact<P=..,Q=..,residual|tangent|diagonal>".  `t.interp` of the diagonal holds the entry-wise SQUARED table.
+hipError_t launch_contact(int P, int Q, int mode, const BasisTables &t, const ContactArgs &a, hipStream_t s, const char **name);
+bool contact_instantiated(int P, int Q);
+
 // Coordinate-driven set-up operators (kernels_coord.hip): opSetupForce and opTrue of setuplibceed.c:555-623.  The 1-D tables of the output
 // (displacement) basis come by value (BasisTables, forcing only); the element results go to `evec` in the E-layout [elem][3][Pout^3] of the
 // output restriction, whose transpose (launch_rstr_transpose) sums them into the L-vector.

@@ -49,10 +49,18 @@ from .solid import SolidProblem
 from .solver import NewtonPMG, SolveStats
 
 
+def _refuse_contact(kw):
+    """Contact (body.LoadedBody, contact=) covers static solves only: the mass term of the coarse levels and stable_dt know nothing of
+    the penalty."""
+    if kw.get("contact"):
+        raise ValueError("contact= is not provided for dynamics (static solves only: stable_dt knows nothing of the penalty)")
+
+
 class NewmarkPMG(NewtonPMG):
     def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, fused_mass=False, **kw):
         if not (density > 0.0 and dt > 0.0 and beta > 0.0):
             raise ValueError("density, dt and beta must be positive")
+        _refuse_contact(kw)
         if not (fused_mass is True or fused_mass is False or fused_mass == "auto"):
             raise ValueError(f"fused_mass must be False, True or 'auto', not {fused_mass!r}")
         if kw.get("smoother", "jacobi") == "pbjacobi":
@@ -255,6 +263,7 @@ class ExplicitDynamics(LoadedBody):
     def __init__(self, prob: SolidProblem, density: float, dt: Optional[float] = None, damping: float = 0.0, safety: float = 0.9, **kw):
         if not (density > 0.0 and (dt is None or dt > 0.0)):
             raise ValueError("density and dt must be positive")
+        _refuse_contact(kw)
         if not damping >= 0.0:
             raise ValueError("damping (the mass-proportional coefficient alpha) must not be negative")
         if not 0.0 < safety <= 1.0:

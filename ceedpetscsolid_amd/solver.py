@@ -44,10 +44,18 @@ class NewtonPMG(LoadedBody):
                  amg_smooth_its: int = 3, amg_smooth_ratio: float = 10.0, amg_max_coarse_dofs: int = 1500, amg_coarse_cycles: int = 1,
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
                  line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi",
-                 traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full"):
-        """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent``): body.LoadedBody.  Of a
-        follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner is
-        the volume operator's."""
+                 traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full",
+                 contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels"):
+        """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact``): body.LoadedBody.
+        Of a follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner
+        is the volume operator's.
+        ``contact_tangent``: "levels" (default) adds the contact tangent C to the operator ``A`` and to the diagonal of EVERY
+        matrix-free level -- one contact.ContactSurface per level with that level's dofmap and mask and the fine Q, all reading the
+        state the fine residual stored, so a coarse level's term is the Galerkin product of the fine one -- and switches the fused
+        consumers off on those levels (the term is added between the apply and its consumer).  "outer" adds it in ``A_outer`` only,
+        the follower pressure's form: the preconditioner then knows nothing of the contact.  With coarse="assembled" or "amg" the
+        assembled level-0 matrix does NOT carry the contact term (the matrix-free levels above it do).  smoother="pbjacobi" with
+        contact is refused: the nodal blocks would lack the term."""
         # smoother: what the Chebyshev iteration of every p-multigrid level, its eigenvalue estimate and the Jacobi-preconditioned
         # coarse CG are preconditioned with -- "jacobi" (default, the reference: PCJACOBI on GetDiag_Ceed) or "pbjacobi": the inverted
         # 3 x 3 nodal blocks (PCPBJACOBI on CeedOperatorLinearAssemblePointBlockDiagonal), which keep the coupling between the
@@ -58,13 +66,15 @@ class NewtonPMG(LoadedBody):
             raise ValueError(f"smoother must be 'jacobi' or 'pbjacobi', not {smoother!r}")
         if smoother == "pbjacobi":
             self._refuse_several_ranks(halo, "smoother='pbjacobi' is", "the nodal blocks of the interface nodes are not summed over the ranks")
+        if smoother == "pbjacobi" and contact:
+            raise ValueError("smoother='pbjacobi' with contact= is not provided: the nodal blocks would lack the contact term")
         if line_search not in ("cp", "cp-petsc", "full"):           # (_line_search)
             raise ValueError(f"line_search {line_search!r}")
         recordable = coarse in ("chebyshev", "assembled", "amg")
         if graph != "auto" and graph and not recordable:
             raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
         super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
-                         pressure_tangent=pressure_tangent, verbose=verbose)
+                         pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent)
         self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
@@ -113,6 +123,16 @@ class NewtonPMG(LoadedBody):
                                           smooth_its=amg_smooth_its, smooth_ratio=amg_smooth_ratio, coarse_cycles=amg_coarse_cycles,
                                           dist_halo=self.halos[0] if self.halos else None)
         self._pc_graph, self._pc_graph_io, self._pc_graph_counts, self._pc_warm = None, None, (0, 0), False
+        # contact_tangent="levels": the levels whose operator carries the contact tangent, and their surfaces (body.destroy_contacts
+        # releases them with the fine one)
+        self._contact_levels = set()
+        if self.contacts and contact_tangent == "levels":
+            from .contact import ContactSurface
+            self._contact_levels = {lv for lv in range(self.nlev) if not (lv == 0 and self.asm is not None)}
+            for c in self.contacts:
+                for lv in self._contact_levels - set(c["levels"]):
+                    level = prob.levels[lv]
+                    c["levels"][lv] = ContactSurface(self.ceed, prob.mesh, level.dofmap, [c["sid"]], prob.Q, mask=level.mask)
         self.ksp_rtol, self.snes_rtol, self.snes_maxit = ksp_rtol, snes_rtol, snes_maxit
         self.w = [{k: self._vec(prob.lsize(lv), lv) for k in ("x", "b", "r", "d", "t", "dinv", "z")} for lv in range(self.nlev)]
         if self._pb:
@@ -155,10 +175,13 @@ class NewtonPMG(LoadedBody):
             self.stats.jacobian_applies += 1
         else:
             super().A(lv, x, y)
+        if lv in self._contact_levels:
+            self.contact_tangent_add(lv, x, y)
 
     def _fused_op(self, lv):
-        """The level's Jacobian operator if its consumers may be fused behind it: matrix-free level, no interface sum."""
-        if not self.fuse_epilogue or self.halos or self.rhalos or (lv == 0 and self.asm is not None):
+        """The level's Jacobian operator if its consumers may be fused behind it: matrix-free level, no interface sum, no contact term
+        (which is added between the apply and its consumer)."""
+        if not self.fuse_epilogue or self.halos or self.rhalos or (lv == 0 and self.asm is not None) or lv in self._contact_levels:
             return None
         return self.p.levels[lv].opJacob
 
@@ -205,6 +228,9 @@ class NewtonPMG(LoadedBody):
     def _get_diag(self, lv, d):
         """The diagonal of level lv's operator (a subclass with more terms in its operator adds theirs)."""
         self.p.get_diag(lv, d)
+        if lv in self._contact_levels:
+            for c in self.contacts:
+                c["levels"][lv].diagonal_add(1.0, c["state"], d)
 
     def _lanczos_host(self, lv, steps):
         """CG coefficients with every dot product read on the host (several ranks: the dots are all-reduced)."""
@@ -381,7 +407,7 @@ class NewtonPMG(LoadedBody):
         its = 0
         if rz0 <= 0.0:
             return 0
-        apply_A = self.A_outer if self.pressure_loads else self.A
+        apply_A = self.A_outer if (self.pressure_loads or (self.contacts and self.contact_tangent == "outer")) else self.A
         for its in range(1, 500):
             apply_A(fine, p, Ap)
             alpha = rz / self.dot(p, Ap, True)

@@ -550,6 +550,8 @@ CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadApplyTangentAdd(CeedXSurfaceLoad sl, Ce
 /* Instantiation of the last launch, e.g. "surface<P=3,Q=3>" (empty before).   */
 CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadGetKernelName(CeedXSurfaceLoad sl, const char **name);
 CEED_EXTERN_OPTIONAL int CeedXSurfaceLoadDestroy(CeedXSurfaceLoad *sl);
+/* (Penalty contact of such faces with a rigid plane or sphere, CeedXContact*: */
+/* include/ceed_contact.h, a header of its own on top of this one.)            */
 /* Assembled sparse operator on L-vectors: the coarse level of the multigrid. */
 /* The reference builds it by finite-difference colouring of the p=1 operator */
 /* (misc.c:151-183, elasticity.c:457-483) and hands it to GAMG; here the      */
