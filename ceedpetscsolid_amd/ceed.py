@@ -394,25 +394,47 @@ class Csr:
             self.h = None
 
 
-SURFACE_TRACTION, SURFACE_PRESSURE = 0, 1
-
-
-class SurfaceLoadHandle:
-    """CeedXSurfaceLoad*: traction, follower pressure and its tangent on a list of element faces, on the device.  CEED_EXTERN_OPTIONAL:
-    only where the library has ``CeedXSurfaceLoadCreate``; surface.py's SurfaceLoad takes its portable NumPy form otherwise."""
+class _FaceHandle:
+    """A term on a list of element faces, on the device: what is common to the entry points ``PREFIX``Create, SetDirichletMask,
+    GetKernelName and Destroy, which every such term has with the same arguments.  Optional in a library: without ``PREFIX``Create the
+    caller (``PORTABLE``) takes its portable NumPy form.  A term spells out its four calls (``_create`` ... ``_destroy``), so that the
+    static check of every call site's argument count still sees them."""
+    PREFIX = PORTABLE = ""
 
     def __init__(self, ceed: "Ceed", P: int, Q: int, offsets, lsize: int):
         self.L, self._ceed = ceed.L, ceed
-        if not self.L.has("CeedXSurfaceLoadCreate"):
-            raise CeedError(f"{self.L.path} has no CeedXSurfaceLoadCreate: use the portable form (surface.SurfaceLoad)")
+        if not self.L.has(self.PREFIX + "Create"):
+            raise CeedError(f"{self.L.path} has no {self.PREFIX}Create: use the portable form ({self.PORTABLE})")
         self.h = C.c_void_p()
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, P * P)
         self.nface = off.shape[0]
-        self.L.CeedXSurfaceLoadCreate(ceed.h, self.nface, P, Q, off.ctypes.data_as(c_int_p), lsize, C.byref(self.h))
+        self._create(ceed.h, P, Q, off.ctypes.data_as(c_int_p), lsize)
 
     def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
         _, p, n = Operator._bytes(mask)
-        self.L.CeedXSurfaceLoadSetDirichletMask(self.h, MEM_HOST, p, n)
+        self._set_mask(p, n)
+
+    @property
+    def kernel_name(self) -> str:
+        return (self._kernel_name() or b"").decode()
+
+    def destroy(self):
+        if self.h:
+            self._destroy()
+            self.h = None
+
+
+SURFACE_TRACTION, SURFACE_PRESSURE = 0, 1
+
+
+class SurfaceLoadHandle(_FaceHandle):
+    """CeedXSurfaceLoad*: traction, follower pressure and its tangent on a list of element faces."""
+    PREFIX, PORTABLE = "CeedXSurfaceLoad", "surface.SurfaceLoad"
+
+    def _create(self, ceed_h, P, Q, off, lsize): self.L.CeedXSurfaceLoadCreate(ceed_h, self.nface, P, Q, off, lsize, C.byref(self.h))
+    def _set_mask(self, p, n): self.L.CeedXSurfaceLoadSetDirichletMask(self.h, MEM_HOST, p, n)
+    def _kernel_name(self): return out_value(self.L.CeedXSurfaceLoadGetKernelName, C.c_char_p, self.h)
+    def _destroy(self): self.L.lib.CeedXSurfaceLoadDestroy(C.byref(self.h))
 
     def apply_add(self, kind: int, coef, scale: float, X: "Vector", u: Optional["Vector"], y: "Vector"):   # y += scale g
         cf = (C.c_double * 3)(*[float(v) for v in coef])
@@ -421,36 +443,19 @@ class SurfaceLoadHandle:
     def apply_tangent_add(self, p: float, scale: float, X: "Vector", u: Optional["Vector"], du: "Vector", y: "Vector"):   # y += scale p T(u) du
         self.L.CeedXSurfaceLoadApplyTangentAdd(self.h, p, scale, X.h, _h(u), du.h, y.h)
 
-    @property
-    def kernel_name(self) -> str:
-        return (out_value(self.L.CeedXSurfaceLoadGetKernelName, C.c_char_p, self.h) or b"").decode()
-
-    def destroy(self):
-        if self.h:
-            self.L.lib.CeedXSurfaceLoadDestroy(C.byref(self.h))
-            self.h = None
-
 
 CONTACT_PLANE, CONTACT_SPHERE = 0, 1
 CONTACT_NSTATE = 7                  # per point: K (xx, yy, zz, yz, xz, xy), then the gap
 
 
-class ContactHandle:
-    """CeedXContact* (include/ceed_contact.h): penalty contact of a list of element faces with a rigid plane or sphere, on the device.
-    Optional: only where the library has ``CeedXContactCreate``; contact.py's ContactSurface takes its portable NumPy form otherwise."""
+class ContactHandle(_FaceHandle):
+    """CeedXContact* (include/ceed_contact.h): penalty contact of a list of element faces with a rigid plane or sphere."""
+    PREFIX, PORTABLE = "CeedXContact", "contact.ContactSurface"
 
-    def __init__(self, ceed: "Ceed", P: int, Q: int, offsets, lsize: int):
-        self.L, self._ceed = ceed.L, ceed
-        if not self.L.has("CeedXContactCreate"):
-            raise CeedError(f"{self.L.path} has no CeedXContactCreate: use the portable form (contact.ContactSurface)")
-        self.h = C.c_void_p()
-        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, P * P)
-        self.nface = off.shape[0]
-        self.L.CeedXContactCreate(ceed.h, self.nface, P, Q, off.ctypes.data_as(c_int_p), lsize, C.byref(self.h))
-
-    def set_dirichlet_mask(self, mask: Optional[np.ndarray]):
-        _, p, n = Operator._bytes(mask)
-        self.L.CeedXContactSetDirichletMask(self.h, MEM_HOST, p, n)
+    def _create(self, ceed_h, P, Q, off, lsize): self.L.CeedXContactCreate(ceed_h, self.nface, P, Q, off, lsize, C.byref(self.h))
+    def _set_mask(self, p, n): self.L.CeedXContactSetDirichletMask(self.h, MEM_HOST, p, n)
+    def _kernel_name(self): return out_value(self.L.CeedXContactGetKernelName, C.c_char_p, self.h)
+    def _destroy(self): self.L.lib.CeedXContactDestroy(C.byref(self.h))
 
     def set_obstacle(self, kind: int, params, penalty: float):
         par = [float(v) for v in params]
@@ -464,15 +469,6 @@ class ContactHandle:
 
     def diagonal_add(self, scale: float, state: "Vector", d: "Vector"):                                    # d += scale diag C
         self.L.CeedXContactDiagonalAdd(self.h, scale, state.h, d.h)
-
-    @property
-    def kernel_name(self) -> str:
-        return (out_value(self.L.CeedXContactGetKernelName, C.c_char_p, self.h) or b"").decode()
-
-    def destroy(self):
-        if self.h:
-            self.L.lib.CeedXContactDestroy(C.byref(self.h))
-            self.h = None
 
 
 class Graph:

@@ -34,8 +34,8 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
-from .mesh import DofMap, HexMesh, side_set_faces
-from .surface import lagrange_tables
+from .mesh import DofMap, HexMesh
+from .surface import FaceTerm
 
 NSTATE = cd.CONTACT_NSTATE
 _SYM = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))            # the six stored entries of K: xx, yy, zz, yz, xz, xy
@@ -67,34 +67,16 @@ def obstacle_parameters(plane=None, sphere=None):
     return cd.CONTACT_SPHERE, par
 
 
-class ContactSurface:
-    """The faces of ``side_ids`` of ``mesh`` under the numbering ``dm`` and the library's handle.  ``Q``: Gauss points per direction, the
-    FINE level's on every level.  ``mask``: the Dirichlet byte mask over the L-vector -- masked rows of y and d are never written, masked
-    entries of du read as zero, u is read as it is (it carries the boundary values).  The state is a vector of the Ceed with
-    ``state_size`` entries (``new_state``); a coarse level's surface takes the one its fine level's residual wrote."""
+class ContactSurface(FaceTerm):
+    """The contact term of the faces of ``side_ids`` (surface.FaceTerm).  ``Q``: Gauss points per direction, the FINE level's on every
+    level.  The state is a vector of the Ceed with ``state_size`` entries (``new_state``); a coarse level's surface takes the one its
+    fine level's residual wrote."""
+    HANDLE = cd.ContactHandle
 
     def __init__(self, ceed: cd.Ceed, mesh: HexMesh, dm: DofMap, side_ids, Q: int, mask=None, portable: bool = False):
-        self.ceed, self.L = ceed, ceed.L
-        self.P, self.lsize, self.Q = dm.P, dm.lsize, int(Q)
-        self.side_ids = list(side_ids)
-        self.faces = side_set_faces(mesh, dm, self.side_ids)
-        self.nface = self.faces.shape[0]
+        super().__init__(ceed, mesh, dm, side_ids, Q, mask, portable)
         self.state_size = self.nface * NSTATE * self.Q ** 2
-        self.Xh = np.ascontiguousarray(dm.node_coords, dtype=np.float64).reshape(-1)
-        self.portable = bool(portable) or not self.L.has("CeedXContactCreate")
-        self.B, self.D, self.w = lagrange_tables(self.P, self.Q)
-        self.mask = None
         self.kind = self.par = self.penalty = None
-        self.handle = self.X = None
-        if not self.portable:
-            self.handle = cd.ContactHandle(ceed, self.P, self.Q, 3 * self.faces, self.lsize)
-        if mask is not None:
-            self.set_mask(mask)
-
-    def set_mask(self, mask):
-        self.mask = None if mask is None else (np.asarray(mask).reshape(-1)[:self.lsize] != 0)
-        if self.handle is not None:
-            self.handle.set_dirichlet_mask(None if mask is None else self.mask.astype(np.uint8))
 
     def set_obstacle(self, plane=None, sphere=None, penalty: float = 1.0):
         """The obstacle and the penalty eps > 0 of the residual evaluations that follow."""
@@ -109,34 +91,14 @@ class ContactSurface:
         """A zeroed state vector (no point active, every gap 0); the caller destroys it."""
         return self.ceed.vector(max(self.state_size, 1)).set_value(0.0)
 
-    @property
-    def kernel_name(self) -> str:
-        return "portable" if self.handle is None else self.handle.kernel_name
-
     # ---- the portable form: NumPy on host arrays ---------------------------------------------------------------------------
-    def _gather(self, field: np.ndarray) -> np.ndarray:
-        return np.asarray(field, dtype=np.float64).reshape(-1)[:self.lsize].reshape(-1, 3)[self.faces].reshape(self.nface, self.P, self.P, 3)
-
-    def _to_nodes(self, val: np.ndarray, B: np.ndarray) -> np.ndarray:
-        """The L-vector of sum_q B_a(q) val(q), val [face][b][a][c] with the weights inside: face results added in face order; masked
-        rows are zero."""
-        ge = np.einsum("ai,bj,fbac->fjic", B, B, val)
-        out = np.zeros((self.lsize // 3, 3))
-        np.add.at(out, self.faces.reshape(-1), ge.reshape(-1, 3))
-        out = out.reshape(-1)
-        if self.mask is not None:
-            out[self.mask] = 0.0
-        return out
-
     def _points(self, u):
         """(w J, g, n, h) at the points [face][b][a]: the weighted reference area element, the gap, n = grad g and the factor of
         grad grad g = h (I - n (x) n)."""
         if self.kind is None:
             raise ValueError("contact: no obstacle set (set_obstacle)")
-        fX = self._gather(self.Xh)
-        fx = fX + self._gather(u)
-        Xa, Xb = np.einsum("ai,bj,fjic->fbac", self.D, self.B, fX), np.einsum("ai,bj,fjic->fbac", self.B, self.D, fX)
-        x = np.einsum("ai,bj,fjic->fbac", self.B, self.B, fx)
+        Xa, Xb = self._derivs(self.Xh)
+        x = np.einsum("ai,bj,fjic->fbac", self.B, self.B, self._gather(self.Xh) + self._gather(u))
         wJ = np.linalg.norm(np.cross(Xa, Xb), axis=-1) * (self.w[:, None] * self.w[None, :])[None]
         if self.kind == cd.CONTACT_PLANE:
             n = np.broadcast_to(self.par[3:6], x.shape)
@@ -182,10 +144,7 @@ class ContactSurface:
 
     def tangent_host(self, state, du) -> np.ndarray:
         """C du as an L-vector from a state (of this or of a finer p-level); masked entries of du read as zero."""
-        du = np.asarray(du, dtype=np.float64).reshape(-1)[:self.lsize]
-        if self.mask is not None:
-            du = np.where(self.mask, 0.0, du)
-        dq = np.einsum("ai,bj,fjic->fbac", self.B, self.B, self._gather(du))
+        dq = np.einsum("ai,bj,fjic->fbac", self.B, self.B, self._gather(self._free(du)))
         return self._to_nodes(np.einsum("fbacd,fbad->fbac", self._K(state), dq), self.B)
 
     def diagonal_host(self, state) -> np.ndarray:
@@ -193,18 +152,10 @@ class ContactSurface:
         K = self._K(state)
         return self._to_nodes(np.stack([K[..., c, c] for c in range(3)], axis=-1), np.square(self.B))
 
-    @staticmethod
-    def _add_host(y: cd.Vector, add: np.ndarray):
-        v = y.to_numpy().copy()
-        v[:add.size] += add
-        y.set_array(v)
-
     # ---- y += ..., on vectors of the Ceed ----------------------------------------------------------------------------------------
     def residual_add(self, scale: float, u: cd.Vector, y: cd.Vector, state: cd.Vector):
         """y += scale r(u); state := the contact state at u (never scaled)."""
         if self.handle is not None:
-            if self.X is None:
-                self.X = self.ceed.vector(self.lsize).set_array(self.Xh)
             self.handle.apply_residual_add(scale, self.X, u, y, state)
         else:
             r, st = self.residual_host(u.to_numpy())
@@ -242,11 +193,3 @@ class ContactSurface:
         """The share of the points in contact (g < 0)."""
         g = self._gaps(state)
         return float((g < 0.0).mean()) if g.size else 0.0
-
-    def destroy(self):
-        if self.handle is not None:
-            self.handle.destroy()
-            self.handle = None
-        if self.X is not None:
-            self.X.destroy()
-            self.X = None

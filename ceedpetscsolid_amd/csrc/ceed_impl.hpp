@@ -279,6 +279,8 @@ int dev_zero(Ceed c, double *p, size_t n);
 // host mirror and drops the qdata provenance
 int vec_dev(CeedVector v, bool write, double **p);
 void vec_drop_geo(CeedVector v);
+// the 1-D tables of a basis as the kernels take them (ceed_operator.cpp)
+void fill_tables(cps::BasisTables &t, CeedBasis b);
 
 // restriction maps (ceed_restriction.cpp)
 int build_csr(CeedElemRestriction r, CsrMap &M, const unsigned char *prio, int skipP = 0);

@@ -84,7 +84,7 @@ extern "C" int CeedOperatorDestroy(CeedOperator *op) {
   return 0;
 }
 
-static void fill_tables(BasisTables &t, CeedBasis b) {
+void fill_tables(BasisTables &t, CeedBasis b) {
   memset(&t, 0, sizeof t);
   memcpy(t.interp, b->interp1d.data(), sizeof(double) * b->interp1d.size());
   memcpy(t.grad, b->grad1d.data(), sizeof(double) * b->grad1d.size());

@@ -188,6 +188,19 @@ inline std::vector<uint32_t> face_offsets(const std::vector<int> &offsets, const
   if (mask) return flagged_offsets(offsets, mask, 3, 1);
   return std::vector<uint32_t>(offsets.begin(), offsets.end());
 }
+// The face offsets a caller hands to a face term, [nface][per_face] component-0 offsets of interlaced nodes in an L-vector of `lsize`
+// entries, checked before anything is built from them: the first face that breaks a rule, its offset and which rule.
+enum FaceOffsetFault : int { FACE_OFFSETS_OK = 0, FACE_OFFSETS_TOO_MANY, FACE_OFFSET_PAST_LSIZE, FACE_OFFSET_NOT_NODE };
+struct FaceOffsetCheck { FaceOffsetFault fault; size_t face; long offset; };
+inline FaceOffsetCheck check_face_offsets(const int *offsets, size_t nface, int per_face, int lsize) {
+  if (nface * (size_t)per_face > (size_t)0x7FFFFFFF / 3) return {FACE_OFFSETS_TOO_MANY, 0, 0};    // the face E-vector is indexed in 32 bits
+  for (size_t i = 0; i < nface * (size_t)per_face; i++) {
+    const long o = offsets[i];
+    if (o < 0 || o + 2 >= (long)lsize) return {FACE_OFFSET_PAST_LSIZE, i / (size_t)per_face, o};
+    if (o % 3) return {FACE_OFFSET_NOT_NODE, i / (size_t)per_face, o};
+  }
+  return {FACE_OFFSETS_OK, 0, 0};
+}
 // the Dirichlet flags of a mask in the row order of a transpose map
 inline std::vector<unsigned char> row_flag_bits(const std::vector<uint32_t> &node_off, const unsigned char *mask, int ncomp, int compstride) {
   std::vector<unsigned char> fl(node_off.size(), 0);

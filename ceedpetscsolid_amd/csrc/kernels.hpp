@@ -318,6 +318,7 @@ hipError_t launch_assemble_epi(const NodeMap &m, const unsigned char *flags, con
 // Surface loads on element faces (kernels_surface.hip, k_surface): per face the P^2 nodal values of one of three geometric vectors,
 //   traction  g_a = int N_a t |X_xi x X_eta|,   pressure  g_a = int N_a (x_xi x x_eta),   tangent  T du |_a = int N_a (du_xi x x_eta + x_xi x du_eta),
 // x = X + u, (xi, eta) the two in-face directions (xi fastest in the face's node list) with X_xi x X_eta pointing out of the body.
+// The face mapping and the passes it shares with k_contact: kernel_face_pass.hpp.
 enum SurfaceKind : int { SURF_TRACTION = 0, SURF_PRESSURE = 1, SURF_TANGENT = 2 };
 struct SurfaceArgs {
   const uint32_t *offsets;  // [nface][P^2] component-0 L-offsets, the Dirichlet flags of their nodes in the top bits
@@ -341,6 +342,7 @@ hipError_t launch_surface_sum(const NodeMap &m, const unsigned char *flags, cons
 //   tangent   C du |_a =  sum_q N_a(q) K_q du(q),   K_q = w_q J_q eps [H(-g) n (x) n - <-g> grad grad g]
 //   diagonal  d_{a,c}  =  sum_q N_a(q)^2 K_q[c][c]                                    (the tables come entry-wise squared)
 // in a face E-vector [face][P^2][3] that launch_surface_sum() adds into y.  The tangent and the diagonal read the state alone.
+// Mapping and passes: kernel_face_pass.hpp, as for k_surface.
 enum ContactMode : int { CONTACT_RESIDUAL = 0, CONTACT_TANGENT = 1, CONTACT_DIAGONAL = 2 };
 enum ContactObstacle : int { CONTACT_PLANE = 0, CONTACT_SPHERE = 1 };
 constexpr int CONTACT_NSTATE = 7;   // K_q as (xx, yy, zz, yz, xz, xy), then the gap g

@@ -12,77 +12,63 @@
 // (its own P, the fine Q) needs no obstacle, no coordinates and no displacement.  grad grad g = 0 for the plane and s (I - n (x) n) / |x - c|
 // for the sphere.
 //
-// Mapping (k_surface's): one wave64 per workgroup owns FPW = max(1, 64 / Q^2) faces, a face owns S = Q^2 lanes (Q >= P: a lane per point,
-// and per node in the last pass).  Residual: the gather of the 24-byte node records (X and X + u), the xi pass (B and D of every line of
-// X, B of x), the eta pass with the obstacle at a lane per point and the seven coalesced state stores, then the two transposed passes
-// back to the nodes.  Tangent: gather du (flagged components as zeros), two B passes, K_q du_q, two transposed passes; no D table.
-// Diagonal: K_q[c][c] at a lane per point and the two transposed passes with the entry-wise squared table (the host passes it, as for
-// k_mass's diagonal).  The obstacle is uniform over the launch.  No atomics, no scratch memory, no waiting on other waves.
+// Mapping, LDS layout and the steps every face kernel takes: kernel_face_pass.hpp.  Here -- residual: X and x = X + u are gathered, X
+// gets B and D of every line and x gets B, the point work is the obstacle and the seven coalesced state stores.  Tangent: du is gathered
+// (flagged components as zeros) and gets B, the point work is K_q du_q; no D table.  Diagonal: K_q[c][c] at a lane per point and the way
+// back with the entry-wise squared table (the host passes it, as for k_mass's diagonal).  The obstacle is uniform over the launch.
 #include "kernel_diag_sf.hpp"      // CPS_DIAG_PQ: the one list of (P, Q) pairs
-#include "kernels_common.hpp"
+#include "kernel_face_pass.hpp"
 
 namespace cps {
 
-template <int P, int Q, int MODE> struct ContactGeom {
-  static_assert(Q >= P && Q <= MAXN1D && P >= 2, "a lane per point covers the nodes too");
-  static constexpr int P2 = P * P, Q2 = Q * Q;
-  static constexpr int S = Q2;                         // lanes of a face
-  static constexpr int FPW = 64 / S < 1 ? 1 : 64 / S;  // faces of a wave
-  static constexpr int NX = 3 * P2;                    // a gathered field         [c][j][i]
-  static constexpr int N1 = 3 * P * Q;                 // one result of the xi pass [c][j][a]
-  static constexpr int NV = 3 * Q2;                    // the values at the points  [c][b][a]
-  static constexpr int NR = 3 * Q * P;                 // first transposed pass     [c][b][i]
-  static constexpr int NIN = MODE == CONTACT_RESIDUAL ? 2 * NX : (MODE == CONTACT_TANGENT ? NX : 0);   // X, x; du; nothing
-  static constexpr int NT1 = MODE == CONTACT_RESIDUAL ? 3 * N1 : (MODE == CONTACT_TANGENT ? N1 : 0);   // B X, D X, B x; B du
-  static constexpr int NF = NIN + NT1 + NV + NR;       // doubles per face
-  static constexpr int NTAB = 2 * Q * P + Q;           // B[a][i], D[a][i], weights
-  static_assert((size_t)(NTAB + FPW * NF) * sizeof(double) <= 64 * 1024, "static LDS of one workgroup");
+template <int P, int Q, int MODE> struct ContactGeom : FaceGeom<P, Q> {
+  using F = FaceGeom<P, Q>;
+  static constexpr int NIN = MODE == CONTACT_RESIDUAL ? 2 * F::NX : (MODE == CONTACT_TANGENT ? F::NX : 0);   // X, x; du; nothing
+  static constexpr int NT1 = MODE == CONTACT_RESIDUAL ? 3 * F::N1 : (MODE == CONTACT_TANGENT ? F::N1 : 0);   // B X, D X, B x; B du
+  static constexpr int NF = NIN + NT1 + F::NV + F::NR;  // doubles per face
+  static_assert((size_t)(F::NTAB + F::FPW * NF) * sizeof(double) <= 64 * 1024, "static LDS of one workgroup");
 };
 
 template <int P, int Q, int MODE>
 __global__ __launch_bounds__(64) void k_contact(const BasisTables tab, const ContactArgs a) {
   using G = ContactGeom<P, Q, MODE>;
-  constexpr int P2 = G::P2, Q2 = G::Q2, S = G::S, FPW = G::FPW, NX = G::NX, N1 = G::N1;
-  __shared__ double lds[G::NTAB + FPW * G::NF];
-  double *sB = lds, *sD = lds + Q * P, *sW = lds + 2 * Q * P;
-  const int lane = threadIdx.x, fl = lane / S, t = lane % S;
-  const int face = blockIdx.x * FPW + fl;
-  const bool live = fl < FPW && face < a.nface;        // (64 % S lanes of the wave own no face)
-  double *sin = lds + G::NTAB + (live ? fl : 0) * G::NF, *t1 = sin + G::NIN, *sv = t1 + G::NT1, *sr = sv + G::NV;
-  double *st = a.state + ((size_t)(live ? face : 0) * CONTACT_NSTATE) * Q2 + t;      // entry k of this lane's point: st[k * Q2]
-  for (int i = lane; i < Q * P; i += 64) { sB[i] = tab.interp[i]; sD[i] = tab.grad[i]; }
-  if (lane < Q) sW[lane] = tab.qw[lane];
+  constexpr int P2 = G::P2, Q2 = G::Q2, NX = G::NX, N1 = G::N1;
+  __shared__ double lds[G::NTAB + G::FPW * G::NF];
+  const double *sB = lds, *sD = lds + Q * P, *sW = lds + 2 * Q * P;
+  const FaceLane L = face_lane<G>(a.nface);
+  const int t = L.t;
+  const bool live = L.live;
+  double *sin = lds + G::NTAB + (live ? L.fl : 0) * G::NF, *t1 = sin + G::NIN, *sv = t1 + G::NT1, *sr = sv + G::NV;
+  double *st = a.state + ((size_t)(live ? L.face : 0) * CONTACT_NSTATE) * Q2 + t;    // entry k of this lane's point: st[k * Q2]
+  face_tables<P, Q>(tab, lds);
   // the node records: X and x = X + u (residual); du with its flagged components as zeros (tangent)
   if (MODE != CONTACT_DIAGONAL && live && t < P2) {
-    const uint32_t off = a.offsets[(size_t)face * P2 + t];
-    const uint32_t o = off & OFF_MASK, flg = off >> OFF_FLAG_SHIFT;
+    const uint32_t off = a.offsets[(size_t)L.face * P2 + t];
+    double v[3], w[3];
+    if (MODE == CONTACT_RESIDUAL) {
+      face_record<false>(a.X, off, v); face_record<false>(a.u, off, w);
+      face_put<P2>(sin, t, v);
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      if (MODE == CONTACT_RESIDUAL) {
-        const double xv = a.X[o + c];
-        sin[c * P2 + t] = xv;
-        sin[NX + c * P2 + t] = xv + a.u[o + c];
-      } else {
-        sin[c * P2 + t] = ((flg >> c) & 1u) ? 0. : a.du[o + c];
-      }
+      for (int c = 0; c < 3; c++) w[c] = v[c] + w[c];
+      face_put<P2>(sin + NX, t, w);
+    } else {
+      face_record<true>(a.du, off, v);
+      face_put<P2>(sin, t, v);
     }
   }
   __syncthreads();
-  // xi: per line (c, j) the values at the Q points -- residual: t1[0] = B X, t1[1] = D X, t1[2] = B x; tangent: t1[0] = B du
+  // xi: the values of every line at the Q points -- residual: t1[0] = B X, t1[1] = D X, t1[2] = B x; tangent: t1[0] = B du
   if (MODE != CONTACT_DIAGONAL && live) {
-    for (int o = t; o < N1; o += S) {
+    for (int o = t; o < N1; o += Q2) {
       const int aa = o % Q, line = o / Q;
       const double *src = sin + line * P, *B = sB + aa * P;
-      double vb = 0.;
-#pragma unroll
-      for (int i = 0; i < P; i++) vb += B[i] * src[i];
-      t1[o] = vb;
       if (MODE == CONTACT_RESIDUAL) {
-        const double *D = sD + aa * P, *cur = src + NX;
-        double vd = 0., xb = 0.;
-#pragma unroll
-        for (int i = 0; i < P; i++) { vd += D[i] * src[i]; xb += B[i] * cur[i]; }
-        t1[N1 + o] = vd; t1[2 * N1 + o] = xb;
+        double vb, vd;
+        face_dot2<P, 1>(B, src, sD + aa * P, src, vb, vd);
+        const double xb = face_dot<P, 1>(B, src + NX);
+        t1[o] = vb; t1[N1 + o] = vd; t1[2 * N1 + o] = xb;
+      } else {
+        t1[o] = face_dot<P, 1>(B, src);
       }
     }
   }
@@ -98,10 +84,7 @@ __global__ __launch_bounds__(64) void k_contact(const BasisTables tab, const Con
 #pragma unroll
       for (int c = 0; c < 3; c++) {
         const double *vb = t1 + c * P * Q + aa, *vd = vb + N1, *xb = vb + 2 * N1;
-        double s0 = 0., s1 = 0., s2 = 0.;
-#pragma unroll
-        for (int j = 0; j < P; j++) { s0 += B[j] * vd[j * Q]; s1 += D[j] * vb[j * Q]; s2 += B[j] * xb[j * Q]; }
-        Xa[c] = s0; Xb[c] = s1; x[c] = s2;
+        face_dot2<P, Q>(B, vd, D, vb, Xa[c], Xb[c]); x[c] = face_dot<P, Q>(B, xb);
       }
       double m[3];
 #pragma unroll
@@ -136,15 +119,8 @@ __global__ __launch_bounds__(64) void k_contact(const BasisTables tab, const Con
 #pragma unroll
       for (int c = 0; c < 3; c++) v[c] = f * n[c];
     } else if (MODE == CONTACT_TANGENT) {
-      double d[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const double *vb = t1 + c * P * Q + aa;
-        double s0 = 0.;
-#pragma unroll
-        for (int j = 0; j < P; j++) s0 += B[j] * vb[j * Q];
-        d[c] = s0;
-      }
+      const double *vb = t1 + aa;
+      const double d[3] = {face_dot<P, Q>(B, vb), face_dot<P, Q>(B, vb + P * Q), face_dot<P, Q>(B, vb + 2 * P * Q)};
       const double kxx = st[0 * Q2], kyy = st[1 * Q2], kzz = st[2 * Q2], kyz = st[3 * Q2], kxz = st[4 * Q2], kxy = st[5 * Q2];
       v[0] = a.scale * (kxx * d[0] + kxy * d[1] + kxz * d[2]);
       v[1] = a.scale * (kxy * d[0] + kyy * d[1] + kyz * d[2]);
@@ -157,58 +133,19 @@ __global__ __launch_bounds__(64) void k_contact(const BasisTables tab, const Con
     for (int c = 0; c < 3; c++) sv[c * Q2 + t] = v[c];
   }
   __syncthreads();
-  // back along xi: sr[c][b][i] = sum_a B[a][i] v[c][b][a]
-  if (live) {
-    for (int o = t; o < G::NR; o += S) {
-      const int i = o % P, cb = o / P;
-      const double *src = sv + cb * Q;
-      double r = 0.;
-#pragma unroll
-      for (int q = 0; q < Q; q++) r += sB[q * P + i] * src[q];
-      sr[o] = r;
-    }
-  }
-  __syncthreads();
-  // back along eta and the stores: a lane per node, 24-byte records in node order
-  if (live && t < P2) {
-    const int i = t % P, j = t / P;
-    double *out = a.evec + ((size_t)face * P2 + t) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      double g = 0.;
-#pragma unroll
-      for (int b = 0; b < Q; b++) g += sB[b * P + j] * sr[(c * Q + b) * P + i];
-      out[c] = g;
-    }
-  }
-}
-
-template <int P, int Q, int MODE>
-static hipError_t contact_t(const BasisTables &t, const ContactArgs &a, hipStream_t s) {
-  if (a.nface <= 0) return hipSuccess;
-  constexpr int FPW = ContactGeom<P, Q, MODE>::FPW;
-  hipLaunchKernelGGL((k_contact<P, Q, MODE>), dim3((a.nface + FPW - 1) / FPW), dim3(64), 0, s, t, a);
-  return hipGetLastError();
+  face_to_nodes<P, Q>(sB, sv, sr, a.evec, L.face, t, live);
 }
 
 hipError_t launch_contact(int P, int Q, int mode, const BasisTables &t, const ContactArgs &a, hipStream_t s, const char **name) {
-#define CPS_CT(Pv, Qv)                                                                             \
-  if (P == Pv && Q == Qv) {                                                                        \
-    if (mode == CONTACT_RESIDUAL) {                                                                \
-      *name = "contact<P=" #Pv ",Q=" #Qv ",residual>";                                             \
-      return contact_t<Pv, Qv, CONTACT_RESIDUAL>(t, a, s);                                         \
-    }                                                                                              \
-    if (mode == CONTACT_TANGENT) {                                                                 \
-      *name = "contact<P=" #Pv ",Q=" #Qv ",tangent>";                                              \
-      return contact_t<Pv, Qv, CONTACT_TANGENT>(t, a, s);                                          \
-    }                                                                                              \
-    if (mode == CONTACT_DIAGONAL) {                                                                \
-      *name = "contact<P=" #Pv ",Q=" #Qv ",diagonal>";                                             \
-      return contact_t<Pv, Qv, CONTACT_DIAGONAL>(t, a, s);                                         \
-    }                                                                                              \
+#define CPS_CM(Pv, Qv, MODE, word)                                                                 \
+  if (P == Pv && Q == Qv && mode == MODE) {                                                        \
+    *name = "contact<P=" #Pv ",Q=" #Qv "," word ">";                                               \
+    return launch_faces<FaceGeom<Pv, Qv>::FPW>(k_contact<Pv, Qv, MODE>, t, a, s);                  \
   }
+#define CPS_CT(Pv, Qv) CPS_CM(Pv, Qv, CONTACT_RESIDUAL, "residual") CPS_CM(Pv, Qv, CONTACT_TANGENT, "tangent") CPS_CM(Pv, Qv, CONTACT_DIAGONAL, "diagonal")
   CPS_DIAG_PQ(CPS_CT)
 #undef CPS_CT
+#undef CPS_CM
   return hipErrorInvalidValue;
 }
 bool contact_instantiated(int P, int Q) {

@@ -9,66 +9,54 @@
 // nodal values in a face E-vector [face][P^2][3]; k_surface_sum adds them into y per row of the faces' transpose map, in face order.
 // Signs and loads are the caller's: the coefficients arrive multiplied by the caller's scale.
 //
-// Mapping: one wave64 per workgroup owns FPW = max(1, 64 / Q^2) faces, a face owns S = Q^2 lanes (Q >= P: a lane per point, and per
-// node in the last pass).  Five steps over LDS: the gather of the 24-byte node records (X, + u, and du), the xi pass (B and D of every
-// line), the eta pass with the cross products and the weight at a lane per point, and the two transposed passes back to the nodes
-// followed by plain coalesced stores.  `kind` is uniform over the launch.  No atomics, no scratch memory, no waiting on other waves.
+// Mapping, LDS layout and the steps every face kernel takes: kernel_face_pass.hpp.  Here: x = X (+ u) and du are gathered, both get B
+// and D of every line, and the point work is the cross product(s) and the weight.  `kind` is uniform over the launch.
+#include "kernel_face_pass.hpp"
 #include "kernel_node_sum.hpp"
-#include "kernels_common.hpp"
 
 namespace cps {
 
-template <int P, int Q> struct SurfGeom {
-  static_assert(Q >= P && Q <= MAXN1D && P >= 2, "a lane per point covers the nodes too");
-  static constexpr int P2 = P * P, Q2 = Q * Q;
-  static constexpr int S = Q2;                         // lanes of a face
-  static constexpr int FPW = 64 / S < 1 ? 1 : 64 / S;  // faces of a wave
-  static constexpr int NX = 3 * P2;                    // a gathered field        [c][j][i]
-  static constexpr int N1 = 3 * P * Q;                 // one result of the xi pass [c][j][a]
-  static constexpr int NV = 3 * Q2;                    // the values at the points  [c][b][a]
-  static constexpr int NR = 3 * Q * P;                 // first transposed pass     [c][b][i]
-  static constexpr int NF = 2 * NX + 4 * N1 + NV + NR; // doubles per face: x, du; (B, D) x (x, du); values; first transposed pass
-  static constexpr int NTAB = 2 * Q * P + Q;           // B[a][i], D[a][i], weights
-  static_assert((size_t)(NTAB + FPW * NF) * sizeof(double) <= 64 * 1024, "static LDS of one workgroup");
+template <int P, int Q> struct SurfGeom : FaceGeom<P, Q> {
+  using F = FaceGeom<P, Q>;
+  static constexpr int NF = 2 * F::NX + 4 * F::N1 + F::NV + F::NR;   // doubles per face: x, du; (B, D) x (x, du); values; first transposed pass
+  static_assert((size_t)(F::NTAB + F::FPW * NF) * sizeof(double) <= 64 * 1024, "static LDS of one workgroup");
 };
 
 template <int P, int Q>
 __global__ __launch_bounds__(64) void k_surface(const BasisTables tab, const SurfaceArgs a) {
   using G = SurfGeom<P, Q>;
-  constexpr int P2 = G::P2, Q2 = G::Q2, S = G::S, FPW = G::FPW, NX = G::NX, N1 = G::N1;
-  __shared__ double lds[G::NTAB + FPW * G::NF];
-  double *sB = lds, *sD = lds + Q * P, *sW = lds + 2 * Q * P;
-  const int lane = threadIdx.x, fl = lane / S, t = lane % S;
-  const int face = blockIdx.x * FPW + fl;
-  const bool live = fl < FPW && face < a.nface;        // (64 % S lanes of the wave own no face)
-  double *sx = lds + G::NTAB + (live ? fl : 0) * G::NF, *sdu = sx + NX, *t1 = sdu + NX, *sv = t1 + 4 * N1, *sr = sv + G::NV;
+  constexpr int P2 = G::P2, Q2 = G::Q2, NX = G::NX, N1 = G::N1;
+  __shared__ double lds[G::NTAB + G::FPW * G::NF];
+  const double *sB = lds, *sD = lds + Q * P, *sW = lds + 2 * Q * P;
+  const FaceLane L = face_lane<G>(a.nface);
+  const int t = L.t;
+  const bool live = L.live;
+  double *sx = lds + G::NTAB + (live ? L.fl : 0) * G::NF, *sdu = sx + NX, *t1 = sdu + NX, *sv = t1 + 4 * N1, *sr = sv + G::NV;
   const int kind = a.kind;
   const bool tang = kind == SURF_TANGENT, cur = kind != SURF_TRACTION && a.u != nullptr;
-  for (int i = lane; i < Q * P; i += 64) { sB[i] = tab.interp[i]; sD[i] = tab.grad[i]; }
-  if (lane < Q) sW[lane] = tab.qw[lane];
+  face_tables<P, Q>(tab, lds);
   // the node records: x = X (+ u); du with its flagged components as zeros
   if (live && t < P2) {
-    const uint32_t off = a.offsets[(size_t)face * P2 + t];
-    const uint32_t o = off & OFF_MASK, flg = off >> OFF_FLAG_SHIFT;
+    const uint32_t off = a.offsets[(size_t)L.face * P2 + t];
+    double x[3], w[3], d[3];
+    face_record<false>(a.X, off, x);
+    if (cur) {
+      face_record<false>(a.u, off, w);
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      double xv = a.X[o + c];
-      if (cur) xv += a.u[o + c];
-      sx[c * P2 + t] = xv;
-      if (tang) sdu[c * P2 + t] = ((flg >> c) & 1u) ? 0. : a.du[o + c];
+      for (int c = 0; c < 3; c++) x[c] += w[c];
     }
+    if (tang) face_record<true>(a.du, off, d);
+    face_put<P2>(sx, t, x);
+    if (tang) face_put<P2>(sdu, t, d);
   }
   __syncthreads();
-  // xi: per field (x; du) and line (c, j) the value and the derivative at the Q points: t1[2 f][..] = B, t1[2 f + 1][..] = D
+  // xi: per field (x; du) the value and the derivative of every line at the Q points: t1[2 f] = B, t1[2 f + 1] = D
   if (live) {
     const int nout = (tang ? 2 : 1) * N1;
-    for (int o = t; o < nout; o += S) {
+    for (int o = t; o < nout; o += Q2) {
       const int f = o / N1, rem = o % N1, aa = rem % Q, line = rem / Q;
-      const double *src = (f ? sdu : sx) + line * P, *B = sB + aa * P, *D = sD + aa * P;
-      double vb = 0., vd = 0.;
-#pragma unroll
-      for (int i = 0; i < P; i++) { vb += B[i] * src[i]; vd += D[i] * src[i]; }
-      t1[(2 * f) * N1 + rem] = vb; t1[(2 * f + 1) * N1 + rem] = vd;
+      const double *src = (f ? sdu : sx) + line * P;
+      face_dot2<P, 1>(sB + aa * P, src, sD + aa * P, src, t1[(2 * f) * N1 + rem], t1[(2 * f + 1) * N1 + rem]);
     }
   }
   __syncthreads();
@@ -80,19 +68,13 @@ __global__ __launch_bounds__(64) void k_surface(const BasisTables tab, const Sur
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const double *vb = t1 + c * P * Q + aa, *vd = vb + N1;
-      double s0 = 0., s1 = 0.;
-#pragma unroll
-      for (int j = 0; j < P; j++) { s0 += B[j] * vd[j * Q]; s1 += D[j] * vb[j * Q]; }
-      xa[c] = s0; xb[c] = s1;
+      face_dot2<P, Q>(B, vd, D, vb, xa[c], xb[c]);
     }
     if (tang) {
 #pragma unroll
       for (int c = 0; c < 3; c++) {
         const double *vb = t1 + 2 * N1 + c * P * Q + aa, *vd = vb + N1;
-        double s0 = 0., s1 = 0.;
-#pragma unroll
-        for (int j = 0; j < P; j++) { s0 += B[j] * vd[j * Q]; s1 += D[j] * vb[j * Q]; }
-        da[c] = s0; db[c] = s1;
+        face_dot2<P, Q>(B, vd, D, vb, da[c], db[c]);
       }
     }
     const double w = sW[aa] * sW[bb];
@@ -123,30 +105,7 @@ __global__ __launch_bounds__(64) void k_surface(const BasisTables tab, const Sur
     for (int c = 0; c < 3; c++) sv[c * Q2 + t] = v[c];
   }
   __syncthreads();
-  // back along xi: sr[c][b][i] = sum_a B[a][i] v[c][b][a]
-  if (live) {
-    for (int o = t; o < G::NR; o += S) {
-      const int i = o % P, cb = o / P;
-      const double *src = sv + cb * Q;
-      double r = 0.;
-#pragma unroll
-      for (int q = 0; q < Q; q++) r += sB[q * P + i] * src[q];
-      sr[o] = r;
-    }
-  }
-  __syncthreads();
-  // back along eta and the stores: a lane per node, 24-byte records in node order
-  if (live && t < P2) {
-    const int i = t % P, j = t / P;
-    double *out = a.evec + ((size_t)face * P2 + t) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      double g = 0.;
-#pragma unroll
-      for (int b = 0; b < Q; b++) g += sB[b * P + j] * sr[(c * Q + b) * P + i];
-      out[c] = g;
-    }
-  }
+  face_to_nodes<P, Q>(sB, sv, sr, a.evec, L.face, t, live);
 }
 
 // A lane per row of the faces' transpose map: the row's contributors summed in face order (node_sum3: the sum k_assemble forms), then one
@@ -165,24 +124,16 @@ __global__ void k_surface_sum(const uint32_t *rowptr, const uint32_t *cols, cons
   }
 }
 
-template <int P, int Q>
-static hipError_t surface_t(const BasisTables &t, const SurfaceArgs &a, hipStream_t s) {
-  if (a.nface <= 0) return hipSuccess;
-  constexpr int FPW = SurfGeom<P, Q>::FPW;
-  hipLaunchKernelGGL((k_surface<P, Q>), dim3((a.nface + FPW - 1) / FPW), dim3(64), 0, s, t, a);
-  return hipGetLastError();
-}
-
 // P = 2 .. 8, Q = P .. min(P + 2, 8): the fine level's Q = P + qextra, qextra <= 2
 #define CPS_SURFACE_PQ(X)                                                                                       \
   X(2, 2) X(2, 3) X(2, 4) X(3, 3) X(3, 4) X(3, 5) X(4, 4) X(4, 5) X(4, 6) X(5, 5) X(5, 6) X(5, 7) X(6, 6) X(6, 7) \
   X(6, 8) X(7, 7) X(7, 8) X(8, 8)
 
 hipError_t launch_surface(int P, int Q, const BasisTables &t, const SurfaceArgs &a, hipStream_t s, const char **name) {
-#define CPS_SF(Pv, Qv)                                   \
-  if (P == Pv && Q == Qv) {                              \
-    *name = "surface<P=" #Pv ",Q=" #Qv ">";              \
-    return surface_t<Pv, Qv>(t, a, s);                   \
+#define CPS_SF(Pv, Qv)                                                              \
+  if (P == Pv && Q == Qv) {                                                         \
+    *name = "surface<P=" #Pv ",Q=" #Qv ">";                                         \
+    return launch_faces<SurfGeom<Pv, Qv>::FPW>(k_surface<Pv, Qv>, t, a, s);         \
   }
   CPS_SURFACE_PQ(CPS_SF)
 #undef CPS_SF

@@ -43,27 +43,24 @@ def lagrange_tables(P: int, Q: int):
     return B, D, w
 
 
-class SurfaceLoad:
-    """The faces of ``side_ids`` of ``mesh`` under the numbering ``dm``, the node coordinates X (a device L-vector with the library's
-    form) and the library's handle.  ``Q``: Gauss points per direction (default P: the fine level's Q = P + qextra is the caller's to
-    pass).  ``mask``: the Dirichlet byte mask over the L-vector -- masked rows of y are never written, masked entries of du read as
-    zero, u is read as it is (it carries the boundary values)."""
+class FaceTerm:
+    """What a term on the faces of ``side_ids`` of ``mesh`` under the numbering ``dm`` keeps: the face list, the node coordinates (``Xh``
+    on the host; ``X``, a device L-vector made when first asked for), the tables of (P nodes, Q Gauss points), the Dirichlet byte mask
+    over the L-vector -- masked rows of a result are never written, masked entries of du read as zero, u is read as it is (it carries the
+    boundary values) -- and the library's handle (``HANDLE``, a ceed._FaceHandle), or none in the portable NumPy form."""
+    HANDLE = None
 
-    def __init__(self, ceed: cd.Ceed, mesh: HexMesh, dm: DofMap, side_ids, Q: Optional[int] = None, mask=None, portable: bool = False):
+    def __init__(self, ceed: cd.Ceed, mesh: HexMesh, dm: DofMap, side_ids, Q: int, mask=None, portable: bool = False):
         self.ceed, self.L = ceed, ceed.L
-        self.P, self.lsize = dm.P, dm.lsize
-        self.Q = self.P if Q is None else int(Q)
+        self.P, self.lsize, self.Q = dm.P, dm.lsize, int(Q)
         self.side_ids = list(side_ids)
         self.faces = side_set_faces(mesh, dm, self.side_ids)
         self.nface = self.faces.shape[0]
         self.Xh = np.ascontiguousarray(dm.node_coords, dtype=np.float64).reshape(-1)
-        self.portable = bool(portable) or not self.L.has("CeedXSurfaceLoadCreate")
+        self.portable = bool(portable) or not self.L.has(self.HANDLE.PREFIX + "Create")
         self.B, self.D, self.w = lagrange_tables(self.P, self.Q)
-        self.mask = None
-        self.handle = self.X = None
-        if not self.portable:
-            self.X = ceed.vector(self.lsize).set_array(self.Xh)
-            self.handle = cd.SurfaceLoadHandle(ceed, self.P, self.Q, 3 * self.faces, self.lsize)
+        self.mask = self._X = None
+        self.handle = None if self.portable else self.HANDLE(ceed, self.P, self.Q, 3 * self.faces, self.lsize)
         if mask is not None:
             self.set_mask(mask)
 
@@ -76,23 +73,68 @@ class SurfaceLoad:
     def kernel_name(self) -> str:
         return "portable" if self.handle is None else self.handle.kernel_name
 
+    @property
+    def X(self) -> Optional[cd.Vector]:
+        if self._X is None and self.handle is not None:
+            self._X = self.ceed.vector(self.lsize).set_array(self.Xh)
+        return self._X
+
+    @X.setter
+    def X(self, v: Optional[cd.Vector]):
+        self._X = v
+
+    def destroy(self):
+        if self.handle is not None:
+            self.handle.destroy()
+            self.handle = None
+        if self._X is not None:
+            self._X.destroy()
+            self._X = None
+
     # ---- the portable form: NumPy on host arrays ---------------------------------------------------------------------------
+    def _gather(self, field: np.ndarray) -> np.ndarray:
+        """The face nodes' values [face][j (eta)][i (xi)][c] of a nodal field (L-vector)."""
+        return np.asarray(field, dtype=np.float64).reshape(-1)[:self.lsize].reshape(-1, 3)[self.faces].reshape(self.nface, self.P, self.P, 3)
+
     def _derivs(self, field: np.ndarray):
         """d / d xi and d / d eta at the points, [face][b][a][c], of a nodal field (L-vector)."""
-        P = self.P
-        f = field.reshape(-1, 3)[self.faces].reshape(self.nface, P, P, 3)          # [face][j (eta)][i (xi)][c]
+        f = self._gather(field)
         return np.einsum("ai,bj,fjic->fbac", self.D, self.B, f), np.einsum("ai,bj,fjic->fbac", self.B, self.D, f)
 
-    def _to_nodes(self, val: np.ndarray) -> np.ndarray:
-        """The L-vector of sum_q w_q N_a(q) val(q): the face results added in face order; masked rows are zero."""
-        W = self.w[:, None] * self.w[None, :]
-        ge = np.einsum("ai,bj,fbac->fjic", self.B, self.B, val * W[None, :, :, None])
+    def _free(self, du) -> np.ndarray:
+        """du with its masked entries as zeros."""
+        du = np.asarray(du, dtype=np.float64).reshape(-1)[:self.lsize]
+        return du if self.mask is None else np.where(self.mask, 0.0, du)
+
+    def _to_nodes(self, val: np.ndarray, B: np.ndarray) -> np.ndarray:
+        """The L-vector of sum_q B_a(q) val(q), val [face][b][a][c] with the weights inside: face results added in face order; masked
+        rows are zero."""
+        ge = np.einsum("ai,bj,fbac->fjic", B, B, val)
         out = np.zeros((self.lsize // 3, 3))
         np.add.at(out, self.faces.reshape(-1), ge.reshape(-1, 3))
         out = out.reshape(-1)
         if self.mask is not None:
             out[self.mask] = 0.0
         return out
+
+    @staticmethod
+    def _add_host(y: cd.Vector, add: np.ndarray):
+        v = y.to_numpy().copy()
+        v[:add.size] += add
+        y.set_array(v)
+
+
+class SurfaceLoad(FaceTerm):
+    """The surface loads of the faces of ``side_ids`` (FaceTerm).  ``Q``: Gauss points per direction (default P: the fine level's
+    Q = P + qextra is the caller's to pass)."""
+    HANDLE = cd.SurfaceLoadHandle
+
+    def __init__(self, ceed: cd.Ceed, mesh: HexMesh, dm: DofMap, side_ids, Q: Optional[int] = None, mask=None, portable: bool = False):
+        super().__init__(ceed, mesh, dm, side_ids, dm.P if Q is None else Q, mask, portable)
+
+    def _weighted(self, val: np.ndarray) -> np.ndarray:
+        """The L-vector of sum_q w_q N_a(q) val(q)."""
+        return self._to_nodes(val * (self.w[:, None] * self.w[None, :])[None, :, :, None], self.B)
 
     def _position(self, u) -> np.ndarray:
         return self.Xh if u is None else self.Xh + np.asarray(u, dtype=np.float64).reshape(-1)[:self.lsize]
@@ -101,27 +143,18 @@ class SurfaceLoad:
         """g of a traction t as an L-vector (NumPy)."""
         Xa, Xb = self._derivs(self.Xh)
         J = np.linalg.norm(np.cross(Xa, Xb), axis=-1)
-        return self._to_nodes(J[..., None] * np.asarray(t, dtype=np.float64))
+        return self._weighted(J[..., None] * np.asarray(t, dtype=np.float64))
 
     def pressure_host(self, u=None) -> np.ndarray:
         """g(u) of a unit pressure as an L-vector (NumPy); ``u`` None: the reference configuration."""
         xa, xb = self._derivs(self._position(u))
-        return self._to_nodes(np.cross(xa, xb))
+        return self._weighted(np.cross(xa, xb))
 
     def tangent_host(self, u, du) -> np.ndarray:
         """T(u) du of a unit pressure as an L-vector (NumPy); masked entries of du read as zero."""
-        du = np.asarray(du, dtype=np.float64).reshape(-1)[:self.lsize]
-        if self.mask is not None:
-            du = np.where(self.mask, 0.0, du)
         xa, xb = self._derivs(self._position(u))
-        da, db = self._derivs(du)
-        return self._to_nodes(np.cross(da, xb) + np.cross(xa, db))
-
-    @staticmethod
-    def _add_host(y: cd.Vector, add: np.ndarray):
-        v = y.to_numpy().copy()
-        v[:add.size] += add
-        y.set_array(v)
+        da, db = self._derivs(self._free(du))
+        return self._weighted(np.cross(da, xb) + np.cross(xa, db))
 
     # ---- y += ..., on vectors of the Ceed ----------------------------------------------------------------------------------------
     def traction_add(self, t, scale: float, y: cd.Vector):
@@ -144,11 +177,3 @@ class SurfaceLoad:
             self.handle.apply_tangent_add(p, scale, self.X, u, du, y)
         else:
             self._add_host(y, scale * p * self.tangent_host(None if u is None else u.to_numpy(), du.to_numpy()))
-
-    def destroy(self):
-        if self.handle is not None:
-            self.handle.destroy()
-            self.handle = None
-        if self.X is not None:
-            self.X.destroy()
-            self.X = None
