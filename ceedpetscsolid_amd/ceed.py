@@ -28,6 +28,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import portable as pt
+from .portable import (BLOCK_HOST_CHUNK, _np_f64, block_combine_host, block_gram_host, chebyshev_step_pointblock_host,  # noqa: F401
+                       leapfrog_step_host, pointblock_invert_host, pointblock_mult_host)          # (the array forms, under their names here too)
+
 c_int = C.c_int32
 c_scalar_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int32)
@@ -187,61 +191,7 @@ def out_value(fn, ctype, *args):
     return v.value
 
 
-def _np_f64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-# ---- point-block Jacobi: the portable forms of the CEED_EXTERN_OPTIONAL vector operations (NumPy on host arrays) -----------------
-def pointblock_invert_host(blocks: np.ndarray):
-    """(inverses, n_bad) of 3 x 3 blocks [n][c out][c in], as CeedXVectorPointBlockInvert defines them: a component whose diagonal
-    entry is exactly zero is dropped, the inverse of the remaining principal sub-block is embedded in zeros; n_bad counts the blocks
-    with a non-finite or non-positive pivot of the elimination without interchanges."""
-    B = _np_f64(blocks).reshape(-1, 3, 3)
-    keep = B[:, [0, 1, 2], [0, 1, 2]] != 0.0
-    kk = keep[:, :, None] & keep[:, None, :]
-    M = np.where(kk, B, np.eye(3)[None])
-    with np.errstate(all="ignore"):
-        p0 = M[:, 0, 0]
-        l1, l2 = M[:, 1, 0] / p0, M[:, 2, 0] / p0
-        b11, b12 = M[:, 1, 1] - l1 * M[:, 0, 1], M[:, 1, 2] - l1 * M[:, 0, 2]
-        b21, b22 = M[:, 2, 1] - l2 * M[:, 0, 1], M[:, 2, 2] - l2 * M[:, 0, 2]
-        p1 = b11
-        p2 = b22 - (b21 / p1) * b12
-        ok = np.ones(len(M), dtype=bool)
-        for p in (p0, p1, p2):
-            ok &= (p > 0.0) & np.isfinite(p)
-        c00 = M[:, 1, 1] * M[:, 2, 2] - M[:, 1, 2] * M[:, 2, 1]
-        c01 = M[:, 1, 2] * M[:, 2, 0] - M[:, 1, 0] * M[:, 2, 2]
-        c02 = M[:, 1, 0] * M[:, 2, 1] - M[:, 1, 1] * M[:, 2, 0]
-        det = (M[:, 0, 0] * c00 + M[:, 0, 1] * c01) + M[:, 0, 2] * c02
-        inv = np.empty_like(M)
-        inv[:, 0, 0], inv[:, 1, 0], inv[:, 2, 0] = c00 / det, c01 / det, c02 / det
-        inv[:, 0, 1] = (M[:, 0, 2] * M[:, 2, 1] - M[:, 0, 1] * M[:, 2, 2]) / det
-        inv[:, 1, 1] = (M[:, 0, 0] * M[:, 2, 2] - M[:, 0, 2] * M[:, 2, 0]) / det
-        inv[:, 2, 1] = (M[:, 0, 1] * M[:, 2, 0] - M[:, 0, 0] * M[:, 2, 1]) / det
-        inv[:, 0, 2] = (M[:, 0, 1] * M[:, 1, 2] - M[:, 0, 2] * M[:, 1, 1]) / det
-        inv[:, 1, 2] = (M[:, 0, 2] * M[:, 1, 0] - M[:, 0, 0] * M[:, 1, 2]) / det
-        inv[:, 2, 2] = (M[:, 0, 0] * M[:, 1, 1] - M[:, 0, 1] * M[:, 1, 0]) / det
-    return np.where(kk, inv, 0.0), int((~ok).sum())
-
-
-def pointblock_mult_host(blocks: np.ndarray, x: np.ndarray) -> np.ndarray:
-    """w_n = B_n x_n on host arrays (x of 3 n entries, blocks of at least 9 n)."""
-    xv = _np_f64(x).reshape(-1, 3)
-    B = _np_f64(blocks)[:9 * len(xv)].reshape(-1, 3, 3)
-    return ((B[:, :, 0] * xv[:, None, 0] + B[:, :, 1] * xv[:, None, 1]) + B[:, :, 2] * xv[:, None, 2]).reshape(-1)
-
-
-def chebyshev_step_pointblock_host(x, d, b, t, blocks, c1, c2, assign_x):
-    """(x, d, ri) after one step of CeedXVectorChebyshevStepPointBlock on host arrays: ri = b - t (t may be None),
-    d = c1 B ri + c2 d, x = d or x + d."""
-    ri = _np_f64(b) - _np_f64(t) if t is not None else _np_f64(b).copy()
-    dn = c1 * pointblock_mult_host(blocks, ri)
-    if c2 != 0.0:
-        dn = c2 * _np_f64(d) + dn
-    return (dn.copy() if assign_x else _np_f64(x) + dn), dn, ri
-
-
+# ---- point-block Jacobi: the CEED_EXTERN_OPTIONAL vector operations; where the library lacks one, its portable form (portable.py) ------
 def _pb_check(who: str, blocks: "Vector", n: int):
     if n % 3:
         raise CeedError(f"{who}: vector length {n} is not a multiple of 3")
@@ -258,7 +208,7 @@ def pointblock_invert(blocks: "Vector", want_n_bad: bool = True) -> Optional[int
     if blocks.n % 9:
         raise CeedError(f"pointblock_invert: vector length {blocks.n} is not a multiple of 9")
     inv, nb = pointblock_invert_host(blocks.to_numpy())
-    blocks.set_array(inv.reshape(-1))
+    pt.assign(blocks, inv)
     return nb if want_n_bad else None
 
 
@@ -271,7 +221,7 @@ def pointblock_mult(w: "Vector", blocks: "Vector", x: "Vector"):
     if w.n != x.n:
         raise CeedError("pointblock_mult: vector lengths differ")
     _pb_check("pointblock_mult", blocks, x.n)
-    w.set_array(pointblock_mult_host(blocks.to_numpy(), x.to_numpy()))
+    pt.assign(w, pointblock_mult_host(blocks.to_numpy(), x.to_numpy()))
 
 
 def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b: "Vector", t: Optional["Vector"], blocks: "Vector",
@@ -286,30 +236,9 @@ def chebyshev_step_pointblock(x: "Vector", d: "Vector", r: Optional["Vector"], b
     _pb_check("chebyshev_step_pointblock", blocks, x.n)
     xn, dn, ri = chebyshev_step_pointblock_host(None if assign_x else x.to_numpy(), d.to_numpy() if c2 != 0.0 else None, b.to_numpy(),
                                                 t.to_numpy() if t is not None else None, blocks.to_numpy(), c1, c2, assign_x)
-    if r is not None:
-        r.set_array(ri)
-    d.set_array(dn)
-    x.set_array(xn)
-
-
-# ---- explicit dynamics: the portable form of CeedXVectorLeapfrogStep (NumPy on host arrays) ----------------------------------------
-def leapfrog_step_host(x: np.ndarray, vh: np.ndarray, r: np.ndarray, f: Optional[np.ndarray], m: np.ndarray, load: float, c1: float,
-                       c2: float, dt: float, tally: bool = True) -> Optional[float]:
-    """One leapfrog step IN PLACE on the float64 host arrays x and vh (all arrays of one length), as CeedXVectorLeapfrogStep defines it
-    (include/ceed.h): the same operations in the same order, each rounded on its own, so x and vh carry the bits of the device kernel.
-    Rows with m <= 0 are neither read into a result nor written.  Returns 0.5 sum m vm^2 (``tally``), else None."""
-    act = m > 0.0
-    mi, ri, vo = m[act], r[act], vh[act]
-    g = load * f[act] - ri if f is not None else -ri
-    q = g / mi
-    vn = c1 * vo + c2 * q
-    ke = None
-    if tally:
-        vm = 0.5 * (vo + vn)
-        ke = 0.5 * float(np.sum(mi * (vm * vm)))
-    vh[act] = vn
-    x[act] = x[act] + dt * vn
-    return ke
+    for v, a in ((r, ri), (d, dn), (x, xn)):
+        if v is not None:
+            pt.assign(v, a)
 
 
 class Csr:
@@ -726,12 +655,9 @@ class Vector:
                 raise CeedError(f"{who}: scalars must not be one of the operands ({name})")
         if scalars is not None and not 0 <= slot < scalars.n:
             raise CeedError(f"{who}: scalar {slot} of {scalars.n}")
-        with self.host_view(True) as xa, vh.host_view(True) as va, r.host_view(False) as ra, m.host_view(False) as ma:
-            if f is not None:
-                with f.host_view(False) as fa:
-                    ke = leapfrog_step_host(xa[:n], va[:n], ra[:n], fa[:n], ma[:n], load, c1, c2, dt, scalars is not None)
-            else:
-                ke = leapfrog_step_host(xa[:n], va[:n], ra[:n], None, ma[:n], load, c1, c2, dt, scalars is not None)
+        with self.host_view(True) as xa, vh.host_view(True) as va, r.host_view(False) as ra, m.host_view(False) as ma, \
+                (f.host_view(False) if f is not None else contextlib.nullcontext()) as fa:
+            ke = leapfrog_step_host(xa[:n], va[:n], ra[:n], None if f is None else fa[:n], ma[:n], load, c1, c2, dt, scalars is not None)
         if scalars is not None:
             with scalars.host_view(True) as sa:
                 sa[slot] = ke
@@ -752,9 +678,8 @@ class Vector:
             self.L.lib.CeedVectorDestroy(C.byref(self.h))
 
 
-# ---- block vectors: CeedXVectorBlockGram / CeedXVectorBlockCombine and their portable forms (NumPy on host arrays) ----------------
+# ---- block vectors: CeedXVectorBlockGram / CeedXVectorBlockCombine; their portable forms are in portable.py ------------------------
 BLOCK_MAX_COLS = 48
-BLOCK_HOST_CHUNK = 1024          # rows per np.add.reduce of the portable Gram matrix: a fixed chunking, so it is deterministic too
 
 
 def block_limits(lib: CeedLib):
@@ -766,27 +691,6 @@ def block_limits(lib: CeedLib):
     v = [c_int() for _ in range(5)]
     lib.CeedXVectorBlockGetLimits(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
-
-
-def block_gram_host(A: np.ndarray, B: np.ndarray, w: Optional[np.ndarray] = None) -> np.ndarray:
-    """G[i][j] = sum_r w[r] (A[i][r] B[j][r]) of host arrays [ka][n], [kb][n]: the products of BLOCK_HOST_CHUNK rows summed by
-    np.add.reduce, the chunks added in row order."""
-    ka, n = A.shape
-    G = np.zeros((ka, B.shape[0]))
-    for c in range(0, n, BLOCK_HOST_CHUNK):
-        T = A[:, None, c:c + BLOCK_HOST_CHUNK] * B[None, :, c:c + BLOCK_HOST_CHUNK]
-        if w is not None:
-            T = w[c:c + BLOCK_HOST_CHUNK] * T
-        G += np.add.reduce(T, axis=2)
-    return G
-
-
-def block_combine_host(Y: np.ndarray, A: np.ndarray, Cm: np.ndarray, beta: float):
-    """Y[j] = sum_i A[i] Cm[i][j] + beta Y[j] in place on host arrays [ky][n], [ka][n]; i in order; beta == 0 does not read Y."""
-    acc = np.zeros(Y.shape)
-    for i in range(A.shape[0]):
-        acc += Cm[i][:, None] * A[i][None, :]
-    Y[...] = acc if beta == 0.0 else acc + beta * Y
 
 
 def _block_check(who: str, n: int, ld: int, ranges):
@@ -893,9 +797,7 @@ class BlockVector:
             raise CeedError(f"BlockVector.gram: G holds {G.n} entries, {ka} x {kb} are written")
         if weight is not None and weight.n < self.n:
             raise CeedError(f"BlockVector.gram: the weight holds {weight.n} entries, n = {self.n} are read")
-        g = G.to_numpy()
-        g[:ka * kb] = block_gram_host(self._host(a0, ka), other._host(b0, kb), None if weight is None else weight.to_numpy()[:self.n]).reshape(-1)
-        G.set_array(g)
+        pt.assign(G, block_gram_host(self._host(a0, ka), other._host(b0, kb), None if weight is None else weight.to_numpy()[:self.n]))
 
     def combine(self, A: "BlockVector", Cm, y0: int = 0, ky: Optional[int] = None, a0: int = 0, ka: Optional[int] = None, beta: float = 0.0):
         """self_{y0+j} = sum_i A_{a0+i} Cm[i][j] + beta self_{y0+j} (CeedXVectorBlockCombine); ``Cm`` is a host array [ka][ky] (written to

@@ -1,7 +1,7 @@
 """Frictionless penalty contact of side sets with a rigid analytic obstacle: a plane or a sphere.
 
 The contact surface Gamma is a union of element faces named by side-set ids; the faces, their node order and their Gauss points are those
-of ``surface.py`` (``mesh.side_set_faces``, ``surface.lagrange_tables``).  The obstacle is a signed distance g(x), g > 0 meaning
+of ``surface.py`` (``mesh.side_set_faces``, ``portable.lagrange_tables``).  The obstacle is a signed distance g(x), g > 0 meaning
 separated, with n = grad g:
 
     plane    g = (x - x0) . n          n the unit normal pointing from the obstacle to the body;  grad grad g = 0
@@ -22,8 +22,7 @@ no obstacle, no geometry and no coarse displacement, and because the p-spaces ar
 Galerkin product P^T C_fine P on the free dofs.  The diagonal is d_{a,c} = sum_q B_a(q)^2 K_q[c][c] (squared tables).
 
 On the device these are the library's CeedXContact* entry points (include/ceed_contact.h, csrc/kernels_contact.hip).  Where the library
-lacks them (the CPU oracle), or with ``portable=True``, the same sums are formed in NumPy: plain ``einsum`` in float64, face
-contributions added in face order.  The portable form is the device tests' yardstick.
+lacks them (the CPU oracle), or with ``portable=True``, the same sums are formed in NumPy on the tensor layer of ``portable.py``.
 
 Out of scope: friction, deformable-deformable contact, augmented Lagrangian updates, several ranks, dynamics.
 """
@@ -34,6 +33,7 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
+from . import portable as pt
 from .mesh import DofMap, HexMesh
 from .surface import FaceTerm
 
@@ -98,7 +98,7 @@ class ContactSurface(FaceTerm):
         if self.kind is None:
             raise ValueError("contact: no obstacle set (set_obstacle)")
         Xa, Xb = self._derivs(self.Xh)
-        x = np.einsum("ai,bj,fjic->fbac", self.B, self.B, self._gather(self.Xh) + self._gather(u))
+        x = pt.to_points(self._gather(self.Xh) + self._gather(u), self.B, self.B)
         wJ = np.linalg.norm(np.cross(Xa, Xb), axis=-1) * (self.w[:, None] * self.w[None, :])[None]
         if self.kind == cd.CONTACT_PLANE:
             n = np.broadcast_to(self.par[3:6], x.shape)
@@ -144,7 +144,7 @@ class ContactSurface(FaceTerm):
 
     def tangent_host(self, state, du) -> np.ndarray:
         """C du as an L-vector from a state (of this or of a finer p-level); masked entries of du read as zero."""
-        dq = np.einsum("ai,bj,fjic->fbac", self.B, self.B, self._gather(self._free(du)))
+        dq = pt.to_points(self._gather(self._free(du)), self.B, self.B)
         return self._to_nodes(np.einsum("fbacd,fbad->fbac", self._K(state), dq), self.B)
 
     def diagonal_host(self, state) -> np.ndarray:
@@ -159,25 +159,23 @@ class ContactSurface(FaceTerm):
             self.handle.apply_residual_add(scale, self.X, u, y, state)
         else:
             r, st = self.residual_host(u.to_numpy())
-            full = state.to_numpy().copy()
-            full[:st.size] = st.reshape(-1)
-            state.set_array(full)
+            pt.assign(state, st)
             if self.nface:
-                self._add_host(y, scale * r)
+                pt.add(y, scale * r)
 
     def tangent_add(self, scale: float, state: cd.Vector, du: cd.Vector, y: cd.Vector):
         """y += scale C du."""
         if self.handle is not None:
             self.handle.apply_tangent_add(scale, state, du, y)
         elif self.nface:
-            self._add_host(y, scale * self.tangent_host(state.to_numpy(), du.to_numpy()))
+            pt.add(y, scale * self.tangent_host(state.to_numpy(), du.to_numpy()))
 
     def diagonal_add(self, scale: float, state: cd.Vector, d: cd.Vector):
         """d += scale diag C."""
         if self.handle is not None:
             self.handle.diagonal_add(scale, state, d)
         elif self.nface:
-            self._add_host(d, scale * self.diagonal_host(state.to_numpy()))
+            pt.add(d, scale * self.diagonal_host(state.to_numpy()))
 
     # ---- read from the state -------------------------------------------------------------------------------------------------------
     def _gaps(self, state) -> np.ndarray:

@@ -7,10 +7,9 @@ N the tensor Lagrange functions of the level's basis (P nodes per direction on t
 level's quadrature data, c a coefficient (the density, or a0 x density in the effective tangent K + a0 M of ``dynamics.NewmarkPMG``).
 
 On the device this is the library's operator graph of the QFunction ``Mass`` (include/ceed.h; csrc/kernels_mass.hip): u INTERP active,
-qdata NONE passive, v INTERP active, the coefficient in the context.  Where the library has no functor of that name
-(``Ceed.has_qfunction``: the CPU oracle), or with ``portable=True``, the same sums are formed in NumPy: plain ``einsum`` in float64 with
-the 1-D table of ``lv.basisu`` and component 0 of the quadrature data read back once, element contributions added in element order.  The
-portable form is the device tests' yardstick, as the surface loads' is.
+qdata NONE passive, v INTERP active, the coefficient in the context.  Where the library has no functor of that name (the CPU oracle), or
+with ``portable=True``, the same sums are formed in NumPy on the tensor layer of ``portable.py`` with the 1-D table of ``lv.basisu`` and
+component 0 of the quadrature data read back once (which form runs where, and why it is the device tests' yardstick: DESIGN.md 2).
 
 Dirichlet mask (the level's, unless a restriction of the caller's is given): masked entries of x read as zero (``mask_mode`` 3, the
 tangent's form) or as they are (``mask_mode`` 2, the residual's form: x carries the boundary values); masked rows of y are stored as
@@ -23,6 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
+from . import portable as pt
 from .solid import SolidProblem
 
 
@@ -47,6 +47,7 @@ class MassOperator:
         if off is None:
             raise ValueError("a restriction of the caller's needs its offsets too")
         self.offsets = np.asarray(off, dtype=np.int64).reshape(self.ne, self.P ** 3)
+        self.nodes = (self.offsets // 3).reshape((self.ne,) + 3 * (self.P,))                      # [e][k][j][i]
         self.mask = (np.asarray(lv.mask).reshape(-1)[:self.lsize] != 0) if own and prob.fused_bc else None
         self.portable = (not c.has_qfunction("Mass")) if portable is None else bool(portable)
         self._B = self._W = None
@@ -81,39 +82,29 @@ class MassOperator:
         return self._B, self._W
 
     def _sum(self, ve: np.ndarray) -> np.ndarray:
-        """Element results [e][n][3] added into an L-vector in element order."""
-        out = np.zeros((self.lsize // 3 + 1, 3))
-        np.add.at(out, (self.offsets // 3).reshape(-1), ve.reshape(-1, 3))
-        return out.reshape(-1)[:self.lsize]
+        """Element results [e][k][j][i][3] added into an L-vector in element order."""
+        return pt.node_sum(self.nodes, ve, self.lsize // 3 + 1).reshape(-1)[:self.lsize]
 
-    def apply_host(self, x) -> np.ndarray:
-        """M x as an L-vector (NumPy); masked rows are NOT dropped here (``apply`` / ``apply_add`` do)."""
+    def apply_host(self, x, mask_mode: Optional[int] = None) -> np.ndarray:
+        """M x as an L-vector (NumPy), in the operator's mask mode unless one is given; masked rows are NOT dropped here (``apply`` /
+        ``apply_add`` do)."""
         B, W = self._tables()
-        P = self.P
         x = np.asarray(x, dtype=np.float64).reshape(-1)[:self.lsize]
-        if self.mask is not None and self.mask_mode & 1:
+        if self.mask is not None and (self.mask_mode if mask_mode is None else mask_mode) & 1:
             x = np.where(self.mask, 0.0, x)
-        xp = np.concatenate([x, np.zeros(3)])
-        ue = xp[(self.offsets[:, :, None] + np.arange(3)).reshape(-1)].reshape(self.ne, P, P, P, 3)      # [e][k][j][i][c]
-        uq = np.einsum("ai,bj,dk,ekjic->edbac", B, B, B, ue)
-        vq = uq * (self.coef * W)[..., None]
-        return self._sum(np.einsum("ai,bj,dk,edbac->ekjic", B, B, B, vq).reshape(self.ne, P ** 3, 3))
+        uq = pt.to_points(pt.gather(x, self.nodes, self.lsize), B, B, B)
+        return self._sum(pt.to_nodes(uq * (self.coef * W)[..., None], B, B, B))
 
     def diagonal_host(self) -> np.ndarray:
         B, W = self._tables()
         B2 = B * B
-        de = np.einsum("ai,bj,dk,edba->ekji", B2, B2, B2, self.coef * W).reshape(self.ne, self.P ** 3)
-        d = self._sum(np.repeat(de[:, :, None], 3, axis=2))
+        d = self._sum(np.repeat(pt.to_nodes(self.coef * W, B2, B2, B2)[..., None], 3, axis=-1))
         if self.mask is not None:
             d[self.mask] = 0.0
         return d
 
-    def _store_host(self, y: cd.Vector, r: np.ndarray, add: bool):
-        v = y.to_numpy().copy() if add else np.zeros(y.n)
-        if self.mask is not None:
-            r = np.where(self.mask, 0.0, r)
-        v[:self.lsize] += r
-        y.fill(v)
+    def _free_rows(self, r: np.ndarray) -> np.ndarray:
+        return r if self.mask is None else np.where(self.mask, 0.0, r)
 
     # ---- on vectors of the Ceed ----------------------------------------------------------------------------------------------
     def apply(self, x: cd.Vector, y: cd.Vector):
@@ -121,33 +112,27 @@ class MassOperator:
         if self.op is not None:
             self.op.apply(x, y)
         else:
-            self._store_host(y, self.apply_host(x.to_numpy()), False)
+            pt.assign(y, self._free_rows(self.apply_host(x.to_numpy())), y.n)
 
     def apply_add(self, x: cd.Vector, y: cd.Vector):
         """y += M x (masked rows and everything beyond the L-size left alone)."""
         if self.op is not None:
             self.op.apply_add(x, y)
         else:
-            self._store_host(y, self.apply_host(x.to_numpy()), True)
+            pt.add(y, self._free_rows(self.apply_host(x.to_numpy())))
 
     def diagonal(self, d: cd.Vector):
         """d = diag M: c sum_q N_a(q)^2 w det J(q), the same for the three components; zero on masked rows."""
         if self.op is not None:
             self.op.assemble_diagonal(d)
         else:
-            v = np.zeros(d.n)
-            v[:self.lsize] = self.diagonal_host()
-            d.fill(v)
+            pt.assign(d, self.diagonal_host(), d.n)
 
     # ---- the lumped mass: row sums ---------------------------------------------------------------------------------------------
     def lumped_host(self) -> np.ndarray:
         """m_i = c sum_e sum_q N_i(q) w det J(q), the row sums of the consistent mass matrix (M 1 with the ones read unmasked, whatever
         the mask mode); zero on masked rows.  Positive on Gauss-Lobatto nodes for the meshes of this project."""
-        mode, self.mask_mode = self.mask_mode, 2
-        try:
-            d = self.apply_host(np.ones(self.lsize))
-        finally:
-            self.mask_mode = mode
+        d = self.apply_host(np.ones(self.lsize), mask_mode=2)
         if self.mask is not None:
             d[self.mask] = 0.0
         return d
@@ -156,10 +141,7 @@ class MassOperator:
         """d = the lumped mass (``lumped_host``) on a vector of the Ceed: the mass apply on a vector of ones; entries of d beyond the
         L-size are zero."""
         if self.op is None:
-            v = np.zeros(d.n)
-            v[:self.lsize] = self.lumped_host()
-            d.fill(v)
-            return
+            return pt.assign(d, self.lumped_host(), d.n)
         ones = self.ceed.vector(self.lsize).set_value(1.0)
         swap = self.mask is not None and self.mask_mode != 2
         m8 = self.mask.astype(np.uint8) if swap else None

@@ -11,6 +11,7 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
+from . import portable as pt
 from .solid import SolidProblem
 
 ENERGY_QF = {"linElas": ("linElas.h", "LinElasEnergy"), "hyperSS": ("hyperSS.h", "HyperSSEnergy"),
@@ -128,10 +129,10 @@ class Stress:
     ``xloc`` is the local displacement vector WITH the boundary values inserted, as ``StrainEnergy`` and ``Diagnostics`` take it.  On the
     device these are two operator graphs of the QFunctions ``{LinElas,HyperSS,HyperFS}Stress`` (csrc/kernels_stress.hip): (du GRAD
     active, qdata NONE) -> stress NONE(6) on a strided restriction, or -> stress INTERP(7) -- w det J {sigma, 1} summed per node in
-    element order -- on a 7-component restriction.  Where the library has no functor of that name (``Ceed.has_qfunction``: the CPU
-    oracle), or with ``portable=True``, the same sums are formed in NumPy: plain ``einsum`` in float64 with the tables of ``lv.basisu``
-    and the quadrature data read back once, element contributions added in element order.  The portable form is the device tests'
-    yardstick.  Several ranks are refused: the interface nodes of an element partition would need both sums exchanged."""
+    element order -- on a 7-component restriction.  Where the library has no functor of that name (the CPU oracle), or with
+    ``portable=True``, the same sums are formed in NumPy on the tensor layer of ``portable.py`` with the tables of ``lv.basisu`` and the
+    quadrature data read back once (which form runs where, and why it is the device tests' yardstick: DESIGN.md 2).  Several ranks
+    are refused: the interface nodes of an element partition would need both sums exchanged."""
 
     def __init__(self, prob: SolidProblem, problem: str, portable: Optional[bool] = None, halo=None):
         if problem not in STRESS_QF:
@@ -149,6 +150,7 @@ class Stress:
         self.nnodes = lv.dofmap.nnodes
         self.nu, self.E = float(prob.phys[0]), float(prob.phys[1])
         self.offsets = (np.asarray(lv.dofmap.offsets(), dtype=np.int64) & 0x1FFFFFFF).reshape(self.ne, self.P ** 3)
+        self.nodes = (self.offsets // 3).reshape((self.ne,) + 3 * (self.P,))                      # [e][k][j][i]
         src, name = STRESS_QF[problem]
         self.portable = (not c.has_qfunction(name)) if portable is None else bool(portable)
         self._tab = None
@@ -196,10 +198,8 @@ class Stress:
     def grad_host(self, x) -> np.ndarray:
         """The physical displacement gradient at the points, [nelem][Q][Q][Q][c][n] = d u_c / d x_n, from a host array."""
         B, G, _, dX = self._tables()
-        P = self.P
-        x = np.asarray(x, dtype=np.float64).reshape(-1)
-        ue = x[(self.offsets[:, :, None] + np.arange(3)).reshape(-1)].reshape(self.ne, P, P, P, 3)        # [e][k][j][i][c]
-        du = np.stack([np.einsum("ai,bj,dk,ekjic->edbac", *t, ue) for t in ((G, B, B), (B, G, B), (B, B, G))], axis=-1)   # [e][k][j][i][c][m]
+        ue = pt.gather(x, self.nodes, 3 * self.nnodes)                                     # [e][k][j][i][c]
+        du = np.stack([pt.to_points(ue, *t) for t in ((G, B, B), (B, G, B), (B, B, G))], axis=-1)          # [e][k][j][i][c][m]
         return np.einsum("ekjicm,emnkji->ekjicn", du, dX)                                  # g[c][n] = sum_m du[c][m] dXdx[m][n]
 
     def points_host(self, x) -> np.ndarray:
@@ -210,12 +210,9 @@ class Stress:
     def nodal_sums_host(self, x) -> np.ndarray:
         """[nnodes][7]: w det J {sigma, 1} through B^T, element contributions added in element order."""
         B, _, W, _ = self._tables()
-        Q, P = self.Q, self.P
+        Q = self.Q
         v = np.concatenate([self.points_host(x).reshape(self.ne, 6, Q, Q, Q), np.ones((self.ne, 1, Q, Q, Q))], axis=1) * W[:, None]
-        ve = np.einsum("ai,bj,dk,emdba->ekjim", B, B, B, v).reshape(self.ne * P ** 3, 7)
-        out = np.zeros((self.nnodes, 7))
-        np.add.at(out, (self.offsets // 3).reshape(-1), ve)
-        return out
+        return pt.node_sum(self.nodes, pt.to_nodes(np.moveaxis(v, 1, -1), B, B, B), self.nnodes)      # (a view: v stays [e][m][d][b][a])
 
     # ---- on vectors of the Ceed ----------------------------------------------------------------------------------------------
     def _sync(self):
@@ -228,7 +225,7 @@ class Stress:
         """The stress at the quadrature points, [nelem][6][Q^3] (point i + Q (j + Q k)): a host copy, or with ``numpy=False`` the
         tensor behind the output vector (valid until the next call)."""
         if self.portable:
-            self.spts.fill(self.points_host(xloc.to_numpy()).reshape(-1))
+            pt.assign(self.spts, self.points_host(xloc.to_numpy()))
         else:
             self._sync()
             self.op_pts.apply(xloc, self.spts)
@@ -240,7 +237,7 @@ class Stress:
         torch = self._torch
         if self.portable:
             x = np.zeros(self.lv.dofmap.lsize) if xloc is None else xloc.to_numpy()
-            self.snod.fill(self.nodal_sums_host(x).reshape(-1))
+            pt.assign(self.snod, self.nodal_sums_host(x))
         else:
             x = xloc if xloc is not None else self.ceed.vector(self.lv.dofmap.lsize).set_value(0.0)
             self._sync()

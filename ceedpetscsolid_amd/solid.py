@@ -31,6 +31,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import ceed as cd
+from . import portable as pt
 from .mesh import DofMap, HexMesh, build_dofmap, dirichlet_mask, side_set_nodes, boundary_nodes
 
 # problemOptions[] of setuplibceed.c:41-107 (hyperFSIncomp is dead code upstream)
@@ -344,9 +345,9 @@ class SolidProblem:
         """The 3 x 3 nodal blocks of the level's Jacobian (CeedOperatorLinearAssemblePointBlockDiagonal): [node][comp out][comp in],
         the block of the node at component-0 L-offset o at 3 * o; ``blocks`` holds 3 x the level's L-size.  Like ``get_diag`` it reads
         the QFunction context of the level's Jacobian as it is at the call (a smoother Poisson ratio swapped in stays in force).
-        Where the library lacks the entry point (the CPU oracle) the blocks are the diagonal blocks of the element
-        matrices of ``AssembledLevel(self, level)``, summed over the elements of a node: 3 P^3 applies through include/ceed.h calls
-        only, exact.  Constrained rows and columns are zero there (not the unit diagonal of the assembled matrix)."""
+        Where the library lacks the entry point (the CPU oracle) the blocks are the diagonal blocks of the element matrices of
+        ``AssembledLevel(self, level)``, summed over the elements of a node (``portable.pointblock_diag_host``): 3 P^3 applies through
+        include/ceed.h calls only, exact.  Constrained rows and columns are zero there (not the unit diagonal of the assembled matrix)."""
         lv = self.levels[level]
         if blocks.n < 3 * lv.dofmap.lsize:
             raise cd.CeedError(f"point-block diagonal vector too short: {blocks.n} entries for 3 x the L-size {lv.dofmap.lsize}")
@@ -359,19 +360,9 @@ class SolidProblem:
         asm = self._pb_asm[level]
         asm.qf.set_context(lv.qfJacob._ctx, reported_size=8)
         asm.assemble()
-        ne, nd = asm.ne, asm.nd
-        P3 = nd // 3
-        K = asm.coo.to_numpy().reshape(P3, 3, ne, P3, 3)              # [n' c_in][e][n c_out]: column (n', c_in) of every element matrix
-        n = np.arange(P3)
-        eb = K[n, :, :, n, :].transpose(2, 0, 3, 1)                   # [e][n][c_out][c_in]
-        off = np.asarray(lv.dofmap.offsets(), dtype=np.int64).reshape(ne, P3)
-        out = np.zeros((blocks.n // 9 + 1, 3, 3))
-        np.add.at(out, off // 3, eb)                                  # elements in order
-        if self.fused_bc:
-            m = (lv.mask.reshape(-1, 3) != 0)
-            nn = m.shape[0]
-            out[:nn][m[:, :, None] | m[:, None, :]] = 0.0
-        blocks.set_array(out.reshape(-1)[:blocks.n])
+        nodes = np.asarray(lv.dofmap.offsets(), dtype=np.int64).reshape(asm.ne, asm.nd // 3) // 3
+        out = pt.pointblock_diag_host(asm.coo.to_numpy(), nodes, blocks.n // 9 + 1, lv.mask if self.fused_bc else None)
+        pt.assign(blocks, out.reshape(-1)[:blocks.n])
 
     # --------------------------------------------------------------- helpers
     def smooth_state(self, amplitude: float = 0.1, origin=None, span=None) -> np.ndarray:

@@ -14,9 +14,8 @@ T(u) is symmetric on the variations that vanish on the rim of the loaded surface
 (a tube with clamped ends) -- and not otherwise: a follower pressure on a patch with a free rim is not conservative.
 
 On the device these are the library's CeedXSurfaceLoad* entry points (csrc/kernels_surface.hip).  Where the library lacks them (the CPU
-oracle), or with ``portable=True``, the same sums are formed in NumPy: plain ``einsum`` in float64 with tables built from
-``mesh.gll_nodes`` and ``numpy.polynomial.legendre.leggauss``, face contributions added in face order.  The portable form is the
-tests' yardstick for the device, as the point-block diagonal's portable form is.
+oracle), or with ``portable=True``, the same sums are formed in NumPy on the tensor layer and the tables of ``portable.py`` (which form
+runs where, and why it is the device tests' yardstick: DESIGN.md 2).
 """
 from __future__ import annotations
 
@@ -25,22 +24,9 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
-from .mesh import DofMap, HexMesh, gll_nodes, side_set_faces
-
-
-def lagrange_tables(P: int, Q: int):
-    """(B, D, w): values and derivatives (Q x P) of the P Lagrange functions on the Gauss-Lobatto points at the Q Gauss points, and the
-    Gauss weights."""
-    nodes = gll_nodes(P)
-    pts, w = np.polynomial.legendre.leggauss(Q)
-    B, D = np.zeros((Q, P)), np.zeros((Q, P))
-    for i in range(P):
-        others = [k for k in range(P) if k != i]
-        den = np.prod([nodes[i] - nodes[k] for k in others])
-        B[:, i] = np.prod([pts - nodes[k] for k in others], axis=0) / den
-        for m in others:
-            D[:, i] += np.prod([pts - nodes[k] for k in others if k != m] + [np.ones(Q)], axis=0) / den
-    return B, D, w
+from . import portable as pt
+from .mesh import DofMap, HexMesh, side_set_faces
+from .portable import lagrange_tables          # (importable from here too, as before)
 
 
 class FaceTerm:
@@ -94,12 +80,12 @@ class FaceTerm:
     # ---- the portable form: NumPy on host arrays ---------------------------------------------------------------------------
     def _gather(self, field: np.ndarray) -> np.ndarray:
         """The face nodes' values [face][j (eta)][i (xi)][c] of a nodal field (L-vector)."""
-        return np.asarray(field, dtype=np.float64).reshape(-1)[:self.lsize].reshape(-1, 3)[self.faces].reshape(self.nface, self.P, self.P, 3)
+        return pt.gather(field, self.faces.reshape(self.nface, self.P, self.P), self.lsize)
 
     def _derivs(self, field: np.ndarray):
         """d / d xi and d / d eta at the points, [face][b][a][c], of a nodal field (L-vector)."""
         f = self._gather(field)
-        return np.einsum("ai,bj,fjic->fbac", self.D, self.B, f), np.einsum("ai,bj,fjic->fbac", self.B, self.D, f)
+        return pt.to_points(f, self.D, self.B), pt.to_points(f, self.B, self.D)
 
     def _free(self, du) -> np.ndarray:
         """du with its masked entries as zeros."""
@@ -109,19 +95,10 @@ class FaceTerm:
     def _to_nodes(self, val: np.ndarray, B: np.ndarray) -> np.ndarray:
         """The L-vector of sum_q B_a(q) val(q), val [face][b][a][c] with the weights inside: face results added in face order; masked
         rows are zero."""
-        ge = np.einsum("ai,bj,fbac->fjic", B, B, val)
-        out = np.zeros((self.lsize // 3, 3))
-        np.add.at(out, self.faces.reshape(-1), ge.reshape(-1, 3))
-        out = out.reshape(-1)
+        out = pt.node_sum(self.faces, pt.to_nodes(val, B, B), self.lsize // 3).reshape(-1)
         if self.mask is not None:
             out[self.mask] = 0.0
         return out
-
-    @staticmethod
-    def _add_host(y: cd.Vector, add: np.ndarray):
-        v = y.to_numpy().copy()
-        v[:add.size] += add
-        y.set_array(v)
 
 
 class SurfaceLoad(FaceTerm):
@@ -162,18 +139,18 @@ class SurfaceLoad(FaceTerm):
         if self.handle is not None:
             self.handle.apply_add(cd.SURFACE_TRACTION, t, scale, self.X, None, y)
         else:
-            self._add_host(y, scale * self.traction_host(t))
+            pt.add(y, scale * self.traction_host(t))
 
     def pressure_add(self, p: float, scale: float, u: Optional[cd.Vector], y: cd.Vector):
         """y += scale p g^pressure(u)."""
         if self.handle is not None:
             self.handle.apply_add(cd.SURFACE_PRESSURE, (p, 0.0, 0.0), scale, self.X, u, y)
         else:
-            self._add_host(y, scale * p * self.pressure_host(None if u is None else u.to_numpy()))
+            pt.add(y, scale * p * self.pressure_host(None if u is None else u.to_numpy()))
 
     def tangent_add(self, p: float, scale: float, u: Optional[cd.Vector], du: cd.Vector, y: cd.Vector):
         """y += scale p T(u) du."""
         if self.handle is not None:
             self.handle.apply_tangent_add(p, scale, self.X, u, du, y)
         else:
-            self._add_host(y, scale * p * self.tangent_host(None if u is None else u.to_numpy(), du.to_numpy()))
+            pt.add(y, scale * p * self.tangent_host(None if u is None else u.to_numpy(), du.to_numpy()))
