@@ -50,6 +50,9 @@ struct CeedOptions {
   int pipe_min_total_rounds = 20;   // CEED_MI355X_PIPE_MIN_TOTAL: rounds a whole apply must have to be pipelined
   int pipe_min_rounds = 4;       // CEED_MI355X_PIPE_MIN_ROUNDS: rounds a segment must have (0: tests on small meshes)
   int pencil_waves = 0;          // CEED_MI355X_PENCIL_WAVES: persistent waves per CU of the fused kernel (tuning hook)
+                                 // KEEP: the one way to shrink the persistent grid below the group count of a test-sized mesh -- with it set to 1
+                                 // tests/test_fused_rounds_gpu.py runs a second and third iteration of the group loop in every instantiation; the
+                                 // sweep of tests/test_kernel_matrix_gpu.py runs one group per wave ("The instantiations are stated twice")
   // split-phase apply with the halo exchange (CeedXOperatorApplyWithHalo): kept for tuning on a real multi-GPU node
   int ovl_mode = 0;              // CEED_MI355X_OVL_MODE: 0 (default) the whole apply, then the exchange, in order on one stream;
                                  // 1 split-phase on one stream (interface elements, exchange started, interior elements: round 2's
