@@ -211,8 +211,14 @@ def test_products_follow_the_variable_operand_on_device(gpu):
     products_follow_the_variable_operand(gpu, 1e-13)
 
 
+# 1023 .. 1025 and 1500: k_symmetrize's grid (grid_for in kernels_csr.hip) covers 4096 x 256 = 1024^2 entries of the matrix -- one short of a grid
+# row-wise, a whole grid, into the second lap, and past two laps (tests/_plain_kernels.py)
+DENSE_INVERSE_SIZES = [1, 31, 32, 33, 64, 65, 70, 1023, 1024, 1025, 1080, 1500]
+DENSE_INVERSE_ENTRIES = [n * n for n in DENSE_INVERSE_SIZES]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [1, 31, 32, 33, 64, 65, 70, 1080, 1500])
+@pytest.mark.parametrize("n", DENSE_INVERSE_SIZES)
 def test_dense_inverse_on_device(gpu, n):
     dense_inverse(gpu, n, 1e-10)
 
