@@ -3,7 +3,8 @@
 // side at P = 2, 3, 5 (three interlaced components, nodes numbered lexicographically over the box), a 6 x 6 x 6 box at P = 3 for the
 // pipelined map.  What is asserted are properties of the results, not the algorithms again:
 //   transpose map (whole, shell, with priority rows), interior nodes, segment count and boundaries (two full-size shapes by arithmetic),
-//   the pipelined re-ordering, the Dirichlet flags, the owner map, the pack fold and the arrival lists of a halo, empty inputs.
+//   the pipelined re-ordering, the Dirichlet flags, the owner map, the pack fold and the arrival lists of a halo, empty inputs;
+//   the flags, row flags, owner map and folded rows once more under component-wise masks of all eight node patterns, entry by entry.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -225,6 +226,87 @@ static void test_halo(int n, int P) {
   CHECK(halo_entry_off_priority(M.node_off, M.nprio, none) == -1, "%s: empty halo off the priority rows", what);
 }
 
+// Component-wise masks: node k carries the pattern (k + shift) % 8, bit c = component c masked, so every one of the eight patterns
+// occurs (asserted).  Every builder that folds mask bytes into flag bits against a loop over the L-vector ENTRIES: one byte, one bit.
+static int test_patterns(int n, int P, int shift) {
+  char what[96];
+  snprintf(what, sizeof what, "patterns on box %d^3 P=%d shift %d", n, P, shift);
+  const Box b = make_box(n, n, P);
+  std::vector<unsigned char> mask((size_t)b.lsize, 0);
+  int seen = 0;
+  for (int k = 0; k < b.nnodes; k++) {
+    const int pat = (k + shift) % 8;
+    seen |= 1 << pat;
+    for (int c = 0; c < 3; c++) mask[(size_t)3 * k + c] = (unsigned char)((pat >> c) & 1 ? 1 + 37 * c : 0);     // any non-zero byte masks
+  }
+  CHECK(seen == 0xFF, "%s: patterns %02x only", what, seen);
+  const std::vector<uint32_t> fo = flagged_offsets(b.off, mask.data(), 3, 1);
+  CHECK(fo.size() == b.off.size(), "%s: %zu flagged offsets", what, fo.size());
+  for (size_t i = 0; i < fo.size() && i < b.off.size(); i++) {
+    CHECK((fo[i] & OFF_MASK) == (uint32_t)b.off[i], "%s: flagged offset %zu lost its offset", what, i);
+    for (int c = 0; c < 3; c++)
+      CHECK(((fo[i] >> (OFF_FLAG_SHIFT + c)) & 1u) == (mask[(size_t)b.off[i] + c] ? 1u : 0u), "%s: flagged offset %zu, component %d", what, i, c);
+  }
+  for (int shell = 0; shell < 2; shell++) {
+    if (shell && P < 3) continue;
+    const TransposeMap M = transpose_map(b.off, b.lsize, b.P3, 3, nullptr, shell ? P : 0);
+    const std::vector<unsigned char> rf = row_flag_bits(M.node_off, mask.data(), 3, 1);
+    CHECK(rf.size() == M.node_off.size(), "%s: %zu row flags", what, rf.size());
+    int rows_seen = 0;
+    for (size_t r = 0; r < rf.size(); r++) {
+      rows_seen |= 1 << (rf[r] & 7);
+      for (int c = 0; c < 3; c++)
+        CHECK(((rf[r] >> c) & 1) == (mask[(size_t)M.node_off[r] + c] ? 1 : 0), "%s: row %zu (%s map), component %d", what, r, shell ? "shell" : "whole", c);
+      CHECK((rf[r] >> 3) == 0, "%s: row flag %zu is %02x", what, r, rf[r]);
+    }
+    CHECK(rows_seen == 0xFF, "%s: the %s map's rows carry the patterns %02x only", what, shell ? "shell" : "whole", rows_seen);
+  }
+  bool cover = false;
+  const std::vector<uint32_t> own = owner_map(b.off, b.lsize, mask.data(), 3, 1, &cover);
+  CHECK(own.size() == b.off.size() && cover, "%s: owner map", what);
+  std::vector<int> owners((size_t)b.lsize, 0);
+  for (size_t i = 0; i < own.size() && i < b.off.size(); i++) {
+    if (own[i] == 0xFFFFFFFFu) continue;
+    const uint32_t o = own[i] & OFF_MASK;
+    CHECK(o == (uint32_t)b.off[i], "%s: owner entry %zu names node %u", what, i, o);
+    if (o >= (uint32_t)b.lsize) continue;
+    owners[o]++;
+    for (int c = 0; c < 3; c++)
+      CHECK(((own[i] >> (OFF_FLAG_SHIFT + c)) & 1u) == (mask[(size_t)o + c] ? 1u : 0u), "%s: owner entry %zu, component %d", what, i, c);
+  }
+  for (int k = 0; k < b.nnodes; k++) CHECK(owners[(size_t)3 * k] == 1, "%s: node %d has %d owners", what, k, owners[(size_t)3 * k]);
+  // the pack fold of the face x = max: the send buffer's entry e takes component comp of its row, and that row's flag bit comp is the
+  // mask byte of the entry itself -- what the folded pack drops is what the mask names, entry by entry
+  std::vector<uint32_t> idx;
+  std::vector<unsigned char> prio((size_t)b.lsize, 0);
+  for (int s = 0; s < b.N; s++)
+    for (int t = 0; t < b.N; t++) {
+      const int node = b.node(b.N - 1, t, s);
+      prio[(size_t)3 * node] = 1;
+      for (int c = 2; c >= 0; c--) idx.push_back((uint32_t)(3 * node + c));        // components in descending order: no order is assumed
+    }
+  const TransposeMap M = transpose_map(b.off, b.lsize, b.P3, 3, prio.data(), P >= 3 ? P : 0);
+  const std::vector<unsigned char> rf = row_flag_bits(M.node_off, mask.data(), 3, 1);
+  const PackFoldLists F = pack_fold(M.node_off, idx, 3, 1);
+  CHECK(F.ok && F.ptr.size() == M.node_off.size() + 1 && F.ptr.back() == idx.size(), "%s: fold", what);
+  int folded_seen = 0;
+  std::vector<int> hits(idx.size(), 0);
+  if (F.ok && F.ptr.size() == M.node_off.size() + 1 && rf.size() == M.node_off.size())
+    for (size_t r = 0; r < M.node_off.size(); r++) {
+      if (F.ptr[r + 1] > F.ptr[r]) folded_seen |= 1 << (rf[r] & 7);
+      for (uint32_t k = F.ptr[r]; k < F.ptr[r + 1]; k++) {
+        const uint32_t e = F.slot[k] & 0x3FFFFFFFu, comp = F.slot[k] >> 30;
+        CHECK(e < idx.size() && comp < 3, "%s: slot %u is %08x", what, k, F.slot[k]);
+        if (e >= idx.size() || comp >= 3) continue;
+        hits[e]++;
+        CHECK(M.node_off[r] + comp == idx[e], "%s: entry %u (dof %u) folded into row %zu as component %u", what, e, idx[e], r, comp);
+        CHECK(((rf[r] >> comp) & 1) == (mask[idx[e]] ? 1 : 0), "%s: entry %u (dof %u): row flag %02x, mask byte %d", what, e, idx[e], rf[r], (int)mask[idx[e]]);
+      }
+    }
+  for (size_t e = 0; e < idx.size(); e++) CHECK(hits[e] == 1, "%s: entry %zu folded %d times", what, e, hits[e]);
+  return folded_seen;
+}
+
 static bool increasing(const std::vector<int> &v) {
   for (size_t i = 1; i < v.size(); i++) if (v[i] <= v[i - 1]) return false;
   return true;
@@ -300,6 +382,14 @@ int main() {
   for (int n = 1; n <= 3; n++)
     for (int P : {2, 3, 5}) { test_box(n, P); test_halo(n, P); }
   test_segments();
+  for (int n = 1; n <= 3; n++)
+    for (int P : {2, 3, 5})
+      for (int shift : {0, 5}) {
+        const int folded = test_patterns(n, P, shift);
+        const int N = n * (P - 1) + 1;
+        if (N % 2) CHECK(folded == 0xFF, "box %d^3 P=%d: the folded rows carry the patterns %02x only", n, P, folded);    // N odd: the face's node numbers run through every residue mod 8
+      }
+  if (!g_fail) printf("component patterns ok\n");
   if (g_fail) { fprintf(stderr, "FAIL: %d checks\n", g_fail); return 1; }
   printf("index_maps_host ok\n");
   return 0;

@@ -2,8 +2,10 @@
 under the address and undefined-behaviour sanitizers and run as a child process.  On boxes of 1, 2 and 3 elements per side at P = 2, 3, 5
 (and a 6 x 6 x 6 box at P = 3 for the pipelined map) it checks the properties the device kernels rely on: every E-vector position in
 exactly one row, its node's, contributors in element order; priority rows first; the interior nodes; the segments of the pipelined map
-and its rows, each behind its last contributor; the Dirichlet flags; the owner map; the pack fold and the arrival lists of a halo.  Any
-sanitizer report or failed check fails it."""
+and its rows, each behind its last contributor; the Dirichlet flags; the owner map; the pack fold and the arrival lists of a halo.  On
+the same boxes under masks whose nodes carry all eight component patterns, flagged_offsets, row_flag_bits, owner_map and the rows
+pack_fold folds a halo into are held against loops over the L-vector entries: one mask byte, one flag bit.  Any sanitizer report or
+failed check fails it."""
 import os
 import shutil
 import subprocess
@@ -27,5 +29,6 @@ def test_index_maps_under_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "index_maps_host ok" in run.stdout
+    assert "component patterns ok" in run.stdout      # flags, row flags, owner map and pack fold under masks of all eight node patterns
     for word in ("Sanitizer", "runtime error", "FAIL"):     # the sanitizers and the program's own checks stayed silent
         assert word not in run.stderr, run.stderr
