@@ -1,7 +1,7 @@
 """A body and its loads: what the quasi-static solve (solver.NewtonPMG) and the implicit and explicit time steppers (dynamics.py) share,
 and nothing of how a system is solved.  ``LoadedBody`` holds the problem, its element partition over several ranks (halo.py: interface
 sums, owner-weighted dots), the boundary values (src/boundary.c), the load vector, the follower pressures (surface.py), the contact
-surfaces with their stored state (contact.py), the static
+surfaces with their stored state (contact.py), the spring and dashpot supports with their states (support.py), the static
 residual and the tangent apply ``A`` in its plain form.  It owns every vector made through ``_vec``, its surface loads and its contact surfaces: ``destroy()``
 releases them, and what it was handed (the problem, the halos, a caller's RcclHalo list) stays the caller's."""
 from __future__ import annotations
@@ -56,7 +56,7 @@ class LoadedBody:
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None, halo=None,
                  rccl="auto", traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None,
                  pressure_tangent: str = "full", verbose: bool = False, contact: Optional[Dict[int, dict]] = None,
-                 contact_tangent: str = "levels"):
+                 contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None):
         """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
         set but absent here are held at zero.
@@ -75,7 +75,11 @@ class LoadedBody:
         s = +1 a ball, -1 a cavity, eps per unit reference area).  The contact term is NOT scaled by the load fraction; only the
         obstacle moves with it: x0 or c at load l is x0 + l travel.  Every residual adds r(u) and refreshes the contact state, which the
         tangent reads: ``contact_tangent`` "levels" (solver.NewtonPMG: C in every matrix-free level's operator and diagonal) or "outer"
-        (C in ``A_outer`` only, the follower pressure's form).  One rank, and never on a clamped side set."""
+        (C in ``A_outer`` only, the follower pressure's form).  One rank, and never on a clamped side set.
+        ``support``: {side_set_id: dict(kn=0., kt=0., cn=0., ct=0.)} -- linear supports of the side set (support.py): springs kn (normal)
+        and kt (tangential) and dashpots cn, ct, all per unit REFERENCE area and fixed in the reference configuration.  NOT scaled by the
+        load fraction.  The residual adds the spring force K_s x (x with its boundary values) and ``A`` the spring tangent K_s on every
+        level it is asked for; the dashpot force C_d v is the time steppers' (dynamics.py).  One rank, and never on a clamped side set."""
         self.p, self.ceed, self.L = prob, prob.ceed, prob.ceed.L
         self.verbose = verbose
         self.nlev = len(prob.levels)
@@ -92,6 +96,8 @@ class LoadedBody:
                                        "the face sums of the interface nodes are not summed over the ranks")
         if contact:
             self._refuse_several_ranks(halo, "contact surfaces (contact=) are", "the face sums of the interface nodes are not summed over the ranks")
+        if support:
+            self._refuse_several_ranks(halo, "supports (support=) are", "the face sums of the interface nodes are not summed over the ranks")
         if many and single and self.nlev > 1:
             raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
         if many and len(halo) != self.nlev:
@@ -135,6 +141,7 @@ class LoadedBody:
         self._bc_nodes = self._collect_bc_nodes()
         self._setup_surface_loads(traction, pressure, pressure_tangent)
         self._setup_contact(contact, contact_tangent)
+        self._setup_support(support)
 
     # ---- several ranks ------------------------------------------------------------------------
     @staticmethod
@@ -253,6 +260,81 @@ class LoadedBody:
             c["state"].destroy()
         self.contacts = []
 
+    # ---- spring and dashpot supports (support.py) ---------------------------------------------
+    def _setup_support(self, support):
+        """With no support given nothing here runs, and no solve takes a new path."""
+        self.supports = []          # per side set: dict(sid, kn, kt, cn, ct, spring=state | None, dashpot=state | None, levels={level: SupportSurface})
+        if not support:
+            return
+        from .mesh import side_set_nodes
+        from .support import SupportSurface
+        prob, top = self.p, self.nlev - 1
+        lv = prob.levels[prob.fine]
+        for sid, spec in support.items():
+            if sid not in prob.mesh.side_sets:
+                raise ValueError(f"support on side set {sid}: the mesh has no such side set")
+            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
+            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
+                raise ValueError(f"support on side set {sid}, which is one of the problem's Dirichlet side sets")
+            if not isinstance(spec, dict) or set(spec) - {"kn", "kt", "cn", "ct"}:
+                raise ValueError(f"support on side set {sid}: dict(kn=0., kt=0., cn=0., ct=0.) expected")
+            co = {k: float(spec.get(k, 0.0)) for k in ("kn", "kt", "cn", "ct")}
+            if not all(v >= 0.0 and np.isfinite(v) for v in co.values()):
+                raise ValueError(f"support on side set {sid}: the coefficients {co} are not finite and non-negative")
+            if not any(v > 0.0 for v in co.values()):
+                raise ValueError(f"support on side set {sid}: all four coefficients are zero")
+            fine = SupportSurface(self.ceed, prob.mesh, lv.dofmap, [sid], prob.Q, mask=lv.mask)
+            s = dict(sid=sid, spring=None, dashpot=None, levels={top: fine}, **co)
+            for name, a, b in (("spring", co["kn"], co["kt"]), ("dashpot", co["cn"], co["ct"])):
+                if a > 0.0 or b > 0.0:
+                    s[name] = fine.new_state()
+                    fine.form_state(a, b, s[name])
+            self.supports.append(s)
+
+    def _support_surface(self, s, lv):
+        """The support's surface on level lv (that level's dofmap and mask, the fine Q), made when first asked for."""
+        if lv not in s["levels"]:
+            from .support import SupportSurface
+            level = self.p.levels[lv]
+            s["levels"][lv] = SupportSurface(self.ceed, self.p.mesh, level.dofmap, [s["sid"]], self.p.Q, mask=level.mask)
+        return s["levels"][lv]
+
+    def _support_tangent_state(self, s):
+        """The state whose B^T K_q B is the support's share of the tangent: the springs' (dynamics.NewmarkPMG: K_s + a1 C_d); or None."""
+        return s["spring"]
+
+    def support_tangent_add(self, lv, x, y):
+        """y += the supports' tangent on level lv applied to x."""
+        for s in self.supports:
+            st = self._support_tangent_state(s)
+            if st is not None:
+                self._support_surface(s, lv).tangent_add(1.0, st, x, y)
+
+    def support_diagonal_add(self, lv, d):
+        """d += the diagonal of the supports' tangent on level lv."""
+        for s in self.supports:
+            st = self._support_tangent_state(s)
+            if st is not None:
+                self._support_surface(s, lv).diagonal_add(1.0, st, d)
+
+    def support_force_add(self, which, x, y):
+        """y += K_s x (``which`` "spring") or C_d x ("dashpot") on the fine level; x is read as it is."""
+        for s in self.supports:
+            if s[which] is not None:
+                s["levels"][self.nlev - 1].force_add(1.0, s[which], x, y)
+
+    def has_dashpots(self) -> bool:
+        return any(s["dashpot"] is not None for s in self.supports)
+
+    def destroy_supports(self):
+        for s in self.supports:
+            for sf in s["levels"].values():
+                sf.destroy()
+            for k in ("spring", "dashpot", "combined"):
+                if s.get(k) is not None:
+                    s[k].destroy()
+        self.supports = []
+
     def destroy_surface_loads(self):
         for sl in self.surface_loads:
             sl.destroy()
@@ -263,6 +345,7 @@ class LoadedBody:
         releases its own first and ends with super().destroy()."""
         self.destroy_surface_loads()
         self.destroy_contacts()
+        self.destroy_supports()
         for o in self._vectors + self._own_rhalos:
             o.destroy()
         self._vectors, self._own_rhalos, self._x0 = [], [], {}
@@ -341,6 +424,8 @@ class LoadedBody:
         self.p.apply_jacobian(lv, x, y)
         self.stats.jacobian_applies += 1
         self._halo_sum(lv, y)
+        if self.supports:
+            self.support_tangent_add(lv, x, y)
 
     def A_outer(self, lv, x, y):
         """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x (and, with
@@ -385,4 +470,6 @@ class LoadedBody:
             self._place_obstacles()
             for c in self.contacts:
                 c["levels"][self.nlev - 1].residual_add(1.0, self.Xloc, R, c["state"])
+        if self.supports:                              # the spring force reads the boundary values too; not scaled by the load
+            self.support_force_add("spring", self.Xloc, R)
         self.stats.residual_evals += 1

@@ -11,7 +11,7 @@ of the reference's ``src/setuplibceed.c`` / ``src/matops.c``.
 Raw pointers only cross the boundary: numpy arrays on the host side, integer
 device addresses (e.g. ``torch.Tensor.data_ptr()``) on the device side.
 
-The prototypes are read out of ``include/ceed.h`` (and ``include/ceed_contact.h``, the contact entry points) at import (``header_prototypes``) and declared on every library loaded, so a call
+The prototypes are read out of ``include/ceed.h`` (and ``include/ceed_contact.h`` and ``include/ceed_support.h``, the contact and the support entry points) at import (``header_prototypes``) and declared on every library loaded, so a call
 with an argument missing or of the wrong kind is a Python exception before anything reaches C.  ``L.lib.CeedName(...)`` is the raw call:
 it returns the library's code and raises nothing (a code that is inspected, the destroy paths).  ``L.CeedName(...)`` is its checked
 twin: same prototype, ``CeedError`` with the library's message on a non-zero code; an optional entry point the library lacks has no
@@ -130,6 +130,9 @@ PROTOTYPES = header_prototypes(HEADER)
 # include/ceed_contact.h (CeedXContact*, all optional) on top of the typedefs of include/ceed.h, which it includes
 CONTACT_HEADER = os.path.join(os.path.dirname(HEADER), "ceed_contact.h")
 CONTACT_PROTOTYPES = header_prototypes(CONTACT_HEADER, PROTOTYPES.types)
+# include/ceed_support.h (CeedXSupport*, all optional), read the same way
+SUPPORT_HEADER = os.path.join(os.path.dirname(HEADER), "ceed_support.h")
+SUPPORT_PROTOTYPES = header_prototypes(SUPPORT_HEADER, PROTOTYPES.types)
 
 
 class CeedLib:
@@ -141,6 +144,7 @@ class CeedLib:
     OPTIONAL = [n for n, p in PROTOTYPES.functions.items() if p.optional]
     DATA = list(PROTOTYPES.data)
     CONTACT = list(CONTACT_PROTOTYPES.functions)       # include/ceed_contact.h: optional like OPTIONAL, declared and checked the same way
+    SUPPORT = list(SUPPORT_PROTOTYPES.functions)       # include/ceed_support.h: likewise
 
     def __init__(self, path: str = PRODUCT_LIB):
         if not os.path.exists(path):
@@ -164,6 +168,7 @@ class CeedLib:
         self.errcheck = errcheck
         vars(self).update(declare(L, PROTOTYPES.functions, errcheck))      # instance attributes: nothing between a call and its function
         vars(self).update(declare(L, CONTACT_PROTOTYPES.functions, errcheck))
+        vars(self).update(declare(L, SUPPORT_PROTOTYPES.functions, errcheck))
         L.CeedXSetErrorReturn(1)
         for s in ("VECTOR_ACTIVE", "VECTOR_NONE", "ELEMRESTRICTION_NONE", "BASIS_COLLOCATED", "QFUNCTION_NONE", "REQUEST_IMMEDIATE"):
             setattr(self, s, C.c_void_p.in_dll(L, "CEED_" + s).value)          # the sentinels: addresses, as integers
@@ -180,7 +185,7 @@ class CeedLib:
     def missing_symbols(self, optional: bool = True):
         """Declared symbols this library lacks.  ``optional=False`` leaves the CEED_EXTERN_OPTIONAL ones out: what another backend of
         the ABI must export; the product library exports all of them (build() checks with the default)."""
-        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL + self.CONTACT if optional else [])
+        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL + self.CONTACT + self.SUPPORT if optional else [])
         return [s for s in want if not hasattr(self.lib, s)]
 
 
@@ -398,6 +403,29 @@ class ContactHandle(_FaceHandle):
 
     def diagonal_add(self, scale: float, state: "Vector", d: "Vector"):                                    # d += scale diag C
         self.L.CeedXContactDiagonalAdd(self.h, scale, state.h, d.h)
+
+
+class SupportHandle(_FaceHandle):
+    """CeedXSupport* (include/ceed_support.h): linear spring and dashpot supports on a list of element faces.  The state has the layout
+    of the contact state (CONTACT_NSTATE per point: K, then w J)."""
+    PREFIX, PORTABLE = "CeedXSupport", "support.SupportSurface"
+
+    def _create(self, ceed_h, P, Q, off, lsize): self.L.CeedXSupportCreate(ceed_h, self.nface, P, Q, off, lsize, C.byref(self.h))
+    def _set_mask(self, p, n): self.L.CeedXSupportSetDirichletMask(self.h, MEM_HOST, p, n)
+    def _kernel_name(self): return out_value(self.L.CeedXSupportGetKernelName, C.c_char_p, self.h)
+    def _destroy(self): self.L.lib.CeedXSupportDestroy(C.byref(self.h))
+
+    def form_state(self, kn: float, kt: float, X: "Vector", state: "Vector"):                              # state := the state of (kn, kt)
+        self.L.CeedXSupportFormState(self.h, kn, kt, X.h, state.h)
+
+    def apply_force_add(self, scale: float, state: "Vector", x: "Vector", y: "Vector"):                    # y += scale K x, x as it is
+        self.L.CeedXSupportApplyForceAdd(self.h, scale, state.h, x.h, y.h)
+
+    def apply_tangent_add(self, scale: float, state: "Vector", dx: "Vector", y: "Vector"):                 # y += scale K dx
+        self.L.CeedXSupportApplyTangentAdd(self.h, scale, state.h, dx.h, y.h)
+
+    def diagonal_add(self, scale: float, state: "Vector", d: "Vector"):                                    # d += scale diag K
+        self.L.CeedXSupportDiagonalAdd(self.h, scale, state.h, d.h)
 
 
 class Graph:

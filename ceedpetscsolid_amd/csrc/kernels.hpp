@@ -343,22 +343,27 @@ hipError_t launch_surface_sum(const NodeMap &m, const unsigned char *flags, cons
 //   diagonal  d_{a,c}  =  sum_q N_a(q)^2 K_q[c][c]                                    (the tables come entry-wise squared)
 // in a face E-vector [face][P^2][3] that launch_surface_sum() adds into y.  The tangent and the diagonal read the state alone.
 // Mapping and passes: kernel_face_pass.hpp, as for k_surface.
-enum ContactMode : int { CONTACT_RESIDUAL = 0, CONTACT_TANGENT = 1, CONTACT_DIAGONAL = 2 };
+// Two further modes serve the spring and dashpot supports (ceed_support.cpp), whose K_q = w_q J_q [k_t I + (k_n - k_t) n (x) n] with
+// n = X_xi x X_eta / J is fixed in the reference configuration: SUPPORT_STATE gathers X alone and writes that K_q per point, entry 6
+// being w_q J_q (no E-vector, no node sum); SUPPORT_FORCE is the tangent's data path on an input read AS IT IS, boundary values included.
+// A support's tangent and diagonal are CONTACT_TANGENT and CONTACT_DIAGONAL on the support state.
+enum ContactMode : int { CONTACT_RESIDUAL = 0, CONTACT_TANGENT = 1, CONTACT_DIAGONAL = 2, CONTACT_SUPPORT_STATE = 3, CONTACT_SUPPORT_FORCE = 4 };
 enum ContactObstacle : int { CONTACT_PLANE = 0, CONTACT_SPHERE = 1 };
 constexpr int CONTACT_NSTATE = 7;   // K_q as (xx, yy, zz, yz, xz, xy), then the gap g
 struct ContactArgs {
   const uint32_t *offsets;  // [nface][P^2] component-0 L-offsets, the Dirichlet flags of their nodes in the top bits
-  const double *X;          // residual: node coordinates, an L-vector interlaced [node][3]
+  const double *X;          // residual, support state: node coordinates, an L-vector interlaced [node][3]
   const double *u;          // residual: displacement, read as it is (boundary values)
-  const double *du;         // tangent: the variation; flagged components read as zero
-  double *state;            // [nface][7][Q^2]: written by the residual, read by the tangent and the diagonal
+  const double *du;         // tangent: the variation; flagged components read as zero.  Support force: the field, read as it is
+  double *state;            // [nface][7][Q^2]: written by the residual (the support state), read by the tangent, the diagonal and the support force
   double *evec;             // face results [face][P^2][3], plain coalesced stores
   int nface, kind;          // kind: ContactObstacle, uniform over the launch (residual)
-  double par[8];            // plane: x0[3], n[3] (unit, from the obstacle to the body); sphere: c[3], R, s = +1 (ball) / -1 (cavity)
+  double par[8];            // plane: x0[3], n[3] (unit, from the obstacle to the body); sphere: c[3], R, s = +1 (ball) / -1 (cavity);
+                            // support state: k_n, k_t
   double penalty, scale;    // eps (residual: it is inside the stored K_q); the caller's factor on the face results (never on the state)
 };
 // hipErrorInvalidValue with *name left empty when (P, Q) is not instantiated: the pairs of CPS_DIAG_PQ (P = 2 .. 8, Q = P .. 8);
-// names "contact<P=..,Q=..,residual|tangent|diagonal>".  `t.interp` of the diagonal holds the entry-wise SQUARED table.
+// names "contact<P=..,Q=..,residual|tangent|diagonal|support_state|support_force>".  `t.interp` of the diagonal holds the entry-wise SQUARED table.
 hipError_t launch_contact(int P, int Q, int mode, const BasisTables &t, const ContactArgs &a, hipStream_t s, const char **name);
 bool contact_instantiated(int P, int Q);
 

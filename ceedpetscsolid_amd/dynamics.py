@@ -32,6 +32,13 @@ The term is state of the PROBLEM's operator (``prob.levels[lv].opJacob``), not o
 K + a0 rho M on the levels of ``_mass_in_op``; a second NewmarkPMG with fused_mass on the same problem overwrites the coefficient
 (another dt), and destroying either clears the term under the other.  One solver with fused_mass per problem at a time.
 
+Supports (``support=``, body.LoadedBody, support.py): springs K_s and dashpots C_d on side sets.  With Newmark's velocity
+v_{n+1} = v_n + dt (1 - gamma) a_n + gamma dt (a0 x_{n+1} + pred) the residual adds K_s x_{n+1} + C_d v_{n+1} and the tangent and the
+diagonal of every matrix-free level K_s + a1 C_d, a1 = gamma / (beta dt): ONE combined state per support (a linear combination of the
+two states, formed once: dt is fixed), so one launch per level.  ``set_initial`` puts -K_s u_0 - C_d v_0 into a_0.  The explicit stepper
+adds K_s x_n + C_d vh_{n-1/2} to its force -- the half-step velocity lagged, the standard central-difference form -- and its
+``stable_dt`` knows both terms.  ``absorbing_support`` gives the dashpots of a Lysmer-Kuhlemeyer boundary.
+
 Refused: ``smoother="pbjacobi"`` (the nodal blocks of M are not built) and a halo with several ranks (the mass operator's interface sums
 were never run there).
 """
@@ -56,7 +63,19 @@ def _refuse_contact(kw):
         raise ValueError("contact= is not provided for dynamics (static solves only: stable_dt knows nothing of the penalty)")
 
 
+def absorbing_support(prob: SolidProblem, density: float) -> dict:
+    """The dashpots of a Lysmer-Kuhlemeyer absorbing boundary for ``support=``: dict(cn=rho c_p, ct=rho c_s) with
+    c_p = sqrt((lambda + 2 mu) / rho) and c_s = sqrt(mu / rho) from the problem's (E, nu).  Exact for plane waves at normal incidence."""
+    if not density > 0.0:
+        raise ValueError("density must be positive")
+    nu, E = (float(v) for v in prob.phys[:2])
+    mu, lam = E / (2.0 * (1.0 + nu)), E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+    return dict(cn=float(np.sqrt((lam + 2.0 * mu) * density)), ct=float(np.sqrt(mu * density)))
+
+
 class NewmarkPMG(NewtonPMG):
+    _DASHPOTS = True
+
     def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, fused_mass=False, **kw):
         if not (density > 0.0 and dt > 0.0 and beta > 0.0):
             raise ValueError("density, dt and beta must be positive")
@@ -71,6 +90,7 @@ class NewmarkPMG(NewtonPMG):
             raise ValueError("NewmarkPMG: line_search must be 'cp' or 'full'")
         self.density, self.dt, self.beta, self.gamma = float(density), float(dt), float(beta), float(gamma)
         self.a0, self.a2, self.a3 = 1.0 / (beta * dt * dt), 1.0 / (beta * dt), 1.0 / (2.0 * beta) - 1.0
+        self.a1 = gamma / (beta * dt)    # d v_{n+1} / d x_{n+1}: the factor of the dashpots in the tangent
         self._asm_kwargs = {"mass_coef": self.a0 * self.density}
         # the tangent's mass term per level (read by A and _get_diag, which the parent's constructor may already call)
         self.mass = [MassOperator(prob, lv, self.a0 * self.density) for lv in range(len(prob.levels))]
@@ -90,6 +110,7 @@ class NewmarkPMG(NewtonPMG):
         n, top = prob.lsize(), self.nlev - 1
         self.mass_res = MassOperator(prob, prob.fine, self.density, mask_mode=2)      # the residual's: reads the boundary values
         self.xn, self.vn, self.an, self._pred, self._acc, self._mt = (self._vec(n, top) for _ in range(6))
+        self._vnew = self._vec(n, top) if self.supports else None      # v_{n+1} of the dashpot force; 1/2 u . K_s u's product
         self.t = 0.0
         self.last_rnorm = 0.0
         self._load_fn: Callable[[float], float] = lambda t: 1.0
@@ -125,6 +146,18 @@ class NewmarkPMG(NewtonPMG):
         """The level's Jacobian operator where it carries the mass term itself (the parent's conditions besides); None: two passes."""
         return super()._fused_op(lv) if lv in self._mass_in_op else None
 
+    def _support_tangent_state(self, s):
+        """K_s + a1 C_d as ONE state, formed at the first call (dt is fixed per solver); its entry 6 means nothing and is never read."""
+        if s["dashpot"] is None:
+            return s["spring"]
+        if s.get("combined") is None:
+            c = s["combined"] = s["levels"][self.nlev - 1].new_state()
+            if s["spring"] is not None:
+                c.waxpby(1.0, s["spring"], self.a1, s["dashpot"])
+            else:
+                c.axpby(self.a1, s["dashpot"], 0.0)
+        return s["combined"]
+
     def _get_diag(self, lv, d):
         super()._get_diag(lv, d)
         if lv not in self._mdiag:                # M does not change: its diagonal is formed once per level
@@ -139,6 +172,18 @@ class NewmarkPMG(NewtonPMG):
         super().residual(U, R)
         self._acc.waxpby(self.a0, self.Xloc, 1.0, self._pred)
         self.mass_res.apply_add(self._acc, R)
+        if self.supports and self.has_dashpots():        # C_d v_{n+1}, v_{n+1} = v_n + dt ((1 - gamma) a_n + gamma a_{n+1})
+            self._vnew.waxpby(1.0, self.vn, self.dt * (1.0 - self.gamma), self.an)
+            self.axpby(self._vnew, self.dt * self.gamma, self._acc, 1.0)
+            self.support_force_add("dashpot", self._vnew, R)
+
+    def support_energy(self) -> float:
+        """1/2 u . K_s u of the springs at the current displacement, over the free rows (the rows the force writes)."""
+        if not self.supports:
+            return 0.0
+        self._vnew.set_value(0.0)
+        self.support_force_add("spring", self.xn, self._vnew)
+        return 0.5 * self.dot(self.xn, self._vnew, True)
 
     def kinetic_energy(self) -> float:
         """1/2 v . rho M v over the free rows."""
@@ -160,6 +205,8 @@ class NewmarkPMG(NewtonPMG):
         self._set(self.vn, (np.zeros(n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)[:n]) * free)
         NewtonPMG.residual(self, self.U, self.R)         # the static residual (no inertia); also Xloc = U + boundary values
         self.copy(self.xn, self.Xloc)
+        if self.supports and self.has_dashpots():        # a_0 takes -C_d v_0 beside the -K_s u_0 of the static residual
+            self.support_force_add("dashpot", self.vn, self.R)
         self.axpby(self.Rtry, -1.0, self.R, 0.0)
         self._mass_solve(self.Rtry, self.an)             # a_0 = -(rho M)^-1 R_static
         self._started = True
@@ -255,7 +302,9 @@ class ExplicitDynamics(LoadedBody):
 
     The step is conditionally stable: dt < 2 / sqrt(lambda_max(m^-1 K_T)).  ``stable_dt`` estimates the bound with the Lanczos
     recurrence of krylov.py and the margin 1.1 the Chebyshev smoothers put on the same estimate; ``dt=None`` takes it at
-    ``set_initial``, a given dt beyond it is refused there.  dt is fixed per object.
+    ``set_initial``, a given dt beyond it is refused there.  dt is fixed per object.  Supports (``support=``): the force adds
+    K_s x_n + C_d vh_{n-1/2} and ``stable_dt`` becomes safety (-c + sqrt(c^2 + 4 w^2)) / w^2 with w^2 = 1.1 emax(m^-1 (K_T + K_s)) and
+    c = 1.1 emax(m^-1 C_d); without a dashpot the old expression is evaluated.
 
     Refused: a halo with several ranks (the mass operator's interface sums were never run there), density <= 0, dt <= 0, damping < 0,
     and at ``set_initial`` a lumped mass with a non-positive free row."""
@@ -287,7 +336,7 @@ class ExplicitDynamics(LoadedBody):
         self._load_const = True
         self._started = self._have_R = False
         self._x_start = None
-        self.emax_K = None
+        self.emax_K = self.emax_C = None
 
     # ---- pieces ---------------------------------------------------------------------------------------------------------------
     def _force(self):
@@ -295,6 +344,9 @@ class ExplicitDynamics(LoadedBody):
         self.p.form_residual(self.x, self.R)
         for sl, pval in self.pressure_loads:
             sl.pressure_add(pval, self.load, self.x, self.R)
+        if self.supports:                        # K_s x_n + C_d vh_{n-1/2}: the half-step velocity lagged
+            self.support_force_add("spring", self.x, self.R)
+            self.support_force_add("dashpot", self.vh, self.R)
         self.stats.residual_evals += 1
         self._have_R = True
 
@@ -336,7 +388,20 @@ class ExplicitDynamics(LoadedBody):
         al, be = lanczos_device(self.ceed, lambda x, y: self.A(top, x, y), lambda z, r: z.pointwise_mult(r, self.minv_m),
                                 self._start_vector(top), *self._lanczos_work, steps)
         self.emax_K = lanczos_emax(al, be)
-        return self.safety * 2.0 / np.sqrt(1.1 * self.emax_K)
+        if not (self.supports and self.has_dashpots()):
+            return self.safety * 2.0 / np.sqrt(1.1 * self.emax_K)
+        # dashpots, lagged: the scalar Jury condition 4 - dt^2 w^2 - 2 c dt > 0 with w^2 = 1.1 emax(m^-1 (K_T + K_s)) (``A`` carries
+        # the springs) and c = 1.1 emax(m^-1 C_d) from a second recurrence
+
+        def C(x, y):
+            y.set_value(0.0)
+            for s in self.supports:
+                if s["dashpot"] is not None:
+                    s["levels"][top].tangent_add(1.0, s["dashpot"], x, y)
+        al, be = lanczos_device(self.ceed, C, lambda z, r: z.pointwise_mult(r, self.minv_m), self._start_vector(top), *self._lanczos_work, steps)
+        self.emax_C = lanczos_emax(al, be)
+        w2, c = 1.1 * self.emax_K, 1.1 * self.emax_C
+        return self.safety * (-c + np.sqrt(c * c + 4.0 * w2)) / w2
 
     # ---- start ---------------------------------------------------------------------------------------------------------------------
     def set_initial(self, u0=None, v0=None, load: Union[float, Callable[[float], float]] = 1.0):
@@ -354,13 +419,17 @@ class ExplicitDynamics(LoadedBody):
         x0 = as_l(u0) * free + self.bc_values(self.load)
         self._set(self.x, x0)
         self._x_start = x0
+        if self.supports and self.has_dashpots():          # the dashpot force of a_0 is C_d v_0
+            self._set(self.vh, as_l(v0) * free)
         self._force()
         limit = self.stable_dt()
         if self.dt is None:
             self.dt = float(limit)
         elif self.dt > limit / self.safety:
-            raise ValueError(f"ExplicitDynamics: dt = {self.dt:.6g} is above the stable step {limit / self.safety:.6g} "
-                             f"(2 / sqrt(1.1 x the estimate {self.emax_K:.6g} of lambda_max(m^-1 K_T)))")
+            how = (f"2 / sqrt(1.1 x the estimate {self.emax_K:.6g} of lambda_max(m^-1 K_T))" if self.emax_C is None else
+                   f"(-c + sqrt(c^2 + 4 w^2)) / w^2 with w^2, c = 1.1 x the estimates {self.emax_K:.6g}, {self.emax_C:.6g} of "
+                   "lambda_max(m^-1 (K_T + K_s)), lambda_max(m^-1 C_d)")
+            raise ValueError(f"ExplicitDynamics: dt = {self.dt:.6g} is above the stable step {limit / self.safety:.6g} ({how})")
         h = 0.5 * self.damping * self.dt
         self.c1, self.c2 = (1.0 - h) / (1.0 + h), self.dt / (1.0 + h)
         v = as_l(v0) * free
@@ -390,6 +459,17 @@ class ExplicitDynamics(LoadedBody):
             self._set_boundary(load)
             self.load = load
         self._force()
+
+    def set_load(self, load: Union[float, Callable[[float], float]]):
+        """Replace the load (a constant, or a function of time) from the current time on.  A constant makes ``run(graph=True)`` possible
+        again after a load function has run its course, e.g. once a ramp has reached its plateau."""
+        self._load_const = not callable(load)
+        self._load_fn = self._load_function(load)
+        value = float(self._load_fn(self.t))
+        if self._started and value != self.load:
+            self._set_boundary(value)
+            self.load = value
+            self._force()
 
     def run(self, nsteps: int, sample_every: int = 0, graph: bool = False) -> dict:
         """``nsteps`` steps from the current state.  Every ``sample_every`` steps (0: never; the kernel then sums nothing) the history

@@ -37,6 +37,7 @@ from .solid import SolidProblem
 
 class NewtonPMG(LoadedBody):
     _asm_kwargs: dict = {}          # keywords of the assembled coarse level (dynamics.NewmarkPMG: its mass term); none here
+    _DASHPOTS = False               # whether support= may carry dashpots (dynamics.NewmarkPMG: yes; a static solve would ignore them)
 
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None,
                  halo=None, rccl="auto", lead_elements: int = 0, smooth_its: int = 3, coarse_rtol: float = 1e-3, coarse_maxit: int = 200,
@@ -45,7 +46,7 @@ class NewtonPMG(LoadedBody):
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
                  line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi",
                  traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full",
-                 contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels"):
+                 contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None):
         """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact``): body.LoadedBody.
         Of a follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner
         is the volume operator's.
@@ -55,7 +56,13 @@ class NewtonPMG(LoadedBody):
         consumers off on those levels (the term is added between the apply and its consumer).  "outer" adds it in ``A_outer`` only,
         the follower pressure's form: the preconditioner then knows nothing of the contact.  With coarse="assembled" or "amg" the
         assembled level-0 matrix does NOT carry the contact term (the matrix-free levels above it do).  smoother="pbjacobi" with
-        contact is refused: the nodal blocks would lack the term."""
+        contact is refused: the nodal blocks would lack the term.
+        ``support`` (body.LoadedBody, support.py): the spring tangent K_s is in ``A`` and in the diagonal of every matrix-free level
+        (one support.SupportSurface per level on the one state, so a coarse level's term is the Galerkin product) and the fused
+        consumers are off on those levels, as for contact.  With coarse="assembled" or "amg" the assembled level-0 matrix does NOT
+        carry the term (the matrix-free levels above it do), so a problem with NO Dirichlet dof, whose assembled matrix would be
+        singular, is refused with those two.  Refused too: smoother="pbjacobi" with support= (the nodal blocks would lack the term) and
+        a dashpot coefficient (cn, ct) in a static solve, which would be ignored."""
         # smoother: what the Chebyshev iteration of every p-multigrid level, its eigenvalue estimate and the Jacobi-preconditioned
         # coarse CG are preconditioned with -- "jacobi" (default, the reference: PCJACOBI on GetDiag_Ceed) or "pbjacobi": the inverted
         # 3 x 3 nodal blocks (PCPBJACOBI on CeedOperatorLinearAssemblePointBlockDiagonal), which keep the coupling between the
@@ -68,13 +75,21 @@ class NewtonPMG(LoadedBody):
             self._refuse_several_ranks(halo, "smoother='pbjacobi' is", "the nodal blocks of the interface nodes are not summed over the ranks")
         if smoother == "pbjacobi" and contact:
             raise ValueError("smoother='pbjacobi' with contact= is not provided: the nodal blocks would lack the contact term")
+        if smoother == "pbjacobi" and support:
+            raise ValueError("smoother='pbjacobi' with support= is not provided: the nodal blocks would lack the support term")
+        if support and not self._DASHPOTS and any(isinstance(sp, dict) and (sp.get("cn") or sp.get("ct")) for sp in support.values()):
+            raise ValueError("support=: a dashpot coefficient (cn, ct) in a static solve would be ignored; dashpots are the time steppers' (dynamics.py)")
+        if support and coarse in ("assembled", "amg") and not np.any(prob.levels[prob.fine].mask):
+            raise ValueError(f"support= with coarse={coarse!r} on a problem with no Dirichlet dof: the assembled level-0 matrix does not carry "
+                             "the support term and would be singular; use coarse='cg' or 'chebyshev'")
         if line_search not in ("cp", "cp-petsc", "full"):           # (_line_search)
             raise ValueError(f"line_search {line_search!r}")
         recordable = coarse in ("chebyshev", "assembled", "amg")
         if graph != "auto" and graph and not recordable:
             raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
         super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
-                         pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent)
+                         pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent,
+                         support=support)
         self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
@@ -183,6 +198,8 @@ class NewtonPMG(LoadedBody):
         (which is added between the apply and its consumer)."""
         if not self.fuse_epilogue or self.halos or self.rhalos or (lv == 0 and self.asm is not None) or lv in self._contact_levels:
             return None
+        if self.supports:            # (the support term is added between the apply and its consumer too)
+            return None
         return self.p.levels[lv].opJacob
 
     def level_residual(self, lv, b, x, z):
@@ -231,6 +248,8 @@ class NewtonPMG(LoadedBody):
         if lv in self._contact_levels:
             for c in self.contacts:
                 c["levels"][lv].diagonal_add(1.0, c["state"], d)
+        if self.supports and not (lv == 0 and self.asm is not None):
+            self.support_diagonal_add(lv, d)
 
     def _lanczos_host(self, lv, steps):
         """CG coefficients with every dot product read on the host (several ranks: the dots are all-reduced)."""
