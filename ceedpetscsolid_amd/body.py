@@ -56,7 +56,9 @@ class LoadedBody:
     def __init__(self, prob: SolidProblem, clamp: Optional[Dict[int, dict]] = None, mms: bool = False, forcing=None, halo=None,
                  rccl="auto", traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None,
                  pressure_tangent: str = "full", verbose: bool = False, contact: Optional[Dict[int, dict]] = None,
-                 contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None):
+                 contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
+                 traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
+                 hydrostatic: Optional[Dict[int, dict]] = None):
         """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
         set but absent here are held at zero.
@@ -70,6 +72,15 @@ class LoadedBody:
         T(u) is symmetric only on the variations that vanish on the rim of the loaded surface: a closed surface, or
         a patch whose rim is clamped (a tube with clamped ends).  A CG iteration assumes a symmetric operator; a follower pressure on a
         patch with a free rim is the caller's responsibility, as with any non-conservative load.
+        Loads that vary over a side set (surface.py, "Fields"; the rules, the load scaling and the symmetry caveat of the two above):
+        ``traction_field``: {side_set_id: array (nnodes, 3) | callable(X) -> (n, 3)} -- a dead traction per unit reference area given
+        at the fine level's nodes and interpolated over the faces; folded once into the load vector, like ``traction``.
+        ``pressure_field``: {side_set_id: array (nnodes,) | callable(X) -> (n,)} -- a pressure given at the nodes (it rides with the
+        material points) on the CURRENT surface; added in every residual like ``pressure``.
+        ``hydrostatic``: {side_set_id: dict(gamma=, level=, up=(0, 0, 1))} -- the pressure gamma <level - e . x> of a fluid of weight
+        gamma per unit volume at rest up to ``level`` along the unit vector e = up / |up|, the depth taken at the CURRENT position of
+        every point; added in every residual.  A callable is evaluated once, on the fine level's ``node_coords``.  With
+        ``pressure_tangent="full"`` the exact tangents of the two followers go to ``A_outer`` beside the constant pressure's.
         ``contact``: {side_set_id: dict(plane=(x0, n) | sphere=(c, R, s), penalty=eps, travel=(0, 0, 0))} -- frictionless penalty
         contact of the side set with a rigid obstacle (contact.py: g > 0 separated, n the unit normal from the obstacle to the body,
         s = +1 a ball, -1 a cavity, eps per unit reference area).  The contact term is NOT scaled by the load fraction; only the
@@ -90,9 +101,10 @@ class LoadedBody:
         single = halo is not None and not isinstance(halo, (list, tuple))
         halo = [halo] if single else halo
         many = self._several_ranks(halo)
-        if traction or pressure:
+        if traction or pressure or traction_field or pressure_field or hydrostatic:
             # partial face sums at the interface nodes would need the exchange between the add and its consumer
-            self._refuse_several_ranks(halo, "surface loads (traction=, pressure=) are",
+            self._refuse_several_ranks(halo, "surface loads (traction=, pressure=, traction_field=, pressure_field=, hydrostatic=) are"
+                                       if (traction_field or pressure_field or hydrostatic) else "surface loads (traction=, pressure=) are",
                                        "the face sums of the interface nodes are not summed over the ranks")
         if contact:
             self._refuse_several_ranks(halo, "contact surfaces (contact=) are", "the face sums of the interface nodes are not summed over the ranks")
@@ -140,6 +152,7 @@ class LoadedBody:
         self.stats = SolveStats()
         self._bc_nodes = self._collect_bc_nodes()
         self._setup_surface_loads(traction, pressure, pressure_tangent)
+        self._setup_surface_fields(traction_field, pressure_field, hydrostatic)
         self._setup_contact(contact, contact_tangent)
         self._setup_support(support)
 
@@ -193,6 +206,86 @@ class LoadedBody:
             sl = make(sid)
             self.pressure_loads.append((sl, float(pval)))
             self.surface_loads.append(sl)
+
+    def _setup_surface_fields(self, traction_field, pressure_field, hydrostatic):
+        """The loads that vary over a side set.  With none of them given nothing here runs, and no solve takes a new path."""
+        self.field_loads = []                        # the followers: ("pressure_field", SurfaceLoad, Vector) | ("hydrostatic", SurfaceLoad, (gamma, level, up))
+        if not traction_field and not pressure_field and not hydrostatic:
+            return
+        from .mesh import side_set_nodes
+        from .surface import SurfaceLoad, check_hydrostatic
+        prob, lv = self.p, self.p.levels[self.p.fine]
+        for sid in list(traction_field or {}) + list(pressure_field or {}) + list(hydrostatic or {}):
+            if sid not in prob.mesh.side_sets:
+                raise ValueError(f"surface load on side set {sid}: the mesh has no such side set")
+            nodes = side_set_nodes(prob.mesh, lv.dofmap, [sid])
+            if sid in prob.bc_sides or (nodes.size and lv.mask.reshape(-1, 3)[nodes].all()):
+                raise ValueError(f"surface load on side set {sid}, which is one of the problem's Dirichlet side sets")
+        n, top, nn = prob.lsize(), self.nlev - 1, lv.dofmap.nnodes
+
+        def nodal(what, sid, f, shape):
+            """The field as a flat array over the fine level's nodes: an array of ``shape``, or a callable of the node coordinates."""
+            f = np.asarray(f(lv.dofmap.node_coords) if callable(f) else f, dtype=np.float64)
+            if f.shape != shape:
+                raise ValueError(f"{what} on side set {sid}: an array of shape {shape} expected (one entry per node of the fine level), "
+                                 f"not {f.shape}")
+            if not np.all(np.isfinite(f)):
+                raise ValueError(f"{what} on side set {sid}: the field is not finite")
+            full = np.zeros(n if len(shape) == 2 else n // 3)       # (an L-vector may be longer than 3 nnodes: a caller's numbering)
+            full[:f.size] = f.reshape(-1)
+            return full
+        make = lambda sid: SurfaceLoad(self.ceed, prob.mesh, lv.dofmap, [sid], Q=prob.Q, mask=lv.mask)
+        # every argument is checked before the first object is made
+        tfields = {sid: nodal("traction_field", sid, f, (nn, 3)) for sid, f in (traction_field or {}).items()}
+        pfields = {sid: nodal("pressure_field", sid, f, (nn,)) for sid, f in (pressure_field or {}).items()}
+        hydro = {}
+        for sid, spec in (hydrostatic or {}).items():
+            if not isinstance(spec, dict) or set(spec) - {"gamma", "level", "up"} or "gamma" not in spec or "level" not in spec:
+                raise ValueError(f"hydrostatic on side set {sid}: dict(gamma=, level=, up=(0, 0, 1)) expected")
+            up = tuple(float(v) for v in np.asarray(spec.get("up", (0.0, 0.0, 1.0)), dtype=np.float64).reshape(-1))
+            check_hydrostatic(spec["gamma"], spec["level"], up)
+            hydro[sid] = (float(spec["gamma"]), float(spec["level"]), up)
+        for sid, t in tfields.items():
+            if self.fv is None:
+                self.fv = self._vec(n, top)
+            sl, tv = make(sid), self._vec(n, top)
+            self._set(tv, t)
+            sl.traction_field_add(tv, 1.0, self.fv)  # masked rows are never written: fv stays zero on the constrained dofs
+            self.surface_loads.append(sl)
+        for sid, pf in pfields.items():
+            sl, pv = make(sid), self._vec(n // 3, top)
+            self._set(pv, pf)
+            self.field_loads.append(("pressure_field", sl, pv))
+            self.surface_loads.append(sl)
+        for sid, par in hydro.items():
+            sl = make(sid)
+            self.field_loads.append(("hydrostatic", sl, par))
+            self.surface_loads.append(sl)
+
+    def has_followers(self) -> bool:
+        """Whether a load follows the surface: a constant pressure, a pressure field or a hydrostatic pressure."""
+        return bool(self.pressure_loads or self.field_loads)
+
+    def follower_add(self, x, R):
+        """R += load sum_s g_s(x) over every load that follows the surface, x the position's displacement WITH its boundary values.
+        The one place the static, the Newmark and the explicit residual add them (constrained rows are not written)."""
+        for sl, pval in self.pressure_loads:
+            sl.pressure_add(pval, self.load, x, R)
+        for kind, sl, par in self.field_loads:
+            if kind == "pressure_field":
+                sl.pressure_field_add(par, self.load, x, R)
+            else:
+                sl.hydrostatic_add(par[0], par[1], par[2], self.load, x, R)
+
+    def follower_tangent_add(self, x, dx, y):
+        """y += load sum_s T_s(x) dx, the exact tangents of ``follower_add``."""
+        for sl, pval in self.pressure_loads:
+            sl.tangent_add(pval, self.load, x, dx, y)
+        for kind, sl, par in self.field_loads:
+            if kind == "pressure_field":
+                sl.pressure_field_tangent_add(par, self.load, x, dx, y)
+            else:
+                sl.hydrostatic_tangent_add(par[0], par[1], par[2], self.load, x, dx, y)
 
     # ---- contact with a rigid obstacle (contact.py) -------------------------------------------
     def _setup_contact(self, contact, contact_tangent):
@@ -338,7 +431,7 @@ class LoadedBody:
     def destroy_surface_loads(self):
         for sl in self.surface_loads:
             sl.destroy()
-        self.surface_loads, self.pressure_loads = [], []
+        self.surface_loads, self.pressure_loads, self.field_loads = [], [], []
 
     def destroy(self):
         """Release what this object made: its vectors, its surface loads and the RcclHalos of rccl="auto".  Idempotent; a subclass
@@ -428,14 +521,14 @@ class LoadedBody:
             self.support_tangent_add(lv, x, y)
 
     def A_outer(self, lv, x, y):
-        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x (and, with
+        """The Jacobian of the outer Krylov iteration: the level's operator plus load sum_s p_s T_s(u) x, the tangents of the pressure
+        fields and the hydrostatic pressures likewise (and, with
         contact_tangent="outer", the contact tangent sum_s C_s x), u the state of the last
         residual evaluation (Xloc: free part + boundary values).  Masked entries of x read as zero and masked rows are not written,
         as in the volume operator."""
         self.A(lv, x, y)
         if self.pressure_tangent == "full":
-            for sl, pval in self.pressure_loads:
-                sl.tangent_add(pval, self.load, self.Xloc, x, y)
+            self.follower_tangent_add(self.Xloc, x, y)
         if self.contacts and self.contact_tangent == "outer":
             self.contact_tangent_add(lv, x, y)
 
@@ -464,8 +557,7 @@ class LoadedBody:
         self._halo_sum(self.nlev - 1, R)
         if self.fv is not None:
             self.axpby(R, -self.load, self.fv, 1.0)
-        for sl, pval in self.pressure_loads:           # follower pressure on the current surface (constrained rows are not written)
-            sl.pressure_add(pval, self.load, self.Xloc, R)
+        self.follower_add(self.Xloc, R)                # follower loads on the current surface (constrained rows are not written)
         if self.contacts:                              # contact is not scaled by the load: only the obstacle travels with it
             self._place_obstacles()
             for c in self.contacts:

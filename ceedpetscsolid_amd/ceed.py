@@ -11,7 +11,7 @@ of the reference's ``src/setuplibceed.c`` / ``src/matops.c``.
 Raw pointers only cross the boundary: numpy arrays on the host side, integer
 device addresses (e.g. ``torch.Tensor.data_ptr()``) on the device side.
 
-The prototypes are read out of ``include/ceed.h`` (and ``include/ceed_contact.h`` and ``include/ceed_support.h``, the contact and the support entry points) at import (``header_prototypes``) and declared on every library loaded, so a call
+The prototypes are read out of ``include/ceed.h`` (and ``include/ceed_contact.h``, ``include/ceed_support.h`` and ``include/ceed_surface_field.h``: the contact, the support and the surface-field entry points) at import (``header_prototypes``) and declared on every library loaded, so a call
 with an argument missing or of the wrong kind is a Python exception before anything reaches C.  ``L.lib.CeedName(...)`` is the raw call:
 it returns the library's code and raises nothing (a code that is inspected, the destroy paths).  ``L.CeedName(...)`` is its checked
 twin: same prototype, ``CeedError`` with the library's message on a non-zero code; an optional entry point the library lacks has no
@@ -133,6 +133,9 @@ CONTACT_PROTOTYPES = header_prototypes(CONTACT_HEADER, PROTOTYPES.types)
 # include/ceed_support.h (CeedXSupport*, all optional), read the same way
 SUPPORT_HEADER = os.path.join(os.path.dirname(HEADER), "ceed_support.h")
 SUPPORT_PROTOTYPES = header_prototypes(SUPPORT_HEADER, PROTOTYPES.types)
+# include/ceed_surface_field.h (the CeedXSurfaceLoadApply* of loads that vary over the faces, all optional), read the same way
+SURFACE_FIELD_HEADER = os.path.join(os.path.dirname(HEADER), "ceed_surface_field.h")
+SURFACE_FIELD_PROTOTYPES = header_prototypes(SURFACE_FIELD_HEADER, PROTOTYPES.types)
 
 
 class CeedLib:
@@ -145,6 +148,7 @@ class CeedLib:
     DATA = list(PROTOTYPES.data)
     CONTACT = list(CONTACT_PROTOTYPES.functions)       # include/ceed_contact.h: optional like OPTIONAL, declared and checked the same way
     SUPPORT = list(SUPPORT_PROTOTYPES.functions)       # include/ceed_support.h: likewise
+    SURFACE_FIELD = list(SURFACE_FIELD_PROTOTYPES.functions)       # include/ceed_surface_field.h: likewise
 
     def __init__(self, path: str = PRODUCT_LIB):
         if not os.path.exists(path):
@@ -169,6 +173,7 @@ class CeedLib:
         vars(self).update(declare(L, PROTOTYPES.functions, errcheck))      # instance attributes: nothing between a call and its function
         vars(self).update(declare(L, CONTACT_PROTOTYPES.functions, errcheck))
         vars(self).update(declare(L, SUPPORT_PROTOTYPES.functions, errcheck))
+        vars(self).update(declare(L, SURFACE_FIELD_PROTOTYPES.functions, errcheck))
         L.CeedXSetErrorReturn(1)
         for s in ("VECTOR_ACTIVE", "VECTOR_NONE", "ELEMRESTRICTION_NONE", "BASIS_COLLOCATED", "QFUNCTION_NONE", "REQUEST_IMMEDIATE"):
             setattr(self, s, C.c_void_p.in_dll(L, "CEED_" + s).value)          # the sentinels: addresses, as integers
@@ -185,7 +190,7 @@ class CeedLib:
     def missing_symbols(self, optional: bool = True):
         """Declared symbols this library lacks.  ``optional=False`` leaves the CEED_EXTERN_OPTIONAL ones out: what another backend of
         the ABI must export; the product library exports all of them (build() checks with the default)."""
-        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL + self.CONTACT + self.SUPPORT if optional else [])
+        want = self.FUNCTIONS + self.DATA + (self.OPTIONAL + self.CONTACT + self.SUPPORT + self.SURFACE_FIELD if optional else [])
         return [s for s in want if not hasattr(self.lib, s)]
 
 
@@ -376,6 +381,22 @@ class SurfaceLoadHandle(_FaceHandle):
 
     def apply_tangent_add(self, p: float, scale: float, X: "Vector", u: Optional["Vector"], du: "Vector", y: "Vector"):   # y += scale p T(u) du
         self.L.CeedXSurfaceLoadApplyTangentAdd(self.h, p, scale, X.h, _h(u), du.h, y.h)
+
+    # include/ceed_surface_field.h: loads that vary over the faces.  ``field``: a Vector of lsize (traction) or lsize / 3 (pressure) values
+    def apply_field_add(self, kind: int, field: "Vector", scale: float, X: "Vector", u: Optional["Vector"], y: "Vector"):
+        self.L.CeedXSurfaceLoadApplyFieldAdd(self.h, int(kind), _h(field), scale, X.h, _h(u), y.h)
+
+    def apply_field_tangent_add(self, field: "Vector", scale: float, X: "Vector", u: Optional["Vector"], du: "Vector", y: "Vector"):
+        self.L.CeedXSurfaceLoadApplyFieldTangentAdd(self.h, _h(field), scale, X.h, _h(u), du.h, y.h)
+
+    def apply_hydrostatic_add(self, gamma: float, level: float, up, scale: float, X: "Vector", u: Optional["Vector"], y: "Vector"):
+        e = (C.c_double * 3)(*[float(v) for v in up])
+        self.L.CeedXSurfaceLoadApplyHydrostaticAdd(self.h, gamma, level, e, scale, X.h, _h(u), y.h)
+
+    def apply_hydrostatic_tangent_add(self, gamma: float, level: float, up, scale: float, X: "Vector", u: Optional["Vector"], du: "Vector",
+                                      y: "Vector"):
+        e = (C.c_double * 3)(*[float(v) for v in up])
+        self.L.CeedXSurfaceLoadApplyHydrostaticTangentAdd(self.h, gamma, level, e, scale, X.h, _h(u), du.h, y.h)
 
 
 CONTACT_PLANE, CONTACT_SPHERE = 0, 1

@@ -1,5 +1,8 @@
 // ceed_surface.cpp -- the face set every term on a side set keeps (face_set.hpp), and the surface loads (CeedXSurfaceLoad*): dead
-// traction, follower pressure and its tangent on a list of element faces (kernels_surface.hip).
+// traction, follower pressure and its tangent on a list of element faces (kernels_surface.hip), and the loads that vary over the faces
+// (include/ceed_surface_field.h): a nodal traction or pressure field, a hydrostatic pressure, and the two followers' tangents.
+#include <cmath>
+#include <ceed_surface_field.h>
 #include "face_set.hpp"
 #include "index_maps.hpp"
 
@@ -72,25 +75,36 @@ extern "C" int CeedXSurfaceLoadSetDirichletMask(CeedXSurfaceLoad S, CeedMemType 
   return face_set_mask(S->fs, "CeedXSurfaceLoadSetDirichletMask", mtype, mask, lsize);
 }
 
-static int surface_apply(FaceSet &F, const char *who, int kind, const double coef[3], CeedVector X, CeedVector u, CeedVector du, CeedVector y) {
+// What the kinds that vary over the faces pass besides: the nodal field with the length it must have (or none), level and unit up.
+struct SurfaceField { CeedVector field = nullptr; int length = 0; double level = 0., up[3] = {0., 0., 0.}; };
+
+static int surface_apply(FaceSet &F, const char *who, int kind, const double coef[3], CeedVector X, CeedVector u, CeedVector du, CeedVector y,
+                         const SurfaceField *fld = nullptr) {
   if (!X || !y) return ceed_error("%s: no coordinate / output vector", who);
   if (X->length < F.lsize || y->length < F.lsize || (u && u->length < F.lsize) || (du && du->length < F.lsize))
     return ceed_error("%s: vector shorter than the L-size %d", who, F.lsize);
-  if (y == X || y == u || y == du) return ceed_error("%s: the output vector aliases an input", who);
+  if (y == X || y == u || y == du || (fld && y == fld->field)) return ceed_error("%s: the output vector aliases an input", who);
+  if (fld && fld->field && fld->field->length != fld->length)
+    return ceed_error("%s: the field holds %d values where %d are expected (L-size %d)", who, (int)fld->field->length, fld->length, F.lsize);
   if (F.nface == 0) return 0;
   CHK(face_set_prepare(F, "a surface load"));
-  SurfaceArgs a{};
-  double *pX = nullptr, *pu = nullptr, *pdu = nullptr, *py = nullptr;
+  SurfaceFieldArgs a{};
+  double *pX = nullptr, *pu = nullptr, *pdu = nullptr, *py = nullptr, *pf = nullptr;
   CHK(vec_dev(X, false, &pX));
   if (u) CHK(vec_dev(u, false, &pu));
   if (du) CHK(vec_dev(du, false, &pdu));
+  if (fld && fld->field) CHK(vec_dev(fld->field, false, &pf));
   CHK(vec_dev(y, true, &py));
   a.offsets = F.d_offsets.get(); a.X = pX; a.u = pu; a.du = pdu;
   a.nface = F.nface; a.kind = kind;
   for (int i = 0; i < 3; i++) a.coef[i] = coef[i];
+  if (fld) {
+    a.field = pf; a.level = fld->level;
+    for (int i = 0; i < 3; i++) a.up[i] = fld->up[i];
+  }
   return face_set_apply(F, "surface", py, [&](double *evec, const char **name) {
     a.evec = evec;
-    return launch_surface(F.P, F.Q, F.tables, a, F.ceed->stream, name);
+    return fld ? launch_surface_field(F.P, F.Q, F.tables, a, F.ceed->stream, name) : launch_surface(F.P, F.Q, F.tables, a, F.ceed->stream, name);
   });
 }
 
@@ -110,3 +124,64 @@ extern "C" int CeedXSurfaceLoadApplyTangentAdd(CeedXSurfaceLoad S, CeedScalar p,
 }
 
 extern "C" int CeedXSurfaceLoadGetKernelName(CeedXSurfaceLoad S, const char **name) { *name = S->fs.kernel_name.c_str(); return 0; }
+
+// ---- loads that vary over the faces (include/ceed_surface_field.h) ------------------------------------------------------------------
+static int field_of(const char *who, const FaceSet &F, int kind, CeedVector field, SurfaceField &fld) {
+  if (!field || field == CEED_VECTOR_NONE) return ceed_error("%s: no field vector", who);
+  fld.field = field;
+  fld.length = kind == CEED_X_SURFACE_TRACTION ? F.lsize : F.lsize / 3;
+  return 0;
+}
+
+static int hydrostatic_of(const char *who, double gamma, double level, const double up[3], SurfaceField &fld) {
+  if (!std::isfinite(gamma) || !std::isfinite(level)) return ceed_error("%s: gamma = %g and level = %g must be finite", who, gamma, level);
+  if (!up) return ceed_error("%s: no up vector", who);
+  const double n2 = up[0] * up[0] + up[1] * up[1] + up[2] * up[2];
+  if (!std::isfinite(n2) || !(n2 > 0.)) return ceed_error("%s: up = (%g, %g, %g) is not a finite, non-zero vector", who, up[0], up[1], up[2]);
+  const double n = std::sqrt(n2);
+  for (int i = 0; i < 3; i++) fld.up[i] = up[i] / n;
+  fld.level = level;
+  return 0;
+}
+
+extern "C" int CeedXSurfaceLoadApplyFieldAdd(CeedXSurfaceLoad S, int kind, CeedVector field, CeedScalar scale, CeedVector X, CeedVector u, CeedVector y) {
+  const char *who = "CeedXSurfaceLoadApplyFieldAdd";
+  if (kind != CEED_X_SURFACE_TRACTION && kind != CEED_X_SURFACE_PRESSURE) return ceed_error("%s: kind %d is neither traction nor pressure", who, kind);
+  if (u == CEED_VECTOR_NONE) u = nullptr;
+  const bool tr = kind == CEED_X_SURFACE_TRACTION;
+  SurfaceField fld;
+  CHK(field_of(who, S->fs, kind, field, fld));
+  const double cf[3] = {scale, 0., 0.};
+  return surface_apply(S->fs, who, tr ? SURF_TRACTION_FIELD : SURF_PRESSURE_FIELD, cf, X, tr ? nullptr : u, nullptr, y, &fld);
+}
+
+extern "C" int CeedXSurfaceLoadApplyFieldTangentAdd(CeedXSurfaceLoad S, CeedVector field, CeedScalar scale, CeedVector X, CeedVector u, CeedVector du, CeedVector y) {
+  const char *who = "CeedXSurfaceLoadApplyFieldTangentAdd";
+  if (!du) return ceed_error("%s: no variation vector", who);
+  if (u == CEED_VECTOR_NONE) u = nullptr;
+  SurfaceField fld;
+  CHK(field_of(who, S->fs, CEED_X_SURFACE_PRESSURE, field, fld));
+  const double cf[3] = {scale, 0., 0.};
+  return surface_apply(S->fs, who, SURF_PRESSURE_FIELD_TANGENT, cf, X, u, du, y, &fld);
+}
+
+extern "C" int CeedXSurfaceLoadApplyHydrostaticAdd(CeedXSurfaceLoad S, CeedScalar gamma, CeedScalar level, const CeedScalar up[3], CeedScalar scale,
+                                                   CeedVector X, CeedVector u, CeedVector y) {
+  const char *who = "CeedXSurfaceLoadApplyHydrostaticAdd";
+  if (u == CEED_VECTOR_NONE) u = nullptr;
+  SurfaceField fld;
+  CHK(hydrostatic_of(who, gamma, level, up, fld));
+  const double cf[3] = {scale * gamma, 0., 0.};
+  return surface_apply(S->fs, who, SURF_HYDRO, cf, X, u, nullptr, y, &fld);
+}
+
+extern "C" int CeedXSurfaceLoadApplyHydrostaticTangentAdd(CeedXSurfaceLoad S, CeedScalar gamma, CeedScalar level, const CeedScalar up[3], CeedScalar scale,
+                                                          CeedVector X, CeedVector u, CeedVector du, CeedVector y) {
+  const char *who = "CeedXSurfaceLoadApplyHydrostaticTangentAdd";
+  if (!du) return ceed_error("%s: no variation vector", who);
+  if (u == CEED_VECTOR_NONE) u = nullptr;
+  SurfaceField fld;
+  CHK(hydrostatic_of(who, gamma, level, up, fld));
+  const double cf[3] = {scale * gamma, 0., 0.};
+  return surface_apply(S->fs, who, SURF_HYDRO_TANGENT, cf, X, u, du, y, &fld);
+}

@@ -319,7 +319,14 @@ hipError_t launch_assemble_epi(const NodeMap &m, const unsigned char *flags, con
 //   traction  g_a = int N_a t |X_xi x X_eta|,   pressure  g_a = int N_a (x_xi x x_eta),   tangent  T du |_a = int N_a (du_xi x x_eta + x_xi x du_eta),
 // x = X + u, (xi, eta) the two in-face directions (xi fastest in the face's node list) with X_xi x X_eta pointing out of the body.
 // The face mapping and the passes it shares with k_contact: kernel_face_pass.hpp.
-enum SurfaceKind : int { SURF_TRACTION = 0, SURF_PRESSURE = 1, SURF_TANGENT = 2 };
+// Five further kinds vary over the faces (k_surface<P, Q, true>, launch_surface_field).  With t_h, p_h, x_h, du_h the nodal values at
+// the point, e = up, d = level - e . x_h, <d> = max(d, 0), H(d) = 1 for d > 0 and 0 otherwise, per face
+//   traction field    g_a = sum_q w_q N_a t_h |X_xi x X_eta|       pressure field  g_a = sum_q w_q N_a p_h (x_xi x x_eta)
+//   hydrostatic       g_a = sum_q w_q N_a gamma <d> (x_xi x x_eta)
+//   and the two followers' tangents: p_h (du_xi x x_eta + x_xi x du_eta);  gamma [<d> (du_xi x x_eta + x_xi x du_eta) - H(d) (e . du_h) (x_xi x x_eta)].
+// The discrete forms are DEFINED by these sums (at Q = P they are not exact integrals for p >= 3); each tangent is their derivative.
+enum SurfaceKind : int { SURF_TRACTION = 0, SURF_PRESSURE = 1, SURF_TANGENT = 2,
+                         SURF_TRACTION_FIELD = 3, SURF_PRESSURE_FIELD = 4, SURF_PRESSURE_FIELD_TANGENT = 5, SURF_HYDRO = 6, SURF_HYDRO_TANGENT = 7 };
 struct SurfaceArgs {
   const uint32_t *offsets;  // [nface][P^2] component-0 L-offsets, the Dirichlet flags of their nodes in the top bits
   const double *X;          // node coordinates, an L-vector interlaced [node][3]
@@ -327,10 +334,17 @@ struct SurfaceArgs {
   const double *du;         // tangent: the variation; flagged components read as zero
   double *evec;             // face results [face][P^2][3], plain coalesced stores; launch_surface_sum() adds them into y
   int nface, kind;
-  double coef[3];           // scale x t (traction); scale x p in coef[0] (pressure, tangent)
+  double coef[3];           // scale x t (traction); scale x p in coef[0] (pressure, tangent); scale (x gamma) in coef[0] (the field kinds)
+};
+// what the field kinds take besides (an argument type of their own: the kernels of the three kinds above keep their argument block)
+struct SurfaceFieldArgs : SurfaceArgs {
+  const double *field;      // traction field: an L-vector read at the offsets; pressure field: a value per node, read at offset / 3
+  double level, up[3];      // hydrostatic: the level of the fluid along the UNIT vector up (gamma rides in coef[0])
 };
 // hipErrorInvalidValue with *name left empty when (P, Q) is not instantiated: P = 2 .. 8, Q = P .. min(P + 2, 8)
 hipError_t launch_surface(int P, int Q, const BasisTables &t, const SurfaceArgs &a, hipStream_t s, const char **name);
+// the field kinds (a.kind >= SURF_TRACTION_FIELD), same pairs; *name is "surface_field<P=..,Q=..>"
+hipError_t launch_surface_field(int P, int Q, const BasisTables &t, const SurfaceFieldArgs &a, hipStream_t s, const char **name);
 bool surface_instantiated(int P, int Q);
 // y[node_off[r] + c] += the sum of row r's face contributions in face order (node_sum3), one read-modify-write per row of the face
 // transpose map; components flagged in `flags` (a byte per row, may be null) are skipped, rows off the faces are never touched

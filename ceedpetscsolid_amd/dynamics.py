@@ -340,10 +340,10 @@ class ExplicitDynamics(LoadedBody):
 
     # ---- pieces ---------------------------------------------------------------------------------------------------------------
     def _force(self):
-        """R = F_int(x) + load sum_s p_s g_s^pressure(x), constrained rows dropped (the load vector enters in the step itself)."""
+        """R = F_int(x) + load sum_s p_s g_s^pressure(x) (every follower load: body.follower_add), constrained rows dropped (the load vector
+        enters in the step itself)."""
         self.p.form_residual(self.x, self.R)
-        for sl, pval in self.pressure_loads:
-            sl.pressure_add(pval, self.load, self.x, self.R)
+        self.follower_add(self.x, self.R)
         if self.supports:                        # K_s x_n + C_d vh_{n-1/2}: the half-step velocity lagged
             self.support_force_add("spring", self.x, self.R)
             self.support_force_add("dashpot", self.vh, self.R)

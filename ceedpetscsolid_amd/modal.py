@@ -86,7 +86,7 @@ class Eigenmodes:
         if sol.halos:
             raise ValueError("Eigenmodes is not provided with a halo (several ranks): the mass operator's interface sums and the block "
                              "reductions have not been run over several ranks")
-        if sol.pressure_loads:
+        if sol.pressure_loads or getattr(sol, "field_loads", None):
             raise ValueError("Eigenmodes is not provided with pressure loads on the solver: the tangent T(u) of a follower pressure is not "
                              "symmetric in general")
         self.shift = 0.0

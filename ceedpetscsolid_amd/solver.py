@@ -46,8 +46,11 @@ class NewtonPMG(LoadedBody):
                  ksp_rtol: float = 1e-10, snes_rtol: float = 1e-8, snes_maxit: int = 50, verbose: bool = False,
                  line_search: str = "cp", fuse_epilogue: bool = True, smoother: str = "jacobi",
                  traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full",
-                 contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None):
-        """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact``): body.LoadedBody.
+                 contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
+                 traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
+                 hydrostatic: Optional[Dict[int, dict]] = None):
+        """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact, traction_field,
+        pressure_field, hydrostatic``): body.LoadedBody.
         Of a follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner
         is the volume operator's.
         ``contact_tangent``: "levels" (default) adds the contact tangent C to the operator ``A`` and to the diagonal of EVERY
@@ -89,7 +92,7 @@ class NewtonPMG(LoadedBody):
             raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
         super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
                          pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent,
-                         support=support)
+                         support=support, traction_field=traction_field, pressure_field=pressure_field, hydrostatic=hydrostatic)
         self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
@@ -426,7 +429,7 @@ class NewtonPMG(LoadedBody):
         its = 0
         if rz0 <= 0.0:
             return 0
-        apply_A = self.A_outer if (self.pressure_loads or (self.contacts and self.contact_tangent == "outer")) else self.A
+        apply_A = self.A_outer if (self.has_followers() or (self.contacts and self.contact_tangent == "outer")) else self.A
         for its in range(1, 500):
             apply_A(fine, p, Ap)
             alpha = rz / self.dot(p, Ap, True)

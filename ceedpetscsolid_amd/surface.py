@@ -13,6 +13,18 @@ and load factors left to the caller (``solver.NewtonPMG``):
 T(u) is symmetric on the variations that vanish on the rim of the loaded surface -- a closed surface, or a patch whose rim is clamped
 (a tube with clamped ends) -- and not otherwise: a follower pressure on a patch with a free rim is not conservative.
 
+Fields.  Five further vectors for loads that vary over the side set, with t_h, p_h, x_h, du_h the nodal values interpolated to the
+point (sum_b N_b t_b, ...), e the unit "up" vector, d = level - e . x_h the depth of the CURRENT point, <d> = max(d, 0), H the step:
+
+    traction field        g_a      = sum_q w_q N_a t_h |X_xi x X_eta|                  t_b a nodal 3-vector field; dead, evaluated once
+    pressure field        g_a(u)   = sum_q w_q N_a p_h (x_xi x x_eta)                  p_b a nodal scalar field on the material points
+    its tangent           T du |_a = sum_q w_q N_a p_h (du_xi x x_eta + x_xi x du_eta)
+    hydrostatic           g_a(u)   = sum_q w_q N_a gamma <d> (x_xi x x_eta)
+    its tangent           T du |_a = sum_q w_q N_a gamma [<d> (du_xi x x_eta + x_xi x du_eta) - H(d) (e . du_h) (x_xi x x_eta)]
+
+These sums are NOT exact integrals at Q = P once p >= 3 (the integrands reach degree 3p - 1 per direction): the discrete form is DEFINED
+by the quadrature, and each tangent is the exact derivative of that discrete form (the hydrostatic one away from d = 0).
+
 On the device these are the library's CeedXSurfaceLoad* entry points (csrc/kernels_surface.hip).  Where the library lacks them (the CPU
 oracle), or with ``portable=True``, the same sums are formed in NumPy on the tensor layer and the tables of ``portable.py`` (which form
 runs where, and why it is the device tests' yardstick: DESIGN.md 2).
@@ -27,6 +39,28 @@ from . import ceed as cd
 from . import portable as pt
 from .mesh import DofMap, HexMesh, side_set_faces
 from .portable import lagrange_tables          # (importable from here too, as before)
+
+
+def check_field(f, n: int, what: str) -> np.ndarray:
+    """The nodal field ``f`` as a flat float64 array of exactly ``n`` values."""
+    f = np.asarray(f, dtype=np.float64).reshape(-1)
+    if f.size != n:
+        raise ValueError(f"{what}: {f.size} values where {n} are expected")
+    return f
+
+
+def unit_vector(up) -> np.ndarray:
+    """up / |up|; a vector that is not three finite components, or is zero, is refused."""
+    e = np.asarray(up, dtype=np.float64).reshape(-1)
+    if e.size != 3 or not np.all(np.isfinite(e)) or not np.any(e != 0.0):
+        raise ValueError(f"hydrostatic: up = {up!r} is not a finite, non-zero 3-vector")
+    return e / np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2])
+
+
+def check_hydrostatic(gamma, level, up):
+    if not (np.isfinite(float(gamma)) and np.isfinite(float(level))):
+        raise ValueError(f"hydrostatic: gamma = {gamma!r} and level = {level!r} must be finite")
+    unit_vector(up)
 
 
 class FaceTerm:
@@ -133,7 +167,93 @@ class SurfaceLoad(FaceTerm):
         da, db = self._derivs(self._free(du))
         return self._weighted(np.cross(da, xb) + np.cross(xa, db))
 
+    # ---- loads that vary over the side set (the module's docstring, "Fields"): NumPy ----------------------------------------------
+    def _values(self, field: np.ndarray) -> np.ndarray:
+        """The values at the points, [face][b][a][c], of a nodal field (L-vector)."""
+        return pt.to_points(self._gather(field), self.B, self.B)
+
+    def _scalar_values(self, p) -> np.ndarray:
+        """The values at the points, [face][b][a], of a nodal scalar field (one value per node)."""
+        p = check_field(p, self.lsize // 3, "pressure field")
+        return pt.to_points(p[self.faces.reshape(self.nface, self.P, self.P)], self.B, self.B)
+
+    def depth_host(self, level: float, up=(0.0, 0.0, 1.0), u=None) -> np.ndarray:
+        """d = level - e . x_h at the points, [face][b][a]: positive under the surface of the fluid."""
+        return float(level) - self._values(self._position(u)) @ unit_vector(up)
+
+    def traction_field_host(self, t) -> np.ndarray:
+        """g of the nodal traction field t (L-vector, or [node][3]) as an L-vector (NumPy)."""
+        Xa, Xb = self._derivs(self.Xh)
+        J = np.linalg.norm(np.cross(Xa, Xb), axis=-1)
+        return self._weighted(J[..., None] * self._values(check_field(t, self.lsize, "traction field")))
+
+    def pressure_field_host(self, p, u=None) -> np.ndarray:
+        """g(u) of the nodal pressure field p (one value per node) as an L-vector (NumPy)."""
+        xa, xb = self._derivs(self._position(u))
+        return self._weighted(self._scalar_values(p)[..., None] * np.cross(xa, xb))
+
+    def pressure_field_tangent_host(self, p, u, du) -> np.ndarray:
+        """The derivative of ``pressure_field_host`` in the direction du (NumPy); masked entries of du read as zero."""
+        xa, xb = self._derivs(self._position(u))
+        da, db = self._derivs(self._free(du))
+        return self._weighted(self._scalar_values(p)[..., None] * (np.cross(da, xb) + np.cross(xa, db)))
+
+    def hydrostatic_host(self, gamma: float, level: float, up=(0.0, 0.0, 1.0), u=None) -> np.ndarray:
+        """g(u) of the pressure gamma <level - e . x> of a fluid at rest as an L-vector (NumPy)."""
+        check_hydrostatic(gamma, level, up)
+        xa, xb = self._derivs(self._position(u))
+        d = self.depth_host(level, up, u)
+        return self._weighted((float(gamma) * np.maximum(d, 0.0))[..., None] * np.cross(xa, xb))
+
+    def hydrostatic_tangent_host(self, gamma: float, level: float, up, u, du) -> np.ndarray:
+        """The derivative of ``hydrostatic_host`` in the direction du away from d = 0 (NumPy); masked entries of du read as zero."""
+        check_hydrostatic(gamma, level, up)
+        xa, xb = self._derivs(self._position(u))
+        free = self._free(du)
+        da, db = self._derivs(free)
+        d = self.depth_host(level, up, u)
+        rise = self._values(free) @ unit_vector(up)
+        val = np.maximum(d, 0.0)[..., None] * (np.cross(da, xb) + np.cross(xa, db)) - ((d > 0.0) * rise)[..., None] * np.cross(xa, xb)
+        return self._weighted(float(gamma) * val)
+
     # ---- y += ..., on vectors of the Ceed ----------------------------------------------------------------------------------------
+    def traction_field_add(self, t: cd.Vector, scale: float, y: cd.Vector):
+        """y += scale g^traction(t), t a nodal traction field (an L-vector)."""
+        if self.handle is not None:
+            self.handle.apply_field_add(cd.SURFACE_TRACTION, t, scale, self.X, None, y)
+        else:
+            pt.add(y, scale * self.traction_field_host(t.to_numpy()))
+
+    def pressure_field_add(self, p: cd.Vector, scale: float, u: Optional[cd.Vector], y: cd.Vector):
+        """y += scale g^pressure(p; u), p a nodal pressure field (a vector of lsize / 3 values)."""
+        if self.handle is not None:
+            self.handle.apply_field_add(cd.SURFACE_PRESSURE, p, scale, self.X, u, y)
+        else:
+            pt.add(y, scale * self.pressure_field_host(p.to_numpy(), None if u is None else u.to_numpy()))
+
+    def pressure_field_tangent_add(self, p: cd.Vector, scale: float, u: Optional[cd.Vector], du: cd.Vector, y: cd.Vector):
+        """y += scale T^pressure(p; u) du."""
+        if self.handle is not None:
+            self.handle.apply_field_tangent_add(p, scale, self.X, u, du, y)
+        else:
+            pt.add(y, scale * self.pressure_field_tangent_host(p.to_numpy(), None if u is None else u.to_numpy(), du.to_numpy()))
+
+    def hydrostatic_add(self, gamma: float, level: float, up, scale: float, u: Optional[cd.Vector], y: cd.Vector):
+        """y += scale g^hydrostatic(u): the fluid of weight gamma per unit volume standing up to ``level`` along ``up``."""
+        if self.handle is not None:
+            check_hydrostatic(gamma, level, up)
+            self.handle.apply_hydrostatic_add(gamma, level, up, scale, self.X, u, y)
+        else:
+            pt.add(y, scale * self.hydrostatic_host(gamma, level, up, None if u is None else u.to_numpy()))
+
+    def hydrostatic_tangent_add(self, gamma: float, level: float, up, scale: float, u: Optional[cd.Vector], du: cd.Vector, y: cd.Vector):
+        """y += scale T^hydrostatic(u) du."""
+        if self.handle is not None:
+            check_hydrostatic(gamma, level, up)
+            self.handle.apply_hydrostatic_tangent_add(gamma, level, up, scale, self.X, u, du, y)
+        else:
+            pt.add(y, scale * self.hydrostatic_tangent_host(gamma, level, up, None if u is None else u.to_numpy(), du.to_numpy()))
+
     def traction_add(self, t, scale: float, y: cd.Vector):
         """y += scale g^traction(t)."""
         if self.handle is not None:
