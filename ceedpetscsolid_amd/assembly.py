@@ -28,9 +28,10 @@ from .solid import SolidProblem
 
 
 class AssembledLevel:
-    def __init__(self, prob: SolidProblem, level: int = 0, mass_coef=None):
+    def __init__(self, prob: SolidProblem, level: int = 0, mass_coef=None, mass_density=None):
         """``mass_coef`` (dynamics.py): the matrix is that of K + mass_coef M -- the level's mass operator (mass.py) on the same
-        element-discontinuous restriction is added to every unit-vector apply.  None: nothing of it exists."""
+        element-discontinuous restriction is added to every unit-vector apply.  None: nothing of it exists.  ``mass_density``: a
+        mass.DensityField, M is then M_rho."""
         self.p, self.level = prob, level
         c = self.ceed = prob.ceed
         lv = prob.levels[level]
@@ -57,7 +58,7 @@ class AssembledLevel:
         self.mass = self._mass_cols = None
         if mass_coef is not None:
             from .mass import MassOperator
-            self.mass = MassOperator(prob, level, mass_coef, rstr=self.rstr, offsets=eoff)
+            self.mass = MassOperator(prob, level, mass_coef, rstr=self.rstr, offsets=eoff, density=mass_density)
         # --- unit vectors and the COO value buffer: entry [j][e][n][c] = K_e[(n,c), j] -----------------
         self.units = []
         for j in range(self.nd):

@@ -58,8 +58,19 @@ class LoadedBody:
                  pressure_tangent: str = "full", verbose: bool = False, contact: Optional[Dict[int, dict]] = None,
                  contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
                  traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
-                 hydrostatic: Optional[Dict[int, dict]] = None):
-        """``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
+                 hydrostatic: Optional[Dict[int, dict]] = None, density=None, gravity=None, acceleration_field=None,
+                 spin: Optional[dict] = None):
+        """Body loads (mass.py; one rank): ``density`` -- a positive float or a ``mass.DensityField`` -- is required by the three below.
+        ``gravity``: (gx, gy, gz), an acceleration; the load int rho N g = M_rho (tile g), through the mass apply with mask mode 2, is
+        folded once into the load vector and scaled by the load fraction like ``forcing``.
+        ``acceleration_field``: array (nnodes, 3) | callable(X) -> (n, 3), a nodal acceleration b_h; the load M_rho b_h likewise
+        (inertia relief: a rigid-body acceleration field is linear in X and lies in the space).
+        ``spin``: dict(omega=, axis=(0, 0, 1), origin=(0, 0, 0), follow=True, tangent="full") -- the centrifugal load
+        rho Omega^2 P (X + u - c), P = I - a a^T.  The part at X is dead and folded in once; with ``follow`` the part in u is added in
+        every residual (``follower_add``, scaled by the load fraction), and with tangent "full" its tangent -load Omega^2 M_rho P --
+        symmetric, negative semi-definite: the spin softening -- goes to ``A_outer`` only: the multigrid levels and smoothers do not
+        see it, as with ``pressure_tangent``.
+        ``clamp``: {side_set_id: dict(translate=(..), axis=(..), angle_over_pi=..)} as
         -bc_clamp_<id>_translate / _rotate (cloptions.c:86-131); ids present in the problem's Dirichlet
         set but absent here are held at zero.
         Surface loads (surface.py; one rank, and never on a clamped side set):
@@ -155,6 +166,75 @@ class LoadedBody:
         self._setup_surface_fields(traction_field, pressure_field, hydrostatic)
         self._setup_contact(contact, contact_tangent)
         self._setup_support(support)
+        self._setup_body_loads(density, gravity, acceleration_field, spin, halo)
+
+    # ---- body loads (mass.py) -----------------------------------------------------------------
+    def _setup_body_loads(self, density, gravity, acceleration_field, spin, halo):
+        """With none of gravity=, acceleration_field=, spin= given nothing here runs and no mass operator is made."""
+        self.body_mass = None                        # M_rho of the fine level, mask mode 2: the loads read the vectors as they are
+        self.spin = None                             # dict(omega2, follow, tangent, blocks, px, mp) of a spinning body
+        if gravity is None and acceleration_field is None and spin is None:
+            return
+        if density is None:
+            raise ValueError("gravity=, acceleration_field= and spin= need density= (a positive float or a mass.DensityField)")
+        self._refuse_several_ranks(halo, "body loads (gravity=, acceleration_field=, spin=) are",
+                                   "the mass operator's sums at the interface nodes have not been run over several ranks")
+        from .mass import DensityField, MassOperator
+        prob, lv = self.p, self.p.levels[self.p.fine]
+        n, top, nn = prob.lsize(), self.nlev - 1, lv.dofmap.nnodes
+        X = np.asarray(lv.dofmap.node_coords, dtype=np.float64)
+        field = density if isinstance(density, DensityField) else None
+        if field is None and not (isinstance(density, (int, float, np.integer, np.floating)) and np.isfinite(density) and density > 0.0):
+            raise ValueError(f"density must be a positive float or a mass.DensityField, not {density!r}")
+        b = np.zeros((nn, 3))
+        if gravity is not None:
+            g = np.asarray(gravity, dtype=np.float64).reshape(-1)
+            if g.size != 3 or not np.all(np.isfinite(g)):
+                raise ValueError("gravity: three finite components (gx, gy, gz) expected")
+            b += g
+        if acceleration_field is not None:
+            a = np.asarray(acceleration_field(X) if callable(acceleration_field) else acceleration_field, dtype=np.float64)
+            if a.shape != (nn, 3) or not np.all(np.isfinite(a)):
+                raise ValueError(f"acceleration_field: a finite array of shape {(nn, 3)} expected (one row per node of the fine level), "
+                                 f"not {a.shape}")
+            b += a
+        if spin is not None:
+            if not isinstance(spin, dict) or set(spin) - {"omega", "axis", "origin", "follow", "tangent"} or "omega" not in spin:
+                raise ValueError("spin: dict(omega=, axis=(0, 0, 1), origin=(0, 0, 0), follow=True, tangent='full') expected")
+            ax = np.asarray(spin.get("axis", (0.0, 0.0, 1.0)), dtype=np.float64).reshape(-1)
+            c0 = np.asarray(spin.get("origin", (0.0, 0.0, 0.0)), dtype=np.float64).reshape(-1)
+            om, tangent = float(spin["omega"]), spin.get("tangent", "full")
+            if ax.size != 3 or c0.size != 3 or not np.isfinite(om) or not np.all(np.isfinite(ax)) or not np.all(np.isfinite(c0)) or not ax @ ax > 0.0:
+                raise ValueError("spin: a finite omega, a non-zero axis and an origin of three components each expected")
+            if tangent not in ("full", "none"):
+                raise ValueError(f"spin: tangent must be 'full' or 'none', not {tangent!r}")
+            ax = ax / np.sqrt(ax @ ax)
+            Pm = np.eye(3) - np.outer(ax, ax)
+            b += om * om * (X - c0) @ Pm                 # (P is symmetric) the dead part, at the reference position
+        self.body_mass = MassOperator(prob, prob.fine, 1.0 if field is not None else float(density), mask_mode=2, density=field)
+        full = np.zeros(n)                               # (an L-vector may be longer than 3 nnodes: a caller's numbering)
+        full[:3 * nn] = b.reshape(-1)
+        bv, out = self._vec(n, top), self._vec(n, top)
+        self._set(bv, full)
+        self.body_mass.apply(bv, out)                    # masked rows are stored as zeros: fv stays zero on the constrained dofs
+        if self.fv is None:
+            self.fv = out
+        else:
+            self.axpby(self.fv, 1.0, out, 1.0)
+        if spin is not None and spin.get("follow", True):
+            blocks = self._vec(3 * n, top)               # P on every node: the point-block multiply forms P u nodewise
+            self._set(blocks, np.tile(Pm.reshape(-1), n // 3))
+            self.spin = dict(omega2=om * om, tangent=tangent, blocks=blocks, px=bv, mp=self._vec(n, top))
+
+    def _spin_add(self, x, y):
+        """y -= load Omega^2 M_rho P x on the free rows (x read as it is).  The sign: the residual is R = F_int - load f + followers,
+        and the centrifugal force +rho Omega^2 P u acts ON the body, so its share of R (``follower_add``'s "R += load g(x)" with
+        g = -Omega^2 M_rho P x) and of the tangent is negative.  ``px`` is the scratch vector the load was set up in, free since."""
+        from .ceed import pointblock_mult
+        s = self.spin
+        pointblock_mult(s["px"], s["blocks"], x)
+        self.body_mass.apply(s["px"], s["mp"])           # masked rows are zeros: y keeps its own there
+        self.axpby(y, -self.load * s["omega2"], s["mp"], 1.0)
 
     # ---- several ranks ------------------------------------------------------------------------
     @staticmethod
@@ -263,8 +343,8 @@ class LoadedBody:
             self.surface_loads.append(sl)
 
     def has_followers(self) -> bool:
-        """Whether a load follows the surface: a constant pressure, a pressure field or a hydrostatic pressure."""
-        return bool(self.pressure_loads or self.field_loads)
+        """Whether a load follows the body: a constant pressure, a pressure field, a hydrostatic pressure or a spin with follow=True."""
+        return bool(self.pressure_loads or self.field_loads or self.spin)
 
     def follower_add(self, x, R):
         """R += load sum_s g_s(x) over every load that follows the surface, x the position's displacement WITH its boundary values.
@@ -276,6 +356,8 @@ class LoadedBody:
                 sl.pressure_field_add(par, self.load, x, R)
             else:
                 sl.hydrostatic_add(par[0], par[1], par[2], self.load, x, R)
+        if self.spin:                                  # the centrifugal load grows with the radius the points have moved to
+            self._spin_add(x, R)
 
     def follower_tangent_add(self, x, dx, y):
         """y += load sum_s T_s(x) dx, the exact tangents of ``follower_add``."""
@@ -286,6 +368,12 @@ class LoadedBody:
                 sl.pressure_field_tangent_add(par, self.load, x, dx, y)
             else:
                 sl.hydrostatic_tangent_add(par[0], par[1], par[2], self.load, x, dx, y)
+
+    def spin_tangent_add(self, dx, y):
+        """y -= load Omega^2 M_rho P dx: the spin softening, linear in dx and independent of the state (masked entries of dx are zero
+        in a Krylov vector; masked rows are not written)."""
+        if self.spin and self.spin["tangent"] == "full":
+            self._spin_add(dx, y)
 
     # ---- contact with a rigid obstacle (contact.py) -------------------------------------------
     def _setup_contact(self, contact, contact_tangent):
@@ -439,6 +527,9 @@ class LoadedBody:
         self.destroy_surface_loads()
         self.destroy_contacts()
         self.destroy_supports()
+        if self.body_mass is not None:
+            self.body_mass.destroy()
+        self.body_mass = self.spin = None
         for o in self._vectors + self._own_rhalos:
             o.destroy()
         self._vectors, self._own_rhalos, self._x0 = [], [], {}
@@ -529,6 +620,7 @@ class LoadedBody:
         self.A(lv, x, y)
         if self.pressure_tangent == "full":
             self.follower_tangent_add(self.Xloc, x, y)
+        self.spin_tangent_add(x, y)
         if self.contacts and self.contact_tangent == "outer":
             self.contact_tangent_add(lv, x, y)
 

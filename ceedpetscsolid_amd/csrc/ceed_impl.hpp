@@ -230,6 +230,7 @@ struct CeedOperator_private {
   // lowering (op_plan)
   int plan = PLAN_NONE;
   int i_active = -1, i_qdata = -1, i_state = -1, i_weight = -1, o_active = -1, o_state = -1, o_qdata = -1;
+  int i_rho = -1;                     // PLAN_MASS of the QFunction "MassField": the passive density field; -1 for "Mass"
   cps::BasisTables tables{};
   cps::BasisTables tables_sq{};       // PLAN_MASS: `interp` squared entry by entry, the table of the mass diagonal
   double eo[6][cps::EO_TAB];          // even-odd forms of the six 1-D products (fused operators with pencil_even_odd(Q))

@@ -2,12 +2,14 @@
 // v = c qdata[0] u with u and v through INTERP -- y (+)= c B^T (w det J) B x on three interlaced components -- and its diagonal.
 // k_mass (kernels_mass.hip) stores the element results into the Ceed's scratch E-vector; launch_assemble sums them per node in element
 // order over the restriction's whole transpose map, under the operator's row flags: no atomics, the same bits every time.
+// QFunction "MassField" (op->i_rho >= 0) is the same operator with a density field: v = c rho_h qdata[0] u, rho a passive scalar field
+// through INTERP on a restriction of its own -- k_mass's modes with a field, the same sum.
 #include "ceed_operator.hpp"
 
 using namespace cps;
 
 // what the apply and the diagonal check and read alike: the qdata vector, the context, the kernel's arguments but for the vectors
-static int mass_args(CeedOperator op, MassArgs &a) {
+static int mass_args(CeedOperator op, MassArgs &a, MassFieldArgs &f) {
   OpField &u = op->in[op->i_active];
   CeedElemRestriction r = u.rstr;
   const int Q = u.basis->Q1d;
@@ -20,7 +22,23 @@ static int mass_args(CeedOperator op, MassArgs &a) {
   a.offsets = op->d_off_flagged ? op->d_off_flagged.get() : r->d_offsets.get();
   a.mask_in = (op->d_off_flagged && (op->mask_mode & 1)) ? 1 : 0;
   a.mask_out = (op->d_off_flagged && (op->mask_mode & 2)) ? 1 : 0;
+  if (op->i_rho >= 0) {
+    // rho's address is the launch argument: new values written behind it are seen by a recorded apply
+    OpField &rh = op->in[op->i_rho];
+    if (!is_passive(rh.vec) || rh.vec->length < rh.rstr->lsize)
+      return ceed_error("rho vector shorter than its restriction's L-size: %d entries for %d", is_passive(rh.vec) ? (int)rh.vec->length : 0, (int)rh.rstr->lsize);
+    double *pr;
+    CHK(vec_dev(rh.vec, false, &pr));
+    f.rho = pr;
+    f.rho_offsets = rh.rstr->d_offsets.get();
+  }
   return 0;
+}
+// the launch of either QFunction: the kernels with the field take the PLAIN table in both forms
+static hipError_t mass_launch(CeedOperator op, bool diag, const MassArgs &a, const MassFieldArgs &f, hipStream_t s, const char **kname) {
+  CeedBasis b = op->in[op->i_active].basis;
+  if (op->i_rho >= 0) return launch_mass_field(b->P1d, b->Q1d, diag, op->tables, a, f, s, kname);
+  return launch_mass(b->P1d, b->Q1d, diag, diag ? op->tables_sq : op->tables, a, s, kname);
 }
 
 int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add) {
@@ -32,7 +50,8 @@ int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   if (in->length < r->lsize || out->length < r->lsize) return ceed_error("active vector shorter than the restriction's L-size");
   if (in == out) return ceed_error("in-place operator apply is not supported");
   MassArgs a{};
-  CHK(mass_args(op, a));
+  MassFieldArgs f{};
+  CHK(mass_args(op, a, f));
   double *px, *py, *pq;
   CHK(vec_dev(in, false, &px));
   CHK(vec_dev(out, true, &py));
@@ -49,7 +68,7 @@ int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   if (!add && (!r->csr.full_cover || out->length > r->lsize)) CHK(dev_zero(c, py, (size_t)out->length));
   TimerScope ts(op, s);
   const char *kname = "";
-  hipError_t e = launch_mass(u.basis->P1d, u.basis->Q1d, false, op->tables, a, s, &kname);
+  hipError_t e = mass_launch(op, false, a, f, s, &kname);
   if (no_kernel(e, kname)) return ceed_error("no mass kernel instantiated for P=%d Q=%d", u.basis->P1d, u.basis->Q1d);
   HIPCHK(e);
   HIPCHK(launch_assemble(r->csr.view(), flags, a.evec, py, add ? 1 : 0, s));
@@ -68,7 +87,8 @@ int mass_diagonal(CeedOperator op, CeedVector assembled) {
   if (!is_passive(assembled) || assembled->length < r->lsize)
     return ceed_error("diagonal vector too short: %d entries for the L-size %d", assembled ? (int)assembled->length : 0, (int)r->lsize);
   MassArgs a{};
-  CHK(mass_args(op, a));
+  MassFieldArgs f{};
+  CHK(mass_args(op, a, f));
   double *pd, *pq;
   CHK(vec_dev(assembled, true, &pd));
   CHK(vec_dev(op->in[op->i_qdata].vec, false, &pq));
@@ -78,7 +98,7 @@ int mass_diagonal(CeedOperator op, CeedVector assembled) {
   a.evec = c->evec.get();
   CHK(dev_zero(c, pd, (size_t)assembled->length));
   const char *kname = "";
-  hipError_t e = launch_mass(u.basis->P1d, u.basis->Q1d, true, op->tables_sq, a, s, &kname);
+  hipError_t e = mass_launch(op, true, a, f, s, &kname);
   if (no_kernel(e, kname)) return ceed_error("no mass diagonal kernel instantiated for P=%d Q=%d", u.basis->P1d, u.basis->Q1d);
   HIPCHK(e);
   HIPCHK(launch_assemble(r->csr.view(), nullptr, a.evec, pd, 0, s));

@@ -129,7 +129,7 @@ int op_plan(CeedOperator op) {
   CeedQFunction qf = op->qf;
   for (size_t i = 0; i < qf->in.size(); i++) if (!op->in[i].set) return ceed_error("operator field '%s' not set", qf->in[i].name.c_str());
   for (size_t i = 0; i < qf->out.size(); i++) if (!op->out[i].set) return ceed_error("operator field '%s' not set", qf->out[i].name.c_str());
-  op->i_active = op->i_qdata = op->i_state = op->i_weight = op->o_active = op->o_state = op->o_qdata = -1;
+  op->i_active = op->i_qdata = op->i_state = op->i_weight = op->o_active = op->o_state = op->o_qdata = op->i_rho = -1;
   const int k = qf->kind;
   auto unsupported = [&](const char *why) {
     return ceed_error("operator with QFunction '%s' is outside the kernel families of /gpu/hip/mi355x: %s", qf->name.c_str(), why);
@@ -279,6 +279,35 @@ int op_plan(CeedOperator op) {
     op->tables_sq = op->tables;
     for (double &v : op->tables_sq.interp) v *= v;
     op->i_active = 0; op->i_qdata = 1; op->o_active = 0;
+    op->plan = PLAN_MASS;
+    return 0;
+  }
+  if (k == QF_MASS_FIELD) {
+    // (u INTERP active (3), rho INTERP passive (1), qdata NONE (10)) -> v INTERP active (3): v = c rho qdata[0] u.  PLAN_MASS with i_rho set:
+    // the mask, the diagonal and the composite treat it as they treat "Mass"
+    if (qf->in.size() != 3 || qf->out.size() != 1) return unsupported("MassField takes (u, rho, qdata) -> v");
+    const QFField &fu = qf->in[0], &fr = qf->in[1], &fq = qf->in[2], &fv = qf->out[0];
+    if (fu.emode != CEED_EVAL_INTERP || fu.size != 3 || fr.emode != CEED_EVAL_INTERP || fr.size != 1 || fq.emode != CEED_EVAL_NONE || fq.size != 10 ||
+        fv.emode != CEED_EVAL_INTERP || fv.size != 3 || op->in[0].vec != CEED_VECTOR_ACTIVE || op->out[0].vec != CEED_VECTOR_ACTIVE)
+      return unsupported("MassField eval modes must be INTERP(3) active, INTERP(1), NONE(10) -> INTERP(3) active");
+    OpField &ai = op->in[0], &ao = op->out[0], &rh = op->in[1], &qd = op->in[2];
+    if (!is_passive(rh.vec)) return unsupported("rho must be a passive field with a vector of its own, not the active one");
+    if (!is_offsets(ai.rstr) || ai.rstr != ao.rstr || ai.basis != ao.basis || ai.basis == CEED_BASIS_COLLOCATED)
+      return unsupported("active input and output must share one offsets restriction and one basis");
+    if (!is_disp(ai)) return unsupported("active fields must be 3 interlaced components");
+    CeedBasis b = ai.basis;
+    const int P = b->P1d, Q = b->Q1d;
+    if (!nodes_fit(ai)) return unsupported("restriction element size is not P^3");
+    if (!is_qdata(qd, Q) || qd.rstr->nelem != ai.rstr->nelem) return unsupported("qdata must be a strided 10 x Q^3 field");
+    if (P > Q) return unsupported("the mass kernel needs P <= Q");
+    if (!is_offsets(rh.rstr) || rh.rstr->ncomp != 1) return unsupported("rho must be on an offsets restriction with 1 component");
+    if (rh.rstr->nelem != ai.rstr->nelem) return unsupported("rho's restriction must have the element count of u's");
+    if (rh.rstr->elemsize != cube(P)) return unsupported("rho's restriction must have the element size P^3 of u's");
+    // (the same nodes and points: the kernel interpolates rho with u's table, compared entry by entry)
+    if (rh.basis == CEED_BASIS_COLLOCATED || rh.basis->P1d != P || rh.basis->Q1d != Q || rh.basis->interp1d != b->interp1d)
+      return unsupported("rho's basis must have u's P, Q and interp table");
+    fill_tables(op->tables, b);      // the diagonal squares the table in the kernel: tables_sq is not used
+    op->i_active = 0; op->i_rho = 1; op->i_qdata = 2; op->o_active = 0;
     op->plan = PLAN_MASS;
     return 0;
   }

@@ -11,7 +11,7 @@ static int resolve_qf(const std::string &name) {
       {"HyperFSdF", QF_HYPERFS_DF},  {"SetupConstantForce", QF_CONST_FORCE}, {"SetupMMSForce", QF_MMS_FORCE},
       {"MMSTrueSoln", QF_MMS_TRUE},  {"LinElasEnergy", QF_ENERGY_LINELAS}, {"HyperSSEnergy", QF_ENERGY_HYPERSS},
       {"HyperFSEnergy", QF_ENERGY_HYPERFS}, {"LinElasDiagnostic", QF_DIAG_LINELAS}, {"HyperSSDiagnostic", QF_DIAG_HYPERSS},
-      {"HyperFSDiagnostic", QF_DIAG_HYPERFS}, {"Mass", QF_MASS},
+      {"HyperFSDiagnostic", QF_DIAG_HYPERFS}, {"Mass", QF_MASS}, {"MassField", QF_MASS_FIELD},
       {"LinElasStress", QF_STRESS_LINELAS}, {"HyperSSStress", QF_STRESS_HYPERSS}, {"HyperFSStress", QF_STRESS_HYPERFS},
   };
   for (auto &t : tab) if (name == t.n) return t.k;

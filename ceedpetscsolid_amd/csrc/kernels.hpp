@@ -28,6 +28,7 @@ enum QFKind : int {
   QF_STRESS_LINELAS,  // the Cauchy stress the residual integrates, at the points or projected to the nodes (kernels_stress.hip)
   QF_STRESS_HYPERSS,
   QF_STRESS_HYPERFS,
+  QF_MASS_FIELD,      // v = c rho qdata[0] u, rho a passive INTERP field: the mass operator with a density field (kernels_mass.hip)
 };
 
 constexpr int MAXN1D = 8;  // largest P or Q supported by the kernel tables
@@ -219,6 +220,13 @@ struct MassArgs {
   double coef;              // the QFunction context c, read by the host at every apply
 };
 
+// The density field of the mass operator (QFunction "MassField"; k_mass's modes MASS_APPLY_RHO and MASS_DIAG_RHO), a struct of its own
+// beside MassArgs, whose layout the kernels without a field keep.
+struct MassFieldArgs {
+  const double *rho;            // the scalar density vector; its address is the launch argument, so a recording sees new values behind it
+  const uint32_t *rho_offsets;  // [nelem][P^3] plain indices into rho: no Dirichlet flags, no factor 3
+};
+
 // Stress recovery (kernels_stress.hip, k_stress): the Cauchy stress the residual integrates (qfunctions_device.hpp, qf_stress), six
 // components in the order xx, yy, zz, yz, xz, xy, from the displacement L-vector read AS IT IS (boundary values included, no mask).
 struct StressArgs {
@@ -254,6 +262,9 @@ hipError_t launch_state_at_points(int Pf, int Qc, const BasisTables &t, const St
                                   const char **name);
 // diag: `t.interp` holds the entry-wise SQUARED table; names "mass<P,Q>" / "mass_diag<P,Q>"; the pairs of CPS_DIAG_PQ (kernel_diag_sf.hpp)
 hipError_t launch_mass(int P, int Q, bool diag, const BasisTables &t, const MassArgs &a, hipStream_t s, const char **name);
+// the same operator with the density field: `t.interp` is the PLAIN table in both forms (the diagonal squares it while staging); names
+// "mass_field<P,Q>" / "mass_field_diag<P,Q>"; the pairs of CPS_DIAG_PQ
+hipError_t launch_mass_field(int P, int Q, bool diag, const BasisTables &t, const MassArgs &a, const MassFieldArgs &f, hipStream_t s, const char **name);
 // names "stress<P=..,Q=..,points>" / "stress<P=..,Q=..,nodal>"; the pairs of CPS_DIAG_PQ
 hipError_t launch_stress(int P, int Q, bool nodal, const BasisTables &t, const StressArgs &a, hipStream_t s, const char **name);
 

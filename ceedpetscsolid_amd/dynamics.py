@@ -51,7 +51,7 @@ import numpy as np
 
 from .body import LoadedBody
 from .krylov import lanczos_device, lanczos_emax, pcg
-from .mass import MassOperator
+from .mass import MassOperator, split_density
 from .solid import SolidProblem
 from .solver import NewtonPMG, SolveStats
 
@@ -76,9 +76,17 @@ def absorbing_support(prob: SolidProblem, density: float) -> dict:
 class NewmarkPMG(NewtonPMG):
     _DASHPOTS = True
 
-    def __init__(self, prob: SolidProblem, density: float, dt: float, beta: float = 0.25, gamma: float = 0.5, fused_mass=False, **kw):
-        if not (density > 0.0 and dt > 0.0 and beta > 0.0):
+    def __init__(self, prob: SolidProblem, density, dt: float, beta: float = 0.25, gamma: float = 0.5, fused_mass=False, **kw):
+        """``density``: a positive float, or a mass.DensityField: every mass operator here is then M_rho of that field (each level's own,
+        the assembled level's too) and ``self.density`` is the factor 1 in front of it.  The fused mass term holds one scalar, so
+        ``fused_mass=True`` with a field is refused and "auto" keeps the two-pass form."""
+        rho, field = split_density(density, "density, dt and beta must be positive")
+        self.density_field = field
+        if not (dt > 0.0 and beta > 0.0):
             raise ValueError("density, dt and beta must be positive")
+        if field is not None and fused_mass is True:
+            raise ValueError("NewmarkPMG(fused_mass=True) with a DensityField is not provided: the fused mass term K + c M holds one scalar; "
+                             "fused_mass='auto' or False takes the two-pass form")
         _refuse_contact(kw)
         if not (fused_mass is True or fused_mass is False or fused_mass == "auto"):
             raise ValueError(f"fused_mass must be False, True or 'auto', not {fused_mass!r}")
@@ -88,15 +96,19 @@ class NewmarkPMG(NewtonPMG):
                                    "over several ranks")
         if kw.get("line_search", "cp") == "cp-petsc":
             raise ValueError("NewmarkPMG: line_search must be 'cp' or 'full'")
-        self.density, self.dt, self.beta, self.gamma = float(density), float(dt), float(beta), float(gamma)
+        self.density, self.dt, self.beta, self.gamma = rho, float(dt), float(beta), float(gamma)
         self.a0, self.a2, self.a3 = 1.0 / (beta * dt * dt), 1.0 / (beta * dt), 1.0 / (2.0 * beta) - 1.0
         self.a1 = gamma / (beta * dt)    # d v_{n+1} / d x_{n+1}: the factor of the dashpots in the tangent
         self._asm_kwargs = {"mass_coef": self.a0 * self.density}
+        if field is not None:
+            self._asm_kwargs["mass_density"] = field
         # the tangent's mass term per level (read by A and _get_diag, which the parent's constructor may already call)
-        self.mass = [MassOperator(prob, lv, self.a0 * self.density) for lv in range(len(prob.levels))]
+        self.mass = [MassOperator(prob, lv, self.a0 * self.density, density=field) for lv in range(len(prob.levels))]
         self._mdiag = {}
-        self.fused_mass = fused_mass
+        self.fused_mass = fused_mass = False if field is not None else fused_mass     # (a field: "auto" is the two-pass form)
         self._mass_in_op = []            # the levels whose Jacobian operator carries a0 rho M (fused_mass): cleared by destroy()
+        if any(kw.get(k) is not None for k in ("gravity", "acceleration_field", "spin")):
+            kw.setdefault("density", density)            # the body loads (body.LoadedBody) weigh the body with the stepper's density
         super().__init__(prob, **kw)
         if fused_mass is not False:
             try:
@@ -108,7 +120,7 @@ class NewmarkPMG(NewtonPMG):
                 NewtonPMG.destroy(self)
                 raise
         n, top = prob.lsize(), self.nlev - 1
-        self.mass_res = MassOperator(prob, prob.fine, self.density, mask_mode=2)      # the residual's: reads the boundary values
+        self.mass_res = MassOperator(prob, prob.fine, self.density, mask_mode=2, density=field)      # the residual's: reads the boundary values
         self.xn, self.vn, self.an, self._pred, self._acc, self._mt = (self._vec(n, top) for _ in range(6))
         self._vnew = self._vec(n, top) if self.supports else None      # v_{n+1} of the dashpot force; 1/2 u . K_s u's product
         self.t = 0.0
@@ -309,8 +321,11 @@ class ExplicitDynamics(LoadedBody):
     Refused: a halo with several ranks (the mass operator's interface sums were never run there), density <= 0, dt <= 0, damping < 0,
     and at ``set_initial`` a lumped mass with a non-positive free row."""
 
-    def __init__(self, prob: SolidProblem, density: float, dt: Optional[float] = None, damping: float = 0.0, safety: float = 0.9, **kw):
-        if not (density > 0.0 and (dt is None or dt > 0.0)):
+    def __init__(self, prob: SolidProblem, density, dt: Optional[float] = None, damping: float = 0.0, safety: float = 0.9, **kw):
+        """``density``: a positive float or a mass.DensityField; the lumped mass is formed from it, and ``stable_dt`` follows."""
+        rho, field = split_density(density, "density and dt must be positive")
+        self.density_field = field
+        if not (dt is None or dt > 0.0):
             raise ValueError("density and dt must be positive")
         _refuse_contact(kw)
         if not damping >= 0.0:
@@ -319,8 +334,10 @@ class ExplicitDynamics(LoadedBody):
             raise ValueError("safety must lie in (0, 1]")
         self._refuse_several_ranks(kw.get("halo"), "ExplicitDynamics is", "the mass operator's sums at the interface nodes have not been "
                                    "run over several ranks")
+        if any(kw.get(k) is not None for k in ("gravity", "acceleration_field", "spin")):
+            kw.setdefault("density", density)            # the body loads (body.LoadedBody) weigh the body with the stepper's density
         super().__init__(prob, **kw)
-        self.density, self.damping, self.safety = float(density), float(damping), float(safety)
+        self.density, self.damping, self.safety = rho, float(damping), float(safety)
         self.dt = None if dt is None else float(dt)
         self.c1 = self.c2 = None
         n, top = prob.lsize(), self.nlev - 1
@@ -328,7 +345,7 @@ class ExplicitDynamics(LoadedBody):
         self.vh, self.m, self.minv_m, self._freev = (self._vec(n, top) for _ in range(4))
         self._tally = self._vec(2, top)         # slot 0: the kinetic energy of a sampled step
         self._lanczos_work = None               # the four work vectors of stable_dt, made at its first call
-        self.mass_lumped = MassOperator(prob, prob.fine, self.density, mask_mode=2)
+        self.mass_lumped = MassOperator(prob, prob.fine, self.density, mask_mode=2, density=field)
         self.mass_lumped.lumped(self.m)         # formed once per solver object
         self._set(self._freev, self.free.astype(np.float64))
         self.t, self.nsteps_done = 0.0, 0

@@ -39,7 +39,7 @@ from typing import Optional
 import numpy as np
 
 from . import ceed as cd
-from .mass import MassOperator
+from .mass import MassOperator, split_density
 
 MAX_COLUMNS = 16
 
@@ -81,8 +81,7 @@ class Eigenmodes:
         if nmodes + guard > MAX_COLUMNS:
             raise ValueError(f"nmodes + guard = {nmodes + guard} > {MAX_COLUMNS}: the 3 (nmodes + guard) columns of [W | X | P] must fit the "
                              f"{cd.BLOCK_MAX_COLS} columns of a block operation")
-        if not density > 0.0:
-            raise ValueError("density must be positive")
+        rho, field = split_density(density, "density must be positive")     # a mass.DensityField: B = M_rho
         if sol.halos:
             raise ValueError("Eigenmodes is not provided with a halo (several ranks): the mass operator's interface sums and the block "
                              "reductions have not been run over several ranks")
@@ -93,7 +92,7 @@ class Eigenmodes:
         if isinstance(sol, NewmarkPMG):
             if sol.smoother == "pbjacobi":
                 raise ValueError("Eigenmodes: smoother='pbjacobi' is not provided with a Newmark solver")
-            if abs(sol.density - density) > 1e-14 * abs(density):
+            if field is not sol.density_field or abs(sol.density - rho) > 1e-14 * abs(rho):
                 raise ValueError(f"Eigenmodes: density {density!r} differs from the Newmark solver's {sol.density!r}: its operator "
                                  "K + a0 rho M shifts the spectrum by a0 only with the same rho")
             self.shift = sol.a0
@@ -101,12 +100,12 @@ class Eigenmodes:
             raise ValueError("Eigenmodes: no constrained dof and no shift: K is singular (six rigid-body modes); build the solver as a "
                              "dynamics.NewmarkPMG, whose operator K + a0 rho M is positive definite")
         self.sol, self.prob, self.ceed = sol, sol.p, sol.ceed
-        self.density, self.nmodes, self.guard, self.m = float(density), int(nmodes), int(guard), int(nmodes + guard)
+        self.density, self.density_field, self.nmodes, self.guard, self.m = rho, field, int(nmodes), int(guard), int(nmodes + guard)
         self.tol, self.maxit, self.seed, self.profile = float(tol), int(maxit), int(seed), bool(profile)
         self.n, self.top = self.prob.lsize(), sol.nlev - 1
         if self.m > int(np.count_nonzero(sol.free)):
             raise ValueError("nmodes + guard exceeds the number of free dofs")
-        self.mass = MassOperator(self.prob, self.prob.fine, self.density)
+        self.mass = MassOperator(self.prob, self.prob.fine, self.density, density=field)
         self.blocks = None
         self.block_calls = {"gram": 0, "combine": 0}
 

@@ -48,9 +48,11 @@ class NewtonPMG(LoadedBody):
                  traction: Optional[Dict[int, tuple]] = None, pressure: Optional[Dict[int, float]] = None, pressure_tangent: str = "full",
                  contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
                  traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
-                 hydrostatic: Optional[Dict[int, dict]] = None):
+                 hydrostatic: Optional[Dict[int, dict]] = None, density=None, gravity=None, acceleration_field=None,
+                 spin: Optional[dict] = None):
         """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact, traction_field,
-        pressure_field, hydrostatic``): body.LoadedBody.
+        pressure_field, hydrostatic, density, gravity, acceleration_field, spin``): body.LoadedBody.  Of a spin's softening tangent, as
+        of a follower pressure's, the V-cycle sees nothing.
         Of a follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner
         is the volume operator's.
         ``contact_tangent``: "levels" (default) adds the contact tangent C to the operator ``A`` and to the diagonal of EVERY
@@ -92,7 +94,8 @@ class NewtonPMG(LoadedBody):
             raise ValueError("graph=True needs coarse='chebyshev', 'assembled' or 'amg' (the CG coarse solve reads dot products on the host)")
         super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
                          pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent,
-                         support=support, traction_field=traction_field, pressure_field=pressure_field, hydrostatic=hydrostatic)
+                         support=support, traction_field=traction_field, pressure_field=pressure_field, hydrostatic=hydrostatic,
+                         density=density, gravity=gravity, acceleration_field=acceleration_field, spin=spin)
         self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
