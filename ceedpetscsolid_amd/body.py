@@ -59,8 +59,15 @@ class LoadedBody:
                  contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
                  traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
                  hydrostatic: Optional[Dict[int, dict]] = None, density=None, gravity=None, acceleration_field=None,
-                 spin: Optional[dict] = None):
-        """Body loads (mass.py; one rank): ``density`` -- a positive float or a ``mass.DensityField`` -- is required by the three below.
+                 spin: Optional[dict] = None, thermal: Optional[dict] = None):
+        """Thermal load (thermal.py; one rank): ``thermal`` = dict(alpha=, theta=, tangent="full") -- a nodal temperature change theta
+        from the stress-free state (a float, an array (nnodes,) of the fine level, or a callable of its node coordinates) with the
+        linearised coefficient of expansion alpha; theta scales with the load fraction, like ``forcing``.  linElas, hyperSS: the dead
+        load +int beta theta_h div v is folded once into the load vector.  hyperFS: the term follows the body -- ``has_followers()`` is
+        true, every residual adds load R_theta(x) (``follower_add``), and with tangent "full" its exact, symmetric tangent
+        load T_theta(x) goes to ``A_outer`` only: the multigrid levels and smoothers do not see it, as with ``pressure_tangent``
+        ("none" omits it).  No stiffness is added on the levels, so ``ExplicitDynamics.stable_dt`` is what it was.
+        Body loads (mass.py; one rank): ``density`` -- a positive float or a ``mass.DensityField`` -- is required by the three below.
         ``gravity``: (gx, gy, gz), an acceleration; the load int rho N g = M_rho (tile g), through the mass apply with mask mode 2, is
         folded once into the load vector and scaled by the load fraction like ``forcing``.
         ``acceleration_field``: array (nnodes, 3) | callable(X) -> (n, 3), a nodal acceleration b_h; the load M_rho b_h likewise
@@ -121,6 +128,9 @@ class LoadedBody:
             self._refuse_several_ranks(halo, "contact surfaces (contact=) are", "the face sums of the interface nodes are not summed over the ranks")
         if support:
             self._refuse_several_ranks(halo, "supports (support=) are", "the face sums of the interface nodes are not summed over the ranks")
+        if thermal is not None:
+            self._refuse_several_ranks(halo, "thermal loads (thermal=) are",
+                                       "the element sums at the interface nodes have not been run over several ranks")
         if many and single and self.nlev > 1:
             raise ValueError("a multi-rank multigrid solve needs one HaloExchange per level")
         if many and len(halo) != self.nlev:
@@ -167,6 +177,34 @@ class LoadedBody:
         self._setup_contact(contact, contact_tangent)
         self._setup_support(support)
         self._setup_body_loads(density, gravity, acceleration_field, spin, halo)
+        self._setup_thermal(thermal, halo)
+
+    # ---- thermal load (thermal.py) ------------------------------------------------------------
+    def _setup_thermal(self, thermal, halo):
+        """With no thermal= given nothing here runs and no thermal operator is made."""
+        self.thermal = None                          # the ThermalLoad of the fine level
+        self.thermal_follows = False                 # hyperFS: added in every residual
+        self.thermal_tangent = "full"
+        if thermal is None:
+            return
+        if not isinstance(thermal, dict) or set(thermal) - {"alpha", "theta", "tangent"} or not {"alpha", "theta"} <= set(thermal):
+            raise ValueError("thermal: dict(alpha=, theta=, tangent='full') expected")
+        tangent = thermal.get("tangent", "full")
+        if tangent not in ("full", "none"):
+            raise ValueError(f"thermal: tangent must be 'full' or 'none', not {tangent!r}")
+        from .thermal import ThermalLoad
+        prob = self.p
+        n, top = prob.lsize(), self.nlev - 1
+        self.thermal = ThermalLoad(prob, prob.fine, thermal["alpha"], thermal["theta"], prob.problem)
+        self.thermal_tangent = tangent
+        if prob.problem == "hyperFS":
+            self.thermal_follows = True
+            return
+        out = self._vec(n, top)
+        self.thermal.force(None, out)                # masked rows are stored as zeros: fv stays zero on the constrained dofs
+        if self.fv is None:
+            self.fv = self._vec(n, top)
+        self.axpby(self.fv, -1.0, out, 1.0)          # R = F_int - load fv: the share R_theta of the residual is -fv's
 
     # ---- body loads (mass.py) -----------------------------------------------------------------
     def _setup_body_loads(self, density, gravity, acceleration_field, spin, halo):
@@ -343,8 +381,9 @@ class LoadedBody:
             self.surface_loads.append(sl)
 
     def has_followers(self) -> bool:
-        """Whether a load follows the body: a constant pressure, a pressure field, a hydrostatic pressure or a spin with follow=True."""
-        return bool(self.pressure_loads or self.field_loads or self.spin)
+        """Whether a load follows the body: a constant pressure, a pressure field, a hydrostatic pressure, a spin with follow=True or a
+        thermal load in the finite-strain model."""
+        return bool(self.pressure_loads or self.field_loads or self.spin or self.thermal_follows)
 
     def follower_add(self, x, R):
         """R += load sum_s g_s(x) over every load that follows the surface, x the position's displacement WITH its boundary values.
@@ -358,6 +397,9 @@ class LoadedBody:
                 sl.hydrostatic_add(par[0], par[1], par[2], self.load, x, R)
         if self.spin:                                  # the centrifugal load grows with the radius the points have moved to
             self._spin_add(x, R)
+        if self.thermal_follows:                       # theta scales with the load fraction
+            self.thermal.set_scale(self.load)
+            self.thermal.force(x, R, add=True)
 
     def follower_tangent_add(self, x, dx, y):
         """y += load sum_s T_s(x) dx, the exact tangents of ``follower_add``."""
@@ -374,6 +416,13 @@ class LoadedBody:
         in a Krylov vector; masked rows are not written)."""
         if self.spin and self.spin["tangent"] == "full":
             self._spin_add(dx, y)
+
+    def thermal_tangent_add(self, x, dx, y):
+        """y += load T_theta(x) dx, the exact tangent of the finite-strain thermal term (masked entries of dx read as zero, masked rows
+        are not written)."""
+        if self.thermal_follows and self.thermal_tangent == "full":
+            self.thermal.set_scale(self.load)
+            self.thermal.tangent(x, dx, y, add=True)
 
     # ---- contact with a rigid obstacle (contact.py) -------------------------------------------
     def _setup_contact(self, contact, contact_tangent):
@@ -530,6 +579,9 @@ class LoadedBody:
         if self.body_mass is not None:
             self.body_mass.destroy()
         self.body_mass = self.spin = None
+        if self.thermal is not None:
+            self.thermal.destroy()
+        self.thermal, self.thermal_follows = None, False
         for o in self._vectors + self._own_rhalos:
             o.destroy()
         self._vectors, self._own_rhalos, self._x0 = [], [], {}
@@ -621,6 +673,7 @@ class LoadedBody:
         if self.pressure_tangent == "full":
             self.follower_tangent_add(self.Xloc, x, y)
         self.spin_tangent_add(x, y)
+        self.thermal_tangent_add(self.Xloc, x, y)
         if self.contacts and self.contact_tangent == "outer":
             self.contact_tangent_add(lv, x, y)
 

@@ -216,7 +216,7 @@ struct CeedQFunction_private {
 
 struct OpField { bool set = false; CeedElemRestriction rstr = nullptr; CeedBasis basis = nullptr; CeedVector vec = nullptr; };
 
-enum PlanKind { PLAN_NONE = 0, PLAN_FUSED_GRAD, PLAN_SETUP_GEO, PLAN_PROLONG, PLAN_RESTRICT, PLAN_COORD, PLAN_ENERGY, PLAN_MASS, PLAN_STRESS };
+enum PlanKind { PLAN_NONE = 0, PLAN_FUSED_GRAD, PLAN_SETUP_GEO, PLAN_PROLONG, PLAN_RESTRICT, PLAN_COORD, PLAN_ENERGY, PLAN_MASS, PLAN_STRESS, PLAN_THERMAL };
 
 struct CeedXHalo_private;
 
@@ -231,6 +231,7 @@ struct CeedOperator_private {
   int plan = PLAN_NONE;
   int i_active = -1, i_qdata = -1, i_state = -1, i_weight = -1, o_active = -1, o_state = -1, o_qdata = -1;
   int i_rho = -1;                     // PLAN_MASS of the QFunction "MassField": the passive density field; -1 for "Mass"
+  int i_theta = -1, i_du = -1;        // PLAN_THERMAL, PLAN_STRESS with a thermal term: the temperature field; the passive displacement of the loads (-1: none)
   cps::BasisTables tables{};
   cps::BasisTables tables_sq{};       // PLAN_MASS: `interp` squared entry by entry, the table of the mass diagonal
   double eo[6][cps::EO_TAB];          // even-odd forms of the six 1-D products (fused operators with pencil_even_odd(Q))

@@ -226,6 +226,7 @@ int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add) {
 // restriction's plain offsets, never an operator's flagged ones.  Points: the kernel stores every entry of [nelem][6][Q^3] and nothing else
 // (a longer vector keeps its tail; ApplyAdd is refused: nothing is summed).  Nodal: the element results of B^T (w det J {sigma, 1}) go to the
 // Ceed's scratch in the E-layout of the 7-component output restriction, whose ordered transpose sums them (cold_sum_prepare / _finish).
+// The QFunctions with the thermal term (op->i_theta >= 0) take a passive temperature field beside: the kernel's modes with a field.
 int apply_stress(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   CeedQFunction qf = op->qf;
   OpField &u = op->in[0], &o = op->out[0];
@@ -242,17 +243,21 @@ int apply_stress(CeedOperator op, CeedVector in, CeedVector out, bool add) {
   if (!is_passive(qd)) return ceed_error("qdata needs a passive vector");
   if ((size_t)qd->length < 10 * npts) return ceed_error("qdata vector too short");
   StressArgs a{};
+  ThermalArgs th{};
+  const bool thermal = op->i_theta >= 0;
   double *pu, *py, *pq;
   CHK(read_phys(qf, &a.nu, &a.E));
   lame_constants(a.nu, a.E, &a.lambda, &a.TwoMu);
-  a.model = qf->kind == QF_STRESS_LINELAS ? 0 : (qf->kind == QF_STRESS_HYPERSS ? 1 : 2);
+  a.model = (qf->kind == QF_STRESS_LINELAS || qf->kind == QF_STRESS_LINELAS_THERMAL) ? 0 : ((qf->kind == QF_STRESS_HYPERSS || qf->kind == QF_STRESS_HYPERSS_THERMAL) ? 1 : 2);
+  if (thermal) CHK(thermal_field_args(op, op->in[op->i_theta].vec, a.nu, a.E, th));      // (the checks come first: nothing is queued before them)
   CHK(vec_dev(in, false, &pu)); CHK(vec_dev(out, true, &py)); CHK(vec_dev(qd, false, &pq));
   a.offsets = u.rstr->d_offsets.get(); a.x = pu; a.qdata = pq; a.nelem = u.rstr->nelem;
   a.out = py;
   if (nodal) CHK(cold_sum_prepare(op, o.rstr, out, py, add, &a.out));
   TimerScope ts(op, op->ceed->stream);
   const char *kname = "";
-  hipError_t e = launch_stress(P, Q, nodal, op->tables, a, op->ceed->stream, &kname);
+  hipError_t e = thermal ? launch_stress_thermal(P, Q, nodal ? THERMAL_MODE_NODAL : THERMAL_MODE_POINTS, op->tables, a, th, op->ceed->stream, &kname)
+                         : launch_stress(P, Q, nodal, op->tables, a, op->ceed->stream, &kname);
   if (no_kernel(e, kname)) return ceed_error("no stress kernel instantiated for P=%d Q=%d", P, Q);
   HIPCHK(e);
   if (nodal) return cold_sum_finish(op, o.rstr, a.out, py, add, kname);

@@ -13,6 +13,7 @@
 //   coord / energy : forcing, MMS, strain energy, diagnostics   (:555-737)
 //   mass       : INTERP active in, NONE qdata, INTERP active out (no call site in the reference: the elastodynamic solve, dynamics.py)
 //   stress     : GRAD active in, NONE qdata -> NONE (6, at the points) or INTERP (7, summed at the nodes) (none either: postprocess.py)
+//   thermal    : INTERP (1) theta, NONE qdata[, GRAD displacement] -> GRAD active out; its tangent; the stress with theta (thermal.py)
 //
 // There is NO host fallback: a graph outside these families or a QFunction without a device functor (ceed_qfunction.cpp) is a loud
 // error.  The families' applies: ceed_op_fused.cpp (fused_grad, with its diagonals and the state kernel), ceed_op_other.cpp (the rest but the mass operator: ceed_op_mass.cpp).
@@ -124,12 +125,25 @@ static bool is_state(const OpField &f, int Q) { return is_strided(f.rstr) && f.r
 // the coordinates of trilinear elements (setuplibceed.c:279,339)
 static bool is_trilinear(const OpField &f) { return is_disp(f) && f.rstr->elemsize == 8 && f.basis->P1d == 2; }
 
+// The temperature field of the thermal loads and of the stress with a thermal term against the displacement field `u` it rides with: the
+// rules of rho in MassField (the same nodes and points: the kernel interpolates theta with u's table, compared entry by entry).
+static const char *const THETA_COMPONENTS = "theta must be a 1-component field through INTERP: a scalar temperature change per node";
+static const char *theta_defect(const OpField &th, const OpField &u) {
+  const int P = u.basis->P1d, Q = u.basis->Q1d;
+  if (!is_offsets(th.rstr) || th.rstr->ncomp != 1) return "theta must be on an offsets restriction with 1 component";
+  if (th.rstr->nelem != u.rstr->nelem) return "theta's restriction must have the element count of u's";
+  if (th.rstr->elemsize != cube(P)) return "theta's restriction must have the element size P^3 of u's";
+  if (th.basis == CEED_BASIS_COLLOCATED || th.basis->P1d != P || th.basis->Q1d != Q || th.basis->interp1d != u.basis->interp1d)
+    return "theta's basis must have u's P, Q and interp table";
+  return nullptr;
+}
+
 int op_plan(CeedOperator op) {
   if (op->plan != PLAN_NONE) return 0;
   CeedQFunction qf = op->qf;
   for (size_t i = 0; i < qf->in.size(); i++) if (!op->in[i].set) return ceed_error("operator field '%s' not set", qf->in[i].name.c_str());
   for (size_t i = 0; i < qf->out.size(); i++) if (!op->out[i].set) return ceed_error("operator field '%s' not set", qf->out[i].name.c_str());
-  op->i_active = op->i_qdata = op->i_state = op->i_weight = op->o_active = op->o_state = op->o_qdata = op->i_rho = -1;
+  op->i_active = op->i_qdata = op->i_state = op->i_weight = op->o_active = op->o_state = op->o_qdata = op->i_rho = op->i_theta = op->i_du = -1;
   const int k = qf->kind;
   auto unsupported = [&](const char *why) {
     return ceed_error("operator with QFunction '%s' is outside the kernel families of /gpu/hip/mi355x: %s", qf->name.c_str(), why);
@@ -311,15 +325,19 @@ int op_plan(CeedOperator op) {
     op->plan = PLAN_MASS;
     return 0;
   }
-  if (k == QF_STRESS_LINELAS || k == QF_STRESS_HYPERSS || k == QF_STRESS_HYPERFS) {
+  const bool stress_thermal = k == QF_STRESS_LINELAS_THERMAL || k == QF_STRESS_HYPERSS_THERMAL || k == QF_STRESS_HYPERFS_THERMAL;
+  if (k == QF_STRESS_LINELAS || k == QF_STRESS_HYPERSS || k == QF_STRESS_HYPERFS || stress_thermal) {
     // (du GRAD(9) active, qdata NONE(10)) -> stress NONE(6) at the points (strided 6 x Q^3, collocated)
     //                                      | stress INTERP(7) at the nodes (7 interlaced components: w det J {sigma, 1} summed per node)
-    if (qf->in.size() != 2 || qf->out.size() != 1) return unsupported("stress takes (du, qdata) -> stress");
-    const QFField &fdu = qf->in[0], &fqd = qf->in[1], &fo = qf->out[0];
+    // the QFunctions with the thermal term: (du, theta INTERP(1) passive, qdata) -> the same outputs
+    const size_t nin = stress_thermal ? 3 : 2;
+    if (qf->in.size() != nin || qf->out.size() != 1) return unsupported(stress_thermal ? "stress with the thermal term takes (du, theta, qdata) -> stress" : "stress takes (du, qdata) -> stress");
+    const QFField &fdu = qf->in[0], &fqd = qf->in[nin - 1], &fo = qf->out[0];
     const bool points = fo.emode == CEED_EVAL_NONE && fo.size == 6, nodal = fo.emode == CEED_EVAL_INTERP && fo.size == 7;
     if (fdu.emode != CEED_EVAL_GRAD || fdu.size != 9 || fqd.emode != CEED_EVAL_NONE || fqd.size != 10 || !(points || nodal))
       return unsupported("stress eval modes must be GRAD(9), NONE(10) -> NONE(6) at the points or INTERP(7) at the nodes");
-    OpField &u = op->in[0], &qd = op->in[1], &o = op->out[0];
+    if (stress_thermal && (qf->in[1].emode != CEED_EVAL_INTERP || qf->in[1].size != 1)) return unsupported(THETA_COMPONENTS);
+    OpField &u = op->in[0], &qd = op->in[nin - 1], &o = op->out[0];
     if (u.vec != CEED_VECTOR_ACTIVE) return unsupported("du must be the active input of a stress operator");
     if (o.vec != CEED_VECTOR_ACTIVE) return unsupported("stress must be the active output");
     if (!is_disp(u)) return unsupported("displacement field");
@@ -339,9 +357,47 @@ int op_plan(CeedOperator op) {
       if (o.basis == CEED_BASIS_COLLOCATED || o.basis->P1d != P || o.basis->Q1d != Q || o.basis->interp1d != u.basis->interp1d)
         return unsupported("nodal stress basis must have the displacement basis's P, Q and interp table");
     }
-    op->i_active = 0; op->i_qdata = 1; op->o_active = 0;
+    if (stress_thermal) {
+      if (!nodes_fit(u)) return unsupported("restriction element size is not P^3");
+      if (const char *why = theta_defect(op->in[1], u)) return unsupported(why);
+      op->i_theta = 1;
+    }
+    op->i_active = 0; op->i_qdata = (int)nin - 1; op->o_active = 0;
     fill_tables(op->tables, u.basis);
     op->plan = PLAN_STRESS;
+    return 0;
+  }
+  if (k == QF_THERMAL_FORCE || k == QF_THERMAL_TANGENT) {
+    // ThermalForce:   (theta INTERP(1) active, qdata NONE(10)[, du GRAD(9) passive]) -> dv GRAD(9) active
+    // ThermalTangent: (ddu GRAD(9) active, du GRAD(9) passive, theta INTERP(1) passive, qdata NONE(10)) -> dv GRAD(9) active
+    // theta rides with the displacement field of dv: a scalar restriction of its own on the same elements, the same nodes and points.
+    // Which model the context states is read at every apply (apply_thermal), where hyperFS without du and a small-strain tangent are refused.
+    const bool tangent = k == QF_THERMAL_TANGENT;
+    if (qf->out.size() != 1 || (tangent ? qf->in.size() != 4 : (qf->in.size() != 2 && qf->in.size() != 3)))
+      return unsupported(tangent ? "ThermalTangent takes (ddu, du, theta, qdata) -> dv" : "ThermalForce takes (theta, qdata[, du]) -> dv");
+    const int it = tangent ? 2 : 0, iq = tangent ? 3 : 1, iu = tangent ? 1 : (qf->in.size() == 3 ? 2 : -1);
+    const QFField &ft = qf->in[it], &fq = qf->in[iq], &fv = qf->out[0];
+    if (ft.emode != CEED_EVAL_INTERP || ft.size != 1) return unsupported(THETA_COMPONENTS);
+    bool modes = fq.emode == CEED_EVAL_NONE && fq.size == 10 && fv.emode == CEED_EVAL_GRAD && fv.size == 9;
+    if (iu >= 0) modes = modes && qf->in[iu].emode == CEED_EVAL_GRAD && qf->in[iu].size == 9;
+    if (tangent) modes = modes && qf->in[0].emode == CEED_EVAL_GRAD && qf->in[0].size == 9;
+    if (!modes) return unsupported(tangent ? "ThermalTangent eval modes must be GRAD(9) active, GRAD(9), INTERP(1), NONE(10) -> GRAD(9) active"
+                                           : "ThermalForce eval modes must be INTERP(1) active, NONE(10)[, GRAD(9)] -> GRAD(9) active");
+    OpField &th = op->in[it], &qd = op->in[iq], &v = op->out[0];
+    if (op->in[0].vec != CEED_VECTOR_ACTIVE || v.vec != CEED_VECTOR_ACTIVE) return unsupported("the first input and dv must be the active fields");
+    if (tangent && !is_passive(th.vec)) return unsupported("theta must be a passive field with a vector of its own, not the active one");
+    if (iu >= 0 && !is_passive(op->in[iu].vec)) return unsupported("du must be a passive field with a vector of its own, not the active one");
+    if (!is_disp(v)) return unsupported("dv must be 3 interlaced components through offsets, on a basis");
+    if (!nodes_fit(v)) return unsupported("restriction element size is not P^3");
+    if (iu >= 0 && (op->in[iu].rstr != v.rstr || op->in[iu].basis != v.basis)) return unsupported("du must share dv's restriction and basis");
+    if (tangent && (op->in[0].rstr != v.rstr || op->in[0].basis != v.basis)) return unsupported("ddu must share dv's restriction and basis");
+    const int P = v.basis->P1d, Q = v.basis->Q1d;
+    if (!is_qdata(qd, Q) || qd.rstr->nelem != v.rstr->nelem) return unsupported("qdata must be a strided 10 x Q^3 field");
+    if (P > Q) return unsupported("the thermal load kernel needs P <= Q");
+    if (const char *why = theta_defect(th, v)) return unsupported(why);
+    op->i_active = 0; op->i_theta = it; op->i_qdata = iq; op->i_du = iu; op->o_active = 0;
+    fill_tables(op->tables, v.basis);
+    op->plan = PLAN_THERMAL;
     return 0;
   }
   return unsupported("no kernel family");
@@ -369,6 +425,7 @@ static int op_apply_single(CeedOperator op, CeedVector in, CeedVector out, bool 
   case PLAN_COORD: return apply_coord(op, in, out, add);
   case PLAN_MASS: return apply_mass(op, in, out, add);
   case PLAN_STRESS: return apply_stress(op, in, out, add);
+  case PLAN_THERMAL: return apply_thermal(op, in, out, add);
   default: return ceed_error("operator has no plan");
   }
 }
@@ -406,6 +463,10 @@ extern "C" int CeedXOperatorSetDirichletMaskMode(CeedOperator op, CeedMemType mt
   if (mtype != CEED_MEM_HOST) return ceed_error("pass the Dirichlet mask in host memory (it is folded into the offsets once)");
   if (op->plan == PLAN_FUSED_GRAD || op->plan == PLAN_MASS) {
     CHK(make_flagged(op->in[op->i_active].rstr, mask, lsize, op->d_off_flagged));
+    op->h_mask.assign(mask, mask + lsize);
+  } else if (op->plan == PLAN_THERMAL) {     // the mask of the DISPLACEMENT L-vector: dv's restriction (ThermalForce's active input is theta)
+    if (!mask) return ceed_error("the thermal load operators take the mask of the displacement vector as the input-side mask");
+    CHK(make_flagged(op->out[0].rstr, mask, lsize, op->d_off_flagged));
     op->h_mask.assign(mask, mask + lsize);
   } else if (op->plan == PLAN_PROLONG || op->plan == PLAN_RESTRICT) {
     if (!mask || !mask_out) return ceed_error("transfer operators need the input-side and the output-side mask");

@@ -1,6 +1,6 @@
 // ceed_operator.hpp -- what the operator sources share: ceed_operator.cpp (the object, op_plan, the dispatch), ceed_op_fused.cpp (the
 // residual / Jacobian family), ceed_op_other.cpp (transfers, SetupGeo, coordinate and energy operators), ceed_op_mass.cpp (the mass
-// operator).  Private, like ceed_impl.hpp.
+// operator), ceed_op_thermal.cpp (the thermal loads).  Private, like ceed_impl.hpp.
 #pragma once
 #include "ceed_impl.hpp"
 #include "index_maps.hpp"
@@ -31,6 +31,10 @@ int apply_energy(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_coord(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_mass(CeedOperator op, CeedVector in, CeedVector out, bool add);
 int apply_stress(CeedOperator op, CeedVector in, CeedVector out, bool add);
+int apply_thermal(CeedOperator op, CeedVector in, CeedVector out, bool add);
+// the temperature field of a thermal load or of a stress with the thermal term: its vector against its restriction, then the kernel's
+// arguments (theta, its offsets, beta from the context {nu, E, alpha[, model]})
+int thermal_field_args(CeedOperator op, CeedVector theta, double nu, double E, cps::ThermalArgs &th);
 // CeedOperatorLinearAssembleDiagonal of a PLAN_MASS operator (overwrites `assembled`; masked rows are zero)
 int mass_diagonal(CeedOperator op, CeedVector assembled);
 // The Dirichlet flags of the operator's mask in the row order of a transpose map, as an apply hands them to launch_assemble (*flags

@@ -13,6 +13,8 @@ static int resolve_qf(const std::string &name) {
       {"HyperFSEnergy", QF_ENERGY_HYPERFS}, {"LinElasDiagnostic", QF_DIAG_LINELAS}, {"HyperSSDiagnostic", QF_DIAG_HYPERSS},
       {"HyperFSDiagnostic", QF_DIAG_HYPERFS}, {"Mass", QF_MASS}, {"MassField", QF_MASS_FIELD},
       {"LinElasStress", QF_STRESS_LINELAS}, {"HyperSSStress", QF_STRESS_HYPERSS}, {"HyperFSStress", QF_STRESS_HYPERFS},
+      {"ThermalForce", QF_THERMAL_FORCE}, {"ThermalTangent", QF_THERMAL_TANGENT}, {"LinElasStressThermal", QF_STRESS_LINELAS_THERMAL},
+      {"HyperSSStressThermal", QF_STRESS_HYPERSS_THERMAL}, {"HyperFSStressThermal", QF_STRESS_HYPERFS_THERMAL},
   };
   for (auto &t : tab) if (name == t.n) return t.k;
   return QF_NONE;

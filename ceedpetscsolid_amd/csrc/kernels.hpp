@@ -29,6 +29,11 @@ enum QFKind : int {
   QF_STRESS_HYPERSS,
   QF_STRESS_HYPERFS,
   QF_MASS_FIELD,      // v = c rho qdata[0] u, rho a passive INTERP field: the mass operator with a density field (kernels_mass.hip)
+  QF_THERMAL_FORCE,   // the residual of the thermal coupling energy from a nodal temperature field (kernels_stress.hip, modes with a field)
+  QF_THERMAL_TANGENT, // its tangent in the finite-strain model
+  QF_STRESS_LINELAS_THERMAL,  // the stress with the thermal term: QF_STRESS_* plus a passive INTERP(1) temperature field
+  QF_STRESS_HYPERSS_THERMAL,
+  QF_STRESS_HYPERFS_THERMAL,
 };
 
 constexpr int MAXN1D = 8;  // largest P or Q supported by the kernel tables
@@ -240,6 +245,18 @@ struct StressArgs {
   double nu, E, lambda, TwoMu;
 };
 
+// The temperature field of the thermal loads and of the stress with a thermal term (QFunctions "ThermalForce", "ThermalTangent",
+// "{LinElas,HyperSS,HyperFS}StressThermal"; k_stress's modes 2 .. 5), a struct of its own beside StressArgs, whose layout the kernels
+// without a field keep.  The two load modes store element results [nelem][P^3][3] into StressArgs::out, which launch_assemble() sums.
+struct ThermalArgs {
+  const double *theta;            // the scalar temperature change; its address is the launch argument, so a recording sees new values behind it
+  const uint32_t *theta_offsets;  // [nelem][P^3] plain indices into theta: no Dirichlet flags, no factor 3
+  double beta;                    // E alpha / (1 - 2 nu), formed on the host at every apply
+  const double *dx;               // tangent: the variation, an L-vector interlaced [node][3], read through StressArgs::offsets
+  int mask_in;                    // tangent: flagged components of dx read as zero (the flags ride in StressArgs::offsets)
+  int mask_out;                   // the loads: flagged rows are dropped -- by launch_assemble's row flags, not by the kernel
+};
+
 // Each returns hipSuccess or the launch error; `name` receives a static string
 // naming the instantiation, or the call returns hipErrorInvalidValue when the
 // (P, Q, qf) combination is not instantiated.
@@ -267,6 +284,10 @@ hipError_t launch_mass(int P, int Q, bool diag, const BasisTables &t, const Mass
 hipError_t launch_mass_field(int P, int Q, bool diag, const BasisTables &t, const MassArgs &a, const MassFieldArgs &f, hipStream_t s, const char **name);
 // names "stress<P=..,Q=..,points>" / "stress<P=..,Q=..,nodal>"; the pairs of CPS_DIAG_PQ
 hipError_t launch_stress(int P, int Q, bool nodal, const BasisTables &t, const StressArgs &a, hipStream_t s, const char **name);
+// the modes with a temperature field (`mode`: THERMAL_MODE_*, the values of kernels_stress.hip's StressMode); names "thermal_force<P=..,Q=..>",
+// "thermal_tangent<P=..,Q=..>", "stress<P=..,Q=..,points+thermal>", "stress<P=..,Q=..,nodal+thermal>"; the pairs of CPS_DIAG_PQ
+enum ThermalMode : int { THERMAL_MODE_FORCE = 2, THERMAL_MODE_TANGENT = 3, THERMAL_MODE_POINTS = 4, THERMAL_MODE_NODAL = 5 };
+hipError_t launch_stress_thermal(int P, int Q, int mode, const BasisTables &t, const StressArgs &a, const ThermalArgs &th, hipStream_t s, const char **name);
 
 // The instantiations of one quadrature size are compiled as pencil_inst_parts(Q) objects (kernels_fused_inst.hip, -DCPS_PART=<k>): the kernels
 // with (Q - P) % parts == k -- the Q = 8 object alone took 72 s of a 90 s build.  csrc/Makefile lists the same parts.

@@ -72,7 +72,7 @@ def _series4_shifted(x):
     return 2 * np.where(lo, -ln2h, np.where(hi, ln2h, 0.0)) + _series4(np.where(lo, 1 + 2 * x, np.where(hi, (x - 1) / 2, x)))
 
 
-def stress_law(problem: str, nu: float, E: float, g: np.ndarray) -> np.ndarray:
+def stress_law(problem: str, nu: float, E: float, g: np.ndarray, iso=None) -> np.ndarray:
     """The Cauchy stress THE RESIDUAL INTEGRATES at physical gradients g[..., c, k] = d u_c / d x_k, as [..., 6] in the order xx, yy, zz,
     yz, xz, xy (float64 NumPy; the portable form of ``Stress`` and the device kernel's yardstick).
 
@@ -80,7 +80,10 @@ def stress_law(problem: str, nu: float, E: float, g: np.ndarray) -> np.ndarray:
     HALF of Hooke's 2 mu e_ij.  That quirk of the reference makes the model anisotropic; the stress reported is the one the residual
     integrates and is NOT corrected here.  hyperSS: lambda log1p(tr e) I + 2 mu e.  hyperFS: F S F^T / det F, S = lambda ln J C^-1 +
     mu C^-1 (C - I) (= mu I + (lambda ln J - mu) C^-1, in the residual's cancellation-free form).  Both logarithms are the reference's
-    four-term series."""
+    four-term series.
+
+    ``iso`` (optional, broadcast over the points): beta theta_h of a thermal field (thermal.py); the stress is then sigma - iso I
+    (linElas, hyperSS) or sigma - (iso / det F) I (hyperFS), the stress the residual with the thermal term integrates."""
     g = np.asarray(g, dtype=np.float64)
     two_mu = E / (1 + nu)
     lam = (3 * (E / (3 * (1 - 2 * nu))) - two_mu) / 3
@@ -114,6 +117,11 @@ def stress_law(problem: str, nu: float, E: float, g: np.ndarray) -> np.ndarray:
         sig = F @ S @ np.swapaxes(F, -1, -2) / np.linalg.det(F)[..., None, None]
     else:
         raise ValueError(f"unknown problem {problem!r}")
+    if iso is not None:
+        iso = np.asarray(iso, dtype=np.float64)
+        if problem == "hyperFS":
+            iso = iso / np.linalg.det(g + eye)
+        sig = sig - iso[..., None, None] * eye
     return np.stack([sig[..., i, j] for i, j in VOIGT], axis=-1)
 
 
@@ -134,7 +142,10 @@ class Stress:
     quadrature data read back once (which form runs where, and why it is the device tests' yardstick: DESIGN.md 2).  Several ranks
     are refused: the interface nodes of an element partition would need both sums exchanged."""
 
-    def __init__(self, prob: SolidProblem, problem: str, portable: Optional[bool] = None, halo=None):
+    def __init__(self, prob: SolidProblem, problem: str, portable: Optional[bool] = None, halo=None, thermal=None):
+        """``thermal``: a ``thermal.ThermalLoad`` of the fine level, or dict(alpha=, theta=) from which one is made (and owned): the stress
+        reported is then the one the residual with the thermal term integrates, sigma - beta theta_h I (hyperFS: / det F), with the
+        load's current ``scale`` on theta.  With ``thermal=None`` this is the object it was."""
         if problem not in STRESS_QF:
             raise ValueError(f"unknown problem {problem!r}")
         hl = halo if halo is None or isinstance(halo, (list, tuple)) else [halo]
@@ -152,7 +163,18 @@ class Stress:
         self.offsets = (np.asarray(lv.dofmap.offsets(), dtype=np.int64) & 0x1FFFFFFF).reshape(self.ne, self.P ** 3)
         self.nodes = (self.offsets // 3).reshape((self.ne,) + 3 * (self.P,))                      # [e][k][j][i]
         src, name = STRESS_QF[problem]
+        self.thermal, self._own_thermal = None, False
+        if thermal is not None:
+            from .thermal import ThermalLoad
+            name += "Thermal"
+            self._own_thermal = not isinstance(thermal, ThermalLoad)
+            if self._own_thermal and (not isinstance(thermal, dict) or set(thermal) != {"alpha", "theta"}):
+                raise ValueError("Stress: thermal is a thermal.ThermalLoad or dict(alpha=, theta=)")
         self.portable = (not c.has_qfunction(name)) if portable is None else bool(portable)
+        if thermal is not None:
+            self.thermal = ThermalLoad(prob, prob.fine, thermal["alpha"], thermal["theta"], problem, portable=self.portable) if self._own_thermal else thermal
+            if self.thermal.problem != problem or self.thermal.lv is not lv or (not self.portable and self.thermal.portable):
+                raise ValueError("Stress: the thermal load must be one of the fine level, of the same problem and, for the device form, on the device")
         self._tab = None
         self._have_volume = False
         self.qf_pts = self.qf_nod = self.op_pts = self.op_nod = self.rstr_pts = self.rstr_nod = self.basis_nod = None
@@ -169,12 +191,17 @@ class Stress:
             self.qf_nod, self.op_nod = self._graph(src, name, 7, cd.EVAL_INTERP, self.rstr_nod, self.basis_nod)
 
     def _graph(self, src, name, size, emode, rstr, basis):
-        c, lv = self.ceed, self.lv
+        c, lv, tl = self.ceed, self.lv, self.thermal
         qf = c.qfunction(name, source=f"qfunctions/{src}:{name}")
-        qf.add_input("du", 9, cd.EVAL_GRAD).add_input("qdata", 10, cd.EVAL_NONE).add_output("stress", size, emode)
-        qf.set_context(self.p.phys)
+        qf.add_input("du", 9, cd.EVAL_GRAD)
+        if tl is not None:
+            qf.add_input("theta", 1, cd.EVAL_INTERP)
+        qf.add_input("qdata", 10, cd.EVAL_NONE).add_output("stress", size, emode)
+        qf.set_context(self.p.phys if tl is None else [self.nu, self.E, tl.alpha * tl.scale])
         op = c.operator(qf)
         op.set_field("du", lv.Erestrictu, lv.basisu, "active")
+        if tl is not None:
+            op.set_field("theta", tl.theta_rstr, tl.theta_basis, tl.theta_vec)
         op.set_field("qdata", self.p.Erestrictqdi, None, self.p.qdata)
         op.set_field("stress", rstr, basis, "active")
         return qf, op
@@ -204,7 +231,9 @@ class Stress:
 
     def points_host(self, x) -> np.ndarray:
         """[nelem][6][Q^3] from a host array."""
-        sig = stress_law(self.problem, self.nu, self.E, self.grad_host(x))                 # [e][k][j][i][6]
+        tl = self.thermal
+        iso = None if tl is None else tl.beta * tl.scale * tl.theta_points()
+        sig = stress_law(self.problem, self.nu, self.E, self.grad_host(x), iso)            # [e][k][j][i][6]
         return np.ascontiguousarray(np.moveaxis(sig, -1, 1)).reshape(self.ne, 6, self.Q ** 3)
 
     def nodal_sums_host(self, x) -> np.ndarray:
@@ -217,6 +246,8 @@ class Stress:
     # ---- on vectors of the Ceed ----------------------------------------------------------------------------------------------
     def _sync(self):
         """The Ceed's stream and torch's are ordered by the host: post-processing, never inside a recording."""
+        if not self.portable and self.thermal is not None:       # the load's current scale on theta rides in the context's alpha
+            self.qf_pts._ctx[2] = self.qf_nod._ctx[2] = self.thermal.alpha * self.thermal.scale
         if not self.portable:
             self.ceed.synchronize()
             self._torch.cuda.current_stream().synchronize()
@@ -279,6 +310,9 @@ class Stress:
         return float(vm[node]), int(node)
 
     def destroy(self):
+        if self._own_thermal and self.thermal is not None:
+            self.thermal.destroy()
+        self.thermal = None
         for o in (self.op_pts, self.op_nod, self.qf_pts, self.qf_nod, self.basis_nod, self.rstr_pts, self.rstr_nod, self.spts, self.snod):
             if o is not None:
                 o.destroy()

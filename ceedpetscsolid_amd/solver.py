@@ -49,10 +49,10 @@ class NewtonPMG(LoadedBody):
                  contact: Optional[Dict[int, dict]] = None, contact_tangent: str = "levels", support: Optional[Dict[int, dict]] = None,
                  traction_field: Optional[Dict[int, object]] = None, pressure_field: Optional[Dict[int, object]] = None,
                  hydrostatic: Optional[Dict[int, dict]] = None, density=None, gravity=None, acceleration_field=None,
-                 spin: Optional[dict] = None):
+                 spin: Optional[dict] = None, thermal: Optional[dict] = None):
         """The body and its loads (``clamp, mms, forcing, halo, rccl, traction, pressure, pressure_tangent, contact, traction_field,
-        pressure_field, hydrostatic, density, gravity, acceleration_field, spin``): body.LoadedBody.  Of a spin's softening tangent, as
-        of a follower pressure's, the V-cycle sees nothing.
+        pressure_field, hydrostatic, density, gravity, acceleration_field, spin, thermal``): body.LoadedBody.  Of a spin's softening
+        tangent and of the finite-strain thermal tangent, as of a follower pressure's, the V-cycle sees nothing.
         Of a follower pressure's tangent the V-cycle, its smoothers, diagonals and eigenvalue estimates see nothing: the preconditioner
         is the volume operator's.
         ``contact_tangent``: "levels" (default) adds the contact tangent C to the operator ``A`` and to the diagonal of EVERY
@@ -95,7 +95,7 @@ class NewtonPMG(LoadedBody):
         super().__init__(prob, clamp=clamp, mms=mms, forcing=forcing, halo=halo, rccl=rccl, traction=traction, pressure=pressure,
                          pressure_tangent=pressure_tangent, verbose=verbose, contact=contact, contact_tangent=contact_tangent,
                          support=support, traction_field=traction_field, pressure_field=pressure_field, hydrostatic=hydrostatic,
-                         density=density, gravity=gravity, acceleration_field=acceleration_field, spin=spin)
+                         density=density, gravity=gravity, acceleration_field=acceleration_field, spin=spin, thermal=thermal)
         self.smoother, self._pb, self.line_search = smoother, smoother == "pbjacobi", line_search
         # fuse_epilogue: the smoother's Chebyshev step and the V-cycle's residual formed in the epilogue of the Jacobian apply
         # (CeedXOperatorApplyChebyshev / ApplyResidual: same bits as apply + update); one rank only (no interface sum in between)
